@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- self-play move-decisions/sec (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (with `roofline`, which the timed
+steps themselves feed). `--full` adds the legs that take runs of their own after it: `fp32_mfma_trunk`,
+`ten_block_net`, `wide_board`, `trained_net`, `trained_net_fp16grid`, `single_game`, `tictactoe` and
+`cpu_baseline`. `--dump-outputs DIR` writes what the last timed step returned for rank 0's games (pi, visits,
+policy, action, win_index) as DIR/<name>.npy in float64; the inputs (weights, seeds) are fixed, so two builds
+can be compared output for output.
 
 Workload (BASELINE.json configs[2], the largest single-GPU configuration; configs[3] is the same
 per GPU x 8): 9x9 Omok, 4096 concurrent self-play games per GPU, 400 MCTS simulations per move,
@@ -584,6 +591,12 @@ def main():
     ap.add_argument("--no-wide-board", action="store_true", help="skip the `wide_board` leg (BASELINE configs[4]'s per-GPU shape: 15x15, 10 blocks, 800 sims, 1024 games)")
     ap.add_argument("--no-fp16-grid", action="store_true", help="skip the `trained_net_fp16grid` leg (the trained checkpoint with its conv weights on the fp16 grid: two-product kernels)")
     ap.add_argument("--no-trained-net", action="store_true", help="skip the `trained_net` leg (the headline workload with trained weights)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs that take runs of their own: fp32-MFMA trunk, 10-block net, "
+                         "wide board, trained nets, single game, tic-tac-toe and the CPU baselines (off: the headline alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0's games: pi, visits, policy, action, win_index) "
+                         "as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_worker:
@@ -647,12 +660,15 @@ def main():
     next_seed = [world * G + rank]
     ply = np.zeros(G, np.int64)
     counters = dict(moves=0, games=0, levels=0, evaluated=0, terminal=0)
+    last = {}   # what the newest counted step returned to its caller (--dump-outputs)
 
     def step(count, use_net=None):
         tau = (ply < 6).astype(np.int8)  # main.py:150-153 TAU_THRES
-        eng.search(use_net if use_net is not None else net, tau=tau)
+        pi, vis, pol = eng.search(use_net if use_net is not None else net, tau=tau)
         st = eng.search_stats()
         act, win = eng.play()
+        if count:
+            last.update(pi=pi, visits=vis, policy=pol, action=act, win_index=win)
         ply[:] += 1
         done = win != 0
         if count:
@@ -742,6 +758,10 @@ def main():
     train_report = trainer.report(dist, dev, dt_max / args.steps * 1e3) if trainer is not None else None  # (collective)
 
     if rank == 0:
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in last.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, np.float64))
         kname, f_launch = net.dominant_kernel(G)
         avg_ms = conv_ms / max(conv_launches, 1)
         achieved = f_launch / (avg_ms * 1e-3) / 1e12 if conv_launches else 0.0
@@ -857,7 +877,7 @@ def main():
         }
         if train_report is not None:
             out["train_step"] = train_report
-        if world == 1 and split16 and not args.no_fp32_compare:
+        if args.full and world == 1 and split16 and not args.no_fp32_compare:
             # the same workload with the fp32-MFMA trunk (k_trunk16), for comparison
             try:
                 net.set_mode(2)
@@ -873,7 +893,7 @@ def main():
             except Exception as e:
                 out["fp32_mfma_trunk"] = {"value": None, "error": repr(e)}
             net.set_mode(args.trunk_mode)
-        if world == 1 and args.blocks != 10 and not args.no_ten_block:
+        if args.full and world == 1 and args.blocks != 10 and not args.no_ten_block:
             # the reference's own default network (main.py:33 N_BLOCKS = 10) on the same workload, five steps
             try:
                 torch.manual_seed(0)
@@ -897,7 +917,7 @@ def main():
         # (the main engine's trees -- 124 GB of arena at 4096 games -- are not needed by any leg below: free them before the
         # legs that build engines of their own)
         eng.close()
-        if world == 1 and not args.no_wide_board and (B, G, S) == (9, 4096, 400) and args.planes == 128:
+        if args.full and world == 1 and not args.no_wide_board and (B, G, S) == (9, 4096, 400) and args.planes == 128:
             # BASELINE configs[4]'s per-GPU shape beside the headline: 15x15 (env_regular), 10-block net, 800 sims, 1024 concurrent games
             # (8192 games on 8 GPUs = 1024 per GPU); 1 untimed + 2 timed move decisions from the empty board. Kernel: k_boardh<15, 2>.
             try:
@@ -966,7 +986,7 @@ def main():
                 netw.close()
             except Exception as e:
                 out.setdefault("wide_board", {"value": None})["error"] = repr(e)
-        if world == 1 and not args.no_trained_net and os.path.exists(args.trained_weights) and (B, args.blocks, args.planes) == (9, 4, 128):
+        if args.full and world == 1 and not args.no_trained_net and os.path.exists(args.trained_weights) and (B, args.blocks, args.planes) == (9, 4, 128):
             try:
                 out["trained_net"] = trained_net_bench(args, local, args.trained_weights, oversubscribe=args.oversubscribe)
             except Exception as e:
@@ -987,7 +1007,7 @@ def main():
                                                                                "terminal_leaf_fraction", "trunk_kernel", "trunk_avg_launch_ms", "roofline")}
                 except Exception as e:
                     out["trained_net_fp16grid"] = {"value": None, "error": repr(e)}
-        if world == 1 and G > 1 and not args.no_single_game:
+        if args.full and world == 1 and G > 1 and not args.no_single_game:
             # BASELINE configs[1] beside the headline: ONE game, 400 sims/move, same network
             # (latency path: per-board conv kernels, no concurrency to hide behind)
             try:
@@ -1009,12 +1029,12 @@ def main():
                 one.close()
             except Exception as e:
                 out["single_game"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_tictactoe:
+        if args.full and world == 1 and not args.no_tictactoe:
             try:
                 out["tictactoe"] = tictactoe_bench(local)
             except Exception as e:
                 out["tictactoe"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(B, S, args.blocks, args.planes, sd, args.cpu_budget)
                 if not args.no_cpu_all_cores:

@@ -1,10 +1,11 @@
-"""CPU: the measurement plumbing of bench.py (round-2 review, item 1).
+"""The measurement plumbing of bench.py (round-2 review, item 1); CPU except where marked gpu.
 
 * the committed rocprofv3 PMC summary bench.py's `roofline.traffic` quotes must be accepted by bench.py's own
   matching rule for the kernel that runs the default workload and for the CURRENT kernel sources -- a stale or
   mis-named profile makes the driver's record say `traffic: null` (that happened in round 2);
 * `python bench.py --gpus N` without a launcher starts the ranks itself and refuses -- exit code 2, nothing on
-  stdout -- when fewer than N GPUs are visible, instead of printing a 1-GPU line under an N-GPU label."""
+  stdout -- when fewer than N GPUs are visible, instead of printing a 1-GPU line under an N-GPU label;
+* (gpu) a plain run is the headline alone, and --dump-outputs writes the last timed step's outputs, the same on every run."""
 import json
 import os
 import subprocess
@@ -120,6 +121,41 @@ def test_build_lists_cover_every_source_and_header_under_csrc():
     finally:
         builtins.open = real_open
     assert h1 != h0, "source_hash() does not cover net_layer_ksplit.hpp"
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_the_headline_alone_and_dumps_its_last_timed_step(tmp_path):
+    """`bench.py` without --full runs the timed steps and nothing else (the legs that take runs of their own are --full's), and
+    `--dump-outputs DIR` writes what the last timed step returned -- pi / visits / policy / action / win_index of the rank's games,
+    float64 -- identically from run to run with the same arguments."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "AO_BENCH_SHARE_GPU")}
+    G, A = 64, 81
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--games", str(G),
+                            "--sims", "16", "--blocks", "1", "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-500:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        assert j["value"] == pytest.approx(G * 3 / (j["ms_per_step"] * 3 * 1e-3), rel=1e-6)
+        for leg in ("fp32_mfma_trunk", "ten_block_net", "wide_board", "trained_net", "trained_net_fp16grid", "single_game", "tictactoe",
+                    "cpu_baseline"):
+            assert leg not in j, "a plain run measured `%s`" % leg
+        got = {n: np.load(str(d / (n + ".npy"))) for n in ("pi", "visits", "policy", "action", "win_index")}
+        assert sorted(os.listdir(str(d))) == sorted(n + ".npy" for n in got)
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert got["pi"].shape == got["visits"].shape == got["policy"].shape == (G, A)
+        assert got["action"].shape == got["win_index"].shape == (G,)
+        assert np.allclose(got["pi"].sum(axis=1), 1.0) and np.all(got["visits"] >= 0)
+        act = got["action"]
+        assert np.array_equal(act, np.round(act)) and act.min() >= 0 and act.max() < A
+        dumps.append(got)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), "%s differs between two runs with the same arguments" % n
 
 
 def test_other_workload_traffic_is_keyed_on_sources_shape_and_kernel():
