@@ -11,10 +11,17 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
 
-def _native(nb, C, planes, B, seed):
+def _native(nb, C, planes, B, seed, weights="golden"):
+    """weights="conditioned": net_reference.conditioned_state_dict -- live heads, O(1) tower -- instead of the golden-vector
+    generator, whose value head is dead at 128 planes (v is then one number, and an equality of two searches says nothing
+    about their value paths)."""
     from alpha_omok_amd.engine import Net
     net = Net(nb, C, planes, B, 0)
-    net.load_state_dict(pvnet_weights.make_state_dict(nb, C, planes, B, seed))
+    if weights == "conditioned":
+        import net_reference
+        net.load_state_dict(net_reference.conditioned_state_dict(nb, C, planes, B, seed))
+    else:
+        net.load_state_dict(pvnet_weights.make_state_dict(nb, C, planes, B, seed))
     return net
 
 
@@ -534,7 +541,7 @@ def test_split_fp16_trunk_reports_activations_beyond_fp16_range(batch):
 
 
 @pytest.mark.parametrize("B,G,S,nb,C", [(9, 64, 24, 2, 5), (9, 3072, 12, 1, 5), (15, 40, 16, 2, 5), (9, 50, 20, 1, 7), (5, 80, 20, 1, 3)])
-def test_fused_search_on_bit_planes_equals_stepwise_on_float_planes(B, G, S, nb, C):
+def test_fused_search_on_bit_planes_equals_stepwise_on_float_planes(B, G, S, nb, C, weights="golden"):
     """ao_search hands the split-fp16 kernels the leaf planes as BITS (one byte per cell, written by the tree kernel;
     k_trunk16hb / k_layer16h<.., 2>), the stepwise protocol hands the same network fp32 NCHW planes through
     ao_net_forward (k_nchw_to_il + the fp32-plane kernels). The planes are 0/1, so conv1 sees identical operands and
@@ -543,7 +550,7 @@ def test_fused_search_on_bit_planes_equals_stepwise_on_float_planes(B, G, S, nb,
     import torch
     from alpha_omok_amd.engine import Engine
     from gpu_helpers import HostEvalRunner
-    net = _native(nb, C, 128, B, 9)
+    net = _native(nb, C, 128, B, 9, weights)
     net.set_mode(5)
     seeds = np.arange(40, 40 + G, dtype=np.uint32)
     e1 = Engine(B, S, C, games=G, noise=True)
@@ -576,7 +583,7 @@ def test_fused_search_on_bit_planes_equals_stepwise_on_float_planes(B, G, S, nb,
 
 
 @pytest.mark.parametrize("mode,planes", [(4, 64), (2, 64), (3, 64), (5, 128)])
-def test_fused_search_packs_active_games_only(mode, planes):
+def test_fused_search_packs_active_games_only(mode, planes, weights="golden"):
     """ao_search runs the network on the ACTIVE games only (rows packed to the front of the batch). With a kernel family
     whose per-board result does not depend on the batch (modes 2 / 3 / 4; mode 5 with every move on the per-layer
     kernel) the packed search must equal the stepwise protocol that evaluates all G slots, bit for bit, under
@@ -585,7 +592,7 @@ def test_fused_search_packs_active_games_only(mode, planes):
     from alpha_omok_amd.engine import Engine
     from gpu_helpers import HostEvalRunner
     B, S, G = 9, 20, 70
-    net = _native(2, 5, planes, B, 21)
+    net = _native(2, 5, planes, B, 21, weights)
     net.set_mode(mode)
     seeds = np.arange(900, 900 + G, dtype=np.uint32)
     e1 = Engine(B, S, 5, games=G, noise=True)
@@ -626,14 +633,14 @@ def test_fused_search_packs_active_games_only(mode, planes):
 
 
 @pytest.mark.parametrize("B,G,S,nb,C", [(9, 1, 64, 2, 5), (9, 5, 48, 2, 5), (15, 3, 24, 1, 5), (9, 40, 16, 1, 7), (5, 7, 20, 1, 3)])
-def test_fused_per_game_step_equals_separate_launches(B, G, S, nb, C, monkeypatch):
+def test_fused_per_game_step_equals_separate_launches(B, G, S, nb, C, monkeypatch, weights="golden"):
     """A few games on a 128-plane network: ao_search runs heads + expansion / backup / selection + the next leaf's conv1 as ONE
     launch per game (k_step_board, step_kernels.hip). The tree code is the same device code; conv1 is formulated differently
     (K = tap * 8 + plane on fp16 MFMAs with split weights instead of fp32 MFMAs per tap), exact products of 0/1 planes with
     fp32 accumulation either way. The searches must agree with the three-launch form (AO_FUSED_STEP=0): same visits, priors,
     moves and stream positions over several plies, with a changing active mask."""
     from alpha_omok_amd.engine import Engine
-    net = _native(nb, C, 128, B, 31)
+    net = _native(nb, C, 128, B, 31, weights)
     seeds = np.arange(70, 70 + G, dtype=np.uint32)
     e1 = Engine(B, S, C, games=G, noise=True)
     e2 = Engine(B, S, C, games=G, noise=True)
@@ -664,6 +671,25 @@ def test_fused_per_game_step_equals_separate_launches(B, G, S, nb, C, monkeypatc
     e1.close()
     e2.close()
     net.close()
+
+
+@pytest.mark.parametrize("B,G,S,nb,C", [(9, 64, 24, 2, 5), (9, 3072, 12, 1, 5), (15, 40, 16, 2, 5), (9, 50, 20, 1, 7), (5, 80, 20, 1, 3)])
+def test_fused_search_on_bit_planes_equals_stepwise_on_float_planes_conditioned_weights(B, G, S, nb, C):
+    """The same equality on a network whose value head is live and whose policy is not one-hot: the bit-plane kernels
+    (k_trunk16hb, k_layer16h<.., 2>) are tied to the float-plane kernels through values that move with the position."""
+    test_fused_search_on_bit_planes_equals_stepwise_on_float_planes(B, G, S, nb, C, weights="conditioned")
+
+
+@pytest.mark.parametrize("mode,planes", [(4, 64), (2, 64), (3, 64), (5, 128)])
+def test_fused_search_packs_active_games_only_conditioned_weights(mode, planes):
+    test_fused_search_packs_active_games_only(mode, planes, weights="conditioned")
+
+
+@pytest.mark.parametrize("B,G,S,nb,C", [(9, 1, 64, 2, 5), (9, 5, 48, 2, 5), (15, 3, 24, 1, 5), (9, 40, 16, 1, 7), (5, 7, 20, 1, 3)])
+def test_fused_per_game_step_equals_separate_launches_conditioned_weights(B, G, S, nb, C, monkeypatch):
+    """The heads fused into the step kernel (k_step_board) against the separate head launch, with a value that depends on
+    the board."""
+    test_fused_per_game_step_equals_separate_launches(B, G, S, nb, C, monkeypatch, weights="conditioned")
 
 
 @pytest.mark.parametrize("nb,B,batch", [(2, 15, 130), (10, 15, 300), (3, 11, 129), (2, 13, 200), (1, 10, 128), (2, 15, 70)])
