@@ -88,6 +88,7 @@ struct ao_net {
     // it was 96 before that kernel; AO_PERBOARD_CELLS)
     long perboard_cells = 2592;
     int force_xt = 0, force_nch = 0;               // AO_XT / AO_NCH: tiling overrides for timing experiments (read at create)  // dynamic-LDS attribute set for this net's device
+    bool force_resident = false;                   // AO_FORCE_RESIDENT=1 (read at create): mode 5 runs the resident trunk at ANY group count (boards up to 9x9; tests of that kernel on a few boards, timing)
     // timing of the dominant kernel (trunk conv launches)
     bool timing = false;                           // THIS forward's launches are timed (see net_forward_il)
     bool timing_on = false;                        // ao_net_conv_timing(enable): every `timing_stride`-th forward is timed
@@ -485,11 +486,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
         }
 #endif
         return 0;
-#ifdef AO_PROF
-    } else if (group == 16 && mode == 5 && (layers_only(n) || !(n->B <= 9 && (groups >= 192 || getenv("AO_FORCE_RESIDENT"))))) {
-#else
-    } else if (group == 16 && mode == 5 && (layers_only(n) || !(n->B <= 9 && groups >= 192))) {
-#endif
+    } else if (group == 16 && mode == 5 && (layers_only(n) || !(n->B <= 9 && (groups >= 192 || n->force_resident)))) {
         // split-fp16 trunk, one launch per conv: workgroup = (16-board group, row chunk, column tile). For batches
         // that cannot give every CU a whole group, and for boards wider than 9 (a staged row must fit LDS twice)
         // Tiling of a wide board: column tiles of XT = 5 or 4 cells (+ a halo column each side) x row chunks. Every
@@ -916,6 +913,7 @@ int ao_net_create(int n_block, int inplanes, int planes, int board, int device, 
     if (n->trunk_fmt < 0) n->trunk_fmt = 0;
     if (const char* v = getenv("AO_XT")) n->force_xt = atoi(v) == 4 ? 4 : (atoi(v) == 5 ? 5 : 0);
     if (const char* v = getenv("AO_NCH")) n->force_nch = atoi(v) > 0 && atoi(v) <= board ? atoi(v) : 0;
+    if (const char* v = getenv("AO_FORCE_RESIDENT")) n->force_resident = atoi(v) != 0;
     *out = n;
     return 0;
 }
@@ -1250,13 +1248,13 @@ static void dominant_name(const ao_net* n, int boards, int in_kind, std::string*
     } else if (group == 16 && mode == 4) {
         nm = "k_layer16<" + bw + "> (one 3x3 conv per launch, 16-board groups x row chunks, fp32 MFMA 16x16x4)";
         f = conv;
-    } else if (group == 16 && mode == 5 && !layers_only(n) && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->rowk_min &&
+    } else if (group == 16 && mode == 5 && !layers_only(n) && !n->force_resident && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->rowk_min &&
                (boards + 15) / 16 <= n->rowk_max) {
         nm = std::string(two_products(n) ? "k_row16hk_w16<" : "k_row16hk<") + bw + "> (one 3x3 conv per launch as split-fp16 MFMA 16x16x32 (" +
              (two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate): one workgroup per "
              "16-board group x output row x cout pair, waves split the contraction by input block, partial tiles exchanged through LDS)";
         f = conv;
-    } else if (group == 16 && mode == 5 && !layers_only(n) && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->ksplit_min &&
+    } else if (group == 16 && mode == 5 && !layers_only(n) && !n->force_resident && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->ksplit_min &&
                (boards + 15) / 16 <= std::max(n->ksplit_max, n->ksplit_max2)) {
         const bool four = (boards + 15) / 16 <= n->ksplit_max;
         const bool two = two_products(n) && four;
@@ -1270,7 +1268,7 @@ static void dominant_name(const ao_net* n, int boards, int in_kind, std::string*
              " 3x3 convs in one launch as split-fp16 MFMA 16x16x32 (" + (two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate): "
              "a workgroup = one board resident in LDS through all layers, the row's cells as the MFMA N dimension, column shifts as DPP row shifts)";
         f = 2.0 * n->nb * 2.0 * n->A * 9.0 * n->planes * n->planes * boards + (in_kind == 2 ? 2.0 * n->A * 9.0 * n->C * n->planes * boards : 0.0);
-    } else if (group == 16 && mode == 5 && (layers_only(n) || !(n->B <= 9 && (boards + 15) / 16 >= 192))) {
+    } else if (group == 16 && mode == 5 && (layers_only(n) || !(n->B <= 9 && ((boards + 15) / 16 >= 192 || n->force_resident)))) {
         nm = std::string(two_products(n) ? "k_layer16h_w16<" : "k_layer16h<") + bw + "> (one 3x3 conv per launch as split-fp16 MFMA 16x16x32 (" +
              (two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate), "
              "16-board groups x row chunks x column tiles)";

@@ -3,6 +3,8 @@
 // (trunk_heads is shared).
 #pragma once
 
+#include <type_traits>
+
 namespace ao {
 
 // ----------------------------------------------------------------------------------------------
@@ -56,7 +58,8 @@ __device__ __forceinline__ void buf_st_h4(half4 v, __amdgpu_buffer_rsrc_t r, int
 
 #ifdef AO_PROF
 // phase timing of k_trunk16h (build with AO_EXTRA_FLAGS=-DAO_PROF; tools/time_net.py prints it): shader-clock
-// cycles per wave of one group, summed over the trunk layers: [0] row-0 staging, [1] slab loops, [2] row
+// cycles per wave of one group, summed over the trunk layers: [0] layer start (4-byte format: one barrier and the first weight
+// slab, rows 0 and 1 were handed over in LDS; 3-byte format: row-0 staging), [1] slab loops, [2] row
 // epilogues, [3] row barriers, [4] last epilogue + layer boundary, [5] heads, [6] conv1 total
 static __device__ unsigned long long ao_prof[8 * 12];   // (static: the header is compiled into two translation units)
 #define AO_T(x) const unsigned long long x = __builtin_amdgcn_s_memtime()
@@ -178,17 +181,28 @@ template <int BW, int NC32, int NCI, int KIND, int FMT = 0, bool W16 = false>
 struct TrunkHLayerFn {
 static __device__ __forceinline__ void run(const void* src, uint4* dst, const TrunkHLayer& L, const bool RES, uint4* s_x,
                                            int tile, int lane, unsigned long long* prof, const bool flip,
-                                           unsigned* s_cnt, const unsigned rows_before) {
+                                           unsigned* s_cnt, const unsigned rows_before, const bool hand_next, const int par) {
     constexpr bool FIRST = KIND != 0;
     constexpr bool BITS = KIND == 2;
+    // Hand-off of the layer boundary through LDS (see the row-buffer life cycle below). hand_next: another resident layer
+    // follows this one and takes its first two input rows from the row buffers; HANDED: the previous layer left this layer's
+    // input rows 0 and 1 there (every trunk layer of the 4-byte format: conv1 and each trunk layer hand off whenever a layer
+    // follows). par: which row buffer holds input row 0 (always 0 for an odd board width). The 3-byte format (FMT 1) keeps
+    // expanded fragments in LDS that differ from what it stores and stays on the HBM round trip; the knock-out builds too,
+    // so that they keep measuring what their notes say.
+    constexpr bool HAND = FMT == 0 && AO_KO == 0;
+    constexpr bool HANDED = HAND && !FIRST;
+    static_assert(!HAND || NC32 >= 2, "conv1's hand-off assumes that its own row buffers lie inside the next layer's buffer 0");
     // flip: this layer walks the board from the LAST row to the first (logical row y = physical row BW-1-y, tap rows
-    // mirrored). Layers alternate direction, so a layer starts with the rows the previous one wrote last -- still in
-    // L2 / the Infinity Cache -- instead of the ones that left the caches 340 MB of traffic ago.
+    // mirrored). Layers alternate direction, so a layer starts with the rows the previous one wrote last: the first two
+    // are handed over in LDS (HAND), the third is still in L2 / the Infinity Cache -- instead of the ones that left the
+    // caches 340 MB of traffic ago.
     auto py = [&](int y) { return flip ? BW - 1 - y : y; };
     constexpr int A = BW * BW;
     constexpr int NT = NC32 * 2;             // 16-channel output tiles = waves (two per SIMD at 128 channels)
     constexpr int NSP = 2;                   // halves of an input fragment
     constexpr int NFR = BW * NCI * NSP;      // input fragments per board row
+    constexpr int NFRO = BW * NC32 * NSP;    // fragments of an OUTPUT row = of an input row of the next layer
     constexpr int NB = NCI * 3;              // (32-channel block, tap row) slabs per input row
     constexpr int NPR = 3;                   // MFMA products per multiply-add
     constexpr int PAIR = static_cast<int>(kPairBytes(FMT));   // bytes of a (cell, block) fragment pair in HBM
@@ -263,7 +277,12 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
     // Output row in two batches of cells: all residual loads of a batch are issued before the first is used
     // (written cell by cell the compiler produced load, wait, store, load, wait-for-everything ...: nine serial
     // memory round trips per row, 3.8 us; the registers of the X fragments are free here)
-    auto epilogue = [&](int yo) {
+    // HO (compile time): this output row is handed to the next layer in LDS row buffer hx -- the same split fragments, at
+    // the same offsets inside the row as in HBM (out_voff addresses a (cell, block) pair in both); the HBM store is then
+    // needed only if something else re-reads the tensor: the residual of the next block (conv1's and every block's
+    // output), not the output of a block's first conv
+    auto epilogue = [&](int yo, auto ho, uint4* hx) {
+        constexpr bool HO = decltype(ho)::value;
         constexpr int HB = (BW + 1) / 2;
 #pragma unroll
         for (int i0 = 0; i0 < BW; i0 += HB) {
@@ -325,6 +344,12 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
                     hh[r] = static_cast<_Float16>(v);
                     hl[r] = static_cast<_Float16>(v - static_cast<float>(hh[r]));
                 }
+                if (HO) {
+                    u32x2* hp = reinterpret_cast<u32x2*>(reinterpret_cast<char*>(hx) + (i * NC32 + (tile >> 1)) * 2048 + out_voff);
+                    hp[0] = __builtin_bit_cast(u32x2, hh);
+                    hp[128] = __builtin_bit_cast(u32x2, hl);   // the low fragment, 1024 bytes on
+                    if (!RES && !FIRST) continue;
+                }
                 buf_st_h4(hh, rs_dst, out_voff, ob);
                 if (AO_KO == 10 || AO_KO == 12) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(u32x2, hl)[0], rs_dst, out_voff >> 1, ob + 1024, AO_AUX_ST);
                 else
@@ -379,9 +404,23 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
         }
     };
 
-    // stage input row 0 (wave w copies fragments w, w + NT, ...)
+    // Life cycle of the two LDS row buffers. Input row yi is read from buffer (yi + po) & 1 while row yi + 1 is staged into
+    // the other one (wave w copies fragments w, w + NT, ...); the barrier that ends iteration yi publishes the staged row
+    // and frees the buffer just read. Nothing is staged in the last iteration: there is no row BW. At that point the
+    // other buffer is free (every wave passed the barrier that ended iteration BW-2), and a layer that hands off writes
+    // output row BW-2, finished in that iteration's epilogue, into it in the NEXT layer's geometry; output row BW-1,
+    // finished after the last row barrier, goes into the buffer just read. Layers alternate direction, so these are the
+    // next layer's input rows 1 and 0: it starts without staging anything, behind the one barrier that publishes the
+    // LDS writes, and stages its row 2 in its first iteration (row 1 is there already). For an even BW the two rows land
+    // in swapped buffers, which the next layer is told through par. conv1's own buffers (one 32-channel block) lie inside
+    // the next layer's buffer 0, so it hands row BW-2 to buffer 1 and row BW-1, after its last read, to buffer 0.
+    const int po = (BW & 1) ? 0 : par;
+    uint4* const hand2 = s_x + static_cast<size_t>(FIRST ? 1 : (BW + po) & 1) * NFRO * 64;       // output row BW-2
+    uint4* const hand1 = s_x + static_cast<size_t>(FIRST ? 0 : (BW - 1 + po) & 1) * NFRO * 64;   // output row BW-1
+    constexpr std::integral_constant<bool, true> kHand{};
+    constexpr std::integral_constant<bool, false> kStore{};
     AO_T(t_a);
-    __syncthreads();  // the previous layer is done with both row buffers
+    __syncthreads();  // the previous layer is done with both row buffers (and its handed-off rows are visible)
     AO_T(t_a1);
     // (all loads of the wave in flight at once: written as a loop over f the compiler emits load, wait, LDS write
     // per fragment -- nine serial HBM round trips, 10 us per layer)
@@ -391,6 +430,8 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
             const int f = tile + NT * k;
             if (f < NFR) s_x[f * 64 + lane] = __builtin_bit_cast(uint4, load_planes(f >> 1, f & 1));
         }
+    } else if (HANDED) {
+        // input rows 0 and 1 are in the row buffers already
     } else if (FMT == 1) {
         stage_pairs(0, s_x, 0, (NPAIR + NT - 1) / NT);
     } else if (!(AO_KO == 13 || AO_KO == 15)) {
@@ -405,13 +446,13 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
     }
     AO_T(t_a2);
     load_w(0, wA);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if (!HANDED) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (FMT == 1 && !FIRST) {
         expand_pairs(s_x, 0, (NPAIR + NT - 1) / NT);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     AO_T(t_a3);
-    __syncthreads();
+    if (!HANDED) __syncthreads();
     AO_T(t_b);
     AO_ACC(0, t_a, t_b);
     AO_ACC(8, t_a, t_a1);
@@ -421,9 +462,10 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
 
     for (int yi = 0; yi < BW; ++yi) {
         AO_T(t_r0);
-        const uint4* xs = s_x + static_cast<size_t>(yi & 1) * NFR * 64;         // this row
-        uint4* xn = s_x + static_cast<size_t>((yi + 1) & 1) * NFR * 64;         // next row's buffer
-        const int yn = yi + 1 < BW ? yi + 1 : yi;                               // next input row (clamped)
+        const uint4* xs = s_x + static_cast<size_t>((yi + po) & 1) * NFR * 64;       // this row
+        uint4* xn = s_x + static_cast<size_t>((yi + 1 + po) & 1) * NFR * 64;       // next row's buffer
+        const int yn = yi + 1;                                                  // next input row
+        const bool stage_next = yn < BW && !(HANDED && yi == 0);                // (uniform) the last row has none; row 1 was handed over
 #pragma unroll
         for (int slab = 0; slab < NB; ++slab) {
             const int c = slab / 3, dy = slab % 3;
@@ -431,7 +473,9 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
             half8 (&w)[2][3] = (slab & 1) ? wB : wA;
             half8 (&wn)[2][3] = (slab & 1) ? wA : wB;
             load_w(slab + 1, wn);
-            if (dy == 1 && !AO_KO_NOSTAGE && FMT == 1 && !FIRST) {
+            if (!stage_next) {
+                // nothing to stage in this iteration
+            } else if (dy == 1 && !AO_KO_NOSTAGE && FMT == 1 && !FIRST) {
                 // next input row into LDS, a share of this wave's fragment pairs per block
                 // (the share staged one block earlier has landed long ago: it is expanded first, so that the wait the
                 // compiler puts in front of its LDS reads does not cover the loads issued below)
@@ -511,7 +555,10 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
         // row are done
         row_arrive(s_cnt, lane);
 #endif
-        if (yi >= 1 && (!AO_KO_NOEPI || (AO_KO == 4 && yi == 1))) epilogue(yi - 1);
+        if (yi >= 1 && (!AO_KO_NOEPI || (AO_KO == 4 && yi == 1))) {
+            if (HAND && hand_next && yi == BW - 1) epilogue(yi - 1, kHand, hand2);
+            else epilogue(yi - 1, kStore, nullptr);
+        }
         else if (yi >= 1 && (AO_KO == 14 || AO_KO == 15)) {
             // (no epilogue, but the row's accumulators stay "used": without a consumer the compiler deletes the MFMAs that
             // feed them -- the first data-like no-epilogue build ran in 0.27 ms, and round 2's AO_KO=4 had lost part of its
@@ -528,7 +575,8 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
         AO_T(t_r2);
 #if AO_SPLIT_BARRIER
         // wait: all NT waves arrived for this row (the layer boundary below is a full barrier: no wait after the last row)
-        if (yi + 1 < BW && AO_KO != 9) row_wait(s_cnt, static_cast<unsigned>(NT) * (rows_before + static_cast<unsigned>(yi) + 1u));
+        // (... unless the last row's buffer is written by the hand-off of the last epilogue)
+        if ((yi + 1 < BW || (HAND && hand_next)) && AO_KO != 9) row_wait(s_cnt, static_cast<unsigned>(NT) * (rows_before + static_cast<unsigned>(yi) + 1u));
 #else
         // next row staged by all waves (LDS-direct loads count in vmcnt), this row's buffer free
         if (AO_KO == 9) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -540,7 +588,10 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
         AO_ACC(3, t_r2, t_r3);
     }
     AO_T(t_c);
-    if (!AO_KO_NOEPI || FIRST) epilogue(BW - 1);
+    if (!AO_KO_NOEPI || FIRST) {
+        if (HAND && hand_next) epilogue(BW - 1, kHand, hand1);
+        else epilogue(BW - 1, kStore, nullptr);
+    }
     if (peak > (FMT == 1 ? 65504.f * kLo8Scale : 65504.f)) atomicOr(L.ovf, 1);
     // layer boundary inside the workgroup (see k_trunk16)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -815,10 +866,10 @@ __device__ __forceinline__ void trunk16h_body(const TrunkHArgs& a) {
     AO_T(t0);
     if (INK == 2)
         TrunkHLayerFn<BW, NC32, 1, 2, FMT, W16>::run(reinterpret_cast<const uint8_t*>(a.in0) + static_cast<size_t>(grp) * 16 * kPlaneRow(BW), bufA,
-                                      a.layers[0], false, s_x, tile, lane, pp, false, s_cnt, 0u);
+                                      a.layers[0], false, s_x, tile, lane, pp, false, s_cnt, 0u, a.nlayers > 1, 0);
     else
         TrunkHLayerFn<BW, NC32, 1, 1, FMT, W16>::run(a.in0 + static_cast<size_t>(grp) * A * 8 * 16, bufA, a.layers[0], false, s_x, tile, lane, pp, false,
-                                      s_cnt, 0u);
+                                      s_cnt, 0u, a.nlayers > 1, 0);
     AO_T(t1);
     if (ko_fill) {   // data-like LDS rows for the trunk layers, never refreshed (see AO_KO)
         __syncthreads();
@@ -828,11 +879,13 @@ __device__ __forceinline__ void trunk16h_body(const TrunkHArgs& a) {
 #ifdef AO_PROF
     for (int k = 0; k < 12; ++k) prof[k] = 0;
 #endif
+    int par = 0;   // the row buffer in which the previous layer left this layer's input row 0 (see TrunkHLayerFn, hand-off)
     for (int l = 1; l < a.nlayers; ++l) {
         // l odd: first conv of a ResBlock (x -> t); l even: second conv (t -> x, + x in place)
         const bool second = (l & 1) == 0;
         TrunkHLayerFn<BW, NC32, NC32, 0, FMT, W16>::run(second ? bufB : bufA, second ? bufA : bufB, a.layers[l], second, s_x, tile, lane, pp,
-                                             (l & 1) != 0, s_cnt, static_cast<unsigned>(l) * BW);
+                                             (l & 1) != 0, s_cnt, static_cast<unsigned>(l) * BW, l + 1 < a.nlayers, par);
+        par = (par + BW - 1) & 1;
     }
     AO_T(t2);
     if (AO_KO != 8) trunk_heads<BW, FMT == 1 ? 2 : 1>(a, reinterpret_cast<const float4*>(a.bufA), static_cast<size_t>(grp) * A, grp);
