@@ -5,3 +5,16 @@ main.self_play): batched MCTS over structure-of-arrays trees in HBM, hand-writte
 for gfx950, behind a C ABI (include/omok_hip.h).
 """
 __version__ = "0.1.0"
+
+__all__ = ["PositionBatch", "positions"]
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package itself loads nothing (the library path is chosen when _lib is imported)
+    if name == "PositionBatch":
+        from .positions import PositionBatch
+        return PositionBatch
+    if name == "positions":
+        import importlib
+        return importlib.import_module(".positions", __name__)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -113,6 +113,12 @@ SYMBOLS = {
     "ao_ttt_get_rng_state": (C.c_int, [_vp, C.c_int, _u32p, _i32p]),
     "ao_ttt_set_rng_state": (C.c_int, [_vp, C.c_int, _u32p, C.c_int32]),
     "ao_ttt_search": (C.c_int, [_vp, _i8p, _i32p, _u8p, _f64p, _f64p, _i32p]),
+    "ao_positions_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(_vp)]),
+    "ao_positions_destroy": (None, [_vp]),
+    "ao_positions_last_error": (C.c_char_p, [_vp]),
+    "ao_positions_check_win": (C.c_int, [_vp, _i8p, C.c_int32, _i32p]),
+    "ao_positions_from_moves": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _i32p, _i32p, _i32p, _i8p, _u8p, _vp, _i32p]),
+    "ao_positions_evaluate": (C.c_int, [_vp, _vp, _i32p, C.c_int32, _i32p, C.c_int32, _P(C.c_float), _P(C.c_float), _i32p, _i32p]),
 }
 
 _lib = None

@@ -81,6 +81,7 @@ class ZeroAgent(Agent):
         self._node_cap = node_cap
         self._engine = None
         self._evaluator = Evaluator(device)
+        self._positions = None
 
     # -- engine plumbing --------------------------------------------------------------------
     def _eng(self):
@@ -140,6 +141,32 @@ class ZeroAgent(Agent):
                     self.model.eval()
                 p, v = self.model(x.to(Evaluator._model_device(self.model)))
         return p.detach().cpu().numpy()[0], v.detach().cpu().numpy()[0]
+
+    def get_pv_batch(self, root_ids):
+        """get_pv for many ids in one call (PositionBatch.evaluate): (policy float32 [n, A], value float32 [n],
+        status int32 [n] -- utils.check_win of each position, terminal ones are evaluated too --, err int32 [n]). The planes
+        are built on the device; a PVNet-shaped model runs on the native forward, any other model is called once on the
+        whole plane batch. Ids with err != 0 (a move off the board or onto a stone) get zeros."""
+        from .positions import PositionBatch
+        if self._positions is None:
+            self._positions = PositionBatch(self.board_size, self.inplanes, self.win_mark, device=self._device)
+        pb = self._positions
+        net = self._evaluator.native_net(self.model, self.board_size, self.inplanes)
+        if net is not None:
+            return pb.evaluate(net, root_ids)
+        import torch
+        d = pb.describe(root_ids)
+        x = pb.planes(root_ids)
+        if hasattr(self.model, "eval"):
+            self.model.eval()
+        with torch.no_grad():
+            p, v = self.model(x.to(Evaluator._model_device(self.model)))
+        n = d["err"].shape[0]
+        p = np.ascontiguousarray(p.detach().reshape(n, -1).float().cpu().numpy())
+        v = np.ascontiguousarray(v.detach().reshape(n).float().cpu().numpy())
+        p[d["err"] != 0] = 0
+        v[d["err"] != 0] = 0
+        return p, v, d["status"], d["err"]
 
 
 class _RolloutAgent(Agent):

@@ -1,0 +1,385 @@
+// positions.hip -- the stateless, batched "position" layer beside the search: rule status, legal moves, input planes and the
+// network's evaluation of positions the CALLER names, no tree and no game involved.
+//
+// One wavefront (64 lanes) owns one position, kPosPerWG positions per workgroup, nothing shared between them (no LDS).
+//
+// Reference map (paths relative to /root/reference/2_AlphaOmok/):
+//   k_check_win_boards      utils.py:30-59 (check_win) on raw boards: the FULL window scan, row-major, black before white
+//                           inside a window -- boards need not be reachable in play, so the scan order decides
+//   k_positions_from_moves  utils.py:171-179 (get_board) + utils.py:182-186 (get_turn) + utils.py:22-27 (legal_actions, as a
+//                           mask: the CPython set ORDER is the tree kernels' business, legal_order) + utils.py:30-59
+//                           (check_win of the final board, and of every prefix through the incremental win_after_move of
+//                           the tree kernels) + utils.py:139-168 (get_state_pt, encode_planes of the tree kernels)
+//   ao_positions_evaluate   agents.py:171-178 for n positions at once: planes on the device, then the ordinary forward
+//
+// The bitboards, pos_place, pos_occupied, win_after_move and encode_planes are the tree kernels' own (tree_device.hpp): a
+// position described here is the position the search would hold.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/omok_hip.h"
+#include "tree_device.hpp"
+
+namespace ao {
+
+int net_check(const ao_net* n, int board, int inplanes, int device, std::string* why);   // net.hip
+
+constexpr int kPosPerWG = 4;
+
+// per-position error codes (ao_positions_from_moves)
+enum : int32_t { PE_OK = 0, PE_RANGE = 1, PE_OCCUPIED = 2, PE_LENGTH = 3 };
+
+// `len` (1..5) bits of a bitboard from bit `off` on (off + len <= 256); no dynamically indexed access (see pick4)
+__device__ __forceinline__ unsigned bb_bits(const uint64_t (&bb)[kBBWords], int off, int len) {
+    const int w = off >> 6, sh = off & 63;
+    const uint64_t lo = pick4(bb[0], bb[1], bb[2], bb[3], w);
+    const uint64_t hi = (w < kBBWords - 1) ? pick4(bb[0], bb[1], bb[2], bb[3], w + 1) : 0ull;
+    uint64_t v = lo >> sh;
+    v |= sh ? (hi << (64 - sh)) : 0ull;
+    return static_cast<unsigned>(v) & ((1u << len) - 1u);
+}
+
+// any complete row, column or diagonal in a k x k window given as k*k bits (bit r*k + c)
+__device__ __forceinline__ bool window_has_line(unsigned m, int k) {
+    const unsigned rowm = (1u << k) - 1u;
+    unsigned colm = 0u, d1 = 0u, d2 = 0u;
+    for (int r = 0; r < k; ++r) {
+        colm |= 1u << (r * k);
+        d1 |= 1u << (r * k + r);
+        d2 |= 1u << (r * k + (k - 1 - r));
+    }
+    bool any = ((m & d1) == d1) || ((m & d2) == d2);
+    for (int i = 0; i < k; ++i) {
+        const unsigned rm = rowm << (i * k), cm = colm << i;
+        any = any || ((m & rm) == rm) || ((m & cm) == cm);
+    }
+    return any;
+}
+
+// utils.check_win (utils.py:30-59) of a whole board, wave-uniform (all 64 lanes call): lane = window, 64 windows per pass
+// in row-major order; the first window holding a line decides, black before white inside it. Overlines count: they
+// contain a window's line. No line anywhere: 3 on a full board, else 0.
+__device__ __forceinline__ int check_win_board(const uint64_t (&black)[kBBWords], const uint64_t (&white)[kBBWords], int B, int k) {
+    const int lane = lane_id();
+    const int W = B - k + 1;
+    const int nw = W > 0 ? W * W : 0;
+    for (int base = 0; base < nw; base += 64) {
+        const int wi = base + lane;
+        const bool in = wi < nw;
+        const int wr = in ? wi / W : 0, wc = in ? wi % W : 0;
+        unsigned mb = 0u, mw = 0u;
+        for (int r = 0; r < k; ++r) {
+            const int off = (wr + r) * B + wc;
+            mb |= bb_bits(black, off, k) << (r * k);
+            mw |= bb_bits(white, off, k) << (r * k);
+        }
+        const bool hb = in && window_has_line(mb, k);
+        const bool hw = in && window_has_line(mw, k);
+        const uint64_t hit = __ballot(hb || hw), hitb = __ballot(hb);
+        if (hit) {
+            const int first = __ffsll(static_cast<long long>(hit)) - 1;
+            return ((hitb >> first) & 1ull) ? 1 : 2;
+        }
+    }
+    int stones = 0;
+#pragma unroll
+    for (int i = 0; i < kBBWords; ++i) stones += __popcll(black[i]) + __popcll(white[i]);
+    return stones == B * B ? 3 : 0;
+}
+
+// boards int8 [n][A] (+1 black, -1 white, anything else empty) -> win int32 [n]
+__global__ __launch_bounds__(64 * kPosPerWG) void k_check_win_boards(const int8_t* __restrict__ boards, int n, int B, int win_mark,
+                                                                     int32_t* __restrict__ win) {
+    const int i = blockIdx.x * kPosPerWG + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    if (i >= n) return;
+    const int lane = lane_id();
+    const int A = B * B;
+    uint64_t bb[2][kBBWords];
+#pragma unroll
+    for (int c = 0; c < kBBWords; ++c) {
+        const int cell = lane + 64 * c;
+        const int v = cell < A ? boards[static_cast<size_t>(i) * A + cell] : 0;
+        bb[0][c] = __ballot(v == 1);
+        bb[1][c] = __ballot(v == -1);
+    }
+    const int w = check_win_board(bb[0], bb[1], B, win_mark);
+    if (lane == 0) win[i] = w;
+}
+
+struct PositionsParams {
+    const int32_t* moves;   // [n][stride]: row i = root_id[1:] of position i
+    const int32_t* nmoves;  // [n]
+    int n, stride, B, A, C, win_mark;
+    int bad_as_empty;       // planes of a position with an error: 0 = zeros, 1 = the planes of the empty board (ao_positions_evaluate)
+    // outputs, any may be null
+    int32_t* status; int32_t* end_ply; int32_t* turn; int32_t* err;
+    int8_t* board;          // [n][A]
+    uint8_t* legal;         // [n][A]
+    float* planes;          // [n][C][A]
+};
+
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_positions_from_moves(PositionsParams q) {
+    const int i = blockIdx.x * kPosPerWG + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    if (i >= q.n) return;
+    const int lane = lane_id();
+    const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
+    const int32_t* mv = q.moves + static_cast<size_t>(i) * q.stride;
+    PosR s;
+    pos_clear(s);
+    int err = (nm < 0 || nm > q.A) ? PE_LENGTH : PE_OK;
+    int end_ply = -1;
+    // the moves 64 at a time, one per lane; each then comes out of a v_readlane (everything below is wave-uniform)
+    for (int base = 0; err == PE_OK && base < nm; base += 64) {
+        const int t_l = base + lane;
+        const int m_l = t_l < nm ? mv[t_l] : 0;
+        const int cnt = nm - base < 64 ? nm - base : 64;
+        for (int j = 0; j < cnt; ++j) {
+            const int m = read_lane(m_l, j);
+            if (m < 0 || m >= q.A) { err = PE_RANGE; break; }
+            if (pos_occupied(s, m)) { err = PE_OCCUPIED; break; }
+            pos_place(s, m);
+            // (every earlier position was not terminal, which is what the incremental test asks for)
+            if (end_ply < 0 && win_after_move(s, m, q.B, q.win_mark) != 0) end_ply = base + j;
+        }
+    }
+    if (err != PE_OK) pos_clear(s);
+    const bool ok = err == PE_OK;
+    const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
+    if (lane == 0) {
+        if (q.status) q.status[i] = status;
+        if (q.end_ply) q.end_ply[i] = ok ? end_ply : 0;
+        if (q.turn) q.turn[i] = ok ? (nm & 1) : 0;
+        if (q.err) q.err[i] = err;
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int cell = lane + 64 * c;
+        if (cell >= q.A) continue;
+        const int b0 = static_cast<int>((s.bb[0][c] >> lane) & 1ull), b1 = static_cast<int>((s.bb[1][c] >> lane) & 1ull);
+        if (q.board) q.board[static_cast<size_t>(i) * q.A + cell] = static_cast<int8_t>(b0 - b1);
+        if (q.legal) q.legal[static_cast<size_t>(i) * q.A + cell] = static_cast<uint8_t>(ok && !(b0 | b1));
+    }
+    if (q.planes) {
+        if (ok || q.bad_as_empty) {
+            TreeParams tp{};   // the encoder's view of the batch: row i of a plain NCHW plane batch
+            tp.C = q.C;
+            tp.A = q.A;
+            tp.batch_nchw = q.planes;
+            encode_planes<NCH>(tp, i, s, i);
+        } else {
+            float* out = q.planes + static_cast<size_t>(i) * q.C * q.A;
+            for (int idx = lane; idx < q.C * q.A; idx += 64) out[idx] = 0.f;
+        }
+    }
+}
+
+}  // namespace ao
+
+struct ao_positions {
+    int B = 0, A = 0, C = 0, win_mark = 0, cap = 0, device = 0;
+    hipStream_t stream = nullptr;
+    int32_t* d_moves = nullptr;    // [cap][A]
+    int32_t* d_n = nullptr;        // [cap]
+    int32_t* d_i32 = nullptr;      // [4][cap]: status, end_ply, turn, err
+    int8_t* d_board = nullptr;     // [cap][A] (boards in for check_win, boards out for from_moves)
+    uint8_t* d_legal = nullptr;    // [cap][A]
+    float* d_planes = nullptr;     // [cap][C][A]   -- the three below: allocated by the first ao_positions_evaluate
+    float* d_policy = nullptr;     // [cap][A]
+    float* d_value = nullptr;      // [cap]
+    std::vector<int32_t> h_moves, h_n;
+    std::string err;
+    int fail(const std::string& m) { err = m; return 1; }
+};
+
+static thread_local std::string g_positions_create_error;
+
+#define PS_HIP(p, call)                                                                        \
+    do {                                                                                       \
+        hipError_t st_ = (call);                                                               \
+        if (st_ != hipSuccess) return (p)->fail(std::string(#call) + ": " + hipGetErrorString(st_)); \
+    } while (0)
+
+namespace {
+
+void positions_free(ao_positions* p) {
+    for (void* d : {static_cast<void*>(p->d_moves), static_cast<void*>(p->d_n), static_cast<void*>(p->d_i32),
+                    static_cast<void*>(p->d_board), static_cast<void*>(p->d_legal), static_cast<void*>(p->d_planes),
+                    static_cast<void*>(p->d_policy), static_cast<void*>(p->d_value)})
+        if (d) hipFree(d);
+    if (p->stream) hipStreamDestroy(p->stream);
+}
+
+// positions [first, first + m) of the caller's move lists -> d_moves [m][A] / d_n [m] (lists the kernel refuses by their
+// length are uploaded empty: only the length is looked at)
+int stage_moves(ao_positions* p, const char* who, const int32_t* host_moves, int32_t stride, const int32_t* host_n, int64_t first, int m) {
+    const int A = p->A;
+    p->h_moves.assign(static_cast<size_t>(m) * A, 0);
+    p->h_n.resize(static_cast<size_t>(m));
+    for (int k = 0; k < m; ++k) {
+        const int32_t nm = host_n[first + k];
+        p->h_n[static_cast<size_t>(k)] = nm;
+        if (nm < 1 || nm > A) continue;
+        if (nm > stride) return p->fail(std::string(who) + ": position " + std::to_string(first + k) + " has more moves than `stride`");
+        std::memcpy(p->h_moves.data() + static_cast<size_t>(k) * A, host_moves + (first + k) * static_cast<int64_t>(stride), sizeof(int32_t) * nm);
+    }
+    PS_HIP(p, hipMemcpyAsync(p->d_moves, p->h_moves.data(), sizeof(int32_t) * m * A, hipMemcpyHostToDevice, p->stream));
+    PS_HIP(p, hipMemcpyAsync(p->d_n, p->h_n.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, p->stream));
+    return 0;
+}
+
+int launch_from_moves(ao_positions* p, int m, bool status, bool end_ply, bool turn, bool board, bool legal, float* planes, bool err,
+                      bool bad_as_empty) {
+    ao::PositionsParams q{};
+    q.moves = p->d_moves; q.nmoves = p->d_n;
+    q.n = m; q.stride = p->A; q.B = p->B; q.A = p->A; q.C = p->C; q.win_mark = p->win_mark;
+    q.bad_as_empty = bad_as_empty ? 1 : 0;
+    q.status = status ? p->d_i32 : nullptr;
+    q.end_ply = end_ply ? p->d_i32 + p->cap : nullptr;
+    q.turn = turn ? p->d_i32 + 2 * static_cast<size_t>(p->cap) : nullptr;
+    q.err = err ? p->d_i32 + 3 * static_cast<size_t>(p->cap) : nullptr;
+    q.board = board ? p->d_board : nullptr;
+    q.legal = legal ? p->d_legal : nullptr;
+    q.planes = planes;
+    const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
+    switch ((p->A + 63) / 64) {
+        case 1: hipLaunchKernelGGL(ao::k_positions_from_moves<1>, grid, block, 0, p->stream, q); break;
+        case 2: hipLaunchKernelGGL(ao::k_positions_from_moves<2>, grid, block, 0, p->stream, q); break;
+        case 3: hipLaunchKernelGGL(ao::k_positions_from_moves<3>, grid, block, 0, p->stream, q); break;
+        default: hipLaunchKernelGGL(ao::k_positions_from_moves<4>, grid, block, 0, p->stream, q); break;
+    }
+    PS_HIP(p, hipGetLastError());
+    return 0;
+}
+
+template <class T>
+int download(ao_positions* p, T* host, const T* dev, size_t count) {
+    if (host) PS_HIP(p, hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, p->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ao_positions_create(int board, int inplanes, int win_mark, int capacity, int device, ao_positions** out) {
+    *out = nullptr;
+    auto bad = [&](const char* m) { g_positions_create_error = m; return 1; };
+    if (board < 3 || board > ao::kMaxBoard) return bad("ao_positions_create: board must be in 3..15");
+    if (inplanes < 1 || inplanes > ao::kMaxPlanes) return bad("ao_positions_create: inplanes must be in 1..9 (the plane encoder keeps eight plies of history)");
+    if (win_mark < 3 || win_mark > 5 || win_mark > board) return bad("ao_positions_create: win_mark must be in 3..5 and at most the board size");
+    if (capacity < 1) return bad("ao_positions_create: capacity must be >= 1");
+    ao_positions* p = new ao_positions;
+    p->B = board; p->A = board * board; p->C = inplanes; p->win_mark = win_mark; p->cap = capacity; p->device = device;
+    const size_t cap = static_cast<size_t>(capacity), A = static_cast<size_t>(p->A);
+    hipError_t st = hipSetDevice(device);
+    if (st == hipSuccess) st = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    if (st == hipSuccess) st = hipMalloc(&p->d_moves, cap * A * sizeof(int32_t));
+    if (st == hipSuccess) st = hipMalloc(&p->d_n, cap * sizeof(int32_t));
+    if (st == hipSuccess) st = hipMalloc(&p->d_i32, 4 * cap * sizeof(int32_t));
+    if (st == hipSuccess) st = hipMalloc(&p->d_board, cap * A);
+    if (st == hipSuccess) st = hipMalloc(&p->d_legal, cap * A);
+    if (st != hipSuccess) {
+        g_positions_create_error = std::string("ao_positions_create: ") + hipGetErrorString(st);
+        positions_free(p);
+        delete p;
+        return 1;
+    }
+    *out = p;
+    return 0;
+}
+
+void ao_positions_destroy(ao_positions* p) {
+    if (!p) return;
+    hipSetDevice(p->device);
+    positions_free(p);
+    delete p;
+}
+
+const char* ao_positions_last_error(const ao_positions* p) { return p ? p->err.c_str() : g_positions_create_error.c_str(); }
+
+int ao_positions_check_win(ao_positions* p, const int8_t* host_boards, int32_t n, int32_t* host_win) {
+    if (n < 0) return p->fail("ao_positions_check_win: negative position count");
+    if (n == 0) return 0;
+    if (!host_boards || !host_win) return p->fail("ao_positions_check_win: null buffer");
+    PS_HIP(p, hipSetDevice(p->device));
+    const size_t A = static_cast<size_t>(p->A);
+    for (int64_t first = 0; first < n; first += p->cap) {
+        const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
+        PS_HIP(p, hipMemcpyAsync(p->d_board, host_boards + first * A, static_cast<size_t>(m) * A, hipMemcpyHostToDevice, p->stream));
+        hipLaunchKernelGGL(ao::k_check_win_boards, dim3(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)),
+                           dim3(64 * ao::kPosPerWG), 0, p->stream, p->d_board, m, p->B, p->win_mark, p->d_i32);
+        PS_HIP(p, hipGetLastError());
+        PS_HIP(p, hipMemcpyAsync(host_win + first, p->d_i32, sizeof(int32_t) * m, hipMemcpyDeviceToHost, p->stream));
+        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+    }
+    return 0;
+}
+
+int ao_positions_from_moves(ao_positions* p, const int32_t* host_moves, int32_t stride, const int32_t* host_n, int32_t n,
+                            int32_t* host_status, int32_t* host_end_ply, int32_t* host_turn, int8_t* host_board,
+                            uint8_t* host_legal, float* dev_planes_nchw, int32_t* host_err) {
+    if (n < 0 || stride < 0) return p->fail("ao_positions_from_moves: negative position count or stride");
+    if (n == 0) return 0;
+    if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_from_moves: null move buffer");
+    PS_HIP(p, hipSetDevice(p->device));
+    // the caller's plane buffer may be memory that work queued on another stream still uses (a caching allocator hands such out)
+    if (dev_planes_nchw) PS_HIP(p, hipDeviceSynchronize());
+    const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
+    for (int64_t first = 0; first < n; first += p->cap) {
+        const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
+        if (stage_moves(p, "ao_positions_from_moves", host_moves, stride, host_n, first, m)) return 1;
+        float* planes = dev_planes_nchw ? dev_planes_nchw + static_cast<size_t>(first) * p->C * A : nullptr;
+        if (launch_from_moves(p, m, host_status, host_end_ply, host_turn, host_board, host_legal, planes, host_err, false)) return 1;
+        if (download(p, host_status ? host_status + first : nullptr, p->d_i32, m) ||
+            download(p, host_end_ply ? host_end_ply + first : nullptr, p->d_i32 + cap, m) ||
+            download(p, host_turn ? host_turn + first : nullptr, p->d_i32 + 2 * cap, m) ||
+            download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m) ||
+            download(p, host_board ? host_board + first * A : nullptr, p->d_board, m * A) ||
+            download(p, host_legal ? host_legal + first * A : nullptr, p->d_legal, m * A))
+            return 1;
+        PS_HIP(p, hipStreamSynchronize(p->stream));   // the planes are complete for any stream; the staging buffers are reused
+    }
+    return 0;
+}
+
+int ao_positions_evaluate(ao_positions* p, ao_net* net, const int32_t* host_moves, int32_t stride, const int32_t* host_n,
+                          int32_t n, float* host_policy, float* host_value, int32_t* host_status, int32_t* host_err) {
+    if (n < 0 || stride < 0) return p->fail("ao_positions_evaluate: negative position count or stride");
+    if (!net) return p->fail("ao_positions_evaluate: null network");
+    std::string why;
+    if (ao::net_check(net, p->B, p->C, p->device, &why)) return p->fail("ao_positions_evaluate: " + why);
+    if (n == 0) return 0;
+    if (!host_n || (!host_moves && stride > 0) || !host_policy || !host_value) return p->fail("ao_positions_evaluate: null buffer");
+    PS_HIP(p, hipSetDevice(p->device));
+    PS_HIP(p, hipDeviceSynchronize());   // the network's workspace may still serve a forward queued on another stream
+    const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
+    if (!p->d_planes) PS_HIP(p, hipMalloc(&p->d_planes, cap * p->C * A * sizeof(float)));
+    if (!p->d_policy) PS_HIP(p, hipMalloc(&p->d_policy, cap * A * sizeof(float)));
+    if (!p->d_value) PS_HIP(p, hipMalloc(&p->d_value, cap * sizeof(float)));
+    std::vector<int32_t> err_chunk;
+    for (int64_t first = 0; first < n; first += p->cap) {
+        const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
+        if (stage_moves(p, "ao_positions_evaluate", host_moves, stride, host_n, first, m)) return 1;
+        // a position with an error is fed as the empty board: its row must not disturb the rest of the chunk
+        if (launch_from_moves(p, m, true, false, false, false, false, p->d_planes, true, true)) return 1;
+        if (ao_net_forward(net, p->d_planes, m, p->d_policy, p->d_value, p->stream))
+            return p->fail(std::string("ao_positions_evaluate: ") + ao_net_last_error(net));
+        err_chunk.resize(static_cast<size_t>(m));
+        if (download(p, host_policy + first * A, p->d_policy, m * A) || download(p, host_value + first, p->d_value, m) ||
+            download(p, host_status ? host_status + first : nullptr, p->d_i32, m) || download(p, err_chunk.data(), p->d_i32 + 3 * cap, m))
+            return 1;
+        PS_HIP(p, hipStreamSynchronize(p->stream));
+        for (int k = 0; k < m; ++k) {
+            if (err_chunk[static_cast<size_t>(k)] == 0) continue;
+            std::fill_n(host_policy + (first + k) * A, A, 0.f);
+            host_value[first + k] = 0.f;
+        }
+        if (host_err) std::memcpy(host_err + first, err_chunk.data(), sizeof(int32_t) * m);
+    }
+    return 0;
+}
+
+}  // extern "C"

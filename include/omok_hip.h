@@ -339,6 +339,49 @@ int  ao_ttt_set_rng_state(ao_ttt *r, int game, const uint32_t *mt624, int32_t po
 int  ao_ttt_search(ao_ttt *r, const int8_t *boards, const int32_t *turns, const uint8_t *active,
                    double *q, double *n, int32_t *action);
 
+/* ---- position batch ---- stateless questions about positions the caller names; no game, no tree. Replaces the
+ * per-position host calls around the search: utils.check_win (utils.py:30-59), utils.get_board / get_turn /
+ * legal_actions (utils.py:171-186, 22-27), utils.get_state_pt (utils.py:139-168) and ZeroAgent.get_pv
+ * (agents.py:252-260; the monitor of eval_main.py:243 calls it for every ply of every match). One wavefront per
+ * position; a call takes any n and works through it in chunks of `capacity` positions (one upload, one launch, one
+ * download per chunk) on the workspace's own stream, and returns with everything complete.
+ * board 3..15; win_mark 3..5 and <= board; inplanes 1..9: what ao_net_create accepts, as far as the plane encoder of the
+ * search reaches (eight plies of history); capacity >= 1. */
+typedef struct ao_positions ao_positions;   /* device workspace for up to `capacity` positions per launch */
+int  ao_positions_create(int board, int inplanes, int win_mark, int capacity, int device, ao_positions **out);
+void ao_positions_destroy(ao_positions *p);
+const char *ao_positions_last_error(const ao_positions *p);   /* p may be NULL: failed create */
+/* utils.check_win(board, win_mark) (utils.py:30-59) for n raw boards: host int8 [n][B][B], +1 black, -1 white, 0 empty
+ * (any other value counts as empty). The boards need not be reachable in play: the reference's scan is reproduced --
+ * win_mark x win_mark windows in row-major order, the first window with a complete row, column or diagonal decides,
+ * black before white inside it; no line: 3 on a full board, else 0. host_win int32 [n]. */
+int  ao_positions_check_win(ao_positions *p, const int8_t *host_boards, int32_t n, int32_t *host_win);
+/* Position i is the id (0, moves[i * stride], ..., moves[i * stride + n[i] - 1]): its moves are placed in order, black
+ * first. Outputs (any may be NULL):
+ *   host_status  int32 [n]        utils.check_win of the final board (utils.py:30-59); moves past a win are placed too
+ *   host_end_ply int32 [n]        index of the first move after which check_win is non-zero, -1 if there is none
+ *   host_turn    int32 [n]        utils.get_turn of the id (utils.py:182-186)
+ *   host_board   int8  [n][B][B]  utils.get_board (utils.py:171-179)
+ *   host_legal   uint8 [n][A]     1 on empty cells: utils.legal_actions as a mask (utils.py:22-27), not its set order
+ *   dev_planes_nchw float32 [n][C][B][B] on the device: utils.get_state_pt (utils.py:139-168), the layout Agent.model
+ *                                 expects (agents.py:175); the device is synchronised before it is written
+ *   host_err     int32 [n]        0 ok, 1 a move outside 0..A-1, 2 a move onto an occupied cell, 3 n[i] < 0 or n[i] > A
+ * A position with an error has every output of its own zeroed (end_ply included) and touches no other position; the
+ * call still returns 0. Non-zero: n[i] in 1..A exceeds stride, or a HIP error. */
+int  ao_positions_from_moves(ao_positions *p, const int32_t *host_moves, int32_t stride, const int32_t *host_n, int32_t n,
+                             int32_t *host_status, int32_t *host_end_ply, int32_t *host_turn, int8_t *host_board,
+                             uint8_t *host_legal, float *dev_planes_nchw, int32_t *host_err);
+/* ZeroAgent.get_pv (agents.py:252-260) for n positions: the planes are built on the device and every chunk runs ONE
+ * ao_net_forward on the workspace's stream, so the result is bit for bit what ao_net_forward gives for the same planes in
+ * the same batch. host_policy float32 [n][A]: the softmax over all A cells, nothing masked; host_value float32 [n].
+ * Terminal positions are evaluated like any other (agents.py:171-178); host_status (may be NULL) says which they are.
+ * A position with an error (host_err, may be NULL; codes as above) is fed as the empty board, so that its row cannot
+ * disturb the rest of its chunk, and gets a zero policy and a zero value. The network must be finalized and match in
+ * board, inplanes and device (as for ao_search); the device is synchronised first, the network's workspace is shared. */
+int  ao_positions_evaluate(ao_positions *p, ao_net *net, const int32_t *host_moves, int32_t stride, const int32_t *host_n,
+                           int32_t n, float *host_policy /*[n][A]*/, float *host_value /*[n]*/,
+                           int32_t *host_status, int32_t *host_err);
+
 #ifdef __cplusplus
 }
 #endif
