@@ -410,6 +410,27 @@ def _split_fp16_cases():
             both("boardh", "k_boardh<%d, 1>" % B, nb, B, batch, what="one board per workgroup")
     for nb, B, batch, mode in [(2, 10, 63, 0), (10, 11, 63, 0), (2, 13, 63, 0), (2, 15, 63, 0), (10, 15, 40, 0), (2, 13, 33, 6)]:
         both("layer16h_wide", "k_layer16h<%d>" % B, nb, B, batch, mode, what="column tiles of a wide board")
+    # the even board widths: every family is instantiated per width, and a row or column-tile seam that is wrong only at an
+    # even width shows on none of the cases above. 4 / 6 / 8 walk the batch-size ladder of the narrow boards, 12 / 14 the two
+    # kernels of the wide ones (ao_net_plan_kernel names these for 2 blocks of 128 planes)
+    first = len(out)
+    for B, ladder in [(4, [("conv_cells_h", "k_conv_cells_h<4, 8>", (5, 130)), ("row16hk", "k_row16hk<4>", (300,)),
+                           ("layer16hk4", "k_layer16hk<4, 4>", (1000,)), ("layer16h", "k_layer16h<4>", (2000,)),
+                           ("trunk16h_fmt0", "k_trunk16h<4, 4, 0>", (3073,))]),
+                      (6, [("conv_cells_h", "k_conv_cells_h<6, 8>", (65,)), ("row16hk", "k_row16hk<6>", (130,)),
+                           ("layer16hk4", "k_layer16hk<6, 4>", (1024,)), ("trunk16h_fmt0", "k_trunk16h<6, 4, 0>", (3073,))]),
+                      (8, [("conv_cells_h", "k_conv_cells_h<8, 8>", (40,)), ("row16hk", "k_row16hk<8>", (61, 300)),
+                           ("layer16hk4", "k_layer16hk<8, 4>", (1000,)), ("layer16h", "k_layer16h<8>", (2000,)),
+                           ("trunk16h_fmt0", "k_trunk16h<8, 4, 0>", (4096,))]),
+                      (12, [("conv_cells_h", "k_conv_cells_h<12, 8>", (5,)), ("layer16h_wide", "k_layer16h<12>", (63,)),
+                            ("boardh", "k_boardh<12, 1>", (64, 65, 130))]),
+                      (14, [("conv_cells_h", "k_conv_cells_h<14, 8>", (5,)), ("layer16h_wide", "k_layer16h<14>", (63,)),
+                            ("boardh", "k_boardh<14, 1>", (64, 65, 130))])]:
+        for family, kernel, batches in ladder:
+            for batch in batches:
+                both(family, kernel, 2, B, batch, env={"AO_TRUNK_FMT": "0"} if family == "trunk16h_fmt0" else None,
+                     what="even width %d" % B)
+    out[first:] = sorted(out[first:], key=lambda c: (c.B, c.grid))       # (stable: the cases of one network stay together)
     return out
 
 
@@ -422,6 +443,13 @@ def _fp32_cases():
         for mode, family, kernel in [(1, "conv3x3", "k_conv3x3<%d>" % B), (2, "trunk16", "k_trunk16<%d>" % B),
                                      (3, cells.split("<")[0][2:], cells), (4, "layer16", "k_layer16<%d>" % B)]:
             out.append(Case(family, kernel, nb, B, batch, mode, planes=planes, what="mode %d" % mode))
+    # ... and at two even widths (a wide board and a narrow one), as (2, 7, 128, 20) and (2, 15, 128, 40) do for 7 and 15
+    # (batches of 20 boards, but 21 on 8x8: the 20 boards batch_indices draws there have z of standard deviation 0.22, under
+    # the 0.3 that test_net_reference.py asks of a batch; likewise 61 boards for k_row16hk<8> above, where 63 give 0.297)
+    for B, batch in ((12, 20), (8, 21)):
+        for mode, family, kernel in [(1, "conv3x3", "k_conv3x3<%d>" % B), (2, "trunk16", "k_trunk16<%d>" % B),
+                                     (3, "conv_cells_h", "k_conv_cells_h<%d, 8>" % B), (4, "layer16", "k_layer16<%d>" % B)]:
+            out.append(Case(family, kernel, 2, B, batch, mode, what="mode %d, even width" % mode))
     # 160 .. 512 planes: the fp32-MFMA layer kernels whatever the mode; widths that are exported zero-padded (100 -> 128 runs
     # on the split-fp16 kernels, 200 -> 224 and 300 -> 320 on k_layer16)
     for nb, B, planes, batch in [(2, 9, 256, 40), (1, 7, 192, 700), (2, 15, 160, 70), (3, 9, 224, 1024), (1, 9, 512, 600), (2, 13, 384, 20),

@@ -540,7 +540,8 @@ def test_split_fp16_trunk_reports_activations_beyond_fp16_range(batch):
         en.close()
 
 
-@pytest.mark.parametrize("B,G,S,nb,C", [(9, 64, 24, 2, 5), (9, 3072, 12, 1, 5), (15, 40, 16, 2, 5), (9, 50, 20, 1, 7), (5, 80, 20, 1, 3)])
+@pytest.mark.parametrize("B,G,S,nb,C", [(9, 64, 24, 2, 5), (9, 3072, 12, 1, 5), (15, 40, 16, 2, 5), (9, 50, 20, 1, 7), (5, 80, 20, 1, 3),
+                                       (12, 40, 16, 1, 5), (13, 70, 12, 1, 5), (6, 80, 20, 1, 5)])
 def test_fused_search_on_bit_planes_equals_stepwise_on_float_planes(B, G, S, nb, C, weights="golden"):
     """ao_search hands the split-fp16 kernels the leaf planes as BITS (one byte per cell, written by the tree kernel;
     k_trunk16hb / k_layer16h<.., 2>), the stepwise protocol hands the same network fp32 NCHW planes through
@@ -632,7 +633,8 @@ def test_fused_search_packs_active_games_only(mode, planes, weights="golden"):
     net.close()
 
 
-@pytest.mark.parametrize("B,G,S,nb,C", [(9, 1, 64, 2, 5), (9, 5, 48, 2, 5), (15, 3, 24, 1, 5), (9, 40, 16, 1, 7), (5, 7, 20, 1, 3)])
+@pytest.mark.parametrize("B,G,S,nb,C", [(9, 1, 64, 2, 5), (9, 5, 48, 2, 5), (15, 3, 24, 1, 5), (9, 40, 16, 1, 7), (5, 7, 20, 1, 3),
+                                       (12, 3, 24, 1, 5), (13, 5, 16, 1, 5), (8, 7, 20, 1, 5)])
 def test_fused_per_game_step_equals_separate_launches(B, G, S, nb, C, monkeypatch, weights="golden"):
     """A few games on a 128-plane network: ao_search runs heads + expansion / backup / selection + the next leaf's conv1 as ONE
     launch per game (k_step_board, step_kernels.hip). The tree code is the same device code; conv1 is formulated differently
@@ -673,7 +675,8 @@ def test_fused_per_game_step_equals_separate_launches(B, G, S, nb, C, monkeypatc
     net.close()
 
 
-@pytest.mark.parametrize("B,G,S,nb,C", [(9, 64, 24, 2, 5), (9, 3072, 12, 1, 5), (15, 40, 16, 2, 5), (9, 50, 20, 1, 7), (5, 80, 20, 1, 3)])
+@pytest.mark.parametrize("B,G,S,nb,C", [(9, 64, 24, 2, 5), (9, 3072, 12, 1, 5), (15, 40, 16, 2, 5), (9, 50, 20, 1, 7), (5, 80, 20, 1, 3),
+                                       (12, 40, 16, 1, 5), (13, 70, 12, 1, 5), (6, 80, 20, 1, 5)])
 def test_fused_search_on_bit_planes_equals_stepwise_on_float_planes_conditioned_weights(B, G, S, nb, C):
     """The same equality on a network whose value head is live and whose policy is not one-hot: the bit-plane kernels
     (k_trunk16hb, k_layer16h<.., 2>) are tied to the float-plane kernels through values that move with the position."""
@@ -685,7 +688,8 @@ def test_fused_search_packs_active_games_only_conditioned_weights(mode, planes):
     test_fused_search_packs_active_games_only(mode, planes, weights="conditioned")
 
 
-@pytest.mark.parametrize("B,G,S,nb,C", [(9, 1, 64, 2, 5), (9, 5, 48, 2, 5), (15, 3, 24, 1, 5), (9, 40, 16, 1, 7), (5, 7, 20, 1, 3)])
+@pytest.mark.parametrize("B,G,S,nb,C", [(9, 1, 64, 2, 5), (9, 5, 48, 2, 5), (15, 3, 24, 1, 5), (9, 40, 16, 1, 7), (5, 7, 20, 1, 3),
+                                       (12, 3, 24, 1, 5), (13, 5, 16, 1, 5), (8, 7, 20, 1, 5)])
 def test_fused_per_game_step_equals_separate_launches_conditioned_weights(B, G, S, nb, C, monkeypatch):
     """The heads fused into the step kernel (k_step_board) against the separate head launch, with a value that depends on
     the board."""

@@ -223,6 +223,28 @@ def test_planes_board_turn_legal_gv3():
     assert checked == int(g["count"])
 
 
+@pytest.mark.parametrize("B", [12, 13])
+def test_planes_board_turn_legal_on_three_word_boards(B):
+    """12x12 and 13x13 (bitboards of three 64-cell words, which gv3 does not hold): planes / board / turn / legal of random
+    legal move lists whose lengths sit on the word seams (0, 1, 64, 65, 128, 129, A - 1) against the host's
+    utils.get_state_pt / get_board / get_turn, C = 5 and C = 7, exactly. Finished games are encoded like any other."""
+    from alpha_omok_amd import utils
+    A = B * B
+    rs = np.random.RandomState(40 + B)
+    ids = [(0,) + tuple(rs.permutation(A)[:n].tolist()) for n in (0, 1, 64, 65, 128, 129, A - 1) for _ in range(2)]
+    for C in (5, 7):
+        with _batch(B, inplanes=C, capacity=8) as pb:        # (two chunks)
+            got = pb.planes(ids).cpu().numpy()
+            d = pb.describe(ids)
+        assert got.dtype == np.float32 and got.shape == (len(ids), C, B, B) and (d["err"] == 0).all()
+        for k, nid in enumerate(ids):
+            np.testing.assert_array_equal(got[k], utils.get_state_pt(nid, B, C).astype(np.float32), err_msg="B=%d C=%d n=%d" % (B, C, len(nid) - 1))
+            board = utils.get_board(nid, B)
+            np.testing.assert_array_equal(d["board"][k], board.astype(np.int8))
+            assert int(d["turn"][k]) == int(utils.get_turn(nid))
+            np.testing.assert_array_equal(d["legal"][k].reshape(B, B), (board == 0).astype(np.uint8))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 5. errors are per position
 # ---------------------------------------------------------------------------------------------------------------------

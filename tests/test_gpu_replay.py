@@ -97,7 +97,7 @@ def test_extend_augmented_arrays_uploads_only_what_survives(board, cap, n):
 
 
 @pytest.mark.parametrize("board,C,cap,E", [(9, 17, 100000, 40), (15, 17, 5000, 12), (9, 5, 300, 30), (3, 5, 64, 6), (10, 3, 4096, 25),
-                                           (9, 1, 900, 7)])
+                                           (9, 1, 900, 7), (13, 5, 600, 8)])
 def test_states_built_on_the_device_from_move_lists(board, C, cap, E):
     """ao_replay_extend_moves (device-side sample emission): the planes a kernel builds from the episodes' moves == the planes
     of utils.get_state_pt (utils.py:139-168) uploaded through extend_augmented_arrays -- same ring contents, order and length,

@@ -33,7 +33,8 @@ def test_dropin_agents_reproduce_reference_under_numpy_seed():
 
 
 @pytest.mark.parametrize("mode,board,sims,games", [(0, 9, 120, 24), (1, 9, 120, 24), (0, 15, 40, 12), (1, 15, 40, 12),
-                                                   (0, 3, 300, 16), (1, 3, 300, 16), (0, 7, 64, 8), (1, 7, 64, 8)])
+                                                   (0, 3, 300, 16), (1, 3, 300, 16), (0, 7, 64, 8), (1, 7, 64, 8),
+                                                   (0, 12, 40, 8), (1, 13, 40, 8), (0, 6, 80, 12)])
 def test_many_games_match_oracle(oracle, mode, board, sims, games):
     """G concurrent searches from different positions with different seeds == G oracle searches: child visit
     counts / q, chosen move, stream position -- two consecutive moves per game."""
@@ -103,7 +104,7 @@ def test_tictactoe_uct_dropin_matches_reference_golden():
         np.testing.assert_array_equal(np.array(st[:624], np.uint32), g["c%d_mt" % ci])
 
 
-@pytest.mark.parametrize("board,sims,games", [(3, 1500, 64), (3, 200, 256), (5, 120, 16), (9, 60, 8)])
+@pytest.mark.parametrize("board,sims,games", [(3, 1500, 64), (3, 200, 256), (5, 120, 16), (9, 60, 8), (13, 40, 8)])
 def test_tictactoe_uct_many_boards_match_oracle(oracle, board, sims, games):
     from alpha_omok_amd.tictactoe import TttEngine
     rs = np.random.RandomState(board * 7 + sims)

@@ -28,15 +28,28 @@ def test_gv2_legal_order(oracle):
     assert nonasc > 50  # the CPython set-order quirk is exercised
 
 
+# stone counts at which CPython's set difference stops / resumes listing the free cells in ascending order, per board size
+# (measured with the live CPython set on random stone sets: first and last count with a non-ascending order)
+NONASC_RANGE = {3: (5, 7), 4: (12, 14), 5: (21, 23), 6: (18, 34), 7: (31, 47), 8: (46, 62), 9: (63, 79), 10: (82, 97), 11: (103, 119),
+                12: (68, 141), 13: (93, 167), 14: (120, 194), 15: (149, 223)}
+
+
 def test_legal_order_matches_live_cpython(oracle):
-    # Same property checked against this interpreter's own set implementation.
+    # Same property checked against this interpreter's own set implementation, on every board size: random stone counts,
+    # then every count of the board's non-ascending range (twice).
     rnd = random.Random(5)
-    for B in (3, 9, 15):
+    for B in range(3, 16):
         A = B * B
-        for _ in range(400):
-            mv = rnd.sample(range(A), rnd.randint(0, A - 1))
+        first, last = NONASC_RANGE[B]
+        assert 0 < first <= last < A
+        counts = [rnd.randint(0, A - 1) for _ in range(150)] + 2 * list(range(first, last + 1))
+        nonasc = 0
+        for ns in counts:
+            mv = rnd.sample(range(A), ns)
             ref = list({a for a in range(A)} - set(mv))
-            assert oracle.legal_actions(mv, B).tolist() == ref
+            assert oracle.legal_actions(mv, B).tolist() == ref, (B, ns)
+            nonasc += int(ref != sorted(ref))
+        assert nonasc >= 1, B
 
 
 def test_gv3_state_planes(oracle):
@@ -76,7 +89,7 @@ def test_gv4_numpy_rng(oracle):
 
 def test_pairwise_sum_matches_numpy(oracle):
     rng = np.random.RandomState(0)
-    for n in (9, 81, 225, 128, 129, 7):
+    for n in [B * B for B in range(3, 16)] + [128, 129, 7]:
         for _ in range(200):
             a = rng.rand(n) * (rng.rand(n) < 0.7)
             assert oracle.pairwise_sum(a) == np.sum(a)
@@ -135,6 +148,21 @@ def test_gv5_tree_parity_deep_roots_15x15(oracle):
         o = g["c%d_order" % ci][0]
         o = o[o >= 0].tolist()
         assert o != sorted(o) and int(g["c%d_root" % ci][0].shape[0]) >= 150
+
+
+def test_gv5_tree_parity_mid_sizes(oracle):
+    """6x6 root with 24 stones (32-slot table), 12x12 roots with 70 / 100 stones (128-slot table, three 64-cell chunks) and a
+    13x13 root with 95 stones: mid-game positions at which CPython's set difference no longer lists the free cells in
+    ascending order. Every root of the fixture lists its children in non-ascending order."""
+    g = load_golden("gv5_tree_stub_midsizes")
+    _check_tree_cases(oracle, g, lambda ci, mode: "stub%d" % mode)
+    meta = g["meta"].tolist()
+    assert [(m[0], int((g["c%d_root" % ci][0] >= 0).sum())) for ci, m in enumerate(meta)] == [(6, 24), (12, 70), (12, 100), (13, 95)]
+    for ci, m in enumerate(meta):
+        for t in range(m[7]):
+            o = g["c%d_order" % ci][t]
+            o = o[o >= 0].tolist()
+            assert o != sorted(o), (ci, t)
 
 
 def test_gv6_tree_parity_real_net_replay(oracle):

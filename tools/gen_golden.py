@@ -10,7 +10,7 @@ the .npz files.
 
 Fixture ids follow SURVEY.md section 8(c): GV1 check_win, GV2 legal_actions order, GV3 state
 planes / board / turn, GV4 numpy RNG stream, GV5 tree parity with the exact-arithmetic stub
-evaluator, GV6 tree parity with the real PVNet (evaluations recorded for replay), GV7 PVNet
+evaluator (gv5mid: its deep roots on 6x6 / 12x12 / 13x13), GV6 tree parity with the real PVNet (evaluations recorded for replay), GV7 PVNet
 forward, GV8 augment_dataset order, GV9 main.self_play memory order + z, GV10 one train step,
 GV11 rollout agents (PUCTAgent / UCTAgent.get_pi: one-hot, child visits / q, stream position),
 GV12 the 3x3 UCT search of 1_tictactoe_MCTS/mcts_vs.py under Python's `random` (BASELINE configs[0]),
@@ -332,6 +332,39 @@ def gv5():
         print("  gv5 deep 15x15 root,", n_stones, "stones ->", len(recs), "plies, win", win)
     out = _pack(cases)
     save("gv5_tree_stub_deeproot15", **out)
+
+
+def five_free_root(B, n_stones, rng):
+    """A root of `n_stones` stones on a BxB board without a five: both colours drawn from the five-free colouring of the
+    15x15 deep roots (runs of two along rows, alternating along columns), black first, the moves interleaved."""
+    full = np.array([[1 if ((c // 2) + r) % 2 == 0 else -1 for c in range(B)] for r in range(B)], np.int64)
+    assert ref_utils.check_win(full.astype(float), 5) in (0, 3), "the colouring holds a five"
+    black = [r * B + c for r in range(B) for c in range(B) if full[r, c] == 1]
+    white = [r * B + c for r in range(B) for c in range(B) if full[r, c] == -1]
+    bsel = rng.permutation(black)[:(n_stones + 1) // 2].tolist()
+    wsel = rng.permutation(white)[:n_stones // 2].tolist()
+    nid = (0,) + tuple(x for pair in zip(bsel, wsel) for x in pair) + tuple(bsel[len(wsel):])
+    assert len(nid) == n_stones + 1 and ref_utils.check_win(ref_utils.get_board(nid, B), 5) == 0
+    return nid
+
+
+def gv5mid():
+    """Deep roots on the board sizes whose CPython set difference leaves ascending order in mid-game: 6x6 (32-slot table, 24
+    stones), 12x12 (128-slot table, 70 and 100 stones: NCH = 3) and 13x13 (95 stones). Record layout of gv5_tree_stub_deeproot15."""
+    rng = np.random.RandomState(612)
+    cases = []
+    for k, (B, n_stones) in enumerate(((6, 24), (12, 70), (12, 100), (13, 95))):
+        for tries in range(200):
+            nid = five_free_root(B, n_stones, rng)
+            legal = ref_utils.legal_actions(nid, B)
+            if legal != sorted(legal):
+                break
+        else:
+            raise AssertionError("no non-ascending child order at %d stones on %dx%d" % (n_stones, B, B))
+        recs, win = _play(B, 40, k % 3, 300 + k, 2, start=nid)
+        cases.append(((B, 40, k % 3, 300 + k, 2, 6, 1), recs, win))
+        print("  gv5 mid-size root, %dx%d," % (B, B), n_stones, "stones ->", len(recs), "plies, win", win)
+    save("gv5_tree_stub_midsizes", **_pack(cases))
 
 
 def gv6():
@@ -720,7 +753,7 @@ def gv14():
 
 
 ALL = dict(gv14=gv14, gv13=gv13, gv12=gv12, gv11=gv11, gv1=gv1, gv2=gv2, gv3=gv3, gv4=gv4, gv5=gv5, gv6=gv6, gv7=gv7, gv8=gv8, gv9=gv9,
-           gv10=gv10)
+           gv10=gv10, gv5mid=gv5mid)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(ALL)
