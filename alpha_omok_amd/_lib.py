@@ -12,6 +12,7 @@ if os.environ.get("AO_LIB_TAG"):   # developer switch: an experiment build made 
     LIB_PATH = os.path.join(HERE, "libomok_hip_%s.so" % os.environ["AO_LIB_TAG"])
 
 AO_ROOT_FRESH, AO_ROOT_UNEXPANDED, AO_ROOT_EXPANDED = 0, 1, 2
+AO_NODE_ABSENT, AO_NODE_LEAF, AO_NODE_TERMINAL, AO_NODE_EXPANDED = 0, 1, 2, 3
 
 
 class AoConfig(C.Structure):
@@ -64,6 +65,10 @@ SYMBOLS = {
     "ao_get_moves": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
     "ao_get_root_children": (C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "ao_tree_nodes": (C.c_int, [_vp, C.c_int, _i64p, _i64p]),
+    "ao_tree_lookup": (C.c_int, [_vp, _i32p, _i32p, C.c_int32, _i32p, C.c_int32, _i32p, _f64p, _i32p, _i32p, _i32p, _P(C.c_float),
+                                 _P(C.c_float), _f64p]),
+    "ao_tree_pv": (C.c_int, [_vp, _u8p, C.c_int32, _i32p, _i32p, _P(C.c_float), _i32p]),
+    "ao_tree_stats": (C.c_int, [_vp, _u8p, _i32p]),
     "ao_tree_timing": (C.c_int, [_vp, C.c_int, _f64p, _i64p]),
     "ao_trim_stats": (C.c_int, [_vp, _i64p, _i64p]),
     "ao_node_cap": (C.c_int, [_vp, _i32p, _i32p]),

@@ -18,7 +18,7 @@ import time
 import numpy as np
 
 from .evaluator import Evaluator
-from .engine import AO_ROOT_FRESH, Engine, EngineError  # noqa: F401
+from .engine import AO_NODE_ABSENT, AO_ROOT_FRESH, Engine, EngineError  # noqa: F401
 
 PRINT_MCTS = True
 
@@ -46,7 +46,10 @@ class Agent(object):
 
 
 class _TreeView(object):
-    """Stands in for the reference's `self.tree` dict where callers only take len() / clear()."""
+    """Stands in for the reference's `self.tree` dict: len() / clear(), and the read idiom `tree[node_id]` /
+    `node_id in tree` (agents.py:52,206-210), answered from the device tree by Engine.tree_lookup. A node's entry is
+    {'child': actions in stored order, 'n': float, 'w' / 'q': np.float32, 'p': np.float64}; the root has no parent edge in
+    the engine, so its 'w' / 'q' / 'p' are NaN."""
 
     def __init__(self, agent):
         self._agent = agent
@@ -57,6 +60,28 @@ class _TreeView(object):
 
     def __bool__(self):
         return len(self) > 0
+
+    def _lookup(self, node_id):
+        eng = self._agent._engine
+        if eng is None or not isinstance(node_id, (tuple, list)) or len(node_id) < 1 or node_id[0] != 0:
+            return None
+        try:
+            ids = [tuple(int(a) for a in node_id)]
+        except (TypeError, ValueError):
+            return None
+        r = eng.tree_lookup(ids, games=[0])
+        return None if r["status"][0] == AO_NODE_ABSENT else r
+
+    def __contains__(self, node_id):
+        return self._lookup(node_id) is not None
+
+    def __getitem__(self, node_id):
+        r = self._lookup(node_id)
+        if r is None:
+            raise KeyError(node_id)
+        k = int(r["nchild"][0])
+        return {'child': r["child_action"][0, :k].tolist(), 'n': float(r["n"][0]), 'w': np.float32(r["w"][0]),
+                'q': np.float32(r["q"][0]), 'p': np.float64(r["p"][0])}
 
     def clear(self):
         if self._agent._engine is not None:
@@ -126,6 +151,19 @@ class ZeroAgent(Agent):
         expanded, entries = (0, 0) if self._engine is None else self._engine.tree_nodes(0)
         print('tree size:', entries)
         print('tree depth:', 0 if expanded == 0 else '>= 1')
+
+    def principal_variation(self, max_len=None):
+        """(actions, n, q) along the most-visited line from the current root (Engine.principal_variations): int32 actions,
+        int32 visit counts and the float32 q of each edge; empty before the first search."""
+        if self._engine is None:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32)
+        r = self._engine.principal_variations(max_len)
+        k = int(r["len"][0])
+        return r["action"][0, :k].copy(), r["n"][0, :k].copy(), r["q"][0, :k].copy()
+
+    def tree_depth(self):
+        """The number del_parents prints as `tree depth` in the reference (agents.py:241-250), from the device tree."""
+        return 0 if self._engine is None else int(self._engine.tree_stats()["depth"][0])
 
     def get_pv(self, root_id):
         import torch

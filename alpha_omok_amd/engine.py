@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import AO_ROOT_EXPANDED, AO_ROOT_FRESH, AO_ROOT_UNEXPANDED  # noqa: F401
+from ._lib import AO_NODE_ABSENT, AO_NODE_EXPANDED, AO_NODE_LEAF, AO_NODE_TERMINAL  # noqa: F401
 
 
 class EngineError(RuntimeError):
@@ -315,6 +316,53 @@ class Engine:
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._L.ao_tree_nodes(self._h, game, C.byref(a), C.byref(b)), "ao_tree_nodes")
         return a.value, b.value
+
+    # -- tree read-out on the device
+    def tree_lookup(self, ids, games=None):
+        """The reference's `self.tree[node_id]` for many ids in one call (ao_tree_lookup). ids: full reference ids
+        (0, a1, a2, ...); games: the game each id is asked of (None: id i belongs to game i). Returns a dict of numpy arrays:
+        status int32 [n] (AO_NODE_ABSENT / LEAF / TERMINAL / EXPANDED), the node's own n float64, w / q float32, p float64 [n]
+        (NaN where the engine has no parent edge: see include/omok_hip.h), nchild int32 [n], and the children in stored order:
+        child_action int32 [n, A] (-1 in unused slots), child_n int32, child_w / child_q float32, child_p float64 [n, A] (0 there)."""
+        ids = [list(i)[1:] for i in ids]
+        n, A = len(ids), self.A
+        g = np.arange(n, dtype=np.int32) if games is None else np.ascontiguousarray(games, np.int32).reshape(-1)
+        if g.size != n:
+            raise ValueError("tree_lookup: one game per id")
+        m = np.array([len(i) for i in ids], np.int32)
+        stride = max(1, int(m.max()) if n else 1)
+        mv = np.zeros((n, stride), np.int32)
+        for k, i in enumerate(ids):
+            mv[k, :len(i)] = i
+        status, nchild = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        nwqp = np.full((n, 4), np.nan)
+        ca, cn = np.full((n, A), -1, np.int32), np.zeros((n, A), np.int32)
+        cw, cq, cp = np.zeros((n, A), np.float32), np.zeros((n, A), np.float32), np.zeros((n, A), np.float64)
+        self._check(self._L.ao_tree_lookup(self._h, _ptr(g, C.c_int32), _ptr(mv, C.c_int32), stride, _ptr(m, C.c_int32), n,
+                                           _ptr(status, C.c_int32), _ptr(nwqp, C.c_double), _ptr(nchild, C.c_int32),
+                                           _ptr(ca, C.c_int32), _ptr(cn, C.c_int32), _ptr(cw, C.c_float), _ptr(cq, C.c_float),
+                                           _ptr(cp, C.c_double)), "ao_tree_lookup")
+        return dict(status=status, n=nwqp[:, 0].copy(), w=nwqp[:, 1].astype(np.float32), q=nwqp[:, 2].astype(np.float32),
+                    p=nwqp[:, 3].copy(), nchild=nchild, child_action=ca, child_n=cn, child_w=cw, child_q=cq, child_p=cp)
+
+    def principal_variations(self, max_len=None, mask=None):
+        """The most-visited line from every masked game's root, first maximum in stored order (ao_tree_pv). Returns a dict:
+        action int32 [G, max_len] (-1 beyond the line), n int32 and q float32 [G, max_len] (0 there), len int32 [G]."""
+        L = self.A if max_len is None else int(max_len)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        act = np.full((self.G, L), -1, np.int32)
+        n, q, ln = np.zeros((self.G, L), np.int32), np.zeros((self.G, L), np.float32), np.zeros(self.G, np.int32)
+        self._check(self._L.ao_tree_pv(self._h, _ptr(mk, C.c_uint8), L, _ptr(act, C.c_int32), _ptr(n, C.c_int32),
+                                       _ptr(q, C.c_float), _ptr(ln, C.c_int32)), "ao_tree_pv")
+        return dict(action=act, n=n, q=q, len=ln)
+
+    def tree_stats(self, mask=None):
+        """Per masked game (ao_tree_stats): expanded nodes the root reaches, dict entries, tree depth (del_parents' print,
+        agents.py:241-250) and nodes_used (arena records in use, dead ones included). int32 [G] each, -1 for unmasked games."""
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        out = np.full((self.G, 4), -1, np.int32)
+        self._check(self._L.ao_tree_stats(self._h, _ptr(mk, C.c_uint8), _ptr(out, C.c_int32)), "ao_tree_stats")
+        return dict(expanded=out[:, 0].copy(), entries=out[:, 1].copy(), depth=out[:, 2].copy(), nodes_used=out[:, 3].copy())
 
     def tree_timing(self, enable=True):
         """(total ms, launches) of the TIMED per-simulation tree kernel launches (k_expand_select) since the last call;

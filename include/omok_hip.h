@@ -132,6 +132,45 @@ int ao_get_moves(ao_engine *e, int game, int32_t *host_moves /*[A]*/, int32_t *n
 int ao_get_root_children(ao_engine *e, int game, int32_t *host_action, double *host_n,
                          double *host_w, double *host_q, double *host_p, int32_t *count);
 int ao_tree_nodes(ao_engine *e, int game, int64_t *expanded, int64_t *dict_entries);
+
+/* ---- tree read-out on the device ---- the reference's `self.tree` is a public dict (agents.py:52); these three read the
+ * trees where they live, for many games in one launch, and download O(result) bytes. All three are read-only: the search
+ * that follows is bit for bit the search that would have run without them. All three fail, with nothing touched, between
+ * ao_begin_move and ao_end_move and on a game index out of range. Each: one upload, one launch, one download and one
+ * synchronisation (ao_tree_lookup: per chunk of 1024 queries). */
+enum { AO_NODE_ABSENT = 0,     /* not a key of the kept subtree: off the tree, an occupied or off-board move, an id that does
+                                  not extend the game's root, any id of a fresh game                                    */
+       AO_NODE_LEAF = 1,       /* a key with n == 0: the entry agents.py:206-210 made when its parent was expanded      */
+       AO_NODE_TERMINAL = 2,   /* a visited key whose position ends the game (never expanded, agents.py:216-221)        */
+       AO_NODE_EXPANDED = 3 }; /* a key with children                                                                   */
+/* self.tree[node_id] (agents.py:52,206-210) for n ids. Query i asks game games[i] for the FULL id
+ * (0, moves[i * stride], ..., moves[i * stride + m[i] - 1]); an id that does not extend the game's root id is ABSENT, not an
+ * error. Host outputs, any may be NULL; A = board * board:
+ *   status       int32   [n]     AO_NODE_*
+ *   node_nwqp    float64 [n][4]  the node's own n, w, q, p (w and q are float32 values, n an integer). The engine keeps them
+ *                                on the PARENT's edge and the root has none: an expanded root gets n = 1 + the sum of its
+ *                                children's n (exact: the simulation that expands a node visits no child) and NaN for w, q, p;
+ *                                a root that is known but not expanded (AO_ROOT_UNEXPANDED) is a LEAF with four NaN; ABSENT: NaN
+ *   nchild       int32   [n]     len(tree[id]['child']); 0 unless EXPANDED
+ *   child_action int32   [n][A]  tree[id]['child'] in stored order; -1 in unused slots
+ *   child_n      int32   [n][A]  tree[id + (a,)]['n'] in the same order; child_w / child_q float32, child_p float64; 0 in
+ *                                unused slots */
+int ao_tree_lookup(ao_engine *e, const int32_t *host_games, const int32_t *host_moves, int32_t stride, const int32_t *host_m,
+                   int32_t n, int32_t *status, double *node_nwqp, int32_t *nchild, int32_t *child_action, int32_t *child_n,
+                   float *child_w, float *child_q, double *child_p);
+/* The principal variation of every game with mask[g] != 0 (NULL = all): from the root, the edge with the most visits -- the
+ * arg-max of the visit vector agents.py:67-69 builds, applied again at the child --, the lowest stored index on a tie. The
+ * line ends when the best n is 0, behind an edge whose child is not expanded, or after max_len (1..A) plies. Host outputs, any
+ * may be NULL: action int32 [G][max_len], n int32 [G][max_len], q float32 [G][max_len] (the stored q of the edge), len int32
+ * [G]. Entries beyond len[g] and the rows of unmasked games are left as they are. */
+int ao_tree_pv(ao_engine *e, const uint8_t *host_mask, int32_t max_len, int32_t *action, int32_t *n, float *q, int32_t *len);
+/* del_parents' prints (agents.py:241-250) for every game with mask[g] != 0 (NULL = all), from a breadth-first walk on the
+ * device: out int32 [G][4] = { expanded nodes the root reaches, dict entries (1 + the sum of their child counts: the numbers
+ * of ao_tree_nodes), tree depth (the longest key of the kept subtree minus one: the largest ply + (nchild > 0) over the
+ * reachable expanded nodes; the root's ply if the root is only known; 0 without a tree), nodes_used (records the arena
+ * holds: what exceeds the first number is dead until the next compaction) }. Rows of unmasked games are left as they are. */
+int ao_tree_stats(ao_engine *e, const uint8_t *host_mask, int32_t *out);
+
 /* HIP-event timing of the per-simulation tree kernel of ao_search (k_expand_select: expansion + backup of one
  * simulation, selection + terminal test + plane encoding of the next -- agents.py:134-239 for every game), recorded
  * on the engine's launch stream. Returns the total and the number of TIMED launches since the previous call and
