@@ -13,6 +13,8 @@ if os.environ.get("AO_LIB_TAG"):   # developer switch: an experiment build made 
 
 AO_ROOT_FRESH, AO_ROOT_UNEXPANDED, AO_ROOT_EXPANDED = 0, 1, 2
 AO_NODE_ABSENT, AO_NODE_LEAF, AO_NODE_TERMINAL, AO_NODE_EXPANDED = 0, 1, 2, 3
+AO_SNAP_HDR = 8
+CH_UNVISITED, CH_TERMINAL = -1, -2   # child codes of a snapshot edge
 
 
 class AoConfig(C.Structure):
@@ -20,6 +22,17 @@ class AoConfig(C.Structure):
                 ("inplanes", C.c_int32), ("games", C.c_int32), ("noise", C.c_int32),
                 ("node_cap", C.c_int32), ("device", C.c_int32), ("c_puct", C.c_double),
                 ("alpha", C.c_double), ("arena_fraction", C.c_double)]
+
+
+class AoTreeSnapshot(C.Structure):
+    """ao_tree_snapshot of include/omok_hip.h: header fields + pointers to caller-owned host arrays."""
+    _fields_ = [("board", C.c_int32), ("inplanes", C.c_int32), ("win_mark", C.c_int32), ("sims", C.c_int32),
+                ("noise", C.c_int32), ("games", C.c_int32), ("c_puct", C.c_double), ("nodes", C.c_int64),
+                ("edges", C.c_int64), ("hdr", C.POINTER(C.c_int32)), ("gauss", C.POINTER(C.c_double)),
+                ("mt", C.POINTER(C.c_uint32)), ("moves", C.POINTER(C.c_int32)), ("nchild", C.POINTER(C.c_int32)),
+                ("parent", C.POINTER(C.c_int32)), ("parent_edge", C.POINTER(C.c_int32)), ("act", C.POINTER(C.c_uint8)),
+                ("n", C.POINTER(C.c_int32)), ("w", C.POINTER(C.c_float)), ("q", C.POINTER(C.c_float)),
+                ("p", C.POINTER(C.c_double)), ("child", C.POINTER(C.c_int32))]
 
 
 class AoRolloutConfig(C.Structure):
@@ -69,6 +82,9 @@ SYMBOLS = {
                                  _P(C.c_float), _f64p]),
     "ao_tree_pv": (C.c_int, [_vp, _u8p, C.c_int32, _i32p, _i32p, _P(C.c_float), _i32p]),
     "ao_tree_stats": (C.c_int, [_vp, _u8p, _i32p]),
+    "ao_tree_export": (C.c_int, [_vp, _u8p, _P(AoTreeSnapshot)]),
+    "ao_tree_import": (C.c_int, [_vp, _i32p, C.c_int32, _P(AoTreeSnapshot)]),
+    "ao_tree_snapshot_check": (C.c_int, [_P(AoTreeSnapshot)]),
     "ao_tree_timing": (C.c_int, [_vp, C.c_int, _f64p, _i64p]),
     "ao_trim_stats": (C.c_int, [_vp, _i64p, _i64p]),
     "ao_node_cap": (C.c_int, [_vp, _i32p, _i32p]),

@@ -161,6 +161,22 @@ class ZeroAgent(Agent):
         k = int(r["len"][0])
         return r["action"][0, :k].copy(), r["n"][0, :k].copy(), r["q"][0, :k].copy()
 
+    def save_tree(self, path):
+        """Puts the searched position aside: the tree below the current root, its id and the numpy stream position the last
+        get_pi left, as a TreeSnapshot file (Engine.export_trees)."""
+        self._eng().export_trees().save(path)
+
+    def load_tree(self, path):
+        """Takes up what save_tree wrote: tree[...], principal_variation() and the next get_pi answer as the saved agent's
+        would. The process-global numpy stream is left alone (get_pi hands it to the engine, as always)."""
+        from .snapshot import TreeSnapshot
+        snap = TreeSnapshot.load(path)
+        if snap.games != 1:
+            raise ValueError("load_tree: the file holds %d games, a ZeroAgent has one" % snap.games)
+        self._eng().import_trees(snap)
+        self.root_id = (0,) + tuple(self._engine.get_moves(0))
+        self.is_real_root = int(snap.hdr[0, 3]) == AO_ROOT_FRESH
+
     def tree_depth(self):
         """The number del_parents prints as `tree depth` in the reference (agents.py:241-250), from the device tree."""
         return 0 if self._engine is None else int(self._engine.tree_stats()["depth"][0])

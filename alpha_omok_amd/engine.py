@@ -364,6 +364,37 @@ class Engine:
         self._check(self._L.ao_tree_stats(self._h, _ptr(mk, C.c_uint8), _ptr(out, C.c_int32)), "ao_tree_stats")
         return dict(expanded=out[:, 0].copy(), entries=out[:, 1].copy(), depth=out[:, 2].copy(), nodes_used=out[:, 3].copy())
 
+    # -- tree snapshots
+    def export_trees(self, mask=None):
+        """The trees and streams of the masked games (None: all) as a TreeSnapshot, games in ascending order (ao_tree_export).
+        Read-only on the engine; fails inside a move."""
+        from .snapshot import TreeSnapshot
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        st = self.tree_stats(mk)                       # sizes every array before the pack launch
+        sel = np.arange(self.G) if mk is None else np.flatnonzero(mk)
+        ng = int(sel.size)
+        N = int(st["expanded"][sel].sum())
+        E = int((st["entries"][sel] - 1)[st["expanded"][sel] > 0].sum())
+        snap = TreeSnapshot(self.board_size, self.inplanes, 0, hdr=np.zeros((ng, _lib.AO_SNAP_HDR), np.int32),
+                            gauss=np.zeros(ng), mt=np.zeros((ng, 624), np.uint32), moves=np.zeros((ng, self.A), np.int32),
+                            nchild=np.zeros(N, np.int32), parent=np.zeros(N, np.int32), parent_edge=np.zeros(N, np.int32),
+                            act=np.zeros(E, np.uint8), n=np.zeros(E, np.int32), w=np.zeros(E, np.float32),
+                            q=np.zeros(E, np.float32), p=np.zeros(E, np.float64), child=np.zeros(E, np.int32))
+        s = snap._struct()
+        self._check(self._L.ao_tree_export(self._h, _ptr(mk, C.c_uint8), C.byref(s)), "ao_tree_export")
+        assert (s.games, s.nodes, s.edges) == (ng, N, E)
+        snap.win_mark, snap.sims, snap.noise, snap.c_puct = s.win_mark, s.sims, s.noise, s.c_puct
+        return snap
+
+    def import_trees(self, snapshot, games=None):
+        """Snapshot game i goes into slot games[i] (None: slot i), tree, stream, moves and root status; other games are
+        untouched (ao_tree_import). The snapshot may come from another slot, engine, `games`, node_cap or num_mcts; board,
+        inplanes and win_mark must match. Raises EngineError, with every game left as it was, on a damaged snapshot, a game
+        with more nodes than node_cap - num_mcts - 1, a bad game index, or inside a move. `play` must follow a search."""
+        g = np.arange(snapshot.games, dtype=np.int32) if games is None else np.ascontiguousarray(games, np.int32).reshape(-1)
+        s = snapshot._struct()
+        self._check(self._L.ao_tree_import(self._h, _ptr(g, C.c_int32), int(g.size), C.byref(s)), "ao_tree_import")
+
     def tree_timing(self, enable=True):
         """(total ms, launches) of the TIMED per-simulation tree kernel launches (k_expand_select) since the last call;
         enable = n > 1 times every n-th launch only."""

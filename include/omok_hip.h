@@ -171,6 +171,63 @@ int ao_tree_pv(ao_engine *e, const uint8_t *host_mask, int32_t max_len, int32_t 
  * holds: what exceeds the first number is dead until the next compaction) }. Rows of unmasked games are left as they are. */
 int ao_tree_stats(ao_engine *e, const uint8_t *host_mask, int32_t *out);
 
+/* ---- tree snapshots ---- the reference's `self.tree` lives as long as its process and can be pickled like any dict
+ * (agents.py:52); these move the engine's trees and streams out of an engine and back in. A snapshot is host data without
+ * device pointers: what the root of each game reaches, breadth first with the root as node 0 (the numbering of a re-rooting),
+ * the game's move list, root status and MT19937 stream. Positions are not stored: a node's position is its parent's plus one
+ * move, and the import rebuilds it. A search resumed from a snapshot is bit for bit the search that never stopped. Per-move
+ * buffers (the Dirichlet draw, pi / visit / policy) are not part of a snapshot: it captures trees and streams, not a move in
+ * progress, and ao_play must follow a search on the importing engine as on a fresh one.
+ * All arrays are caller-owned host memory. Games are stored one after the other: game i owns hdr[i][0] nodes and hdr[i][1]
+ * edges, behind those of the games before it; a node's first edge follows from the running sum of nchild over its game. A
+ * game packs to exactly 25 * edges + 12 * nodes bytes behind its fixed-size header row. */
+enum { AO_SNAP_HDR = 8 };
+typedef struct ao_tree_snapshot {
+    int32_t board, inplanes, win_mark;   /* of the exporting engine; the importing engine must have the same              */
+    int32_t sims, noise;                 /* of the exporting engine: information only                                      */
+    int32_t games;                       /* games in the snapshot                                                          */
+    double  c_puct;                      /* information only                                                               */
+    int64_t nodes, edges;                /* lengths of the node / edge arrays. ao_tree_export reads them as the capacity of
+                                            the caller's arrays and writes back what it used                              */
+    int32_t  *hdr;          /* [games][8] nodes, edges, number of moves, AO_ROOT_* status, over (win index of a finished
+                               game, else 0), MT19937 pos, has_gauss, 0                                                   */
+    double   *gauss;        /* [games]      cached gaussian of the numpy-legacy stream                                    */
+    uint32_t *mt;           /* [games][624] MT19937 state                                                                 */
+    int32_t  *moves;        /* [games][A]   the root id without its leading 0 (ao_get_moves)                              */
+    int32_t  *nchild;       /* [nodes]      edges of the node: 1 .. A - ply                                               */
+    int32_t  *parent;       /* [nodes]      the node's parent, as a node number inside its game; -1 for the root          */
+    int32_t  *parent_edge;  /* [nodes]      stored index of the edge of `parent` that leads here; -1 for the root         */
+    uint8_t  *act;          /* [edges]      action of the edge, in stored child order; no padding                         */
+    int32_t  *n;            /* [edges]                                                                                    */
+    float    *w, *q;        /* [edges]                                                                                    */
+    double   *p;            /* [edges]                                                                                    */
+    int32_t  *child;        /* [edges]      the child's node number inside its game, -1 unvisited, -2 terminal            */
+} ao_tree_snapshot;
+/* Packs the games with mask[g] != 0 (NULL = all), in ascending game order, into the caller's arrays (size them with
+ * ao_tree_stats: nodes = expanded, edges = dict entries - 1). One stats pass over the masked games, then one pack launch and
+ * one download per chunk of games. The device workspace is the read-out workspace, grown on demand: a chunk is closed when
+ * its packed games reach 64 MiB, so the workspace is bounded by 64 MiB plus one game's packed size (plus 16 bytes per game),
+ * whatever node_cap is; nothing transferred scales with node_cap. Read-only on the trees: the search that follows is bit for
+ * bit the search without the export. Fails, with nothing touched, between ao_begin_move and ao_end_move, when a capacity is
+ * too small, and when the breadth-first queue of a node_cap arena does not fit the LDS of a workgroup (as ao_tree_stats). */
+int ao_tree_export(ao_engine *e, const uint8_t *host_mask, ao_tree_snapshot *out);
+/* Imports snapshot game i into slot host_games[i], i < n = snap->games (other games are untouched): node i becomes record i
+ * of the game's current arena, the positions are rebuilt level by level, the stream, the move list, the root status and the
+ * root position are restored. The destination may be another slot, another engine, or an engine with other `games`,
+ * node_cap or sims; board, inplanes and win_mark must be the snapshot's. Refused with every game left as it was: a call
+ * between ao_begin_move and ao_end_move, a game index out of range or listed twice, a snapshot that fails
+ * ao_tree_snapshot_check (checked before anything is uploaded), and a game with more nodes than node_cap - sims - 1 (the
+ * next move's expansions must fit; nothing is trimmed silently). An action that lands on an occupied cell when the positions
+ * are rebuilt resets that game and fails the call; the other games of the call are imported. Trim and search counters keep
+ * the importing engine's values. One upload and one launch per chunk of games (chunks as in ao_tree_export). */
+int ao_tree_import(ao_engine *e, const int32_t *host_games, int32_t n, const ao_tree_snapshot *snap);
+/* Consistency of a snapshot; needs no engine and no device. Per game: the sizes and running sums agree; 1 <= nchild <= A - ply;
+ * actions are < A and distinct within a node; n >= 0, and >= 1 on an edge with an expanded or terminal child; w, q, p are
+ * finite; every child is -1, -2 or a later node number; every node but the root is named by exactly one edge, the one its
+ * parent / parent_edge name; child numbers increase in scan order (breadth first); 0 <= pos <= 624; moves are < A and
+ * distinct. Non-zero on the first violation; ao_last_error(NULL) describes it. */
+int ao_tree_snapshot_check(const ao_tree_snapshot *snap);
+
 /* HIP-event timing of the per-simulation tree kernel of ao_search (k_expand_select: expansion + backup of one
  * simulation, selection + terminal test + plane encoding of the next -- agents.py:134-239 for every game), recorded
  * on the engine's launch stream. Returns the total and the number of TIMED launches since the previous call and
