@@ -35,6 +35,14 @@ class AoTreeSnapshot(C.Structure):
                 ("p", C.POINTER(C.c_double)), ("child", C.POINTER(C.c_int32))]
 
 
+class AoReplaySnapshot(C.Structure):
+    """ao_replay_snapshot of include/omok_hip.h: header fields + pointers to caller-owned host arrays."""
+    _fields_ = [("board", C.c_int32), ("inplanes", C.c_int32), ("format", C.c_int32), ("words", C.c_int32),
+                ("entries", C.c_int64), ("pi_values", C.c_int64), ("raw_entries", C.c_int64),
+                ("kind", C.POINTER(C.c_uint8)), ("z", C.POINTER(C.c_float)), ("bits", C.POINTER(C.c_uint64)),
+                ("pi_mask", C.POINTER(C.c_uint64)), ("pi_val", C.POINTER(C.c_double)), ("raw", C.POINTER(C.c_float))]
+
+
 class AoRolloutConfig(C.Structure):
     _fields_ = [("board", C.c_int32), ("win_mark", C.c_int32), ("sims", C.c_int32), ("games", C.c_int32),
                 ("mode", C.c_int32), ("device", C.c_int32), ("c_puct", C.c_double)]
@@ -120,6 +128,10 @@ SYMBOLS = {
                                          C.c_int64, C.c_int, C.c_int64, _vp]),
     "ao_replay_gather": (C.c_int, [_vp, _i64p, C.c_int64, _vp, _vp, _vp, _vp]),
     "ao_replay_read": (C.c_int, [_vp, C.c_int64, C.c_int64, _f64p, _f64p, _f64p]),
+    "ao_replay_export_size": (C.c_int, [_vp, C.c_int64, C.c_int64, _i64p, _i64p]),
+    "ao_replay_export": (C.c_int, [_vp, C.c_int64, C.c_int64, _P(AoReplaySnapshot), C.c_int64, _vp]),
+    "ao_replay_import": (C.c_int, [_vp, _P(AoReplaySnapshot), C.c_int64, _vp]),
+    "ao_replay_snapshot_check": (C.c_int, [_P(AoReplaySnapshot)]),
     "ao_rollout_create": (C.c_int, [_P(AoRolloutConfig), _P(_vp)]),
     "ao_rollout_destroy": (None, [_vp]),
     "ao_rollout_last_error": (C.c_char_p, [_vp]),

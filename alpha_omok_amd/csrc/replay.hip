@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/omok_hip.h"
+#include "replay_ring.hpp"
 
 namespace ao {
 
@@ -125,29 +125,6 @@ __global__ void k_replay_gather(const float* __restrict__ s_ring, const double* 
 }
 
 }  // namespace ao
-
-struct ao_replay {
-    int B = 0, C = 0, A = 0, device = 0;
-    int64_t cap = 0, head = 0, count = 0;  // deque index i lives in slot (head + i) % cap
-    float* s_ring = nullptr;
-    double* pi_ring = nullptr;
-    float* z_ring = nullptr;
-    // staging (grow-only)
-    float* st_s = nullptr; double* st_pi = nullptr; float* st_z = nullptr; long* st_idx = nullptr;
-    int64_t st_n = 0, st_m = 0;
-    short* st_mv = nullptr; int* st_ep = nullptr; int* st_ply = nullptr;   // moves-based extend: episodes' moves, (episode, ply) per sample
-    int64_t st_mv_n = 0, st_ep_n = 0;
-    std::string err;
-    int fail(const std::string& m) { err = m; return 1; }
-};
-
-static thread_local std::string g_replay_create_error;
-
-#define RP_HIP(r, call)                                                                        \
-    do {                                                                                       \
-        hipError_t st_ = (call);                                                               \
-        if (st_ != hipSuccess) return (r)->fail(std::string(#call) + ": " + hipGetErrorString(st_)); \
-    } while (0)
 
 extern "C" {
 

@@ -944,6 +944,41 @@ def save_dataset(memory, n_iter, step_, directory='data', datetime_now=None):
     return path
 
 
+def save_replay(path):
+    """rep_memory as a replay snapshot (replay.ReplaySnapshot: planes as bits, pi as mask + values, lossless) in an
+    uncompressed .npz at exactly `path` -- rank-local naming is the caller's business. A DeviceReplay is packed on the
+    device, a deque by the same packing in numpy. Entries only: not cur_memory, the optimiser or the iteration counters.
+    save_dataset (the reference's pickle, main.py:345-348) stays as it is."""
+    train_join()
+    from .replay import ReplaySnapshot
+    if hasattr(rep_memory, "export_snapshot"):
+        snap = rep_memory.export_snapshot()
+    else:
+        entries = list(rep_memory)
+        snap = ReplaySnapshot.from_arrays(np.array([e[0] for e in entries], np.float32).reshape(-1, IN_PLANES, BOARD_SIZE, BOARD_SIZE),
+                                          np.array([e[1] for e in entries], np.float64).reshape(-1, BOARD_SIZE ** 2),
+                                          np.array([e[2] for e in entries], np.float32), BOARD_SIZE, IN_PLANES)
+    snap.save(path)
+    return path
+
+
+def load_replay(path):
+    """Clears rep_memory and fills it from what save_replay wrote: deque.extend semantics, the newest MEMORY_SIZE entries
+    survive. A deque gets the reference's (state float64 [C, B, B], pi float64 [A], z) tuples."""
+    train_join()
+    from .replay import ReplayError, ReplaySnapshot
+    snap = ReplaySnapshot.load(path)
+    if (snap.board, snap.inplanes) != (BOARD_SIZE, IN_PLANES):
+        raise ReplayError("%s holds board %d, inplanes %d; the memory has board %d, inplanes %d"
+                          % (path, snap.board, snap.inplanes, BOARD_SIZE, IN_PLANES))
+    rep_memory.clear()
+    if hasattr(rep_memory, "import_snapshot"):
+        rep_memory.import_snapshot(snap)
+    else:
+        s, pi, z = snap.to_arrays()
+        rep_memory.extend((s[i], pi[i], float(z[i])) for i in range(len(snap)))
+
+
 def load_data(model_path, dataset_path):
     """Tolerant load like the reference: state.update(torch.load(path)); iteration / step come from
     the file NAME ({yymmdd}_{iter}_{step}_step_model.pickle)."""

@@ -384,6 +384,52 @@ int  ao_replay_gather(ao_replay *r, const int64_t *idx, int64_t m, float *dev_st
  * main.save_dataset pickles. */
 int  ao_replay_read(ao_replay *r, int64_t first, int64_t n, double *states, double *pi, double *z);
 
+/* ---- replay snapshots ---- the reference keeps its memory by pickling the deque (main.save_dataset, main.py:345-348) and
+ * rebuilds the deque from the pickle (main.load_data, main.py:351-365); these move the ring, or a range of it, out
+ * of HBM and back in, packed and unpacked by kernels on the ring itself, bit for bit. A snapshot is host data without device
+ * pointers and holds entries only -- (state, pi, z) in deque order, oldest first. The engine's planes are 0/1, so a plane
+ * packs to one bit per cell; pi is exact float64 but sparse, so it packs to a cell mask and its non-zero values. An entry is
+ * kind 0 only when every plane value has the bit pattern of +0.0f or 1.0f; anything else (-0.0f, 0.5f, the arbitrary floats
+ * ao_replay_extend accepts) makes it kind 1, whose planes are kept raw. A packed entry is 5 + 8 * W * (C + 1) + 8 * nnz bytes
+ * (W = words, nnz its non-zero pi cells), plus 4 * C * A for kind 1. The form is canonical: one ring content has exactly
+ * one snapshot. All arrays are caller-owned host memory. */
+typedef struct ao_replay_snapshot {
+    int32_t board, inplanes;          /* of the exporting memory; the importing memory must have the same                  */
+    int32_t format, words;            /* format = 1; words = W = (board * board + 63) / 64                                 */
+    int64_t entries;                  /* ao_replay_export reads it as the capacity of the per-entry arrays, writes n back  */
+    int64_t pi_values, raw_entries;   /* lengths of pi_val / raw (raw counted in entries). ao_replay_export reads them as the
+                                         capacity of the caller's arrays and writes back what it used                      */
+    uint8_t  *kind;     /* [entries]        0 = planes as bits, 1 = planes raw                                             */
+    float    *z;        /* [entries]        the stored float32, bits preserved                                             */
+    uint64_t *bits;     /* [entries][C][W]  bit (c % 64) of word c / 64 is set when the plane's cell c holds exactly 1.0f;
+                                            all zero for kind 1                                                            */
+    uint64_t *pi_mask;  /* [entries][W]     bit set when the 64-bit PATTERN of pi[c] is non-zero (-0.0 and NaN are values)   */
+    double   *pi_val;   /* [pi_values]      the non-zero patterns, ascending cell order, entry after entry; an entry owns
+                                            popcount(its mask) of them                                                     */
+    float    *raw;      /* [raw_entries][C][A]  the planes of the kind-1 entries, in entry order                           */
+} ao_replay_snapshot;
+/* The count pass of an export over deque entries [first, first + n): what pi_val and raw must hold. Synchronises like
+ * ao_replay_read; read-only on the ring. */
+int  ao_replay_export_size(ao_replay *r, int64_t first, int64_t n, int64_t *pi_values, int64_t *raw_entries);
+/* Packs deque entries [first, first + n) on the device into the caller's arrays and downloads only packed bytes. A count pass
+ * sizes the variable-length parts; a chunk of entries is closed when its packed size reaches chunk_bytes (0 = 64 MiB, at most
+ * 1 GiB), so the device workspace is bounded by chunk_bytes plus one entry (plus 13 bytes per entry of a chunk), whatever the
+ * capacity of the ring. Read-only on the ring; sees everything queued before it (synchronises like ao_replay_read) and returns
+ * with the arrays complete; `stream` carries its launches and copies. Fails with nothing written when the range is outside
+ * the memory or a capacity (entries, pi_values, raw_entries) is too small. */
+int  ao_replay_export(ao_replay *r, int64_t first, int64_t n, ao_replay_snapshot *snap, int64_t chunk_bytes, void *stream);
+/* deque.extend(entries of the snapshot) -- on a cleared memory, main.load_data's deque(pickle.load(f), maxlen) (main.py:365): appended in order behind what the ring holds, only the newest `capacity`
+ * survive; entries of the snapshot that cannot survive are neither uploaded nor unpacked. The destination may have any
+ * capacity and any fill. Every byte of every slot it claims is written. Refused with the ring untouched when board or
+ * inplanes differ or when the snapshot fails ao_replay_snapshot_check (checked before anything is uploaded). Chunks as in
+ * ao_replay_export. */
+int  ao_replay_import(ao_replay *r, const ao_replay_snapshot *snap, int64_t chunk_bytes, void *stream);
+/* Holds a snapshot to the canonical form; needs no memory and no device. board 3..15, inplanes 1..32, format 1, words as
+ * derived from the board; no mask or plane bit at or above cell A; kind is 0 or 1; bits is zero on kind-1 rows; pi_values
+ * equals the sum of the mask popcounts; raw_entries equals the number of kind-1 entries; no all-zero pattern in pi_val.
+ * Non-zero on the first violation; ao_replay_last_error(NULL) describes it. */
+int  ao_replay_snapshot_check(const ao_replay_snapshot *snap);
+
 /* ---- rollout agents ---- replace PUCTAgent.get_pi (agents.py:263-441) and UCTAgent.get_pi
  * (agents.py:443-614): net-free searches with random playouts. One handle owns G independent
  * games, each with its own numpy-legacy MT19937 stream; a search runs entirely in one kernel. */

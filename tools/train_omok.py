@@ -72,6 +72,10 @@ def main():
                          "plain fp32 state_dict the reference loads")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--resume", default=None, help="state_dict to start from")
+    ap.add_argument("--save-replay", default=None, metavar="PATH",
+                    help="write the replay memory as a snapshot (main.save_replay: packed on the device, lossless) with every kept "
+                         "checkpoint and at the end, always to this path")
+    ap.add_argument("--resume-replay", default=None, metavar="PATH", help="replay snapshot to start from (main.load_replay)")
     a = ap.parse_args()
 
     import torch
@@ -97,6 +101,8 @@ def main():
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
+    if a.resume_replay:
+        m.load_replay(a.resume_replay)
     dev = m.device
     base = PVNet(a.blocks, m.IN_PLANES, a.planes, a.board).to(dev)
     base.load_state_dict(m.Agent.model.state_dict())
@@ -208,10 +214,14 @@ def main():
             path = os.path.join(a.out, "ckpt_%d.pt" % it)
             torch.save(m.Agent.model.state_dict(), path)
             kept.append(path)
+            if a.save_replay:
+                m.save_replay(a.save_replay)
             while len(kept) > a.max_ckpts:                # thin out: drop the second-oldest, keep the spread
                 os.remove(kept.pop(1 if len(kept) > 2 else 0))
     m.train_join()
     torch.save(m.Agent.model.state_dict(), os.path.join(a.out, "final.pt"))
+    if a.save_replay:
+        m.save_replay(a.save_replay)
     emit(dict(kind="done", iters=it, games_total=games_total, moves_total=moves_total))
 
 
