@@ -152,6 +152,8 @@ SYMBOLS = {
     "ao_positions_check_win": (C.c_int, [_vp, _i8p, C.c_int32, _i32p]),
     "ao_positions_from_moves": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _i32p, _i32p, _i32p, _i8p, _u8p, _vp, _i32p]),
     "ao_positions_evaluate": (C.c_int, [_vp, _vp, _i32p, C.c_int32, _i32p, C.c_int32, _P(C.c_float), _P(C.c_float), _i32p, _i32p]),
+    "ao_positions_win_cells": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _u8p, _u8p, _i32p, _i32p, _i32p]),
+    "ao_positions_audit": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _u8p, _i32p, _i32p]),
 }
 
 _lib = None

@@ -196,15 +196,28 @@ class ZeroAgent(Agent):
                 p, v = self.model(x.to(Evaluator._model_device(self.model)))
         return p.detach().cpu().numpy()[0], v.detach().cpu().numpy()[0]
 
+    def _position_batch(self):
+        from .positions import PositionBatch
+        if self._positions is None:
+            self._positions = PositionBatch(self.board_size, self.inplanes, self.win_mark, device=self._device)
+        return self._positions
+
+    def get_win_cells(self, root_id):
+        """The cells that win at once in the position of `root_id` (PositionBatch.win_cells): (mine, theirs), bool [B, B]
+        -- where the side to move completes a line, and where its opponent would: the cells to show as "must block
+        here" beside get_pv. Both are empty on a finished game. ValueError for an id that is not a legal move list."""
+        d = self._position_batch().win_cells([root_id])
+        if d["err"][0]:
+            raise ValueError("root_id %r is not a legal move list (err %d)" % (root_id, int(d["err"][0])))
+        B = self.board_size
+        return d["mine"][0].reshape(B, B).astype(bool), d["theirs"][0].reshape(B, B).astype(bool)
+
     def get_pv_batch(self, root_ids):
         """get_pv for many ids in one call (PositionBatch.evaluate): (policy float32 [n, A], value float32 [n],
         status int32 [n] -- utils.check_win of each position, terminal ones are evaluated too --, err int32 [n]). The planes
         are built on the device; a PVNet-shaped model runs on the native forward, any other model is called once on the
         whole plane batch. Ids with err != 0 (a move off the board or onto a stone) get zeros."""
-        from .positions import PositionBatch
-        if self._positions is None:
-            self._positions = PositionBatch(self.board_size, self.inplanes, self.win_mark, device=self._device)
-        pb = self._positions
+        pb = self._position_batch()
         net = self._evaluator.native_net(self.model, self.board_size, self.inplanes)
         if net is not None:
             return pb.evaluate(net, root_ids)

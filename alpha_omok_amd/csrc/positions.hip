@@ -11,6 +11,8 @@
 //                           (check_win of the final board, and of every prefix through the incremental win_after_move of
 //                           the tree kernels) + utils.py:139-168 (get_state_pt, encode_planes of the tree kernels)
 //   ao_positions_evaluate   agents.py:171-178 for n positions at once: planes on the device, then the ordinary forward
+//   k_win_cells, k_audit_games  no counterpart: the cells that win at once and the per-ply tactical flags of game records,
+//                           defined through utils.py:30-59 (check_win of the board with one more stone)
 //
 // The bitboards, pos_place, pos_occupied, win_after_move and encode_planes are the tree kernels' own (tree_device.hpp): a
 // position described here is the position the search would hold.
@@ -27,6 +29,7 @@ namespace ao {
 int net_check(const ao_net* n, int board, int inplanes, int device, std::string* why);   // net.hip
 
 constexpr int kPosPerWG = 4;
+constexpr int kMaxWinMark = 5;   // ao_positions_create: win_mark 3..5
 
 // per-position error codes (ao_positions_from_moves)
 enum : int32_t { PE_OK = 0, PE_RANGE = 1, PE_OCCUPIED = 2, PE_LENGTH = 3 };
@@ -108,6 +111,32 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_check_win_boards(const int8_
     if (lane == 0) win[i] = w;
 }
 
+// The position of the id (0, mv[0], ..., mv[nm - 1]) into `s`, wave-uniform (all 64 lanes call): the moves are placed in
+// order, black first, moves past a win too. Returns the id's error code; `s` is then the empty board. end_ply: index of
+// the first move after which check_win is non-zero, -1 if there is none.
+__device__ __forceinline__ int replay_moves(PosR& s, const int32_t* __restrict__ mv, int nm, int A, int B, int win_mark, int& end_ply) {
+    const int lane = lane_id();
+    pos_clear(s);
+    int err = (nm < 0 || nm > A) ? PE_LENGTH : PE_OK;
+    end_ply = -1;
+    // the moves 64 at a time, one per lane; each then comes out of a v_readlane (everything below is wave-uniform)
+    for (int base = 0; err == PE_OK && base < nm; base += 64) {
+        const int t_l = base + lane;
+        const int m_l = t_l < nm ? mv[t_l] : 0;
+        const int cnt = nm - base < 64 ? nm - base : 64;
+        for (int j = 0; j < cnt; ++j) {
+            const int m = read_lane(m_l, j);
+            if (m < 0 || m >= A) { err = PE_RANGE; break; }
+            if (pos_occupied(s, m)) { err = PE_OCCUPIED; break; }
+            pos_place(s, m);
+            // (every earlier position was not terminal, which is what the incremental test asks for)
+            if (end_ply < 0 && win_after_move(s, m, B, win_mark) != 0) end_ply = base + j;
+        }
+    }
+    if (err != PE_OK) pos_clear(s);
+    return err;
+}
+
 struct PositionsParams {
     const int32_t* moves;   // [n][stride]: row i = root_id[1:] of position i
     const int32_t* nmoves;  // [n]
@@ -126,26 +155,9 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_positions_from_moves(Positio
     if (i >= q.n) return;
     const int lane = lane_id();
     const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
-    const int32_t* mv = q.moves + static_cast<size_t>(i) * q.stride;
     PosR s;
-    pos_clear(s);
-    int err = (nm < 0 || nm > q.A) ? PE_LENGTH : PE_OK;
-    int end_ply = -1;
-    // the moves 64 at a time, one per lane; each then comes out of a v_readlane (everything below is wave-uniform)
-    for (int base = 0; err == PE_OK && base < nm; base += 64) {
-        const int t_l = base + lane;
-        const int m_l = t_l < nm ? mv[t_l] : 0;
-        const int cnt = nm - base < 64 ? nm - base : 64;
-        for (int j = 0; j < cnt; ++j) {
-            const int m = read_lane(m_l, j);
-            if (m < 0 || m >= q.A) { err = PE_RANGE; break; }
-            if (pos_occupied(s, m)) { err = PE_OCCUPIED; break; }
-            pos_place(s, m);
-            // (every earlier position was not terminal, which is what the incremental test asks for)
-            if (end_ply < 0 && win_after_move(s, m, q.B, q.win_mark) != 0) end_ply = base + j;
-        }
-    }
-    if (err != PE_OK) pos_clear(s);
+    int end_ply;
+    const int err = replay_moves(s, q.moves + static_cast<size_t>(i) * q.stride, nm, q.A, q.B, q.win_mark, end_ply);
     const bool ok = err == PE_OK;
     const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
     if (lane == 0) {
@@ -176,6 +188,176 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_positions_from_moves(Positio
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// tactical cells: which empty cells win at once. No reference counterpart; the definition is utils.check_win
+// (utils.py:30-59) of the board with one more stone -- see ao_positions_win_cells in omok_hip.h.
+// ---------------------------------------------------------------------------------------------------------------------
+// flag bits of one audited ply (ao_positions_audit)
+enum : int { TF_WIN_AVAILABLE = 1, TF_WIN_TAKEN = 2, TF_THREAT = 4, TF_BLOCKED = 8, TF_LOST = 16 };
+
+// The empty cells on which a stone of `colour` (0 black / 1 white) completes a line of win_mark or more, as 64-cell mask
+// words (wave-uniform; all 64 lanes call). Lane = cell, NCH passes. In each direction the lane counts the colour's
+// contiguous stones on either side of its cell, up to win_mark - 1 a side, every probed cell checked by ROW and COLUMN (a
+// run that reaches column B-1 does not go on at column 0 of the next row); 1 + left + right >= win_mark wins, overlines
+// included. On a position without a line that is check_win == colour + 1 after the stone: only a line through the new
+// stone can be new, and it is the colour's. The ballot of the predicate is the mask word.
+template <int NCH>
+__device__ __forceinline__ void winning_cells(const PosR& s, int colour, int B, int A, int win_mark, uint64_t (&out)[kBBWords]) {
+    const int lane = lane_id();
+    // the colour's stones by a mask blend and by value (see win_after_move_by and pick4)
+    const uint64_t mk = 0ull - static_cast<uint64_t>(colour & 1);
+    const uint64_t a0 = (s.bb[0][0] & ~mk) | (s.bb[1][0] & mk), a1 = (s.bb[0][1] & ~mk) | (s.bb[1][1] & mk);
+    const uint64_t a2 = (s.bb[0][2] & ~mk) | (s.bb[1][2] & mk), a3 = (s.bb[0][3] & ~mk) | (s.bb[1][3] & mk);
+#pragma unroll
+    for (int c = 0; c < kBBWords; ++c) {
+        if (c >= NCH) { out[c] = 0ull; continue; }
+        const int cell = lane + 64 * c;
+        const bool empty = cell < A && !(((s.bb[0][c] | s.bb[1][c]) >> lane) & 1ull);
+        const int r = cell / B, col = cell % B;
+        bool win = false;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const int dr = (d == 0) ? 0 : 1;
+            const int dc = (d == 0) ? 1 : (d == 1) ? 0 : (d == 2) ? 1 : -1;
+            int run = 1;
+#pragma unroll
+            for (int side = -1; side <= 1; side += 2) {
+                bool on = empty;
+#pragma unroll
+                for (int t = 1; t < kMaxWinMark; ++t) {
+                    const int rr = r + side * t * dr, cc = col + side * t * dc;
+                    const bool in = t < win_mark && rr >= 0 && rr < B && cc >= 0 && cc < B;
+                    const int cl = in ? rr * B + cc : 0;                       // 0 .. A-1 < 64 * kBBWords
+                    on = on && in && ((pick4(a0, a1, a2, a3, cl >> 6) >> (cl & 63)) & 1ull);
+                    run += on ? 1 : 0;
+                }
+            }
+            win = win || run >= win_mark;
+        }
+        out[c] = __ballot(empty && win);
+    }
+}
+
+__device__ __forceinline__ int popcount4(const uint64_t (&m)[kBBWords]) {
+    return __popcll(m[0]) + __popcll(m[1]) + __popcll(m[2]) + __popcll(m[3]);
+}
+
+struct TacticsParams {
+    const int32_t* moves;   // [n][stride]
+    const int32_t* nmoves;  // [n]
+    int n, stride, B, A, win_mark;
+    // outputs, any may be null
+    uint8_t* mine; uint8_t* theirs;                 // [n][A]   (k_win_cells)
+    int32_t* status; int32_t* turn; int32_t* err;   // [n]      (err: both kernels)
+    uint8_t* flags;                                 // [n][A]   (k_audit_games)
+    int32_t* counts;                                // [n][8]
+};
+
+// the winning cells of the side to move and of its opponent in the position of id i
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_win_cells(TacticsParams q) {
+    const int i = blockIdx.x * kPosPerWG + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    if (i >= q.n) return;
+    const int lane = lane_id();
+    const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
+    PosR s;
+    int end_ply;
+    const int err = replay_moves(s, q.moves + static_cast<size_t>(i) * q.stride, nm, q.A, q.B, q.win_mark, end_ply);
+    const bool ok = err == PE_OK;
+    const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
+    const bool open = ok && status == 0;          // a terminal position has no winning cells, for anyone
+    const int turn = ok ? (nm & 1) : 0;
+    uint64_t mine[kBBWords], theirs[kBBWords];
+    winning_cells<NCH>(s, turn, q.B, q.A, q.win_mark, mine);
+    winning_cells<NCH>(s, turn ^ 1, q.B, q.A, q.win_mark, theirs);
+    if (lane == 0) {
+        if (q.status) q.status[i] = status;
+        if (q.turn) q.turn[i] = turn;
+        if (q.err) q.err[i] = err;
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int cell = lane + 64 * c;
+        if (cell >= q.A) continue;
+        if (q.mine) q.mine[static_cast<size_t>(i) * q.A + cell] = static_cast<uint8_t>(open && ((mine[c] >> lane) & 1ull));
+        if (q.theirs) q.theirs[static_cast<size_t>(i) * q.A + cell] = static_cast<uint8_t>(open && ((theirs[c] >> lane) & 1ull));
+    }
+}
+
+// the tactical audit of game record i: one flag byte per ply and eight counters
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_audit_games(TacticsParams q) {
+    const int i = blockIdx.x * kPosPerWG + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    if (i >= q.n) return;
+    const int lane = lane_id();
+    const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
+    const int32_t* mv = q.moves + static_cast<size_t>(i) * q.stride;
+    PosR s;
+    pos_clear(s);
+    int err = (nm < 0 || nm > q.A) ? PE_LENGTH : PE_OK;
+    int end_ply = -1;
+    int fl[kBBWords] = {0, 0, 0, 0};   // lane l of fl[c]: the flag byte of ply l + 64 c
+    int n_win = 0, n_missed = 0, n_single = 0, n_unblocked = 0, n_lost = 0;
+    for (int base = 0; err == PE_OK && base < nm; base += 64) {
+        const int t_l = base + lane;
+        const int m_l = t_l < nm ? mv[t_l] : 0;
+        const int cnt = nm - base < 64 ? nm - base : 64;
+        for (int j = 0; j < cnt; ++j) {
+            const int m = read_lane(m_l, j);
+            if (m < 0 || m >= q.A) { err = PE_RANGE; break; }
+            if (pos_occupied(s, m)) { err = PE_OCCUPIED; break; }
+            if (end_ply < 0) {             // the position before this move is not terminal: audit the move
+                const int t = base + j;
+                uint64_t mine[kBBWords], theirs[kBBWords];
+                winning_cells<NCH>(s, t & 1, q.B, q.A, q.win_mark, mine);
+                winning_cells<NCH>(s, (t & 1) ^ 1, q.B, q.A, q.win_mark, theirs);
+                const int n_mine = popcount4(mine), n_theirs = popcount4(theirs);
+                const bool in_mine = (pick4(mine[0], mine[1], mine[2], mine[3], m >> 6) >> (m & 63)) & 1ull;
+                const bool in_theirs = (pick4(theirs[0], theirs[1], theirs[2], theirs[3], m >> 6) >> (m & 63)) & 1ull;
+                int f = 0;
+                if (n_mine > 0) {
+                    f = TF_WIN_AVAILABLE | (in_mine ? TF_WIN_TAKEN : 0);
+                    n_win += 1;
+                    n_missed += in_mine ? 0 : 1;
+                } else if (n_theirs > 0) {
+                    f = TF_THREAT | (in_theirs ? TF_BLOCKED : 0) | (n_theirs >= 2 ? TF_LOST : 0);
+                    n_single += n_theirs >= 2 ? 0 : 1;
+                    n_unblocked += (n_theirs >= 2 || in_theirs) ? 0 : 1;
+                    n_lost += n_theirs >= 2 ? 1 : 0;
+                }
+#pragma unroll
+                for (int c = 0; c < kBBWords; ++c) fl[c] = (c == (t >> 6) && lane == (t & 63)) ? f : fl[c];
+            }
+            pos_place(s, m);
+            if (end_ply < 0 && win_after_move(s, m, q.B, q.win_mark) != 0) end_ply = base + j;
+        }
+    }
+    if (err != PE_OK) pos_clear(s);
+    const bool ok = err == PE_OK;
+    const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
+    if (lane == 0) {
+        if (q.err) q.err[i] = err;
+        if (q.counts) {
+            int32_t* cn = q.counts + static_cast<size_t>(i) * 8;
+            cn[0] = ok ? (end_ply >= 0 ? end_ply + 1 : nm) : 0;
+            cn[1] = ok ? n_win : 0;
+            cn[2] = ok ? n_missed : 0;
+            cn[3] = ok ? n_single : 0;
+            cn[4] = ok ? n_unblocked : 0;
+            cn[5] = ok ? n_lost : 0;
+            cn[6] = ok ? end_ply : 0;
+            cn[7] = status;
+        }
+    }
+    if (q.flags) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int t = lane + 64 * c;
+            if (t < q.A) q.flags[static_cast<size_t>(i) * q.A + t] = static_cast<uint8_t>(ok ? fl[c] : 0);
+        }
+    }
+}
+
 }  // namespace ao
 
 struct ao_positions {
@@ -189,6 +371,7 @@ struct ao_positions {
     float* d_planes = nullptr;     // [cap][C][A]   -- the three below: allocated by the first ao_positions_evaluate
     float* d_policy = nullptr;     // [cap][A]
     float* d_value = nullptr;      // [cap]
+    int32_t* d_counts = nullptr;   // [cap][8]      -- allocated by the first ao_positions_audit
     std::vector<int32_t> h_moves, h_n;
     std::string err;
     int fail(const std::string& m) { err = m; return 1; }
@@ -207,7 +390,7 @@ namespace {
 void positions_free(ao_positions* p) {
     for (void* d : {static_cast<void*>(p->d_moves), static_cast<void*>(p->d_n), static_cast<void*>(p->d_i32),
                     static_cast<void*>(p->d_board), static_cast<void*>(p->d_legal), static_cast<void*>(p->d_planes),
-                    static_cast<void*>(p->d_policy), static_cast<void*>(p->d_value)})
+                    static_cast<void*>(p->d_policy), static_cast<void*>(p->d_value), static_cast<void*>(p->d_counts)})
         if (d) hipFree(d);
     if (p->stream) hipStreamDestroy(p->stream);
 }
@@ -250,6 +433,39 @@ int launch_from_moves(ao_positions* p, int m, bool status, bool end_ply, bool tu
         case 3: hipLaunchKernelGGL(ao::k_positions_from_moves<3>, grid, block, 0, p->stream, q); break;
         default: hipLaunchKernelGGL(ao::k_positions_from_moves<4>, grid, block, 0, p->stream, q); break;
     }
+    PS_HIP(p, hipGetLastError());
+    return 0;
+}
+
+// k_win_cells (audit false) or k_audit_games on the m staged ids; the kernel's outputs land in the staging buffers
+int launch_tactics(ao_positions* p, int m, bool audit) {
+    ao::TacticsParams q{};
+    q.moves = p->d_moves; q.nmoves = p->d_n;
+    q.n = m; q.stride = p->A; q.B = p->B; q.A = p->A; q.win_mark = p->win_mark;
+    q.err = p->d_i32 + 3 * static_cast<size_t>(p->cap);
+    if (audit) {
+        q.flags = p->d_legal;
+        q.counts = p->d_counts;
+    } else {
+        q.mine = reinterpret_cast<uint8_t*>(p->d_board);
+        q.theirs = p->d_legal;
+        q.status = p->d_i32;
+        q.turn = p->d_i32 + 2 * static_cast<size_t>(p->cap);
+    }
+    const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
+    const int nch = (p->A + 63) / 64;
+#define AO_TACTICS(NCH)                                                                        \
+    do {                                                                                       \
+        if (audit) hipLaunchKernelGGL(ao::k_audit_games<NCH>, grid, block, 0, p->stream, q);   \
+        else hipLaunchKernelGGL(ao::k_win_cells<NCH>, grid, block, 0, p->stream, q);           \
+    } while (0)
+    switch (nch) {
+        case 1: AO_TACTICS(1); break;
+        case 2: AO_TACTICS(2); break;
+        case 3: AO_TACTICS(3); break;
+        default: AO_TACTICS(4); break;
+    }
+#undef AO_TACTICS
     PS_HIP(p, hipGetLastError());
     return 0;
 }
@@ -341,6 +557,49 @@ int ao_positions_from_moves(ao_positions* p, const int32_t* host_moves, int32_t 
             download(p, host_legal ? host_legal + first * A : nullptr, p->d_legal, m * A))
             return 1;
         PS_HIP(p, hipStreamSynchronize(p->stream));   // the planes are complete for any stream; the staging buffers are reused
+    }
+    return 0;
+}
+
+int ao_positions_win_cells(ao_positions* p, const int32_t* host_moves, int32_t stride, const int32_t* host_n, int32_t n,
+                           uint8_t* host_mine, uint8_t* host_theirs, int32_t* host_status, int32_t* host_turn, int32_t* host_err) {
+    if (n < 0 || stride < 0) return p->fail("ao_positions_win_cells: negative position count or stride");
+    if (n == 0) return 0;
+    if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_win_cells: null move buffer");
+    PS_HIP(p, hipSetDevice(p->device));
+    const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
+    for (int64_t first = 0; first < n; first += p->cap) {
+        const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
+        if (stage_moves(p, "ao_positions_win_cells", host_moves, stride, host_n, first, m)) return 1;
+        if (launch_tactics(p, m, false)) return 1;
+        if (download(p, host_mine ? host_mine + first * A : nullptr, reinterpret_cast<const uint8_t*>(p->d_board), m * A) ||
+            download(p, host_theirs ? host_theirs + first * A : nullptr, p->d_legal, m * A) ||
+            download(p, host_status ? host_status + first : nullptr, p->d_i32, m) ||
+            download(p, host_turn ? host_turn + first : nullptr, p->d_i32 + 2 * cap, m) ||
+            download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
+            return 1;
+        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+    }
+    return 0;
+}
+
+int ao_positions_audit(ao_positions* p, const int32_t* host_moves, int32_t stride, const int32_t* host_n, int32_t n,
+                       uint8_t* host_flags, int32_t* host_counts, int32_t* host_err) {
+    if (n < 0 || stride < 0) return p->fail("ao_positions_audit: negative record count or stride");
+    if (n == 0) return 0;
+    if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_audit: null move buffer");
+    PS_HIP(p, hipSetDevice(p->device));
+    const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
+    if (!p->d_counts) PS_HIP(p, hipMalloc(&p->d_counts, cap * 8 * sizeof(int32_t)));
+    for (int64_t first = 0; first < n; first += p->cap) {
+        const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
+        if (stage_moves(p, "ao_positions_audit", host_moves, stride, host_n, first, m)) return 1;
+        if (launch_tactics(p, m, true)) return 1;
+        if (download(p, host_flags ? host_flags + first * A : nullptr, p->d_legal, m * A) ||
+            download(p, host_counts ? host_counts + first * 8 : nullptr, p->d_counts, static_cast<size_t>(m) * 8) ||
+            download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
+            return 1;
+        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
     }
     return 0;
 }

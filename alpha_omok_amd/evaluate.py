@@ -221,3 +221,26 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
             pw, ew = 0.0, 1.0
         player_elo, enemy_elo = elo(player_elo, enemy_elo, pw, ew)
     return result, (player_elo, enemy_elo), games
+
+
+def tactical_summary(games, board_size, win_mark=None, device=0):
+    """What the games of an evaluation say about tactics, beyond who won: `games` is the [(win_index, moves)] list of
+    evaluate(..., return_games=True) / evaluate_batched, audited in ONE PositionBatch.audit call (every ply of every game
+    on the device). Returns {'black': {...}, 'white': {...}} by the ply parity of the flags, each with plies, wins_available,
+    wins_missed, single_threats, blocks_missed, lost_positions (the definitions of utils.audit_moves)."""
+    from . import positions as P
+    records = [list(moves) for _, moves in games]
+    with P.PositionBatch(board_size, win_mark=win_mark, capacity=max(1, min(len(records), 4096)), device=device) as pb:
+        d = pb.audit(records, leading_zero=False)
+    if d["err"].any():
+        raise ValueError("games %s are not legal move lists" % np.flatnonzero(d["err"]).tolist())
+    out = {}
+    for colour, name in enumerate(("black", "white")):
+        f = d["flags"][:, colour::2].astype(np.int64)
+        plies = ((d["counts"][:, 0].astype(np.int64) + 1 - colour) // 2).sum()    # black has the even plies of the audited ones
+        avail, taken = (f & P.WIN_AVAILABLE) != 0, (f & P.WIN_TAKEN) != 0
+        threat, blocked, lost = (f & P.THREAT) != 0, (f & P.BLOCKED) != 0, (f & P.LOST) != 0
+        out[name] = dict(plies=int(plies), wins_available=int(avail.sum()), wins_missed=int((avail & ~taken).sum()),
+                         single_threats=int((threat & ~lost).sum()), blocks_missed=int((threat & ~lost & ~blocked).sum()),
+                         lost_positions=int(lost.sum()))
+    return out

@@ -21,6 +21,8 @@ from . import _lib
 from .engine import EngineError, _ptr
 
 ERR_OK, ERR_RANGE, ERR_OCCUPIED, ERR_LENGTH = 0, 1, 2, 3
+# flag bits of one audited ply (PositionBatch.audit; the same values as utils.audit_moves)
+WIN_AVAILABLE, WIN_TAKEN, THREAT, BLOCKED, LOST = 1, 2, 4, 8, 16
 
 
 def default_win_mark(board_size):
@@ -216,6 +218,36 @@ class PositionBatch:
             _ptr(pol, C.c_float), _ptr(val, C.c_float), _ptr(status, C.c_int32), _ptr(err, C.c_int32)),
             "ao_positions_evaluate")
         return pol, val, status, err
+
+    # -- tactics: defined through utils.check_win alone (utils.win_cells / utils.audit_moves are the host definition)
+    def win_cells(self, root_ids, leading_zero=True):
+        """The cells that win at once, one row per id: dict of mine (uint8 [n, A], 1 where a stone of the side to move
+        completes a line: check_win of the board with that stone is the mover's index), theirs (the same for the
+        opponent, as if it were to move: the cells the mover must occupy), status (check_win of the position; a terminal
+        position has no winning cells), turn, err (as describe; rows with err != 0 are all zero)."""
+        moves, n = pack_ids(root_ids, leading_zero)
+        cnt = n.shape[0]
+        out = dict(mine=np.zeros((cnt, self.A), np.uint8), theirs=np.zeros((cnt, self.A), np.uint8),
+                   status=np.zeros(cnt, np.int32), turn=np.zeros(cnt, np.int32), err=np.zeros(cnt, np.int32))
+        self._check(self._L.ao_positions_win_cells(
+            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, _ptr(out["mine"], C.c_uint8),
+            _ptr(out["theirs"], C.c_uint8), _ptr(out["status"], C.c_int32), _ptr(out["turn"], C.c_int32),
+            _ptr(out["err"], C.c_int32)), "ao_positions_win_cells")
+        return out
+
+    def audit(self, root_ids, leading_zero=True):
+        """The tactical audit of game records, one row per id: dict of flags (uint8 [n, A]: the flag byte of ply t at
+        [i, t] -- WIN_AVAILABLE, WIN_TAKEN, THREAT, BLOCKED, LOST, set while the position before the move is not terminal;
+        zeros from the first terminal position on and beyond the record), counts (int32 [n, 8]: plies audited,
+        WIN_AVAILABLE, wins missed, single threats, blocks missed, LOST, end_ply and status as describe), err (as
+        describe; rows with err != 0 are all zero)."""
+        moves, n = pack_ids(root_ids, leading_zero)
+        cnt = n.shape[0]
+        out = dict(flags=np.zeros((cnt, self.A), np.uint8), counts=np.zeros((cnt, 8), np.int32), err=np.zeros(cnt, np.int32))
+        self._check(self._L.ao_positions_audit(
+            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, _ptr(out["flags"], C.c_uint8),
+            _ptr(out["counts"], C.c_int32), _ptr(out["err"], C.c_int32)), "ao_positions_audit")
+        return out
 
     # -- lifetime
     def close(self):

@@ -50,6 +50,114 @@ def check_win(board, win_mark):
     return 0
 
 
+# flag bits of one audited ply (audit_moves, PositionBatch.audit)
+WIN_AVAILABLE, WIN_TAKEN, THREAT, BLOCKED, LOST = 1, 2, 4, 8, 16
+
+
+def check_win_boards(boards, win_mark):
+    """check_win for a stack of boards [n, B, B]: int32 [n]. The same scan -- windows row-major, black before white inside
+    a window -- with the line sums taken once per start cell for all boards instead of once per window and board."""
+    b = np.asarray(boards).astype(np.int8)
+    n, B, k = b.shape[0], b.shape[1], win_mark
+    win = np.where((b != 0).all(axis=(1, 2)), 3, 0).astype(np.int32)
+    W = B - k + 1
+    if n == 0 or W < 1:
+        return win
+    b = np.ascontiguousarray(b.transpose(1, 2, 0))                           # [B, B, n]: every slice below is long runs
+    # sums of the k cells of the line that STARTS at a cell: to the right, downwards, down-right, down-left
+    right = sum(b[:, i:i + W] for i in range(k))                             # [B, W, n]
+    down = sum(b[i:i + W] for i in range(k))                                 # [W, B, n]
+    diag = sum(b[i:i + W, i:i + W] for i in range(k))                        # [W, W, n]
+    anti = sum(b[i:i + W, k - 1 - i:k - 1 - i + W] for i in range(k))        # [W, W, n], by the window's top-left cell
+
+    def windows_with_line(total):
+        hit = (diag == total) | (anti == total)
+        in_row, in_col = right == total, down == total
+        for i in range(k):                                                   # the window's k rows and k columns
+            hit |= in_row[i:i + W]
+            hit |= in_col[:, i:i + W]
+        return hit.reshape(W * W, n)
+
+    black, white = windows_with_line(k), windows_with_line(-k)
+    either = black | white
+    first = either.argmax(axis=0)
+    decided = either.any(axis=0)
+    win[decided] = np.where(black[first[decided], decided], 1, 2)
+    return win
+
+
+def win_cells(board, turn, win_mark):
+    """The cells that win at once, by the definition alone: try every empty cell with check_win (all the tried boards in
+    one check_win_boards call). No reference counterpart; pinned to the reference's check_win (utils.py:30-59). `board`
+    [B, B] of +1 black / -1 white / 0, `turn` 0 black / 1 white to move. Returns (mine, theirs), bool [A]: cell c is in
+    `mine` if check_win(board) == 0, c is empty and check_win of the board with a stone of the mover on c is the mover's
+    win index (overlines count; a move that only fills the board, win index 3, does not); `theirs` the same for the
+    opponent, as if it were to move. Both are empty on a terminal board. This is the yardstick the device is held to: A
+    whole-board scans per colour, obviously right rather than fast."""
+    b = np.asarray(board).astype(np.int8)
+    A = b.size
+    sets = np.zeros((2, A), bool)
+    if check_win(b, win_mark) != 0:
+        return sets[0], sets[1]
+    empty = np.flatnonzero(b.ravel() == 0)
+    tried = np.repeat(b.reshape(1, 1, A), empty.size, axis=1).repeat(2, axis=0)      # [who, empty cell, A]
+    for who, colour in ((0, turn), (1, 1 - turn)):
+        tried[who, np.arange(empty.size), empty] = 1 if colour == 0 else -1
+    win = check_win_boards(tried.reshape((2 * empty.size,) + b.shape), win_mark).reshape(2, empty.size)
+    sets[0, empty] = win[0] == turn + 1
+    sets[1, empty] = win[1] == 2 - turn
+    return sets[0], sets[1]
+
+
+def audit_moves(moves, board_size, win_mark):
+    """The tactical audit of ONE record of legal moves (black first): (flags uint8 [A], counts int32 [8]). flags[t]
+    describes the move moves[t] played in the position before it, while that position is not terminal: WIN_AVAILABLE
+    mine not empty, WIN_TAKEN the move is in mine, THREAT mine empty and theirs not, BLOCKED a THREAT and the move is in
+    theirs, LOST a THREAT with two or more cells in theirs (win_cells). Plies from the first terminal position on, and
+    beyond the record, are 0. counts: plies audited, WIN_AVAILABLE, wins missed, single threats (THREAT without LOST),
+    blocks missed, LOST, end_ply (index of the first move after which check_win is non-zero, -1 if none), final
+    check_win. ValueError for a move off the board or onto a stone."""
+    A = board_size * board_size
+    moves = [int(m) for m in moves]
+    if len(moves) > A:
+        raise ValueError("%d moves on a board of %d cells" % (len(moves), A))
+    flags = np.zeros(A, np.uint8)
+    counts = np.zeros(8, np.int32)
+    board = np.zeros(A)
+    for t, m in enumerate(moves):
+        if not 0 <= m < A:
+            raise ValueError("move %d is off the board" % m)
+        if board[m] != 0:
+            raise ValueError("move %d is onto a stone" % m)
+        board[m] = 1.0 if t % 2 == 0 else -1.0
+    # check_win after every move: the first non-zero one ends the audit
+    after = np.zeros((len(moves), board_size, board_size))
+    for t in range(len(moves)):
+        after[t] = get_board([0] + moves[:t + 1], board_size)
+    status = check_win_boards(after, win_mark)
+    end_ply = int(np.flatnonzero(status)[0]) if status.any() else -1
+    board = np.zeros(A)
+    for t, m in enumerate(moves):
+        if end_ply < 0 or t <= end_ply:
+            mine, theirs = win_cells(board.reshape(board_size, board_size), t % 2, win_mark)
+            f = 0
+            if mine.any():
+                f = WIN_AVAILABLE | (WIN_TAKEN if mine[m] else 0)
+            elif theirs.any():
+                f = THREAT | (BLOCKED if theirs[m] else 0) | (LOST if theirs.sum() >= 2 else 0)
+            flags[t] = f
+            counts[0] += 1
+            counts[1] += bool(f & WIN_AVAILABLE)
+            counts[2] += bool(f & WIN_AVAILABLE) and not f & WIN_TAKEN
+            counts[3] += bool(f & THREAT) and not f & LOST
+            counts[4] += bool(f & THREAT) and not f & LOST and not f & BLOCKED
+            counts[5] += bool(f & LOST)
+        board[m] = 1.0 if t % 2 == 0 else -1.0
+    counts[6] = end_ply
+    counts[7] = status[-1] if moves else 0
+    return flags, counts
+
+
 def get_state_pt(node_id, board_size, channel_size):
     """Network input planes, float64 [C, B, B] (utils.py:139-168): the stones of the mover of each
     of the last C-1 plies as they stood after that ply, oldest first, then the colour plane."""

@@ -523,6 +523,37 @@ int  ao_positions_from_moves(ao_positions *p, const int32_t *host_moves, int32_t
 int  ao_positions_evaluate(ao_positions *p, ao_net *net, const int32_t *host_moves, int32_t stride, const int32_t *host_n,
                            int32_t n, float *host_policy /*[n][A]*/, float *host_value /*[n]*/,
                            int32_t *host_status, int32_t *host_err);
+/* The cells that win at once. No reference counterpart: the definition is utils.check_win (utils.py:30-59) and nothing
+ * else. P is the position of id i (moves as for ao_positions_from_moves), k its side to move (black on even plies). A
+ * cell c is a WINNING CELL of colour j in P if check_win(P) == 0, c is empty, and check_win of P's board with a stone of
+ * colour j on c returns j's win index (1 black, 2 white). Overlines count, as in the reference; a move that fills the
+ * board without a line (win index 3) is not a winning move; on a terminal position no cell is a winning cell for anyone.
+ * Outputs (any may be NULL):
+ *   host_mine    uint8 [n][A]     1 on the winning cells of k
+ *   host_theirs  uint8 [n][A]     1 on the winning cells of the opponent, as if it were to move: the cells k must occupy
+ *   host_status  int32 [n]        check_win(P)
+ *   host_turn    int32 [n]        utils.get_turn of the id
+ *   host_err     int32 [n]        as ao_positions_from_moves; a position with an error has every output of its own zeroed
+ * Chunks, staging and return value as ao_positions_from_moves; n == 0 is a no-op. */
+int  ao_positions_win_cells(ao_positions *p, const int32_t *host_moves, int32_t stride, const int32_t *host_n, int32_t n,
+                            uint8_t *host_mine, uint8_t *host_theirs, int32_t *host_status, int32_t *host_turn,
+                            int32_t *host_err);
+/* The tactical audit of n game records (move lists as above), every ply of each: with mine(P) / theirs(P) the winning
+ * cells of the side to move / of its opponent as defined above (through utils.check_win, utils.py:30-59), the flag byte
+ * of the move m_t played in P_t, set only while check_win(P_t) == 0, is
+ *    1 WIN_AVAILABLE  mine(P_t) is not empty            2 WIN_TAKEN  m_t is in mine(P_t)
+ *    4 THREAT         mine(P_t) is empty and theirs(P_t) is not
+ *    8 BLOCKED        THREAT and m_t is in theirs(P_t)
+ *   16 LOST           THREAT and theirs(P_t) holds two or more cells (one stone cannot answer both)
+ * Plies from the first terminal position on get 0; their moves are still placed and validated. Outputs (any may be NULL):
+ *   host_flags   uint8 [n][A]     flag byte of ply t at [i][t], zeros beyond the record
+ *   host_counts  int32 [n][8]     0 plies audited, 1 WIN_AVAILABLE, 2 wins missed (WIN_AVAILABLE without WIN_TAKEN),
+ *                                 3 single threats (THREAT without LOST), 4 blocks missed (single threat without BLOCKED),
+ *                                 5 LOST, 6 end_ply and 7 status as ao_positions_from_moves
+ *   host_err     int32 [n]        as ao_positions_from_moves; a record with an error has all-zero outputs
+ * Chunks, staging and return value as ao_positions_from_moves; n == 0 is a no-op. */
+int  ao_positions_audit(ao_positions *p, const int32_t *host_moves, int32_t stride, const int32_t *host_n, int32_t n,
+                        uint8_t *host_flags, int32_t *host_counts, int32_t *host_err);
 
 #ifdef __cplusplus
 }

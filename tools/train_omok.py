@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--eval-sims", type=int, default=None)
     ap.add_argument("--yardstick", default=None, help="'puct:400' / 'uct:400': also play every evaluation against the rollout agent "
                                                       "(agents.py:263-634) with that many simulations -- a fixed opponent that needs no network")
+    ap.add_argument("--audit", action="store_true",
+                    help="add the tactical summary of every evaluation's games (evaluate.tactical_summary: wins in one available / "
+                         "missed, single threats / blocks missed, lost positions, by colour) to its 'elo' log line as `tactics`")
     ap.add_argument("--eval-dense-until", type=int, default=0, help="evaluate after EVERY iteration up to this one (the steep part of the curve)")
     ap.add_argument("--ckpt-every", type=int, default=10)
     ap.add_argument("--max-ckpts", type=int, default=6, help="checkpoints kept on disk besides iteration 0 and final (gpurun_out is merged back up to 64 MiB)")
@@ -85,6 +88,9 @@ def main():
 
     os.makedirs(a.out, exist_ok=True)
     log = open(os.path.join(a.out, "log.jsonl"), "a")
+
+    def tactics(games):   # the extra field of an 'elo' line under --audit (none without it)
+        return dict(tactics=evaluate.tactical_summary(games, a.board, device=0)) if a.audit else {}
 
     def emit(rec):
         log.write(json.dumps(rec) + "\n")
@@ -117,7 +123,7 @@ def main():
                                                        n_match=a.eval_matches, seed=9000, device=0)
         emit(dict(kind="elo", iter=0, vs=a.yardstick, matches=a.eval_matches, result=yr, elo_gain_reference_K32=round(ype - 1500.0, 1),
                   score=round((yr["Player"] + 0.5 * yr["Draw"]) / max(sum(yr.values()), 1), 4),
-                  mean_plies=round(float(np.mean([len(g[1]) for g in yg])), 1), eval_s=round(time.time() - t0, 2)))
+                  mean_plies=round(float(np.mean([len(g[1]) for g in yg])), 1), eval_s=round(time.time() - t0, 2), **tactics(yg)))
     kept = []
     t_end = time.time() + 60.0 * a.minutes
     games_total = moves_total = 0
@@ -180,7 +186,7 @@ def main():
                                                                n_match=a.eval_matches, seed=9000 + it, device=0)
                 ysc = (yr["Player"] + 0.5 * yr["Draw"]) / max(sum(yr.values()), 1)
                 emit(dict(kind="elo", iter=it, vs=a.yardstick, matches=a.eval_matches, result=yr, elo_gain_reference_K32=round(ype - 1500.0, 1),
-                          score=round(ysc, 4), mean_plies=round(float(np.mean([len(g[1]) for g in yg])), 1), eval_s=round(time.time() - t0, 2)))
+                          score=round(ysc, 4), mean_plies=round(float(np.mean([len(g[1]) for g in yg])), 1), eval_s=round(time.time() - t0, 2), **tactics(yg)))
                 t0 = time.time()
             result, (pe, ee), games = evaluate.evaluate_batched(m.Agent.model, base, a.board, a.eval_sims or a.sims,
                                                                 n_match=a.eval_matches, seed=1000 + it, device=0)
@@ -190,7 +196,7 @@ def main():
             emit(dict(kind="elo", iter=it, vs="iter0", matches=a.eval_matches, sims=a.eval_sims or a.sims, result=result,
                       player_elo=round(pe, 1), enemy_elo=round(ee, 1), elo_gain_reference_K32=round(pe - 1500.0, 1),
                       score=round(score, 4), elo_diff_from_score=round(float(ml), 1),
-                      mean_plies=round(float(np.mean([len(g[1]) for g in games])), 1), eval_s=round(time.time() - t0, 2)))
+                      mean_plies=round(float(np.mean([len(g[1]) for g in games])), 1), eval_s=round(time.time() - t0, 2), **tactics(games)))
             # ... and against the network of the previous evaluation point: the chain of these differences keeps measuring
             # progress after "beats iteration 0 every time" has saturated
             if prev_model is not None and it % a.eval_every == 0:
@@ -204,7 +210,7 @@ def main():
                 emit(dict(kind="elo", iter=it, vs="iter%d" % prev_iter, matches=a.eval_matches, result=result,
                           elo_gain_reference_K32=round(pe - 1500.0, 1), score=round(score, 4),
                           elo_diff_from_score=round(float(ml), 1), chain_elo_from_scores=round(chain, 1),
-                          mean_plies=round(float(np.mean([len(g[1]) for g in games])), 1), eval_s=round(time.time() - t0, 2)))
+                          mean_plies=round(float(np.mean([len(g[1]) for g in games])), 1), eval_s=round(time.time() - t0, 2), **tactics(games)))
             if it % a.eval_every == 0:
                 prev_model = PVNet(a.blocks, m.IN_PLANES, a.planes, a.board).to(dev)
                 prev_model.load_state_dict(m.Agent.model.state_dict())
