@@ -212,6 +212,18 @@ class ZeroAgent(Agent):
         B = self.board_size
         return d["mine"][0].reshape(B, B).astype(bool), d["theirs"][0].reshape(B, B).astype(bool)
 
+    def get_forced_win(self, root_id, max_depth=8, max_nodes=2000):
+        """Is there a forced win by continuous fours for the side to move in the position of `root_id`
+        (PositionBatch.forced_wins)? (result, depth, moves, line): result 0 no / 1 yes / 2 the node budget ran out, depth
+        the fewest attacker moves, moves bool [B, B] every first move that wins that fast, line the principal line as a
+        list of cells. ValueError for an id that is not a legal move list or limits outside 1..16 / 1..65536."""
+        d = self._position_batch().forced_wins([root_id], max_depth, max_nodes)
+        if d["err"][0]:
+            raise ValueError("root_id %r is not a legal move list (err %d)" % (root_id, int(d["err"][0])))
+        B = self.board_size
+        return (int(d["result"][0]), int(d["depth"][0]), d["moves"][0].reshape(B, B).astype(bool),
+                d["line"][0, :int(d["line_len"][0])].tolist())
+
     def get_pv_batch(self, root_ids):
         """get_pv for many ids in one call (PositionBatch.evaluate): (policy float32 [n, A], value float32 [n],
         status int32 [n] -- utils.check_win of each position, terminal ones are evaluated too --, err int32 [n]). The planes

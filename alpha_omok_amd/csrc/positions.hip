@@ -1,7 +1,8 @@
 // positions.hip -- the stateless, batched "position" layer beside the search: rule status, legal moves, input planes and the
 // network's evaluation of positions the CALLER names, no tree and no game involved.
 //
-// One wavefront (64 lanes) owns one position, kPosPerWG positions per workgroup, nothing shared between them (no LDS).
+// One wavefront (64 lanes) owns one position, kPosPerWG positions per workgroup, nothing shared between them (no LDS but
+// k_forced_wins' search stack, one per wave).
 //
 // Reference map (paths relative to /root/reference/2_AlphaOmok/):
 //   k_check_win_boards      utils.py:30-59 (check_win) on raw boards: the FULL window scan, row-major, black before white
@@ -13,6 +14,8 @@
 //   ao_positions_evaluate   agents.py:171-178 for n positions at once: planes on the device, then the ordinary forward
 //   k_win_cells, k_audit_games  no counterpart: the cells that win at once and the per-ply tactical flags of game records,
 //                           defined through utils.py:30-59 (check_win of the board with one more stone)
+//   k_forced_wins           no counterpart: forced wins by continuous fours, a depth-first search per position over the same
+//                           winning cells (utils.forced_win of this package is the host definition)
 //
 // The bitboards, pos_place, pos_occupied, win_after_move and encode_planes are the tree kernels' own (tree_device.hpp): a
 // position described here is the position the search would hold.
@@ -358,6 +361,304 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_audit_games(TacticsParams q)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// forced wins by continuous fours (VCF). No reference counterpart; the definition is utils.forced_win, which asks
+// utils.check_win (utils.py:30-59) and nothing else -- see ao_positions_forced_wins in omok_hip.h for the text.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kFwMaxDepth = 16;            // ao_positions_forced_wins: max_depth 1..16
+constexpr int kFwMaxNodes = 65536;         //                           max_nodes 1..65536
+constexpr int kFwLine = 2 * kFwMaxDepth;   // a line has at most 2 * 16 - 1 stones; the last slot holds its length
+enum : int32_t { FW_NONE = 0, FW_WIN = 1, FW_UNKNOWN = 2 };
+
+// one level of the search stack = one attacker node and the four being tried there
+struct FwLevel {
+    uint64_t cand[kBBWords];   // candidates not tried yet
+    uint64_t rep[kBBWords];    // forced replies to the four on `c` not tried yet
+    int32_t c, b;              // the attacker's stone and the defender's reply on the board below this level's child
+    int32_t b0;                // min(replies): the reply the line follows
+    int32_t pad_;
+};
+struct FwWave {
+    FwLevel lv[kFwMaxDepth];               // 16 x 80 B
+    int16_t line[kFwMaxDepth][kFwLine];    // line[L]: the line from the node of level L on, [kFwLine - 1] = its length; 1 KB
+};
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v));
+    const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
+    return lo | (static_cast<uint64_t>(hi) << 32);
+}
+
+// a stone of `colour` on `cell` comes or goes (wave-uniform cell; selects, no dynamically indexed access: see pick4)
+__device__ __forceinline__ void pos_toggle(PosR& s, int colour, int cell) {
+    const int w = cell >> 6;
+    const uint64_t bit = 1ull << (cell & 63);
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int i = 0; i < kBBWords; ++i) s.bb[c][i] ^= (c == colour && i == w) ? bit : 0ull;
+}
+
+// lowest set cell of a 256-cell mask that is not empty, and the mask without it
+__device__ __forceinline__ int pop_lowest(uint64_t (&m)[kBBWords]) {
+    int cell = -1;
+#pragma unroll
+    for (int i = 0; i < kBBWords; ++i) {
+        const bool here = cell < 0 && m[i] != 0ull;
+        cell = here ? 64 * i + __ffsll(static_cast<long long>(m[i])) - 1 : cell;
+        m[i] = here ? m[i] & (m[i] - 1ull) : m[i];
+    }
+    return cell;
+}
+__device__ __forceinline__ int lowest_cell(const uint64_t (&m)[kBBWords]) {
+    uint64_t t[kBBWords] = {m[0], m[1], m[2], m[3]};
+    return pop_lowest(t);
+}
+__device__ __forceinline__ void mask_add(uint64_t (&m)[kBBWords], int cell) {
+#pragma unroll
+    for (int i = 0; i < kBBWords; ++i) m[i] |= (i == (cell >> 6)) ? 1ull << (cell & 63) : 0ull;
+}
+
+// The empty cells on which a stone of `colour` makes a four: afterwards the colour has a winning cell that goes through the
+// new stone (wave-uniform; all 64 lanes call). Lane = cell, NCH passes. Some win_mark-window through the cell holds
+// win_mark - 2 stones of the colour, the cell, no stone of the other colour and nothing off the board -- so exactly one more
+// empty cell, which then wins. Where the colour has NO winning cell before the stone this is "winning_cells after the stone
+// is not empty": a winning cell e after the stone on c lies with c on one line of >= win_mark; were they win_mark or more
+// apart on it, the win_mark-window from e towards c would hold e and stones only, and e would have won before. Probed cells
+// are checked by row and column like winning_cells'.
+template <int NCH>
+__device__ __forceinline__ void four_cells(const PosR& s, int colour, int B, int A, int win_mark, uint64_t (&out)[kBBWords]) {
+    const int lane = lane_id();
+    const uint64_t mk = 0ull - static_cast<uint64_t>(colour & 1);
+    const uint64_t a0 = (s.bb[0][0] & ~mk) | (s.bb[1][0] & mk), a1 = (s.bb[0][1] & ~mk) | (s.bb[1][1] & mk);
+    const uint64_t a2 = (s.bb[0][2] & ~mk) | (s.bb[1][2] & mk), a3 = (s.bb[0][3] & ~mk) | (s.bb[1][3] & mk);
+    const uint64_t d0 = (s.bb[1][0] & ~mk) | (s.bb[0][0] & mk), d1 = (s.bb[1][1] & ~mk) | (s.bb[0][1] & mk);
+    const uint64_t d2 = (s.bb[1][2] & ~mk) | (s.bb[0][2] & mk), d3 = (s.bb[1][3] & ~mk) | (s.bb[0][3] & mk);
+    constexpr int R = kMaxWinMark - 1;     // offsets -R..R along a line, bit t + R of the two masks below
+    const unsigned wm = (1u << win_mark) - 1u;
+#pragma unroll
+    for (int c = 0; c < kBBWords; ++c) {
+        if (c >= NCH) { out[c] = 0ull; continue; }
+        const int cell = lane + 64 * c;
+        const bool empty = cell < A && !(((s.bb[0][c] | s.bb[1][c]) >> lane) & 1ull);
+        const int r = cell / B, col = cell % B;
+        bool four = false;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const int dr = (d == 0) ? 0 : 1;
+            const int dc = (d == 0) ? 1 : (d == 1) ? 0 : (d == 2) ? 1 : -1;
+            unsigned own = 0u, shut = 0u;  // the colour's stones / cells no line of the colour can use
+#pragma unroll
+            for (int t = -R; t <= R; ++t) {
+                if (t == 0) continue;
+                const int rr = r + t * dr, cc = col + t * dc;
+                const bool in = rr >= 0 && rr < B && cc >= 0 && cc < B;
+                const int cl = in ? rr * B + cc : 0;                           // 0 .. A-1 < 64 * kBBWords
+                const bool mine = in && ((pick4(a0, a1, a2, a3, cl >> 6) >> (cl & 63)) & 1ull);
+                const bool his = in && ((pick4(d0, d1, d2, d3, cl >> 6) >> (cl & 63)) & 1ull);
+                own |= mine ? 1u << (t + R) : 0u;
+                shut |= (!in || his) ? 1u << (t + R) : 0u;
+            }
+#pragma unroll
+            for (int st = 0; st < kMaxWinMark; ++st) {                         // the window of offsets -st .. -st + win_mark - 1
+                const unsigned w = wm << (R - st);
+                const bool ok = st < win_mark && (shut & w) == 0u && __popc(own & w) == win_mark - 2;
+                four = four || ok;
+            }
+        }
+        out[c] = __ballot(empty && four);
+    }
+}
+
+struct ForcedParams {
+    const int32_t* moves;   // [n][stride]
+    const int32_t* nmoves;  // [n]
+    int n, stride, B, A, win_mark, max_depth, max_nodes, line_stride;
+    // outputs, any may be null
+    int32_t* result; int32_t* depth; int32_t* move; int32_t* line_len; int32_t* nodes;   // [n]
+    int32_t* status; int32_t* turn; int32_t* err;                                        // [n]
+    uint8_t* mask;          // [n][A]
+    int16_t* line;          // [n][line_stride], line_stride = 2 max_depth - 1
+};
+
+// utils.forced_win of the position of id i: iterative deepening over a depth-first search that the wave walks as ONE
+// thread of control -- every value that steers it is wave-uniform (ballots, counters, words read back from the wave's own
+// LDS stack), the 64 lanes only share the work inside winning_cells / four_cells / check_win_board. No recursion: the
+// states below are the call and return points of wins_within / four of the definition. The board is one PosR; stones are
+// toggled on the way down and up.
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) {
+    __shared__ FwWave s_wave[kPosPerWG];
+    const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    const int i = blockIdx.x * kPosPerWG + wv;
+    if (i >= q.n) return;
+    FwWave& W = s_wave[wv];
+    const int lane = lane_id();
+    const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
+    PosR s;
+    int end_ply;
+    const int err = replay_moves(s, q.moves + static_cast<size_t>(i) * q.stride, nm, q.A, q.B, q.win_mark, end_ply);
+    const bool ok = err == PE_OK;
+    const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
+    const int a = ok ? (nm & 1) : 0;       // the attacker
+
+    int result = FW_NONE, depth = 0, nodes = 0;
+    uint64_t won[kBBWords] = {0ull, 0ull, 0ull, 0ull};
+    enum { ENTER, NEXT_C, NEXT_B, RETURN };
+
+    for (int D = 1; ok && result == FW_NONE && D <= q.max_depth; ++D) {
+        int L = 0, state = ENTER;
+        bool yes = false;                  // what the node that RETURNs answers
+        for (;;) {
+            // The lanes' geometry inside winning_cells / four_cells (the cells a lane probes, and whether they are on the
+            // board) depends on B alone. Hoisted out of the search it would have to live in registers throughout -- some
+            // 300 VGPRs at four mask words, spilling to scratch; behind a B the compiler cannot see through it is worked
+            // out again at each call.
+            int B = q.B;
+            asm volatile("" : "+s"(B));
+            if (state == ENTER) {          // wins_within(P, D - L); the node's level is L <= D - 1 <= 15
+                if (nodes >= q.max_nodes) { result = FW_UNKNOWN; break; }
+                nodes += 1;
+                yes = false;
+                state = RETURN;
+                // below the root a position cannot hold a line (the attacker's stone was no winning cell, the defender
+                // had none), it can only be full
+                const bool terminal = L == 0 ? status != 0 : nm + 2 * L >= q.A;
+                if (!terminal) {
+                    uint64_t mine[kBBWords], theirs[kBBWords];
+                    winning_cells<NCH>(s, a, B, q.A, q.win_mark, mine);
+                    winning_cells<NCH>(s, a ^ 1, B, q.A, q.win_mark, theirs);
+                    const int n_theirs = popcount4(theirs);
+                    if (popcount4(mine) > 0) {
+                        yes = true;
+                        if (lane == 0) {
+                            W.line[L][0] = static_cast<int16_t>(lowest_cell(mine));
+                            W.line[L][kFwLine - 1] = 1;
+                        }
+                        if (L == 0) {
+#pragma unroll
+                            for (int w = 0; w < kBBWords; ++w) won[w] = mine[w];
+                        }
+                    } else if (D - L > 1 && n_theirs < 2) {
+                        uint64_t cand[kBBWords];
+                        four_cells<NCH>(s, a, B, q.A, q.win_mark, cand);
+                        if (lane == 0) {
+#pragma unroll
+                            for (int w = 0; w < kBBWords; ++w) W.lv[L].cand[w] = n_theirs ? cand[w] & theirs[w] : cand[w];
+                        }
+                        state = NEXT_C;
+                    }
+                }
+                wsync();
+            } else if (state == NEXT_C) {  // the next candidate of level L, or the end of its loop
+                uint64_t cand[kBBWords];
+#pragma unroll
+                for (int w = 0; w < kBBWords; ++w) cand[w] = uniform64(W.lv[L].cand[w]);
+                const int c = pop_lowest(cand);
+                if (c < 0) {               // (the root's answer is `won`)
+                    yes = false;
+                    state = RETURN;
+                    continue;
+                }
+                // four(P, c, D - L): the defender has no winning cell after it -- before it he had at most one, and then c is
+                // that cell -- so the four stands or falls with its forced replies
+                pos_toggle(s, a, c);
+                uint64_t rep[kBBWords];
+                winning_cells<NCH>(s, a, B, q.A, q.win_mark, rep);
+                wsync();                   // the reads of cand above are done before lane 0 overwrites it
+                if (lane == 0) {
+#pragma unroll
+                    for (int w = 0; w < kBBWords; ++w) { W.lv[L].cand[w] = cand[w]; W.lv[L].rep[w] = rep[w]; }
+                    W.lv[L].c = c;
+                    W.lv[L].b0 = lowest_cell(rep);
+                }
+                wsync();
+                if (popcount4(rep) == 0) pos_toggle(s, a, c);     // (four_cells says this cannot happen)
+                else state = NEXT_B;
+            } else if (state == NEXT_B) {  // the next forced reply to the four of level L, or the four has held
+                uint64_t rep[kBBWords];
+#pragma unroll
+                for (int w = 0; w < kBBWords; ++w) rep[w] = uniform64(W.lv[L].rep[w]);
+                const int c = __builtin_amdgcn_readfirstlane(W.lv[L].c);
+                const int b = pop_lowest(rep);
+                if (b < 0) {               // every reply loses: c succeeds
+                    pos_toggle(s, a, c);
+                    if (L == 0) {          // the root collects and goes on
+                        mask_add(won, c);
+                        state = NEXT_C;
+                    } else {
+                        yes = true;
+                        state = RETURN;
+                    }
+                    continue;
+                }
+                wsync();
+                if (lane == 0) {
+#pragma unroll
+                    for (int w = 0; w < kBBWords; ++w) W.lv[L].rep[w] = rep[w];
+                    W.lv[L].b = b;
+                }
+                wsync();
+                pos_toggle(s, a ^ 1, b);
+                L += 1;
+                state = ENTER;
+            } else {                       // RETURN: the node of level L answers `yes` to the four of level L - 1
+                if (L == 0) break;
+                L -= 1;
+                const int c = __builtin_amdgcn_readfirstlane(W.lv[L].c);
+                const int b = __builtin_amdgcn_readfirstlane(W.lv[L].b);
+                const int b0 = __builtin_amdgcn_readfirstlane(W.lv[L].b0);
+                pos_toggle(s, a ^ 1, b);
+                if (yes) {
+                    // the line follows the first reply; the root keeps the line of its first success (min(moves))
+                    if (b == b0 && (L > 0 || popcount4(won) == 0)) {
+                        const int len = __builtin_amdgcn_readfirstlane(static_cast<int>(W.line[L + 1][kFwLine - 1]));   // <= 2 (D - L - 1) - 1
+                        const int16_t v = lane < len ? W.line[L + 1][lane] : static_cast<int16_t>(0);
+                        wsync();
+                        if (lane < len) W.line[L][lane + 2] = v;               // lane + 2 <= len + 1 <= 2 (D - L) - 2 <= 30
+                        if (lane == 0) {
+                            W.line[L][0] = static_cast<int16_t>(c);
+                            W.line[L][1] = static_cast<int16_t>(b);
+                            W.line[L][kFwLine - 1] = static_cast<int16_t>(len + 2);
+                        }
+                        wsync();
+                    }
+                    state = NEXT_B;
+                } else {
+                    pos_toggle(s, a, c);
+                    state = NEXT_C;
+                }
+            }
+        }
+        if (result == FW_NONE && popcount4(won) > 0) {
+            result = FW_WIN;
+            depth = D;
+        }
+    }
+    wsync();
+    const bool win = result == FW_WIN;
+    const int len = win ? __builtin_amdgcn_readfirstlane(static_cast<int>(W.line[0][kFwLine - 1])) : 0;
+    if (lane == 0) {
+        if (q.result) q.result[i] = result;
+        if (q.depth) q.depth[i] = depth;
+        if (q.move) q.move[i] = win ? lowest_cell(won) : -1;
+        if (q.line_len) q.line_len[i] = len;
+        if (q.nodes) q.nodes[i] = nodes;
+        if (q.status) q.status[i] = status;
+        if (q.turn) q.turn[i] = a;
+        if (q.err) q.err[i] = err;
+    }
+    if (q.mask) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int cell = lane + 64 * c;
+            if (cell < q.A) q.mask[static_cast<size_t>(i) * q.A + cell] = static_cast<uint8_t>(win && ((won[c] >> lane) & 1ull));
+        }
+    }
+    if (q.line && lane < q.line_stride)    // line_stride = 2 max_depth - 1 <= 31 < 64; len <= 2 depth - 1 <= line_stride
+        q.line[static_cast<size_t>(i) * q.line_stride + lane] = lane < len ? W.line[0][lane] : static_cast<int16_t>(-1);
+}
+
 }  // namespace ao
 
 struct ao_positions {
@@ -372,6 +673,8 @@ struct ao_positions {
     float* d_policy = nullptr;     // [cap][A]
     float* d_value = nullptr;      // [cap]
     int32_t* d_counts = nullptr;   // [cap][8]      -- allocated by the first ao_positions_audit
+    int32_t* d_forced = nullptr;   // [5][cap]: result, depth, move, line_len, nodes -- these two: by the first ao_positions_forced_wins
+    int16_t* d_line = nullptr;     // [cap][2 * 16 - 1]
     std::vector<int32_t> h_moves, h_n;
     std::string err;
     int fail(const std::string& m) { err = m; return 1; }
@@ -390,7 +693,8 @@ namespace {
 void positions_free(ao_positions* p) {
     for (void* d : {static_cast<void*>(p->d_moves), static_cast<void*>(p->d_n), static_cast<void*>(p->d_i32),
                     static_cast<void*>(p->d_board), static_cast<void*>(p->d_legal), static_cast<void*>(p->d_planes),
-                    static_cast<void*>(p->d_policy), static_cast<void*>(p->d_value), static_cast<void*>(p->d_counts)})
+                    static_cast<void*>(p->d_policy), static_cast<void*>(p->d_value), static_cast<void*>(p->d_counts),
+                    static_cast<void*>(p->d_forced), static_cast<void*>(p->d_line)})
         if (d) hipFree(d);
     if (p->stream) hipStreamDestroy(p->stream);
 }
@@ -466,6 +770,29 @@ int launch_tactics(ao_positions* p, int m, bool audit) {
         default: AO_TACTICS(4); break;
     }
 #undef AO_TACTICS
+    PS_HIP(p, hipGetLastError());
+    return 0;
+}
+
+// k_forced_wins on the m staged ids; the outputs land in d_forced, d_line, d_board (the mask) and d_i32
+int launch_forced(ao_positions* p, int m, int max_depth, int max_nodes) {
+    ao::ForcedParams q{};
+    const size_t cap = static_cast<size_t>(p->cap);
+    q.moves = p->d_moves; q.nmoves = p->d_n;
+    q.n = m; q.stride = p->A; q.B = p->B; q.A = p->A; q.win_mark = p->win_mark;
+    q.max_depth = max_depth; q.max_nodes = max_nodes; q.line_stride = 2 * max_depth - 1;
+    q.result = p->d_forced; q.depth = p->d_forced + cap; q.move = p->d_forced + 2 * cap;
+    q.line_len = p->d_forced + 3 * cap; q.nodes = p->d_forced + 4 * cap;
+    q.status = p->d_i32; q.turn = p->d_i32 + 2 * cap; q.err = p->d_i32 + 3 * cap;
+    q.mask = reinterpret_cast<uint8_t*>(p->d_board);
+    q.line = p->d_line;
+    const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
+    switch ((p->A + 63) / 64) {
+        case 1: hipLaunchKernelGGL(ao::k_forced_wins<1>, grid, block, 0, p->stream, q); break;
+        case 2: hipLaunchKernelGGL(ao::k_forced_wins<2>, grid, block, 0, p->stream, q); break;
+        case 3: hipLaunchKernelGGL(ao::k_forced_wins<3>, grid, block, 0, p->stream, q); break;
+        default: hipLaunchKernelGGL(ao::k_forced_wins<4>, grid, block, 0, p->stream, q); break;
+    }
     PS_HIP(p, hipGetLastError());
     return 0;
 }
@@ -597,6 +924,40 @@ int ao_positions_audit(ao_positions* p, const int32_t* host_moves, int32_t strid
         if (launch_tactics(p, m, true)) return 1;
         if (download(p, host_flags ? host_flags + first * A : nullptr, p->d_legal, m * A) ||
             download(p, host_counts ? host_counts + first * 8 : nullptr, p->d_counts, static_cast<size_t>(m) * 8) ||
+            download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
+            return 1;
+        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+    }
+    return 0;
+}
+
+int ao_positions_forced_wins(ao_positions* p, const int32_t* host_moves, int32_t stride, const int32_t* host_n, int32_t n,
+                             int32_t max_depth, int32_t max_nodes, int32_t* host_result, int32_t* host_depth, int32_t* host_move,
+                             uint8_t* host_moves_mask, int16_t* host_line, int32_t* host_line_len, int32_t* host_nodes,
+                             int32_t* host_status, int32_t* host_turn, int32_t* host_err) {
+    if (n < 0 || stride < 0) return p->fail("ao_positions_forced_wins: negative position count or stride");
+    if (max_depth < 1 || max_depth > ao::kFwMaxDepth) return p->fail("ao_positions_forced_wins: max_depth must be in 1..16");
+    if (max_nodes < 1 || max_nodes > ao::kFwMaxNodes) return p->fail("ao_positions_forced_wins: max_nodes must be in 1..65536");
+    if (n == 0) return 0;
+    if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_forced_wins: null move buffer");
+    PS_HIP(p, hipSetDevice(p->device));
+    const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
+    const size_t lw = static_cast<size_t>(2 * max_depth - 1);
+    if (!p->d_forced) PS_HIP(p, hipMalloc(&p->d_forced, 5 * cap * sizeof(int32_t)));
+    if (!p->d_line) PS_HIP(p, hipMalloc(&p->d_line, cap * (2 * ao::kFwMaxDepth - 1) * sizeof(int16_t)));
+    for (int64_t first = 0; first < n; first += p->cap) {
+        const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
+        if (stage_moves(p, "ao_positions_forced_wins", host_moves, stride, host_n, first, m)) return 1;
+        if (launch_forced(p, m, max_depth, max_nodes)) return 1;
+        if (download(p, host_result ? host_result + first : nullptr, p->d_forced, m) ||
+            download(p, host_depth ? host_depth + first : nullptr, p->d_forced + cap, m) ||
+            download(p, host_move ? host_move + first : nullptr, p->d_forced + 2 * cap, m) ||
+            download(p, host_line_len ? host_line_len + first : nullptr, p->d_forced + 3 * cap, m) ||
+            download(p, host_nodes ? host_nodes + first : nullptr, p->d_forced + 4 * cap, m) ||
+            download(p, host_moves_mask ? host_moves_mask + first * A : nullptr, reinterpret_cast<const uint8_t*>(p->d_board), m * A) ||
+            download(p, host_line ? host_line + first * lw : nullptr, p->d_line, m * lw) ||
+            download(p, host_status ? host_status + first : nullptr, p->d_i32, m) ||
+            download(p, host_turn ? host_turn + first : nullptr, p->d_i32 + 2 * cap, m) ||
             download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
             return 1;
         PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk

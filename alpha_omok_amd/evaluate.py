@@ -244,3 +244,33 @@ def tactical_summary(games, board_size, win_mark=None, device=0):
                          single_threats=int((threat & ~lost).sum()), blocks_missed=int((threat & ~lost & ~blocked).sum()),
                          lost_positions=int(lost.sum()))
     return out
+
+
+def forced_win_summary(games, board_size, max_depth=8, max_nodes=2000, win_mark=None, device=0):
+    """How the games of an evaluation dealt with forced wins by continuous fours: `games` as for tactical_summary; every
+    prefix of every game before its end goes through ONE PositionBatch.forced_wins call. Returns {'black': {...}, 'white':
+    {...}} by the side to move, each with plies (positions searched), forced_wins (result 1 with depth >= 2: a win in one
+    is tactical_summary's business), followed (of those, the move played is one of `moves`), missed (the others) and
+    unknown (the node budget ran out)."""
+    from . import positions as P
+    ids, played = [], []
+    for _, moves in games:
+        moves = [int(m) for m in moves]
+        for t in range(len(moves)):
+            ids.append(moves[:t])
+            played.append(moves[t])
+    with P.PositionBatch(board_size, win_mark=win_mark, capacity=max(1, min(len(ids), 4096)), device=device) as pb:
+        d = pb.forced_wins(ids, max_depth, max_nodes, leading_zero=False)
+    if d["err"].any():
+        raise ValueError("games hold moves that are not legal (prefixes %s)" % np.flatnonzero(d["err"]).tolist()[:8])
+    played = np.array(played, np.int64).reshape(len(ids))
+    open_ = d["status"] == 0                                              # (moves after the end of a game are not plies)
+    forced = open_ & (d["result"] == P.FW_WIN) & (d["depth"] >= 2)
+    followed = forced & (d["moves"][np.arange(len(ids)), played] != 0) if len(ids) else forced
+    out = {}
+    for colour, name in enumerate(("black", "white")):
+        side = d["turn"] == colour
+        out[name] = dict(plies=int((open_ & side).sum()), forced_wins=int((forced & side).sum()),
+                         followed=int((followed & side).sum()), missed=int((forced & ~followed & side).sum()),
+                         unknown=int((open_ & side & (d["result"] == P.FW_UNKNOWN)).sum()))
+    return out

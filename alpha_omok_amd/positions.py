@@ -23,6 +23,9 @@ from .engine import EngineError, _ptr
 ERR_OK, ERR_RANGE, ERR_OCCUPIED, ERR_LENGTH = 0, 1, 2, 3
 # flag bits of one audited ply (PositionBatch.audit; the same values as utils.audit_moves)
 WIN_AVAILABLE, WIN_TAKEN, THREAT, BLOCKED, LOST = 1, 2, 4, 8, 16
+# `result` of PositionBatch.forced_wins and the limits of its search (the same values as utils.forced_win)
+FW_NONE, FW_WIN, FW_UNKNOWN = 0, 1, 2
+FW_MAX_DEPTH, FW_MAX_NODES = 16, 65536
 
 
 def default_win_mark(board_size):
@@ -247,6 +250,31 @@ class PositionBatch:
         self._check(self._L.ao_positions_audit(
             self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, _ptr(out["flags"], C.c_uint8),
             _ptr(out["counts"], C.c_int32), _ptr(out["err"], C.c_int32)), "ao_positions_audit")
+        return out
+
+    def forced_wins(self, root_ids, max_depth=8, max_nodes=2000, leading_zero=True):
+        """Forced wins by continuous fours (VCF) for the side to move, one row per id; utils.forced_win is the definition.
+        dict of result (FW_NONE no forced win within max_depth attacker moves, FW_WIN, FW_UNKNOWN the budget of max_nodes
+        search nodes ran out: everything else of the search is then as for FW_NONE), depth (the fewest attacker moves,
+        0 unless FW_WIN), move (the lowest winning first move, -1 if none), moves (uint8 [n, A]: every first move that
+        wins within depth), line (int16 [n, 2 max_depth - 1]: the principal line, padded with -1), line_len, nodes, and
+        status, turn, err as win_cells (a terminal position has result 0; rows with err != 0 are all zero, move and line
+        -1). 1 <= max_depth <= 16, 1 <= max_nodes <= 65536, ValueError otherwise: the node budget bounds the launch."""
+        for name, v, hi in (("max_depth", max_depth, FW_MAX_DEPTH), ("max_nodes", max_nodes, FW_MAX_NODES)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+                raise ValueError("%s must be an integer in 1..%d, got %r" % (name, hi, v))
+        moves, n = pack_ids(root_ids, leading_zero)
+        cnt = n.shape[0]
+        i32 = lambda: np.zeros(cnt, np.int32)
+        out = dict(result=i32(), depth=i32(), move=i32(), moves=np.zeros((cnt, self.A), np.uint8),
+                   line=np.zeros((cnt, 2 * int(max_depth) - 1), np.int16), line_len=i32(), nodes=i32(), status=i32(),
+                   turn=i32(), err=i32())
+        self._check(self._L.ao_positions_forced_wins(
+            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, int(max_depth), int(max_nodes),
+            _ptr(out["result"], C.c_int32), _ptr(out["depth"], C.c_int32), _ptr(out["move"], C.c_int32),
+            _ptr(out["moves"], C.c_uint8), _ptr(out["line"], C.c_int16), _ptr(out["line_len"], C.c_int32),
+            _ptr(out["nodes"], C.c_int32), _ptr(out["status"], C.c_int32), _ptr(out["turn"], C.c_int32),
+            _ptr(out["err"], C.c_int32)), "ao_positions_forced_wins")
         return out
 
     # -- lifetime

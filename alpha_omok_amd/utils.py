@@ -158,6 +158,210 @@ def audit_moves(moves, board_size, win_mark):
     return flags, counts
 
 
+FW_NONE, FW_WIN, FW_UNKNOWN = 0, 1, 2      # `result` of forced_win / PositionBatch.forced_wins
+FW_MAX_DEPTH, FW_MAX_NODES = 16, 65536
+
+
+class _OutOfNodes(Exception):
+    pass
+
+
+class ArrayPosition:
+    """A position for forced_win with the two inner questions asked literally: check_win and win_cells of the board array.
+    Slow; the yardstick WindowPosition is held to."""
+
+    def __init__(self, board_size, win_mark):
+        self.B, self.k = board_size, win_mark
+        self.board = np.zeros(board_size * board_size, np.int8)
+
+    def place(self, cell, colour):
+        self.board[cell] = 1 if colour == 0 else -1
+
+    def remove(self, cell, colour):
+        self.board[cell] = 0
+
+    def terminal(self):
+        return check_win(self.board.reshape(self.B, self.B), self.k) != 0
+
+    def win_cells(self, turn):
+        mine, theirs = win_cells(self.board.reshape(self.B, self.B), turn, self.k)
+        return np.flatnonzero(mine).tolist(), np.flatnonzero(theirs).tolist()
+
+    def empty_cells(self):
+        return np.flatnonzero(self.board == 0).tolist()
+
+
+class WindowPosition(ArrayPosition):
+    """The same answers from a table of all k-windows (the k cells of every line segment of length k, four directions)
+    with the stones of either colour counted per window as stones come and go: the board has a line if a window holds k
+    stones of one colour, and a window holding k-1 stones of one colour and one empty cell marks that cell as a winning
+    cell of the colour (a stone there completes the window; an overline contains a window). In the style of
+    check_win_boards: the same definition, asked of sums that are kept instead of recomputed. A window's two counts are
+    kept as one code, black + 8 white, and a table turns the code into what the window says: 0 nothing, 1 / 2 black /
+    white is one stone short of it and nothing else is in it, 3 it is a line."""
+    _tables = {}
+
+    def __init__(self, board_size, win_mark):
+        ArrayPosition.__init__(self, board_size, win_mark)
+        key = (board_size, win_mark)
+        if key not in self._tables:
+            B, k = key
+            wins = []
+            for r in range(B):
+                for c in range(B):
+                    for dr, dc in ((0, 1), (1, 0), (1, 1), (1, -1)):
+                        if 0 <= r + (k - 1) * dr < B and 0 <= c + (k - 1) * dc < B:
+                            wins.append([(r + i * dr) * B + c + i * dc for i in range(k)])
+            wins = np.array(wins, np.int64).reshape(-1, k)
+            through = [np.flatnonzero((wins == cell).any(axis=1)) for cell in range(B * B)]
+            says = np.zeros(9 * k + 1, np.int8)
+            says[[k - 1, 8 * (k - 1)]] = 1, 2
+            says[[k, 8 * k]] = 3
+            self._tables[key] = (wins, through, says)
+        self.windows, self.through, self.says = self._tables[key]
+        self.code = np.zeros(self.windows.shape[0], np.int64)
+        self.stones = 0
+        self._said = None                     # says[code] of the position as it stands
+
+    def place(self, cell, colour):
+        ArrayPosition.place(self, cell, colour)
+        self.code[self.through[cell]] += 1 + 7 * colour
+        self.stones += 1
+        self._said = None
+
+    def remove(self, cell, colour):
+        ArrayPosition.remove(self, cell, colour)
+        self.code[self.through[cell]] -= 1 + 7 * colour
+        self.stones -= 1
+        self._said = None
+
+    def _look(self):
+        if self._said is None:
+            said = self.says[self.code]
+            self._said = (said, int(said.max()) if said.size else 0)
+        return self._said
+
+    def terminal(self):
+        return self.stones == self.board.size or self._look()[1] == 3
+
+    def win_cells(self, turn):
+        said, top = self._look()
+        if top == 0 or self.terminal():
+            return [], []
+        out = []
+        for colour in (turn, 1 - turn):
+            cells = self.windows[said == colour + 1].ravel()
+            out.append(np.unique(cells[self.board[cells] == 0]).tolist())
+        return out[0], out[1]
+
+
+def forced_win(moves, board_size, win_mark, max_depth=8, max_nodes=2000, position=WindowPosition):
+    """Is there a forced win by continuous fours (VCF) for the side to move in the position reached by `moves` (legal moves,
+    black first)? No reference counterpart; defined through check_win / win_cells alone. The attacker a is the side to
+    move, cells are always tried in ascending order, and `nodes` counts the wins_within calls of all iterations:
+
+        wins_within(P, d): a to move, at most d attacker moves. No on a terminal P. With (mine, theirs) = win_cells(P, a):
+            yes if mine is not empty; no if d == 1 or theirs holds two or more cells; otherwise yes if four(P, c, d) for
+            some c of theirs (a single threat must be answered) or, theirs empty, of all empty cells -- the first such c.
+        four(P, c, d): P1 = P with a on c. No on a terminal P1. With (his, replies) = win_cells(P1, 1 - a): no if his is
+            not empty (the defender wins first) or replies is empty (c made no four); yes if wins_within(P1 with the
+            defender on b, d - 1) for EVERY b of replies.
+        for D = 1 .. max_depth (iterative deepening, no iteration skipped): the root is wins_within(P, D), except that it
+            tries every candidate and collects those that succeed (mine, if that is not empty) into `moves`; the first
+            D with moves ends the search: result 1, depth D.
+
+    Returns a dict: result (FW_NONE no forced win within max_depth, FW_WIN, FW_UNKNOWN: the wins_within call number
+    max_nodes + 1 was asked for -- then nodes is max_nodes and everything else of the search is zero / -1 / empty, even if
+    a winning move had been found in that iteration), depth (attacker moves, 0 unless result is 1), moves (bool [A]: every
+    first move that wins within depth), move (min(moves) or -1), line (list: min(moves), min(replies), then at every
+    later attacker node the first c that succeeded or min(mine), the defender always on min(replies); it ends on the stone
+    that makes the line and may be shorter than 2 depth - 1), line_len, nodes, status (check_win of the position), turn, and stats
+    (host only: `block_fours` nodes at which a candidate taken from theirs succeeded, `multi_reply` fours with two or more
+    replies that were tried). ValueError for an illegal move list or limits outside 1..16 / 1..65536.
+    `position`: WindowPosition (fast) or ArrayPosition (check_win / win_cells of the array, literally)."""
+    for name, v, hi in (("max_depth", max_depth, FW_MAX_DEPTH), ("max_nodes", max_nodes, FW_MAX_NODES)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError("%s must be an integer in 1..%d, got %r" % (name, hi, v))
+    A = board_size * board_size
+    moves = [int(m) for m in moves]
+    if len(moves) > A:
+        raise ValueError("%d moves on a board of %d cells" % (len(moves), A))
+    pos = position(board_size, win_mark)
+    for t, m in enumerate(moves):
+        if not 0 <= m < A:
+            raise ValueError("move %d is off the board" % m)
+        if pos.board[m] != 0:
+            raise ValueError("move %d is onto a stone" % m)
+        pos.place(m, t % 2)
+    a = len(moves) % 2
+    stats = dict(block_fours=0, multi_reply=0)
+    count = [0]
+    won = []                                  # the root's collection
+
+    def wins_within(d, root=False):
+        """None for no, else the line from here"""
+        count[0] += 1
+        if count[0] > max_nodes:
+            raise _OutOfNodes()
+        if pos.terminal():
+            return None
+        mine, theirs = pos.win_cells(a)
+        if mine:
+            if root:
+                won.extend(mine)
+            return [mine[0]]
+        if d == 1 or len(theirs) >= 2:
+            return None
+        first = None
+        for c in (theirs if theirs else pos.empty_cells()):
+            line = four(c, d)
+            if line is not None:
+                stats["block_fours"] += bool(theirs)
+                if not root:
+                    return line
+                won.append(c)
+                first = first or line
+        return first
+
+    def four(c, d):
+        pos.place(c, a)
+        try:
+            if pos.terminal():                # (only the full board: c is not in mine)
+                return None
+            his, replies = pos.win_cells(1 - a)
+            if his or not replies:
+                return None
+            stats["multi_reply"] += len(replies) >= 2
+            line = None
+            for b in replies:
+                pos.place(b, 1 - a)
+                try:
+                    rest = wins_within(d - 1)
+                finally:
+                    pos.remove(b, 1 - a)
+                if rest is None:
+                    return None
+                line = line or [c, b] + rest
+            return line
+        finally:
+            pos.remove(c, a)
+
+    out = dict(result=FW_NONE, depth=0, moves=np.zeros(A, bool), move=-1, line=[], line_len=0, nodes=0,
+               status=check_win(get_board([0] + moves, board_size), win_mark), turn=a, stats=stats)
+    try:
+        for D in range(1, max_depth + 1):
+            line = wins_within(D, root=True)
+            if won:
+                out["moves"][won] = True
+                out.update(result=FW_WIN, depth=D, move=min(won), line=line, line_len=len(line))
+                break
+    except _OutOfNodes:
+        out.update(result=FW_UNKNOWN, nodes=max_nodes)
+        return out
+    out["nodes"] = count[0]
+    return out
+
+
 def get_state_pt(node_id, board_size, channel_size):
     """Network input planes, float64 [C, B, B] (utils.py:139-168): the stones of the mover of each
     of the last C-1 plies as they stood after that ply, oldest first, then the colour plane."""

@@ -554,6 +554,39 @@ int  ao_positions_win_cells(ao_positions *p, const int32_t *host_moves, int32_t 
  * Chunks, staging and return value as ao_positions_from_moves; n == 0 is a no-op. */
 int  ao_positions_audit(ao_positions *p, const int32_t *host_moves, int32_t stride, const int32_t *host_n, int32_t n,
                         uint8_t *host_flags, int32_t *host_counts, int32_t *host_err);
+/* Forced wins by continuous fours (VCF) for n positions (ids as above). No reference counterpart: the definition asks
+ * utils.check_win (utils.py:30-59) and nothing else, through the winning cells defined above. a is the side to move (the
+ * attacker), cells are always tried in ascending order:
+ *   wins_within(P, d)  a to move, at most d attacker moves. No if check_win(P) != 0. With mine / theirs the winning cells of
+ *                      a / of its opponent in P: yes if mine is not empty; no if d == 1 or theirs holds two or more cells;
+ *                      otherwise yes if four(P, c, d) for some c of theirs or, theirs empty, of all empty cells -- the
+ *                      first such c.
+ *   four(P, c, d)      P1 = P with a on c. No if check_win(P1) != 0, if the defender has a winning cell in P1 or if a has
+ *                      none (c made no four); yes if wins_within(P1 with the defender on b, d - 1) for EVERY winning cell
+ *                      b of a in P1 (the forced replies).
+ *   for D = 1 .. max_depth, no iteration skipped: the root is wins_within(P, D), except that it tries every candidate and
+ *                      collects those that succeed (mine, if that is not empty); the first D with any ends the search.
+ * `nodes` counts the wins_within calls of all iterations; the call number max_nodes + 1 ends the search as UNKNOWN.
+ * utils.forced_win of the Python package is this text on the host. 1 <= max_depth <= 16, 1 <= max_nodes <= 65536 (the
+ * node cap bounds the launch: there is no unlimited mode); outside: non-zero return. Outputs (any may be NULL):
+ *   host_result     int32 [n]     0 no forced win within max_depth, 1 forced win, 2 UNKNOWN: nodes is then max_nodes and
+ *                                 every other output of the search is as for 0, even if a winning move had been found
+ *   host_depth      int32 [n]     the smallest D, in attacker moves; 0 unless result is 1
+ *   host_move       int32 [n]     the lowest cell of host_moves_mask, -1 if there is none
+ *   host_moves_mask uint8 [n][A]  1 on every first move that wins within depth
+ *   host_line       int16 [n][2 * max_depth - 1]  the principal line, padded with -1: host_move, the lowest forced reply,
+ *                                 then at every later attacker node the first c that succeeded (or the lowest cell of
+ *                                 mine) and the lowest forced reply to it; it ends on the stone that makes the line
+ *   host_line_len   int32 [n]     stones in host_line; may be less than 2 * depth - 1
+ *   host_nodes      int32 [n]
+ *   host_status, host_turn, host_err  int32 [n]  as ao_positions_win_cells; a terminal position has result 0, a position
+ *                                 with an error has every output zeroed, move -1 and line -1
+ * One wavefront walks one position depth first (explicit stack in LDS, no recursion). Chunks, staging and return value
+ * as ao_positions_from_moves; n == 0 is a no-op. */
+int  ao_positions_forced_wins(ao_positions *p, const int32_t *host_moves, int32_t stride, const int32_t *host_n, int32_t n,
+                              int32_t max_depth, int32_t max_nodes, int32_t *host_result, int32_t *host_depth,
+                              int32_t *host_move, uint8_t *host_moves_mask, int16_t *host_line, int32_t *host_line_len,
+                              int32_t *host_nodes, int32_t *host_status, int32_t *host_turn, int32_t *host_err);
 
 #ifdef __cplusplus
 }
