@@ -20,6 +20,7 @@
 
 #include "../../include/omok_hip.h"
 #include "engine_types.hpp"
+#include "host_handle.hpp"
 #include "host_rng.hpp"
 #include "snapshot_check.hpp"
 #include "tree_snapshot.hpp"
@@ -54,16 +55,13 @@ void net_plan(const ao_net* n, int boards, int* group, int* nchq, int* kind);
 int net_check(const ao_net* n, int board, int inplanes, int device, std::string* why);
 }  // namespace ao
 
-static thread_local std::string g_create_error;
-
-struct ao_engine {
+struct ao_engine : ao::HandleBase {
     ao_config cfg{};
     ao::TreeParams tp{};
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
-    std::string err;
     int A = 0, Ap = 0, G = 0, Gp = 0, S = 0;
-    std::vector<void*> allocs;
+    ao::DevPool pool;
     // device scratch
     uint8_t* d_active = nullptr; int8_t* d_tau = nullptr; int32_t* d_extra = nullptr;
     uint8_t* d_mask = nullptr;
@@ -104,59 +102,18 @@ struct ao_engine {
     int64_t fp16_events = 0, fp16_games_redone = 0;
     int node_cap_auto = 0;           // 1: node_cap was derived from the free HBM (ao_config.node_cap == -1)
     // tree read-out (ao_tree_lookup / ao_tree_pv / ao_tree_stats): one device workspace, grown on demand, and its host mirror
-    unsigned char* d_ro = nullptr; size_t ro_bytes = 0;
+    ao::DevBuf<unsigned char> d_ro{&pool};
     std::vector<unsigned char> h_ro;
-    // HIP-event timing of the per-simulation tree kernel (k_expand_select) on the launch stream
-    bool timing = false;
-    int timing_stride = 1;      // ao_tree_timing(enable = n > 1): every n-th launch is timed
-    unsigned timing_tick = 0;
-    static constexpr int kRing = 256;
-    std::vector<hipEvent_t> ev0, ev1;
-    int ring_head = 0, ring_count = 0;
-    double ms_total = 0.0;
-    int64_t launches = 0;
-
-    int fail(const std::string& m) { err = m; return 1; }
+    // HIP-event timing of the per-simulation tree kernel (k_expand_select) on the launch stream (ao_tree_timing)
+    ao::EventTimer timer{256};
 };
-
-#define AO_HIP(e, call)                                                                       \
-    do {                                                                                      \
-        hipError_t st_ = (call);                                                              \
-        if (st_ != hipSuccess)                                                                \
-            return (e)->fail(std::string(#call) + ": " + hipGetErrorString(st_));             \
-    } while (0)
-
-template <typename T>
-static int dev_alloc(ao_engine* e, T** out, size_t count) {
-    void* p = nullptr;
-    hipError_t st = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16));
-    if (st != hipSuccess)
-        return e->fail(std::string("hipMalloc(") + std::to_string(count * sizeof(T)) + " B): " +
-                       hipGetErrorString(st));
-    e->allocs.push_back(p);
-    *out = static_cast<T*>(p);
-    return 0;
-}
-
-static void tree_harvest(ao_engine* e, int count) {
-    for (int i = 0; i < count; ++i) {
-        const int idx = (e->ring_head - e->ring_count + ao_engine::kRing * 2) % ao_engine::kRing;
-        (void)hipEventSynchronize(e->ev1[idx]);
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e->ev0[idx], e->ev1[idx]) == hipSuccess) {
-            e->ms_total += ms;
-            e->launches += 1;
-        }
-        --e->ring_count;
-    }
-}
 
 extern "C" {
 
 const char* ao_version(void) { return "alpha_omok_amd 0.1 (gfx950)"; }
 int ao_abi_version(void) { return AO_ABI_VERSION; }
 
-const char* ao_last_error(const ao_engine* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
+const char* ao_last_error(const ao_engine* e) { return e ? e->err.c_str() : ao::create_error<ao_engine>().c_str(); }
 void* ao_stream(ao_engine* e) { return e ? e->stream : nullptr; }
 
 int ao_sync(ao_engine* e) {
@@ -175,16 +132,14 @@ void ao_destroy(ao_engine* e) {
     if (!e) return;
     hipSetDevice(e->cfg.device);
     if (e->stream) hipStreamSynchronize(e->stream);
-    for (void* p : e->allocs) hipFree(p);
-    if (e->d_ro) hipFree(e->d_ro);
+    e->pool.free_all();
     if (e->h_mt) hipHostFree(e->h_mt);
     if (e->h_pos) hipHostFree(e->h_pos);
     if (e->h_noise) hipHostFree(e->h_noise);
     if (e->h_out) hipHostFree(e->h_out);
     if (e->h_i32) hipHostFree(e->h_i32);
     if (e->h_live) hipHostFree(e->h_live);
-    for (auto ev : e->ev0) (void)hipEventDestroy(ev);
-    for (auto ev : e->ev1) (void)hipEventDestroy(ev);
+    e->timer.destroy();
     if (e->own_stream) hipStreamDestroy(e->own_stream);
     delete e;
 }
@@ -271,7 +226,7 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
         void* arena = nullptr;
         const hipError_t st = hipMalloc(&arena, std::max<size_t>(slots * p.rec, 16));
         if (st == hipSuccess) {
-            e->allocs.push_back(arena);
+            e->pool.adopt(arena);
             p.arena = static_cast<unsigned char*>(arena);
             break;
         }
@@ -283,28 +238,28 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
         c.node_cap = p.cap;
         p.keep_max = c.node_cap - c.sims - 1;
     }
-    if (dev_alloc(e, &p.cur, G) || dev_alloc(e, &p.root_node, G) || dev_alloc(e, &p.nodes_used, G) ||
-        dev_alloc(e, &p.rootpos, G) || dev_alloc(e, &p.mt, static_cast<size_t>(G) * 624) ||
-        dev_alloc(e, &p.mtpos, G) || dev_alloc(e, &p.noise_buf, static_cast<size_t>(G) * Ap) ||
-        dev_alloc(e, &p.sims_target, G) || dev_alloc(e, &p.sims_done, G) || dev_alloc(e, &p.gflags, G) ||
-        dev_alloc(e, &p.rstatus, G) || dev_alloc(e, &p.pending_root, G) || dev_alloc(e, &p.leaf_status, G) || dev_alloc(e, &p.path_len, G) ||
-        dev_alloc(e, &p.path_node, static_cast<size_t>(G) * p.maxd) ||
-        dev_alloc(e, &p.path_edge, static_cast<size_t>(G) * p.maxd) || dev_alloc(e, &p.leaf_pos, G) ||
-        dev_alloc(e, &p.err, G) || dev_alloc(e, &p.trimmed, static_cast<size_t>(G) * 2) || dev_alloc(e, &p.stats, static_cast<size_t>(G) * 4) ||
-        dev_alloc(e, &p.out_pi, static_cast<size_t>(G) * A) || dev_alloc(e, &p.out_visit, static_cast<size_t>(G) * A) ||
-        dev_alloc(e, &p.out_policy, static_cast<size_t>(G) * A) || dev_alloc(e, &p.action, G) ||
-        dev_alloc(e, &p.win, G) || dev_alloc(e, &e->d_active, G) || dev_alloc(e, &e->d_tau, G) ||
-        dev_alloc(e, &e->d_extra, static_cast<size_t>(G) * A + 4 * static_cast<size_t>(G)) || dev_alloc(e, &e->d_mask, G))
+    if (e->pool.alloc(e, &p.cur, G) || e->pool.alloc(e, &p.root_node, G) || e->pool.alloc(e, &p.nodes_used, G) ||
+        e->pool.alloc(e, &p.rootpos, G) || e->pool.alloc(e, &p.mt, static_cast<size_t>(G) * 624) ||
+        e->pool.alloc(e, &p.mtpos, G) || e->pool.alloc(e, &p.noise_buf, static_cast<size_t>(G) * Ap) ||
+        e->pool.alloc(e, &p.sims_target, G) || e->pool.alloc(e, &p.sims_done, G) || e->pool.alloc(e, &p.gflags, G) ||
+        e->pool.alloc(e, &p.rstatus, G) || e->pool.alloc(e, &p.pending_root, G) || e->pool.alloc(e, &p.leaf_status, G) || e->pool.alloc(e, &p.path_len, G) ||
+        e->pool.alloc(e, &p.path_node, static_cast<size_t>(G) * p.maxd) ||
+        e->pool.alloc(e, &p.path_edge, static_cast<size_t>(G) * p.maxd) || e->pool.alloc(e, &p.leaf_pos, G) ||
+        e->pool.alloc(e, &p.err, G) || e->pool.alloc(e, &p.trimmed, static_cast<size_t>(G) * 2) || e->pool.alloc(e, &p.stats, static_cast<size_t>(G) * 4) ||
+        e->pool.alloc(e, &p.out_pi, static_cast<size_t>(G) * A) || e->pool.alloc(e, &p.out_visit, static_cast<size_t>(G) * A) ||
+        e->pool.alloc(e, &p.out_policy, static_cast<size_t>(G) * A) || e->pool.alloc(e, &p.action, G) ||
+        e->pool.alloc(e, &p.win, G) || e->pool.alloc(e, &e->d_active, G) || e->pool.alloc(e, &e->d_tau, G) ||
+        e->pool.alloc(e, &e->d_extra, static_cast<size_t>(G) * A + 4 * static_cast<size_t>(G)) || e->pool.alloc(e, &e->d_mask, G))
         return 1;
     // evaluation batches of the native network: interleaved input, policy/value rows for Gp boards
     float* il = nullptr;
-    if (dev_alloc(e, &il, static_cast<size_t>(Gp) * A * p.nchq * 4) ||
-        dev_alloc(e, &e->d_policy, static_cast<size_t>(Gp) * A) || dev_alloc(e, &e->d_value, Gp))
+    if (e->pool.alloc(e, &il, static_cast<size_t>(Gp) * A * p.nchq * 4) ||
+        e->pool.alloc(e, &e->d_policy, static_cast<size_t>(Gp) * A) || e->pool.alloc(e, &e->d_value, Gp))
         return 1;
     p.u8_row = A <= 128 ? 128 : 256;
-    if (dev_alloc(e, &e->d_planes_u8, static_cast<size_t>(Gp) * p.u8_row) || dev_alloc(e, &e->d_row, 2 * static_cast<size_t>(G))) return 1;
-    if (dev_alloc(e, &e->d_mt_backup, static_cast<size_t>(G) * 624) || dev_alloc(e, &e->d_pos_backup, G)) return 1;
-    if (dev_alloc(e, &e->d_live, ao_engine::kLive) || dev_alloc(e, &e->d_log_games, G) || dev_alloc(e, &e->d_ctl, 8) || dev_alloc(e, &e->d_order, G)) return 1;
+    if (e->pool.alloc(e, &e->d_planes_u8, static_cast<size_t>(Gp) * p.u8_row) || e->pool.alloc(e, &e->d_row, 2 * static_cast<size_t>(G))) return 1;
+    if (e->pool.alloc(e, &e->d_mt_backup, static_cast<size_t>(G) * 624) || e->pool.alloc(e, &e->d_pos_backup, G)) return 1;
+    if (e->pool.alloc(e, &e->d_live, ao_engine::kLive) || e->pool.alloc(e, &e->d_log_games, G) || e->pool.alloc(e, &e->d_ctl, 8) || e->pool.alloc(e, &e->d_order, G)) return 1;
     e->order_on = !(getenv("AO_TREE_ORDER") && atoi(getenv("AO_TREE_ORDER")) == 0);
     p.order = nullptr;
     AO_HIP(e, hipMemsetAsync(e->d_row, 0, sizeof(int32_t) * 2 * G, e->stream));
@@ -326,7 +281,7 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
     std::vector<double> lut(lut_n);
     for (int i = 0; i < lut_n; ++i) lut[i] = std::sqrt(static_cast<double>(i));
     double* d_lut = nullptr;
-    if (dev_alloc(e, &d_lut, lut_n)) return 1;
+    if (e->pool.alloc(e, &d_lut, lut_n)) return 1;
     AO_HIP(e, hipMemcpy(d_lut, lut.data(), sizeof(double) * lut_n, hipMemcpyHostToDevice));
     p.sqrt_lut = d_lut; p.sqrt_lut_n = lut_n;
 
@@ -359,16 +314,9 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
 }
 
 int ao_create(const ao_config* cfg, ao_engine** out) {
-    if (!cfg || !out) { g_create_error = "null argument"; return 1; }
+    if (!cfg || !out) { ao::create_error<ao_engine>() = "null argument"; return 1; }
     ao_engine* e = new ao_engine();
-    if (create_impl(e, cfg)) {
-        g_create_error = e->err;
-        ao_destroy(e);
-        *out = nullptr;
-        return 1;
-    }
-    *out = e;
-    return 0;
+    return ao::finish_create(e, create_impl(e, cfg), out, ao_destroy);
 }
 
 // ---- RNG -------------------------------------------------------------------------------------
@@ -885,11 +833,8 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
             return e->fail(std::string("network forward failed: ") + ao_net_last_error(net));
         first_sim = false;
         log_evals(fused ? 2 : 3);   // (before the tree kernel moves on / hands out the next simulation's rows)
-        const bool timed = e->timing && (e->timing_tick++ % static_cast<unsigned>(e->timing_stride) == 0u);   // (see ao_tree_timing)
-        if (timed) {
-            if (e->ring_count == ao_engine::kRing) tree_harvest(e, ao_engine::kRing / 2);
-            (void)hipEventRecord(e->ev0[e->ring_head], e->stream);
-        }
+        const bool timed = e->timer.tick();   // (see ao_tree_timing)
+        if (timed) e->timer.begin(e->stream);
         ++launch;
         if (dynamic && launch % ao_engine::kLive == 0) {   // the counter ring wraps (more than kLive launches in one move): sum it up, zero it
             if (harvest_rows(launch)) return 1;
@@ -903,11 +848,7 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
             set_sit(launch);
             ao::launch_expand_select(p, e->stream);
         }
-        if (timed) {
-            (void)hipEventRecord(e->ev1[e->ring_head], e->stream);
-            e->ring_head = (e->ring_head + 1) % ao_engine::kRing;
-            ++e->ring_count;
-        }
+        if (timed) e->timer.end(e->stream);
         AO_HIP(e, hipGetLastError());
         return 0;
     };
@@ -1163,15 +1104,9 @@ int ao_tree_nodes(ao_engine* e, int g, int64_t* expanded, int64_t* dict_entries)
 static int readout_begin(ao_engine* e, const char* who, size_t bytes) {
     if (e->in_move) return e->fail(std::string(who) + " inside a move (between ao_begin_move and ao_end_move)");
     AO_HIP(e, hipSetDevice(e->cfg.device));
-    if (bytes > e->ro_bytes) {
-        AO_HIP(e, hipStreamSynchronize(e->stream));
-        if (e->d_ro) (void)hipFree(e->d_ro);
-        e->d_ro = nullptr;
-        e->ro_bytes = 0;
-        void* d = nullptr;
-        AO_HIP(e, hipMalloc(&d, bytes));
-        e->d_ro = static_cast<unsigned char*>(d);
-        e->ro_bytes = bytes;
+    if (bytes > e->d_ro.n) {
+        AO_HIP(e, hipStreamSynchronize(e->stream));   // nothing queued reads the old workspace
+        if (e->d_ro.reserve(e, bytes)) return 1;
     }
     if (e->h_ro.size() < bytes) e->h_ro.resize(bytes);
     return 0;
@@ -1220,7 +1155,7 @@ int ao_tree_lookup(ao_engine* e, const int32_t* games, const int32_t* moves, int
             if (extends) std::copy(id + cur.size(), id + m[i], row + 3);
         }
         // device layout of a chunk of c queries: the 8-byte arrays first
-        unsigned char* d = e->d_ro + in_bytes;
+        unsigned char* d = e->d_ro.p + in_bytes;
         double* d_nwqp = reinterpret_cast<double*>(d);
         double* d_cp = d_nwqp + 4 * static_cast<size_t>(c);
         int32_t* d_status = reinterpret_cast<int32_t*>(d_cp + (kids ? cA : 0));
@@ -1230,8 +1165,8 @@ int ao_tree_lookup(ao_engine* e, const int32_t* games, const int32_t* moves, int
         float* d_cw = reinterpret_cast<float*>(d_cn + cA);
         float* d_cq = d_cw + cA;
         const size_t used = static_cast<size_t>(c) * (32 + 8 + (kids ? 24 * static_cast<size_t>(A) : 0));
-        AO_HIP(e, hipMemcpyAsync(e->d_ro, hq, static_cast<size_t>(c) * qs * 4, hipMemcpyHostToDevice, e->stream));
-        ao::launch_tree_lookup(e->tp, reinterpret_cast<const int32_t*>(e->d_ro), c, static_cast<int>(qs), d_status, d_nchild, d_nwqp,
+        AO_HIP(e, hipMemcpyAsync(e->d_ro.p, hq, static_cast<size_t>(c) * qs * 4, hipMemcpyHostToDevice, e->stream));
+        ao::launch_tree_lookup(e->tp, reinterpret_cast<const int32_t*>(e->d_ro.p), c, static_cast<int>(qs), d_status, d_nchild, d_nwqp,
                                kids ? d_ca : nullptr, kids ? d_cn : nullptr, kids ? d_cw : nullptr, kids ? d_cq : nullptr,
                                kids ? d_cp : nullptr, e->stream);
         AO_HIP(e, hipGetLastError());
@@ -1260,15 +1195,15 @@ int ao_tree_pv(ao_engine* e, const uint8_t* mask, int32_t max_len, int32_t* acti
     if (readout_begin(e, "ao_tree_pv", out_bytes + G)) return 1;
     uint8_t* h_mask = e->h_ro.data() + out_bytes;
     readout_mask(e, mask, h_mask);
-    uint8_t* d_mask = e->d_ro + out_bytes;
-    int32_t* d_act = reinterpret_cast<int32_t*>(e->d_ro);
+    uint8_t* d_mask = e->d_ro.p + out_bytes;
+    int32_t* d_act = reinterpret_cast<int32_t*>(e->d_ro.p);
     int32_t* d_n = d_act + GL;
     float* d_q = reinterpret_cast<float*>(d_n + GL);
     int32_t* d_len = reinterpret_cast<int32_t*>(d_q + GL);
     AO_HIP(e, hipMemcpyAsync(d_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
     ao::launch_tree_pv(e->tp, d_mask, max_len, d_act, d_n, d_q, d_len, e->stream);
     AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro, out_bytes, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, out_bytes, hipMemcpyDeviceToHost, e->stream));
     AO_HIP(e, hipStreamSynchronize(e->stream));
     const int32_t* h_act = reinterpret_cast<const int32_t*>(e->h_ro.data());
     const int32_t* h_n = h_act + GL;
@@ -1293,12 +1228,12 @@ int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
     if (readout_begin(e, "ao_tree_stats", 16 * G + G)) return 1;
     uint8_t* h_mask = e->h_ro.data() + 16 * G;
     readout_mask(e, mask, h_mask);
-    uint8_t* d_mask = e->d_ro + 16 * G;
+    uint8_t* d_mask = e->d_ro.p + 16 * G;
     AO_HIP(e, hipMemcpyAsync(d_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
-    if (ao::launch_tree_stats(e->tp, d_mask, reinterpret_cast<int32_t*>(e->d_ro), e->stream))
+    if (ao::launch_tree_stats(e->tp, d_mask, reinterpret_cast<int32_t*>(e->d_ro.p), e->stream))
         return e->fail("ao_tree_stats: the breadth-first queue of a node_cap = " + std::to_string(e->tp.cap) + " arena does not fit the LDS of a workgroup");
     AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro, 16 * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, 16 * G, hipMemcpyDeviceToHost, e->stream));
     AO_HIP(e, hipStreamSynchronize(e->stream));
     const int32_t* h = reinterpret_cast<const int32_t*>(e->h_ro.data());
     for (size_t g = 0; g < G; ++g)
@@ -1381,12 +1316,12 @@ int ao_tree_export(ao_engine* e, const uint8_t* mask, ao_tree_snapshot* out) {
             no += nodes[i];
             eo += edges[i];
         }
-        const ao::SnapDev d = ao::snap_dev_at(e->d_ro, c.N, c.E);
-        AO_HIP(e, hipMemcpyAsync(e->d_ro + tab_at, h_tab, static_cast<size_t>(c.count) * ao::kSnapRow * 4, hipMemcpyHostToDevice, e->stream));
-        if (ao::launch_tree_pack(e->tp, d, reinterpret_cast<const int32_t*>(e->d_ro + tab_at), c.count, e->stream))
+        const ao::SnapDev d = ao::snap_dev_at(e->d_ro.p, c.N, c.E);
+        AO_HIP(e, hipMemcpyAsync(e->d_ro.p + tab_at, h_tab, static_cast<size_t>(c.count) * ao::kSnapRow * 4, hipMemcpyHostToDevice, e->stream));
+        if (ao::launch_tree_pack(e->tp, d, reinterpret_cast<const int32_t*>(e->d_ro.p + tab_at), c.count, e->stream))
             return e->fail("ao_tree_export: the breadth-first queue of a node_cap = " + std::to_string(e->tp.cap) + " arena does not fit the LDS of a workgroup");
         AO_HIP(e, hipGetLastError());
-        AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro, ao::snap_packed_bytes(c.N, c.E), hipMemcpyDeviceToHost, e->stream));
+        AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, ao::snap_packed_bytes(c.N, c.E), hipMemcpyDeviceToHost, e->stream));
         AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffers are reused by the next chunk
         const ao::SnapDev h = ao::snap_dev_at(e->h_ro.data(), c.N, c.E);
         std::memcpy(out->p + e0, h.p, 8 * c.E);
@@ -1423,8 +1358,9 @@ int ao_tree_export(ao_engine* e, const uint8_t* mask, ao_tree_snapshot* out) {
 }
 
 int ao_tree_snapshot_check(const ao_tree_snapshot* snap) {
-    g_create_error = ao::snapshot_check(snap);
-    return g_create_error.empty() ? 0 : 1;
+    std::string& why = ao::create_error<ao_engine>();
+    why = ao::snapshot_check(snap);
+    return why.empty() ? 0 : 1;
 }
 
 int ao_tree_import(ao_engine* e, const int32_t* host_games, int32_t n, const ao_tree_snapshot* snap) {
@@ -1492,10 +1428,10 @@ int ao_tree_import(ao_engine* e, const int32_t* host_games, int32_t n, const ao_
             eo += edges[i];
         }
         const size_t bytes = snap_chunk_bytes(c, A, true);
-        AO_HIP(e, hipMemcpyAsync(e->d_ro, e->h_ro.data(), bytes, hipMemcpyHostToDevice, e->stream));
-        const int32_t* d_tab = reinterpret_cast<const int32_t*>(e->d_ro + tab_at);
+        AO_HIP(e, hipMemcpyAsync(e->d_ro.p, e->h_ro.data(), bytes, hipMemcpyHostToDevice, e->stream));
+        const int32_t* d_tab = reinterpret_cast<const int32_t*>(e->d_ro.p + tab_at);
         const int32_t* d_mv = d_tab + static_cast<size_t>(c.count) * ao::kSnapRow;
-        ao::launch_tree_unpack(e->tp, ao::snap_dev_at(e->d_ro, c.N, c.E), d_tab, d_mv,
+        ao::launch_tree_unpack(e->tp, ao::snap_dev_at(e->d_ro.p, c.N, c.E), d_tab, d_mv,
                                reinterpret_cast<const uint32_t*>(d_mv + static_cast<size_t>(c.count) * A), c.count, e->stream);
         AO_HIP(e, hipGetLastError());
         n0 += c.N;
@@ -1531,23 +1467,7 @@ int ao_tree_import(ao_engine* e, const int32_t* host_games, int32_t n, const ao_
 
 int ao_tree_timing(ao_engine* e, int enable, double* ms_total, int64_t* launches) {
     AO_HIP(e, hipSetDevice(e->cfg.device));
-    if (e->ev0.empty() && enable) {
-        e->ev0.resize(ao_engine::kRing);
-        e->ev1.resize(ao_engine::kRing);
-        for (int i = 0; i < ao_engine::kRing; ++i) {
-            AO_HIP(e, hipEventCreate(&e->ev0[i]));
-            AO_HIP(e, hipEventCreate(&e->ev1[i]));
-        }
-    }
-    tree_harvest(e, e->ring_count);
-    if (ms_total) *ms_total = e->ms_total;
-    if (launches) *launches = e->launches;
-    e->ms_total = 0.0;
-    e->launches = 0;
-    e->timing = enable != 0;
-    e->timing_stride = enable > 1 ? enable : 1;   // every n-th launch carries the event pair (their cost: see net_forward_il)
-    e->timing_tick = 0;
-    return 0;
+    return e->timer.enable(e, enable, ms_total, launches);   // enable = n > 1: every n-th launch carries the event pair (their cost: see net_forward_il)
 }
 
 int ao_trim_stats(ao_engine* e, int64_t* subtrees_dropped, int64_t* reroots_trimmed) {

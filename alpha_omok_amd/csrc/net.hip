@@ -18,6 +18,7 @@
 
 #include "../../include/omok_hip.h"
 #include "engine_types.hpp"
+#include "host_handle.hpp"
 #include "net_device.hpp"
 #include "net_common.hpp"
 #include "net_trunk_f32.hpp"
@@ -31,7 +32,7 @@
 // ==============================================================================================
 // host side
 // ==============================================================================================
-struct ao_net {
+struct ao_net : ao::HandleBase {
     int nb = 0, C = 0, planes = 0, B = 0, A = 0, device = 0;
     int nchq32 = 0;  // input channel quads of the layer-kernel path (groups of 32 boards)
     int nchq16 = 0;  // ... of the group-resident path (groups of 16 boards): multiple of 8
@@ -42,9 +43,8 @@ struct ao_net {
     bool forced_fp32 = false;
     int num_cu = 256;
     bool finalized = false;
-    std::string err;
     std::map<std::string, std::vector<float>> params;
-    std::vector<void*> allocs;                      // workspace (grow-only)
+    ao::DevPool pool;                               // the workspace (grow-only: old buffers stay until destroy) and the parameter buffers
     // parameter buffers: ao_net_finalize runs again after every training step (weights re-exported), always with
     // the same sequence of sizes, so the buffers of the previous export are reused in order instead of ~60
     // hipFree + hipMalloc per export
@@ -89,44 +89,16 @@ struct ao_net {
     long perboard_cells = 2592;
     int force_xt = 0, force_nch = 0;               // AO_XT / AO_NCH: tiling overrides for timing experiments (read at create)  // dynamic-LDS attribute set for this net's device
     bool force_resident = false;                   // AO_FORCE_RESIDENT=1 (read at create): mode 5 runs the resident trunk at ANY group count (boards up to 9x9; tests of that kernel on a few boards, timing)
-    // timing of the dominant kernel (trunk conv launches)
+    // timing of the dominant kernel (trunk conv launches): ao_net_conv_timing(enable), one tick per forward
+    ao::EventTimer timer{512};
     bool timing = false;                           // THIS forward's launches are timed (see net_forward_il)
-    bool timing_on = false;                        // ao_net_conv_timing(enable): every `timing_stride`-th forward is timed
-    int timing_stride = 1;
-    unsigned timing_tick = 0;
-    static constexpr int kRing = 512;
-    std::vector<hipEvent_t> ev0, ev1;
-    int ring_head = 0, ring_count = 0;
-    double ms_total = 0.0;
-    int64_t launches = 0;
     int last_in_kind = 1;                          // input of the most recent forward: 1 fp32 plane batch, 2 the engine's bit planes
     // Two products instead of three (net_trunk_h16.hpp, W16): every conv weight x its layer's power of two is an fp16 number --
     // found out by ao_net_finalize, per export. products_req: 0 = use it when the weights allow, 3 = always three (ao_net_products)
     bool w16 = false;
     int products_req = 0;
     int trunk_fmt = -1;                            // activation format inside the resident split-fp16 trunk (kPairBytes): 0 = two fp16 halves (default), 1 = fp16 high half + one low byte (AO_TRUNK_FMT=1)
-
-    int fail(const std::string& m) { err = m; return 1; }
 };
-
-#define NET_HIP(n, call)                                                                      \
-    do {                                                                                      \
-        hipError_t st_ = (call);                                                              \
-        if (st_ != hipSuccess)                                                                \
-            return (n)->fail(std::string(#call) + ": " + hipGetErrorString(st_));             \
-    } while (0)
-
-static thread_local std::string g_net_create_error;
-
-template <typename T>
-static int net_alloc(ao_net* n, T** out, size_t count) {
-    void* p = nullptr;
-    hipError_t st = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16));
-    if (st != hipSuccess) return n->fail(std::string("hipMalloc: ") + hipGetErrorString(st));
-    n->allocs.push_back(p);
-    *out = static_cast<T*>(p);
-    return 0;
-}
 
 template <typename T>
 static int param_alloc(ao_net* n, T** out, size_t count) {
@@ -137,9 +109,10 @@ static int param_alloc(ao_net* n, T** out, size_t count) {
     }
     void* p = nullptr;
     hipError_t st = hipMalloc(&p, bytes);
-    if (st != hipSuccess) return n->fail(std::string("hipMalloc: ") + hipGetErrorString(st));
+    if (st != hipSuccess) return n->fail(std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(st));
+    n->pool.adopt(p);
     if (n->pcursor < n->pallocs.size()) {
-        (void)hipFree(n->pallocs[n->pcursor].first);
+        n->pool.release(n->pallocs[n->pcursor].first);
         n->pallocs[n->pcursor] = {p, bytes};
     } else {
         n->pallocs.push_back({p, bytes});
@@ -152,34 +125,8 @@ static int param_alloc(ao_net* n, T** out, size_t count) {
 // uploads are queued on the null stream from a staging copy that lives until the end of ao_net_finalize
 static int upload(ao_net* n, float** dst, const std::vector<float>& src) {
     if (param_alloc(n, dst, src.size())) return 1;
-    NET_HIP(n, hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
+    AO_HIP(n, hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
     return 0;
-}
-
-static void harvest(ao_net* n, int count) {
-    for (int i = 0; i < count; ++i) {
-        const int idx = (n->ring_head - n->ring_count + ao_net::kRing * 2) % ao_net::kRing;
-        hipEventSynchronize(n->ev1[idx]);
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, n->ev0[idx], n->ev1[idx]) == hipSuccess) {
-            n->ms_total += ms;
-            n->launches += 1;
-        }
-        --n->ring_count;
-    }
-}
-
-static int timer_begin(ao_net* n, hipStream_t s) {
-    if (n->ring_count == ao_net::kRing) harvest(n, ao_net::kRing / 2);
-    const int idx = n->ring_head;
-    hipEventRecord(n->ev0[idx], s);
-    return idx;
-}
-
-static void timer_end(ao_net* n, int idx, hipStream_t s) {
-    hipEventRecord(n->ev1[idx], s);
-    n->ring_head = (n->ring_head + 1) % ao_net::kRing;
-    ++n->ring_count;
 }
 
 // mode 5 (split-fp16 MFMA trunk: k_trunk16h resident for boards up to 9x9 with >= 192 groups, k_layer16h per
@@ -268,7 +215,7 @@ static void launch_conv(ao_net* n, int layer, const float* in, int cqi, const fl
     const int nblk = groups * BW * NXT;
     const dim3 grid(nblk), block(64 * (n->planes / 32));
     const bool timed = n->timing && layer > 0;
-    const int idx = timed ? timer_begin(n, s) : 0;
+    if (timed) n->timer.begin(s);
     const float4* in4 = reinterpret_cast<const float4*>(in);
     const float4* w4 = reinterpret_cast<const float4*>(n->conv_w[layer]);
     const float4* sc4 = reinterpret_cast<const float4*>(n->conv_sc[layer]);
@@ -280,7 +227,7 @@ static void launch_conv(ao_net* n, int layer, const float* in, int cqi, const fl
     else
         hipLaunchKernelGGL((k_conv3x3<BW, XT, false>), grid, block, 0, s, in4, w4, sc4, sh4,
                            static_cast<const float4*>(nullptr), out4, cqi, n->planes, nblk);
-    if (timed) timer_end(n, idx, s);
+    if (timed) n->timer.end(s);
 }
 
 template <int BW>
@@ -305,13 +252,13 @@ static void launch_trunk16(ao_net* n, const float* in_il, int groups, float* pol
         a.layers[l].sc = reinterpret_cast<const float4*>(n->conv_sc[l]);
         a.layers[l].sh = reinterpret_cast<const float4*>(n->conv_sh[l]);
     }
-    const int idx = n->timing ? timer_begin(n, s) : 0;
+    if (n->timing) n->timer.begin(s);
     // 96 KiB of (unused) dynamic LDS pins one workgroup per CU: with 256 groups every CU of the
     // chip gets exactly one group instead of some CUs receiving two
     // one wave per output-channel tile: 8 waves (2 per SIMD) at 128 channels. (A 2-tiles-per-wave
     // variant with the window in AGPRs was slower and is not instantiated.)
     hipLaunchKernelGGL((k_trunk16<BW, XT, 1>), dim3(groups), dim3(64 * (n->planes / 16)), 96 * 1024, s, a);
-    if (n->timing) timer_end(n, idx, s);
+    if (n->timing) n->timer.end(s);
 }
 
 #if AO_KO == 14 || AO_KO == 15
@@ -325,18 +272,18 @@ __global__ void k_ko_fill(uint4* buf, size_t nquads) {
 static int ensure_workspace(ao_net* n, int boards) {
     boards = (boards + 31) / 32 * 32;
     if (boards <= n->ws_boards) return 0;
-    // grow-only; old buffers stay in n->allocs until destroy (forward sizes rarely change)
+    // grow-only; old buffers stay in n->pool until destroy (forward sizes rarely change)
     const size_t act = static_cast<size_t>(boards) * n->A * n->planes;
-    if (net_alloc(n, &n->act_x, act) || net_alloc(n, &n->act_t, act) ||
-        net_alloc(n, &n->hbuf, static_cast<size_t>(boards) * 3 * n->A) ||
-        net_alloc(n, &n->il_in, static_cast<size_t>(boards) * n->A * std::max(std::max(n->nchq16, n->nchq32), n->nchq1) * 4) ||
-        net_alloc(n, &n->tmp_p, static_cast<size_t>(boards) * n->A) || net_alloc(n, &n->tmp_v, boards))
+    if (n->pool.alloc(n, &n->act_x, act) || n->pool.alloc(n, &n->act_t, act) ||
+        n->pool.alloc(n, &n->hbuf, static_cast<size_t>(boards) * 3 * n->A) ||
+        n->pool.alloc(n, &n->il_in, static_cast<size_t>(boards) * n->A * std::max(std::max(n->nchq16, n->nchq32), n->nchq1) * 4) ||
+        n->pool.alloc(n, &n->tmp_p, static_cast<size_t>(boards) * n->A) || n->pool.alloc(n, &n->tmp_v, boards))
         return 1;
     n->ws_boards = boards;
 #if AO_KO == 14 || AO_KO == 15
     hipLaunchKernelGGL(k_ko_fill, dim3(2048), dim3(256), 0, 0, reinterpret_cast<uint4*>(n->act_x), act / 4);
     hipLaunchKernelGGL(k_ko_fill, dim3(2048), dim3(256), 0, 0, reinterpret_cast<uint4*>(n->act_t), act / 4);
-    NET_HIP(n, hipDeviceSynchronize());
+    AO_HIP(n, hipDeviceSynchronize());
 #endif
     return 0;
 }
@@ -379,11 +326,11 @@ int net_step_params(ao_net* n, int boards, float* policy, float* value, StepNet*
 int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, float* value, hipStream_t s, int in_kind, int parts,
                    const unsigned* live, unsigned row_cap) {
     if (!n->finalized) return n->fail("ao_net_finalize has not been called");
-    NET_HIP(n, hipSetDevice(n->device));
+    AO_HIP(n, hipSetDevice(n->device));
     if (ensure_workspace(n, boards)) return 1;
     // HIP-event timing of the conv launches: a pair of event records costs ~1 % of a 1.5 ms step when every launch carries one
     // (tools/time_move_phases.py --events); with a stride only every n-th forward is timed -- the mean is the same estimate
-    n->timing = n->timing_on && (n->timing_tick++ % static_cast<unsigned>(n->timing_stride) == 0u);
+    n->timing = n->timer.tick();
     int group = 32, nchq = 0, nch = 1;
     bool heads_h16 = false;   // the separate head kernels read the split-fp16 layout
     net_plan(n, boards, &group, &nchq, nullptr);
@@ -402,7 +349,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             const dim3 grid(((n->A + 15) / 16) * (n->planes / 16) * boards), block(64 * nw);
             const float4* w4 = reinterpret_cast<const float4*>(layer == 0 ? n->conv0_w1 : n->conv_w[layer]);
             const bool timed = n->timing && layer > 0;
-            const int idx = timed ? timer_begin(n, s) : 0;
+            if (timed) n->timer.begin(s);
             const bool use_h = nw == 9 && layer > 0 && h16_supported(n) && !getenv("AO_CELLS_F32");
             if (use_h) {
                 // boards per workgroup: the weights are loaded once per workgroup, so as many boards as still leave every CU
@@ -430,7 +377,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
                     AO_BW_CASE(10) AO_BW_CASE(11) AO_BW_CASE(12) AO_BW_CASE(13) AO_BW_CASE(14) AO_BW_CASE(15)
 #undef AO_BW_CASE
                 }
-                if (timed) timer_end(n, idx, s);
+                if (timed) n->timer.end(s);
                 return;
             }
             switch (n->B) {
@@ -460,7 +407,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
 #undef AO_CELLS_LAUNCH
 #undef AO_CELLS_LAUNCH2
             }
-            if (timed) timer_end(n, idx, s);
+            if (timed) n->timer.end(s);
         };
         if (parts & 1) conv(0, in_il, n->nchq1, nullptr, n->act_x);
         for (int i = 0; i < n->nb && (parts & 2); ++i) {
@@ -471,7 +418,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
         if (parts & 4)
             hipLaunchKernelGGL(k_heads_board, dim3(boards), dim3(1024), lds1, s, head_params(n),
                                reinterpret_cast<const float4*>(n->act_x), policy, value, n->A, n->planes);
-        NET_HIP(n, hipGetLastError());
+        AO_HIP(n, hipGetLastError());
 #ifdef AO_PROF
         if (getenv("AO_PROF_PRINT")) {
             unsigned long long h[8];
@@ -534,11 +481,11 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             a.nch = groups;
             a.live = live; a.row_cap = row_cap;
             const dim3 grid(rowk ? (groups + 7) / 8 * 8 * 4 * n->B : (groups + 7) / 8 * 8 * ks), block(512);
-            const int idx = n->timing ? timer_begin(n, s) : 0;
+            if (n->timing) n->timer.begin(s);
             if (two_products(n) && (rowk || ks == 4)) {
-                if (rowk) NET_HIP(n, ao::launch_row16hk_w16(n->device, n->B, grid, s, a));
-                else NET_HIP(n, ao::launch_layer16hk_w16(n->device, n->B, grid, s, a));
-                if (n->timing) timer_end(n, idx, s);
+                if (rowk) AO_HIP(n, ao::launch_row16hk_w16(n->device, n->B, grid, s, a));
+                else AO_HIP(n, ao::launch_layer16hk_w16(n->device, n->B, grid, s, a));
+                if (n->timing) n->timer.end(s);
                 return 0;
             }
             if (rowk) {
@@ -547,7 +494,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
     case W: {                                                                                                          \
         constexpr size_t lds_ = static_cast<size_t>(W) * 8 * 1024;                                                     \
         if (!n->attr_r[W]) {                                                                                           \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_row16hk<W>),                               \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_row16hk<W>),                               \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
             n->attr_r[W] = true;                                                                                       \
         }                                                                                                              \
@@ -557,7 +504,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
 #undef AO_BW_CASE
                     default: return n->fail("k_row16hk: board outside 4 .. 9");
                 }
-                if (n->timing) timer_end(n, idx, s);
+                if (n->timing) n->timer.end(s);
                 return 0;
             }
             switch (n->B) {
@@ -565,9 +512,9 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
     case W: {                                                                                                          \
         constexpr size_t lds_ = static_cast<size_t>(2) * W * 8 * 1024;                                                 \
         if (!n->attr_k[W]) {                                                                                           \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16hk<W, 4>),                          \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16hk<W, 4>),                          \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16hk<W, 2>),                          \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16hk<W, 2>),                          \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
             n->attr_k[W] = true;                                                                                       \
         }                                                                                                              \
@@ -578,7 +525,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
 #undef AO_BW_CASE
                 default: return n->fail("k_layer16hk: board outside 4 .. 9");
             }
-            if (n->timing) timer_end(n, idx, s);
+            if (n->timing) n->timer.end(s);
             return 0;
         };
         auto layer = [&](int l) -> int {
@@ -596,10 +543,10 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             a.live = live; a.row_cap = row_cap;
             const dim3 grid(groups * nchh * nxt), block(512);
             const bool timed = n->timing && l > 0;
-            const int idx = timed ? timer_begin(n, s) : 0;
+            if (timed) n->timer.begin(s);
             if (l > 0 && two_products(n)) {
-                NET_HIP(n, ao::launch_layer16h_w16(n->device, n->B, xt, grid, s, a));
-                if (timed) timer_end(n, idx, s);
+                AO_HIP(n, ao::launch_layer16h_w16(n->device, n->B, xt, grid, s, a));
+                if (timed) n->timer.end(s);
                 return 0;
             }
 #define AO_LAYERH_LAUNCH(W, XT_)                                                                                       \
@@ -607,11 +554,11 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
         constexpr int NX_ = (XT_ < W) ? XT_ + 2 : XT_;                                                                 \
         constexpr size_t lds_ = static_cast<size_t>(2) * NX_ * 4 * 2 * 1024;                                           \
         if (!n->attr_l[W][XT_ == 4]) {                                                                                 \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16h<W, XT_, 4, 0>),                   \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16h<W, XT_, 4, 0>),                   \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16h<W, XT_, 4, 1>),                   \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16h<W, XT_, 4, 1>),                   \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16h<W, XT_, 4, 2>),                   \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_layer16h<W, XT_, 4, 2>),                   \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
             n->attr_l[W][XT_ == 4] = true;                                                                             \
         }                                                                                                              \
@@ -631,7 +578,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
 #undef AO_BW_CASE
 #undef AO_LAYERH_LAUNCH
             }
-            if (timed) timer_end(n, idx, s);
+            if (timed) n->timer.end(s);
             return 0;
         };
         if (board_resident(n, boards)) {
@@ -656,18 +603,18 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             }
             // (the kernel deals boards to workgroups in rounds of 8 groups -- a group's 16 boards on one XCD --, so the grid covers whole rounds)
             const dim3 grid(std::min((boards + 127) / 128 * 128, n->num_cu)), block(512);
-            const int idx = n->timing ? timer_begin(n, s) : 0;
+            if (n->timing) n->timer.begin(s);
             if (two_products(n)) {
-                NET_HIP(n, ao::launch_boardh_w16(n->device, n->B, bits, grid, s, a));
+                AO_HIP(n, ao::launch_boardh_w16(n->device, n->B, bits, grid, s, a));
             } else
             switch (n->B) {
 #define AO_BW_CASE(W)                                                                                                  \
     case W: {                                                                                                          \
         constexpr size_t lds_ = static_cast<size_t>(W) * 8 * 1024;                                                     \
         if (!n->attr_b[W]) {                                                                                           \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_boardh<W, 1>),                             \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_boardh<W, 1>),                             \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_boardh<W, 2>),                             \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_boardh<W, 2>),                             \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_)));       \
             n->attr_b[W] = true;                                                                                       \
         }                                                                                                              \
@@ -678,19 +625,19 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
 #undef AO_BW_CASE
                 default: return n->fail("k_boardh: board outside 10 .. 15");
             }
-            if (n->timing) timer_end(n, idx, s);
-            NET_HIP(n, hipGetLastError());
+            if (n->timing) n->timer.end(s);
+            AO_HIP(n, hipGetLastError());
             // the FC layers of the heads on the kernel's hbuf (the 1x1 head convs ran in its last epilogue)
             const size_t lds1 = (static_cast<size_t>(4) * n->A + n->planes + 8) * sizeof(float);
             hipLaunchKernelGGL(k_head_fc, dim3(boards), dim3(256), lds1, s, n->hbuf, n->wp_t, n->bp, n->w1_t, n->b1, n->w2, n->b2, policy, value,
                                n->A, n->planes);
-            NET_HIP(n, hipGetLastError());
+            AO_HIP(n, hipGetLastError());
             return 0;
         } else {
             for (int l = 0; l <= 2 * n->nb; ++l)
                 if (layer(l)) return 1;
         }
-        NET_HIP(n, hipGetLastError());
+        AO_HIP(n, hipGetLastError());
         heads_h16 = true;   // k_head_conv<true> / k_head_fc below
     } else if (group == 16 && mode == 5) {
         // split-fp16 resident trunk: one launch carries every 16-board group through conv1 (fp32 planes converted
@@ -714,10 +661,10 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             a.layers[l].sh = reinterpret_cast<const float4*>(n->conv_sh[l]);
             a.layers[l].ovf = n->d_status;
         }
-        const int idx = n->timing ? timer_begin(n, s) : 0;
+        if (n->timing) n->timer.begin(s);
         if (two_products(n) && n->trunk_fmt != 1) {
             if (n->B > 9) return n->fail("split-fp16 trunk: board larger than 9x9");
-            NET_HIP(n, ao::launch_trunk16h_w16(n->device, n->B, in_kind, groups, s, a));
+            AO_HIP(n, ao::launch_trunk16h_w16(n->device, n->B, in_kind, groups, s, a));
         } else
         switch (n->B) {
 #define AO_BW_CASE(W)                                                                                        \
@@ -726,13 +673,13 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
         constexpr size_t rows_ = static_cast<size_t>(2) * W * 4 * 2 * 1024 + 64;   /* two row buffers + the split-barrier counter */ \
         constexpr size_t lds_ = (rows_ > heads_) ? rows_ : heads_;                                            \
         if (!n->attr_done[W]) {                                                                                 \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16h<W, 4, 0>),              \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16h<W, 4, 0>),              \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_))); \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16hb<W, 4, 0>),              \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16hb<W, 4, 0>),              \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_))); \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16h<W, 4, 1>),              \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16h<W, 4, 1>),              \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_))); \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16hb<W, 4, 1>),              \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16hb<W, 4, 1>),              \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_))); \
             n->attr_done[W] = true;                                                                           \
         }                                                                                                    \
@@ -748,8 +695,8 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
 #undef AO_BW_CASE
             default: return n->fail("split-fp16 trunk: board larger than 9x9");
         }
-        if (n->timing) timer_end(n, idx, s);
-        NET_HIP(n, hipGetLastError());
+        if (n->timing) n->timer.end(s);
+        AO_HIP(n, hipGetLastError());
 #ifdef AO_PROF
         if (getenv("AO_PROF_PRINT")) {
             unsigned long long h[96];
@@ -777,7 +724,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             a.nsplit = (n->planes + 127) / 128;           // output channels beyond 128: a second workgroup per (group, chunk)
             const dim3 grid(groups * nch * a.nsplit), block(64 * std::min(8, n->planes / 16));
             const bool timed = n->timing && l > 0;
-            const int idx = timed ? timer_begin(n, s) : 0;
+            if (timed) n->timer.begin(s);
             switch (n->B) {
 #define AO_BW_CASE(W)                                                                       \
     case W: {                                                                               \
@@ -788,7 +735,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
                 AO_BW_CASE(10) AO_BW_CASE(11) AO_BW_CASE(12) AO_BW_CASE(13) AO_BW_CASE(14) AO_BW_CASE(15)
 #undef AO_BW_CASE
             }
-            if (timed) timer_end(n, idx, s);
+            if (timed) n->timer.end(s);
         };
         layer(0, in_il, n->nchq16, (n->C + 3) / 4, false, n->act_x);
         for (int i = 0; i < n->nb; ++i) {
@@ -802,7 +749,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
     case W: {                                                                                                \
         constexpr int XT_ = (W <= 9) ? W : 5;                                                                \
         if (!n->lds_attr_done[W]) {                                                                             \
-            NET_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16<W, XT_, 1>),             \
+            AO_HIP(n, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trunk16<W, XT_, 1>),             \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));          \
         }                                                                                                    \
         n->lds_attr_done[W] = true;                                                                             \
@@ -812,7 +759,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             AO_BW_CASE(10) AO_BW_CASE(11) AO_BW_CASE(12) AO_BW_CASE(13) AO_BW_CASE(14) AO_BW_CASE(15)
 #undef AO_BW_CASE
         }
-        NET_HIP(n, hipGetLastError());
+        AO_HIP(n, hipGetLastError());
         return 0;  // the heads ran inside the resident kernel
     } else {
         auto conv = [&](int layer, const float* in, int cqi, const float* res, float* out) {
@@ -842,7 +789,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
     const size_t lds = (static_cast<size_t>(4) * n->A + n->planes + 8) * sizeof(float);
     hipLaunchKernelGGL(k_head_fc, dim3(groups * group), dim3(256), lds, s, n->hbuf, n->wp_t, n->bp, n->w1_t,
                        n->b1, n->w2, n->b2, policy, value, n->A, n->planes);
-    NET_HIP(n, hipGetLastError());
+    AO_HIP(n, hipGetLastError());
     return 0;
 }
 
@@ -866,26 +813,22 @@ int net_fp16_fallback_end(ao_net* n) {
 
 extern "C" {
 
-const char* ao_net_last_error(const ao_net* n) { return n ? n->err.c_str() : g_net_create_error.c_str(); }
+const char* ao_net_last_error(const ao_net* n) { return n ? n->err.c_str() : ao::create_error<ao_net>().c_str(); }
 
-int ao_net_create(int n_block, int inplanes, int planes, int board, int device, ao_net** out) {
-    if (!out) return 1;
-    *out = nullptr;
-    auto bad = [&](const char* m) { g_net_create_error = m; return 1; };
-    if (n_block < 0 || n_block > 64) return bad("n_block out of range");
-    if (inplanes < 1 || inplanes > 12) return bad("inplanes must be in 1..12");
+static int net_create_impl(ao_net* n, int n_block, int inplanes, int planes, int board, int device) {
+    n->device = device;
+    if (n_block < 0 || n_block > 64) return n->fail("n_block out of range");
+    if (inplanes < 1 || inplanes > 12) return n->fail("inplanes must be in 1..12");
     // 32 .. 128 planes: every path (128: the split-fp16 MFMA kernels). 160 .. 512: the row-chunked fp32-MFMA layer kernels
     // (mode 4) for every batch size, a group's output channels split over two .. four workgroups (k_layer16) -- model.py:76-85
     // takes any `planes`: other widths reach this call zero-padded to the next multiple of 32 (pvnet.pad_state_dict); beyond 512
     // the caller's torch module evaluates (alpha_omok_amd/evaluator.py: a RuntimeWarning, or an error with strict_native)
-    if (planes < 32 || planes > 512 || planes % 32) return bad("planes must be a multiple of 32 in 32 .. 512");
-    if (board < 3 || board > ao::kMaxBoard) return bad("board must be in 3..15");
+    if (planes < 32 || planes > 512 || planes % 32) return n->fail("planes must be a multiple of 32 in 32 .. 512");
+    if (board < 3 || board > ao::kMaxBoard) return n->fail("board must be in 3..15");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return bad("no HIP device available");
-    if (device < 0 || device >= ndev) return bad("device ordinal out of range");
-    ao_net* n = new ao_net();
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return n->fail("no HIP device available");
+    if (device < 0 || device >= ndev) return n->fail("device ordinal out of range");
     n->nb = n_block; n->C = inplanes; n->planes = planes; n->B = board; n->A = board * board;
-    n->device = device;
     n->nchq32 = (((inplanes + 3) / 4) + 1) & ~1;  // consumed in pairs (32x32x2 MFMA, two quads per step)
     n->nchq16 = (((inplanes + 3) / 4) + 7) & ~7;  // 16 channels per k-step, steps taken in pairs
     n->nchq1 = (((inplanes + 3) / 4) + 3) & ~3;   // 16 channels per k-step
@@ -914,7 +857,6 @@ int ao_net_create(int n_block, int inplanes, int planes, int board, int device, 
     if (const char* v = getenv("AO_XT")) n->force_xt = atoi(v) == 4 ? 4 : (atoi(v) == 5 ? 5 : 0);
     if (const char* v = getenv("AO_NCH")) n->force_nch = atoi(v) > 0 && atoi(v) <= board ? atoi(v) : 0;
     if (const char* v = getenv("AO_FORCE_RESIDENT")) n->force_resident = atoi(v) != 0;
-    *out = n;
     return 0;
 }
 
@@ -922,11 +864,15 @@ void ao_net_destroy(ao_net* n) {
     if (!n) return;
     hipSetDevice(n->device);
     hipDeviceSynchronize();
-    for (void* p : n->allocs) hipFree(p);
-    for (auto& pa : n->pallocs) hipFree(pa.first);
-    for (auto e : n->ev0) hipEventDestroy(e);
-    for (auto e : n->ev1) hipEventDestroy(e);
+    n->pool.free_all();
+    n->timer.destroy();
     delete n;
+}
+
+int ao_net_create(int n_block, int inplanes, int planes, int board, int device, ao_net** out) {
+    if (!out) return 1;
+    ao_net* n = new ao_net();
+    return ao::finish_create(n, net_create_impl(n, n_block, inplanes, planes, board, device), out, ao_net_destroy);
 }
 
 int ao_net_set_mode(ao_net* n, int mode) {
@@ -1016,8 +962,8 @@ static void pack_conv_h(const std::vector<float>& w, int cout, int cin, int s, s
 
 
 int ao_net_finalize(ao_net* n) {
-    NET_HIP(n, hipSetDevice(n->device));
-    NET_HIP(n, hipDeviceSynchronize());   // nothing may still read the buffers that are overwritten below
+    AO_HIP(n, hipSetDevice(n->device));
+    AO_HIP(n, hipDeviceSynchronize());   // nothing may still read the buffers that are overwritten below
     n->pcursor = 0;
     n->fp16_fallbacks = 0;                // new weights: what the old ones did to the fp16 range says nothing about these
     n->forced_fp32 = false;
@@ -1025,7 +971,7 @@ int ao_net_finalize(ao_net* n) {
     n->conv_w.clear(); n->conv_sc.clear(); n->conv_sh.clear();
     n->convh_wh.clear(); n->convh_wl.clear(); n->convh_sc.clear();
     if (param_alloc(n, &n->d_status, 4)) return 1;
-    NET_HIP(n, hipMemset(n->d_status, 0, 16));
+    AO_HIP(n, hipMemset(n->d_status, 0, 16));
     const int P = n->planes, A = n->A;
     // The repacking of the conv weights (strided scatters over 147 k weights per layer and layout) is the bulk of a
     // re-export: it runs on one host thread per layer, the uploads follow in a fixed order (param_alloc's sequence).
@@ -1102,8 +1048,8 @@ int ao_net_finalize(ao_net* n) {
             uint16_t *dh = nullptr, *dl = nullptr;
             float* dsc = nullptr;
             if (param_alloc(n, &dh, pk[l].hi.size()) || param_alloc(n, &dl, pk[l].lo.size())) return 1;
-            NET_HIP(n, hipMemcpy(dh, pk[l].hi.data(), pk[l].hi.size() * 2, hipMemcpyHostToDevice));
-            NET_HIP(n, hipMemcpy(dl, pk[l].lo.data(), pk[l].lo.size() * 2, hipMemcpyHostToDevice));
+            AO_HIP(n, hipMemcpy(dh, pk[l].hi.data(), pk[l].hi.size() * 2, hipMemcpyHostToDevice));
+            AO_HIP(n, hipMemcpy(dl, pk[l].lo.data(), pk[l].lo.size() * 2, hipMemcpyHostToDevice));
             if (upload(n, &dsc, sc)) return 1;
             n->convh_wh.push_back(reinterpret_cast<uint4*>(dh));
             n->convh_wl.push_back(reinterpret_cast<uint4*>(dl));
@@ -1130,8 +1076,8 @@ int ao_net_finalize(ao_net* n) {
                 }
         uint16_t *dh = nullptr, *dl = nullptr;
         if (param_alloc(n, &dh, hi.size()) || param_alloc(n, &dl, lo.size())) return 1;
-        NET_HIP(n, hipMemcpy(dh, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
-        NET_HIP(n, hipMemcpy(dl, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
+        AO_HIP(n, hipMemcpy(dh, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
+        AO_HIP(n, hipMemcpy(dl, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
         n->step_w1h = reinterpret_cast<uint4*>(dh);
         n->step_w1l = reinterpret_cast<uint4*>(dl);
     }
@@ -1161,7 +1107,7 @@ int ao_net_finalize(ao_net* n) {
         upload(n, &n->wp_t, wp_t) || upload(n, &n->bp, *fcb) || upload(n, &n->w1_t, w1_t) ||
         upload(n, &n->b1, *f1b) || upload(n, &n->w2, *f2w) || upload(n, &n->b2, *f2b))
         return 1;
-    NET_HIP(n, hipDeviceSynchronize());
+    AO_HIP(n, hipDeviceSynchronize());
     n->finalized = true;
     return 0;
 }
@@ -1170,7 +1116,7 @@ int ao_net_forward(ao_net* n, const float* dev_planes_nchw, int batch, float* de
                    void* stream) {
     if (!n->finalized) return n->fail("ao_net_finalize has not been called");
     if (batch < 1) return n->fail("batch must be >= 1");
-    NET_HIP(n, hipSetDevice(n->device));
+    AO_HIP(n, hipSetDevice(n->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (ao::ensure_workspace(n, batch)) return 1;
     int group = 32, nchq = 0;
@@ -1184,47 +1130,31 @@ int ao_net_forward(ao_net* n, const float* dev_planes_nchw, int batch, float* de
                        dev_planes_nchw, reinterpret_cast<float4*>(n->il_in), batch, n->C, n->A, nchq, boards, group);
     if (ao::net_forward_il(n, n->il_in, batch, pol, val, s, 1, 7, nullptr, 0u)) return 1;
     if (boards != batch) {
-        NET_HIP(n, hipMemcpyAsync(dev_policy, n->tmp_p, sizeof(float) * batch * n->A, hipMemcpyDeviceToDevice, s));
-        NET_HIP(n, hipMemcpyAsync(dev_value, n->tmp_v, sizeof(float) * batch, hipMemcpyDeviceToDevice, s));
+        AO_HIP(n, hipMemcpyAsync(dev_policy, n->tmp_p, sizeof(float) * batch * n->A, hipMemcpyDeviceToDevice, s));
+        AO_HIP(n, hipMemcpyAsync(dev_value, n->tmp_v, sizeof(float) * batch, hipMemcpyDeviceToDevice, s));
     }
     return 0;
 }
 
 int ao_net_status(ao_net* n, void* stream, int32_t* flags, int clear) {
     if (!n->finalized) return n->fail("ao_net_finalize has not been called");
-    NET_HIP(n, hipSetDevice(n->device));
+    AO_HIP(n, hipSetDevice(n->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     int32_t f = 0;
-    NET_HIP(n, hipMemcpyAsync(&f, n->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    NET_HIP(n, hipStreamSynchronize(s));
+    AO_HIP(n, hipMemcpyAsync(&f, n->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    AO_HIP(n, hipStreamSynchronize(s));
     if (clear && f) {
-        NET_HIP(n, hipMemsetAsync(n->d_status, 0, sizeof(int32_t), s));
-        NET_HIP(n, hipStreamSynchronize(s));
+        AO_HIP(n, hipMemsetAsync(n->d_status, 0, sizeof(int32_t), s));
+        AO_HIP(n, hipStreamSynchronize(s));
     }
     if (flags) *flags = f;
     return 0;
 }
 
 int ao_net_conv_timing(ao_net* n, int enable, double* ms_total, int64_t* launches) {
-    NET_HIP(n, hipSetDevice(n->device));
-    if (n->ev0.empty() && enable) {
-        n->ev0.resize(ao_net::kRing);
-        n->ev1.resize(ao_net::kRing);
-        for (int i = 0; i < ao_net::kRing; ++i) {
-            NET_HIP(n, hipEventCreate(&n->ev0[i]));
-            NET_HIP(n, hipEventCreate(&n->ev1[i]));
-        }
-    }
-    harvest(n, n->ring_count);
-    if (ms_total) *ms_total = n->ms_total;
-    if (launches) *launches = n->launches;
-    n->ms_total = 0.0;
-    n->launches = 0;
-    n->timing_on = enable != 0;
-    n->timing_stride = enable > 1 ? enable : 1;
-    n->timing_tick = 0;
+    AO_HIP(n, hipSetDevice(n->device));
     n->timing = false;
-    return 0;
+    return n->timer.enable(n, enable, ms_total, launches);
 }
 
 // Name (as rocprofv3 prints it, template arguments included) and algorithmic FLOPs per launch of the kernel that

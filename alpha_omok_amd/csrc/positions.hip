@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/omok_hip.h"
+#include "host_handle.hpp"
 #include "tree_device.hpp"
 
 namespace ao {
@@ -661,43 +662,25 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
 
 }  // namespace ao
 
-struct ao_positions {
+struct ao_positions : ao::HandleBase {
     int B = 0, A = 0, C = 0, win_mark = 0, cap = 0, device = 0;
     hipStream_t stream = nullptr;
+    ao::DevPool pool;
     int32_t* d_moves = nullptr;    // [cap][A]
     int32_t* d_n = nullptr;        // [cap]
     int32_t* d_i32 = nullptr;      // [4][cap]: status, end_ply, turn, err
     int8_t* d_board = nullptr;     // [cap][A] (boards in for check_win, boards out for from_moves)
     uint8_t* d_legal = nullptr;    // [cap][A]
-    float* d_planes = nullptr;     // [cap][C][A]   -- the three below: allocated by the first ao_positions_evaluate
-    float* d_policy = nullptr;     // [cap][A]
-    float* d_value = nullptr;      // [cap]
-    int32_t* d_counts = nullptr;   // [cap][8]      -- allocated by the first ao_positions_audit
-    int32_t* d_forced = nullptr;   // [5][cap]: result, depth, move, line_len, nodes -- these two: by the first ao_positions_forced_wins
-    int16_t* d_line = nullptr;     // [cap][2 * 16 - 1]
+    ao::DevBuf<float> d_planes{&pool};     // [cap][C][A]   -- the three below: allocated by the first ao_positions_evaluate
+    ao::DevBuf<float> d_policy{&pool};     // [cap][A]
+    ao::DevBuf<float> d_value{&pool};      // [cap]
+    ao::DevBuf<int32_t> d_counts{&pool};   // [cap][8]      -- allocated by the first ao_positions_audit
+    ao::DevBuf<int32_t> d_forced{&pool};   // [5][cap]: result, depth, move, line_len, nodes -- these two: by the first ao_positions_forced_wins
+    ao::DevBuf<int16_t> d_line{&pool};     // [cap][2 * 16 - 1]
     std::vector<int32_t> h_moves, h_n;
-    std::string err;
-    int fail(const std::string& m) { err = m; return 1; }
 };
 
-static thread_local std::string g_positions_create_error;
-
-#define PS_HIP(p, call)                                                                        \
-    do {                                                                                       \
-        hipError_t st_ = (call);                                                               \
-        if (st_ != hipSuccess) return (p)->fail(std::string(#call) + ": " + hipGetErrorString(st_)); \
-    } while (0)
-
 namespace {
-
-void positions_free(ao_positions* p) {
-    for (void* d : {static_cast<void*>(p->d_moves), static_cast<void*>(p->d_n), static_cast<void*>(p->d_i32),
-                    static_cast<void*>(p->d_board), static_cast<void*>(p->d_legal), static_cast<void*>(p->d_planes),
-                    static_cast<void*>(p->d_policy), static_cast<void*>(p->d_value), static_cast<void*>(p->d_counts),
-                    static_cast<void*>(p->d_forced), static_cast<void*>(p->d_line)})
-        if (d) hipFree(d);
-    if (p->stream) hipStreamDestroy(p->stream);
-}
 
 // positions [first, first + m) of the caller's move lists -> d_moves [m][A] / d_n [m] (lists the kernel refuses by their
 // length are uploaded empty: only the length is looked at)
@@ -712,8 +695,8 @@ int stage_moves(ao_positions* p, const char* who, const int32_t* host_moves, int
         if (nm > stride) return p->fail(std::string(who) + ": position " + std::to_string(first + k) + " has more moves than `stride`");
         std::memcpy(p->h_moves.data() + static_cast<size_t>(k) * A, host_moves + (first + k) * static_cast<int64_t>(stride), sizeof(int32_t) * nm);
     }
-    PS_HIP(p, hipMemcpyAsync(p->d_moves, p->h_moves.data(), sizeof(int32_t) * m * A, hipMemcpyHostToDevice, p->stream));
-    PS_HIP(p, hipMemcpyAsync(p->d_n, p->h_n.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, p->stream));
+    AO_HIP(p, hipMemcpyAsync(p->d_moves, p->h_moves.data(), sizeof(int32_t) * m * A, hipMemcpyHostToDevice, p->stream));
+    AO_HIP(p, hipMemcpyAsync(p->d_n, p->h_n.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, p->stream));
     return 0;
 }
 
@@ -731,13 +714,8 @@ int launch_from_moves(ao_positions* p, int m, bool status, bool end_ply, bool tu
     q.legal = legal ? p->d_legal : nullptr;
     q.planes = planes;
     const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
-    switch ((p->A + 63) / 64) {
-        case 1: hipLaunchKernelGGL(ao::k_positions_from_moves<1>, grid, block, 0, p->stream, q); break;
-        case 2: hipLaunchKernelGGL(ao::k_positions_from_moves<2>, grid, block, 0, p->stream, q); break;
-        case 3: hipLaunchKernelGGL(ao::k_positions_from_moves<3>, grid, block, 0, p->stream, q); break;
-        default: hipLaunchKernelGGL(ao::k_positions_from_moves<4>, grid, block, 0, p->stream, q); break;
-    }
-    PS_HIP(p, hipGetLastError());
+    AO_DISPATCH_NCH(ao::nch_of_cells(p->A), hipLaunchKernelGGL(ao::k_positions_from_moves<NCH>, grid, block, 0, p->stream, q));
+    AO_HIP(p, hipGetLastError());
     return 0;
 }
 
@@ -749,7 +727,7 @@ int launch_tactics(ao_positions* p, int m, bool audit) {
     q.err = p->d_i32 + 3 * static_cast<size_t>(p->cap);
     if (audit) {
         q.flags = p->d_legal;
-        q.counts = p->d_counts;
+        q.counts = p->d_counts.p;
     } else {
         q.mine = reinterpret_cast<uint8_t*>(p->d_board);
         q.theirs = p->d_legal;
@@ -757,20 +735,10 @@ int launch_tactics(ao_positions* p, int m, bool audit) {
         q.turn = p->d_i32 + 2 * static_cast<size_t>(p->cap);
     }
     const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
-    const int nch = (p->A + 63) / 64;
-#define AO_TACTICS(NCH)                                                                        \
-    do {                                                                                       \
-        if (audit) hipLaunchKernelGGL(ao::k_audit_games<NCH>, grid, block, 0, p->stream, q);   \
-        else hipLaunchKernelGGL(ao::k_win_cells<NCH>, grid, block, 0, p->stream, q);           \
-    } while (0)
-    switch (nch) {
-        case 1: AO_TACTICS(1); break;
-        case 2: AO_TACTICS(2); break;
-        case 3: AO_TACTICS(3); break;
-        default: AO_TACTICS(4); break;
-    }
-#undef AO_TACTICS
-    PS_HIP(p, hipGetLastError());
+    AO_DISPATCH_NCH(ao::nch_of_cells(p->A),
+                    if (audit) hipLaunchKernelGGL(ao::k_audit_games<NCH>, grid, block, 0, p->stream, q);
+                    else hipLaunchKernelGGL(ao::k_win_cells<NCH>, grid, block, 0, p->stream, q));
+    AO_HIP(p, hipGetLastError());
     return 0;
 }
 
@@ -781,82 +749,73 @@ int launch_forced(ao_positions* p, int m, int max_depth, int max_nodes) {
     q.moves = p->d_moves; q.nmoves = p->d_n;
     q.n = m; q.stride = p->A; q.B = p->B; q.A = p->A; q.win_mark = p->win_mark;
     q.max_depth = max_depth; q.max_nodes = max_nodes; q.line_stride = 2 * max_depth - 1;
-    q.result = p->d_forced; q.depth = p->d_forced + cap; q.move = p->d_forced + 2 * cap;
-    q.line_len = p->d_forced + 3 * cap; q.nodes = p->d_forced + 4 * cap;
+    int32_t* forced = p->d_forced.p;
+    q.result = forced; q.depth = forced + cap; q.move = forced + 2 * cap;
+    q.line_len = forced + 3 * cap; q.nodes = forced + 4 * cap;
     q.status = p->d_i32; q.turn = p->d_i32 + 2 * cap; q.err = p->d_i32 + 3 * cap;
     q.mask = reinterpret_cast<uint8_t*>(p->d_board);
-    q.line = p->d_line;
+    q.line = p->d_line.p;
     const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
-    switch ((p->A + 63) / 64) {
-        case 1: hipLaunchKernelGGL(ao::k_forced_wins<1>, grid, block, 0, p->stream, q); break;
-        case 2: hipLaunchKernelGGL(ao::k_forced_wins<2>, grid, block, 0, p->stream, q); break;
-        case 3: hipLaunchKernelGGL(ao::k_forced_wins<3>, grid, block, 0, p->stream, q); break;
-        default: hipLaunchKernelGGL(ao::k_forced_wins<4>, grid, block, 0, p->stream, q); break;
-    }
-    PS_HIP(p, hipGetLastError());
+    AO_DISPATCH_NCH(ao::nch_of_cells(p->A), hipLaunchKernelGGL(ao::k_forced_wins<NCH>, grid, block, 0, p->stream, q));
+    AO_HIP(p, hipGetLastError());
     return 0;
 }
 
 template <class T>
 int download(ao_positions* p, T* host, const T* dev, size_t count) {
-    if (host) PS_HIP(p, hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, p->stream));
+    if (host) AO_HIP(p, hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, p->stream));
     return 0;
 }
 
 }  // namespace
 
-extern "C" {
-
-int ao_positions_create(int board, int inplanes, int win_mark, int capacity, int device, ao_positions** out) {
-    *out = nullptr;
-    auto bad = [&](const char* m) { g_positions_create_error = m; return 1; };
-    if (board < 3 || board > ao::kMaxBoard) return bad("ao_positions_create: board must be in 3..15");
-    if (inplanes < 1 || inplanes > ao::kMaxPlanes) return bad("ao_positions_create: inplanes must be in 1..9 (the plane encoder keeps eight plies of history)");
-    if (win_mark < 3 || win_mark > 5 || win_mark > board) return bad("ao_positions_create: win_mark must be in 3..5 and at most the board size");
-    if (capacity < 1) return bad("ao_positions_create: capacity must be >= 1");
-    ao_positions* p = new ao_positions;
-    p->B = board; p->A = board * board; p->C = inplanes; p->win_mark = win_mark; p->cap = capacity; p->device = device;
+static int positions_create_impl(ao_positions* p, int board, int inplanes, int win_mark, int capacity, int device) {
+    p->device = device;
+    if (board < 3 || board > ao::kMaxBoard) return p->fail("board must be in 3..15");
+    if (inplanes < 1 || inplanes > ao::kMaxPlanes) return p->fail("inplanes must be in 1..9 (the plane encoder keeps eight plies of history)");
+    if (win_mark < 3 || win_mark > 5 || win_mark > board) return p->fail("win_mark must be in 3..5 and at most the board size");
+    if (capacity < 1) return p->fail("capacity must be >= 1");
+    p->B = board; p->A = board * board; p->C = inplanes; p->win_mark = win_mark; p->cap = capacity;
     const size_t cap = static_cast<size_t>(capacity), A = static_cast<size_t>(p->A);
-    hipError_t st = hipSetDevice(device);
-    if (st == hipSuccess) st = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-    if (st == hipSuccess) st = hipMalloc(&p->d_moves, cap * A * sizeof(int32_t));
-    if (st == hipSuccess) st = hipMalloc(&p->d_n, cap * sizeof(int32_t));
-    if (st == hipSuccess) st = hipMalloc(&p->d_i32, 4 * cap * sizeof(int32_t));
-    if (st == hipSuccess) st = hipMalloc(&p->d_board, cap * A);
-    if (st == hipSuccess) st = hipMalloc(&p->d_legal, cap * A);
-    if (st != hipSuccess) {
-        g_positions_create_error = std::string("ao_positions_create: ") + hipGetErrorString(st);
-        positions_free(p);
-        delete p;
-        return 1;
-    }
-    *out = p;
-    return 0;
+    AO_HIP(p, hipSetDevice(device));
+    AO_HIP(p, hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    return p->pool.alloc(p, &p->d_moves, cap * A) || p->pool.alloc(p, &p->d_n, cap) || p->pool.alloc(p, &p->d_i32, 4 * cap) ||
+           p->pool.alloc(p, &p->d_board, cap * A) || p->pool.alloc(p, &p->d_legal, cap * A);
 }
+
+extern "C" {
 
 void ao_positions_destroy(ao_positions* p) {
     if (!p) return;
     hipSetDevice(p->device);
-    positions_free(p);
+    if (p->stream) hipStreamSynchronize(p->stream);
+    p->pool.free_all();
+    if (p->stream) hipStreamDestroy(p->stream);
     delete p;
 }
 
-const char* ao_positions_last_error(const ao_positions* p) { return p ? p->err.c_str() : g_positions_create_error.c_str(); }
+int ao_positions_create(int board, int inplanes, int win_mark, int capacity, int device, ao_positions** out) {
+    ao_positions* p = new ao_positions;
+    return ao::finish_create(p, positions_create_impl(p, board, inplanes, win_mark, capacity, device), out, ao_positions_destroy,
+                             "ao_positions_create: ");
+}
+
+const char* ao_positions_last_error(const ao_positions* p) { return p ? p->err.c_str() : ao::create_error<ao_positions>().c_str(); }
 
 int ao_positions_check_win(ao_positions* p, const int8_t* host_boards, int32_t n, int32_t* host_win) {
     if (n < 0) return p->fail("ao_positions_check_win: negative position count");
     if (n == 0) return 0;
     if (!host_boards || !host_win) return p->fail("ao_positions_check_win: null buffer");
-    PS_HIP(p, hipSetDevice(p->device));
+    AO_HIP(p, hipSetDevice(p->device));
     const size_t A = static_cast<size_t>(p->A);
     for (int64_t first = 0; first < n; first += p->cap) {
         const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
-        PS_HIP(p, hipMemcpyAsync(p->d_board, host_boards + first * A, static_cast<size_t>(m) * A, hipMemcpyHostToDevice, p->stream));
+        AO_HIP(p, hipMemcpyAsync(p->d_board, host_boards + first * A, static_cast<size_t>(m) * A, hipMemcpyHostToDevice, p->stream));
         hipLaunchKernelGGL(ao::k_check_win_boards, dim3(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)),
                            dim3(64 * ao::kPosPerWG), 0, p->stream, p->d_board, m, p->B, p->win_mark, p->d_i32);
-        PS_HIP(p, hipGetLastError());
-        PS_HIP(p, hipMemcpyAsync(host_win + first, p->d_i32, sizeof(int32_t) * m, hipMemcpyDeviceToHost, p->stream));
-        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+        AO_HIP(p, hipGetLastError());
+        AO_HIP(p, hipMemcpyAsync(host_win + first, p->d_i32, sizeof(int32_t) * m, hipMemcpyDeviceToHost, p->stream));
+        AO_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
     }
     return 0;
 }
@@ -867,9 +826,9 @@ int ao_positions_from_moves(ao_positions* p, const int32_t* host_moves, int32_t 
     if (n < 0 || stride < 0) return p->fail("ao_positions_from_moves: negative position count or stride");
     if (n == 0) return 0;
     if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_from_moves: null move buffer");
-    PS_HIP(p, hipSetDevice(p->device));
+    AO_HIP(p, hipSetDevice(p->device));
     // the caller's plane buffer may be memory that work queued on another stream still uses (a caching allocator hands such out)
-    if (dev_planes_nchw) PS_HIP(p, hipDeviceSynchronize());
+    if (dev_planes_nchw) AO_HIP(p, hipDeviceSynchronize());
     const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
     for (int64_t first = 0; first < n; first += p->cap) {
         const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
@@ -883,7 +842,7 @@ int ao_positions_from_moves(ao_positions* p, const int32_t* host_moves, int32_t 
             download(p, host_board ? host_board + first * A : nullptr, p->d_board, m * A) ||
             download(p, host_legal ? host_legal + first * A : nullptr, p->d_legal, m * A))
             return 1;
-        PS_HIP(p, hipStreamSynchronize(p->stream));   // the planes are complete for any stream; the staging buffers are reused
+        AO_HIP(p, hipStreamSynchronize(p->stream));   // the planes are complete for any stream; the staging buffers are reused
     }
     return 0;
 }
@@ -893,7 +852,7 @@ int ao_positions_win_cells(ao_positions* p, const int32_t* host_moves, int32_t s
     if (n < 0 || stride < 0) return p->fail("ao_positions_win_cells: negative position count or stride");
     if (n == 0) return 0;
     if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_win_cells: null move buffer");
-    PS_HIP(p, hipSetDevice(p->device));
+    AO_HIP(p, hipSetDevice(p->device));
     const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
     for (int64_t first = 0; first < n; first += p->cap) {
         const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
@@ -905,7 +864,7 @@ int ao_positions_win_cells(ao_positions* p, const int32_t* host_moves, int32_t s
             download(p, host_turn ? host_turn + first : nullptr, p->d_i32 + 2 * cap, m) ||
             download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
             return 1;
-        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+        AO_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
     }
     return 0;
 }
@@ -915,18 +874,18 @@ int ao_positions_audit(ao_positions* p, const int32_t* host_moves, int32_t strid
     if (n < 0 || stride < 0) return p->fail("ao_positions_audit: negative record count or stride");
     if (n == 0) return 0;
     if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_audit: null move buffer");
-    PS_HIP(p, hipSetDevice(p->device));
+    AO_HIP(p, hipSetDevice(p->device));
     const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
-    if (!p->d_counts) PS_HIP(p, hipMalloc(&p->d_counts, cap * 8 * sizeof(int32_t)));
+    if (p->d_counts.reserve(p, cap * 8)) return 1;
     for (int64_t first = 0; first < n; first += p->cap) {
         const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
         if (stage_moves(p, "ao_positions_audit", host_moves, stride, host_n, first, m)) return 1;
         if (launch_tactics(p, m, true)) return 1;
         if (download(p, host_flags ? host_flags + first * A : nullptr, p->d_legal, m * A) ||
-            download(p, host_counts ? host_counts + first * 8 : nullptr, p->d_counts, static_cast<size_t>(m) * 8) ||
+            download(p, host_counts ? host_counts + first * 8 : nullptr, p->d_counts.p, static_cast<size_t>(m) * 8) ||
             download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
             return 1;
-        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+        AO_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
     }
     return 0;
 }
@@ -940,27 +899,26 @@ int ao_positions_forced_wins(ao_positions* p, const int32_t* host_moves, int32_t
     if (max_nodes < 1 || max_nodes > ao::kFwMaxNodes) return p->fail("ao_positions_forced_wins: max_nodes must be in 1..65536");
     if (n == 0) return 0;
     if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_forced_wins: null move buffer");
-    PS_HIP(p, hipSetDevice(p->device));
+    AO_HIP(p, hipSetDevice(p->device));
     const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
     const size_t lw = static_cast<size_t>(2 * max_depth - 1);
-    if (!p->d_forced) PS_HIP(p, hipMalloc(&p->d_forced, 5 * cap * sizeof(int32_t)));
-    if (!p->d_line) PS_HIP(p, hipMalloc(&p->d_line, cap * (2 * ao::kFwMaxDepth - 1) * sizeof(int16_t)));
+    if (p->d_forced.reserve(p, 5 * cap) || p->d_line.reserve(p, cap * (2 * ao::kFwMaxDepth - 1))) return 1;
     for (int64_t first = 0; first < n; first += p->cap) {
         const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
         if (stage_moves(p, "ao_positions_forced_wins", host_moves, stride, host_n, first, m)) return 1;
         if (launch_forced(p, m, max_depth, max_nodes)) return 1;
-        if (download(p, host_result ? host_result + first : nullptr, p->d_forced, m) ||
-            download(p, host_depth ? host_depth + first : nullptr, p->d_forced + cap, m) ||
-            download(p, host_move ? host_move + first : nullptr, p->d_forced + 2 * cap, m) ||
-            download(p, host_line_len ? host_line_len + first : nullptr, p->d_forced + 3 * cap, m) ||
-            download(p, host_nodes ? host_nodes + first : nullptr, p->d_forced + 4 * cap, m) ||
+        if (download(p, host_result ? host_result + first : nullptr, p->d_forced.p, m) ||
+            download(p, host_depth ? host_depth + first : nullptr, p->d_forced.p + cap, m) ||
+            download(p, host_move ? host_move + first : nullptr, p->d_forced.p + 2 * cap, m) ||
+            download(p, host_line_len ? host_line_len + first : nullptr, p->d_forced.p + 3 * cap, m) ||
+            download(p, host_nodes ? host_nodes + first : nullptr, p->d_forced.p + 4 * cap, m) ||
             download(p, host_moves_mask ? host_moves_mask + first * A : nullptr, reinterpret_cast<const uint8_t*>(p->d_board), m * A) ||
-            download(p, host_line ? host_line + first * lw : nullptr, p->d_line, m * lw) ||
+            download(p, host_line ? host_line + first * lw : nullptr, p->d_line.p, m * lw) ||
             download(p, host_status ? host_status + first : nullptr, p->d_i32, m) ||
             download(p, host_turn ? host_turn + first : nullptr, p->d_i32 + 2 * cap, m) ||
             download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
             return 1;
-        PS_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+        AO_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
     }
     return 0;
 }
@@ -973,25 +931,23 @@ int ao_positions_evaluate(ao_positions* p, ao_net* net, const int32_t* host_move
     if (ao::net_check(net, p->B, p->C, p->device, &why)) return p->fail("ao_positions_evaluate: " + why);
     if (n == 0) return 0;
     if (!host_n || (!host_moves && stride > 0) || !host_policy || !host_value) return p->fail("ao_positions_evaluate: null buffer");
-    PS_HIP(p, hipSetDevice(p->device));
-    PS_HIP(p, hipDeviceSynchronize());   // the network's workspace may still serve a forward queued on another stream
+    AO_HIP(p, hipSetDevice(p->device));
+    AO_HIP(p, hipDeviceSynchronize());   // the network's workspace may still serve a forward queued on another stream
     const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
-    if (!p->d_planes) PS_HIP(p, hipMalloc(&p->d_planes, cap * p->C * A * sizeof(float)));
-    if (!p->d_policy) PS_HIP(p, hipMalloc(&p->d_policy, cap * A * sizeof(float)));
-    if (!p->d_value) PS_HIP(p, hipMalloc(&p->d_value, cap * sizeof(float)));
+    if (p->d_planes.reserve(p, cap * p->C * A) || p->d_policy.reserve(p, cap * A) || p->d_value.reserve(p, cap)) return 1;
     std::vector<int32_t> err_chunk;
     for (int64_t first = 0; first < n; first += p->cap) {
         const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
         if (stage_moves(p, "ao_positions_evaluate", host_moves, stride, host_n, first, m)) return 1;
         // a position with an error is fed as the empty board: its row must not disturb the rest of the chunk
-        if (launch_from_moves(p, m, true, false, false, false, false, p->d_planes, true, true)) return 1;
-        if (ao_net_forward(net, p->d_planes, m, p->d_policy, p->d_value, p->stream))
+        if (launch_from_moves(p, m, true, false, false, false, false, p->d_planes.p, true, true)) return 1;
+        if (ao_net_forward(net, p->d_planes.p, m, p->d_policy.p, p->d_value.p, p->stream))
             return p->fail(std::string("ao_positions_evaluate: ") + ao_net_last_error(net));
         err_chunk.resize(static_cast<size_t>(m));
-        if (download(p, host_policy + first * A, p->d_policy, m * A) || download(p, host_value + first, p->d_value, m) ||
+        if (download(p, host_policy + first * A, p->d_policy.p, m * A) || download(p, host_value + first, p->d_value.p, m) ||
             download(p, host_status ? host_status + first : nullptr, p->d_i32, m) || download(p, err_chunk.data(), p->d_i32 + 3 * cap, m))
             return 1;
-        PS_HIP(p, hipStreamSynchronize(p->stream));
+        AO_HIP(p, hipStreamSynchronize(p->stream));
         for (int k = 0; k < m; ++k) {
             if (err_chunk[static_cast<size_t>(k)] == 0) continue;
             std::fill_n(host_policy + (first + k) * A, A, 0.f);

@@ -126,44 +126,30 @@ __global__ void k_replay_gather(const float* __restrict__ s_ring, const double* 
 
 }  // namespace ao
 
-extern "C" {
-
-int ao_replay_create(int board, int inplanes, int64_t capacity, int device, ao_replay** out) {
-    *out = nullptr;
-    if (board < 3 || board > 15 || inplanes < 1 || inplanes > 32 || capacity < 1) {
-        g_replay_create_error = "ao_replay_create: board 3..15, inplanes 1..32, capacity >= 1";
-        return 1;
-    }
-    ao_replay* r = new ao_replay;
-    r->B = board; r->C = inplanes; r->A = board * board; r->device = device; r->cap = capacity;
-    hipError_t st = hipSetDevice(device);
-    if (st == hipSuccess) st = hipMalloc(&r->s_ring, static_cast<size_t>(capacity) * r->C * r->A * sizeof(float));
-    if (st == hipSuccess) st = hipMalloc(&r->pi_ring, static_cast<size_t>(capacity) * r->A * sizeof(double));
-    if (st == hipSuccess) st = hipMalloc(&r->z_ring, static_cast<size_t>(capacity) * sizeof(float));
-    if (st != hipSuccess) {
-        g_replay_create_error = std::string("ao_replay_create: ") + hipGetErrorString(st);
-        if (r->s_ring) hipFree(r->s_ring);
-        if (r->pi_ring) hipFree(r->pi_ring);
-        if (r->z_ring) hipFree(r->z_ring);
-        delete r;
-        return 1;
-    }
-    *out = r;
-    return 0;
+static int replay_create_impl(ao_replay* r, int board, int inplanes, int64_t capacity, int device) {
+    r->device = device;
+    if (board < 3 || board > 15 || inplanes < 1 || inplanes > 32 || capacity < 1) return r->fail("board 3..15, inplanes 1..32, capacity >= 1");
+    r->B = board; r->C = inplanes; r->A = board * board; r->cap = capacity;
+    const size_t cap = static_cast<size_t>(capacity);
+    AO_HIP(r, hipSetDevice(device));
+    return r->pool.alloc(r, &r->s_ring, cap * r->C * r->A) || r->pool.alloc(r, &r->pi_ring, cap * r->A) || r->pool.alloc(r, &r->z_ring, cap);
 }
+
+extern "C" {
 
 void ao_replay_destroy(ao_replay* r) {
     if (!r) return;
     hipSetDevice(r->device);
-    for (void* p : {static_cast<void*>(r->s_ring), static_cast<void*>(r->pi_ring), static_cast<void*>(r->z_ring),
-                    static_cast<void*>(r->st_s), static_cast<void*>(r->st_pi), static_cast<void*>(r->st_z),
-                    static_cast<void*>(r->st_idx), static_cast<void*>(r->st_mv), static_cast<void*>(r->st_ep),
-                    static_cast<void*>(r->st_ply)})
-        if (p) hipFree(p);
+    r->pool.free_all();
     delete r;
 }
 
-const char* ao_replay_last_error(const ao_replay* r) { return r ? r->err.c_str() : g_replay_create_error.c_str(); }
+int ao_replay_create(int board, int inplanes, int64_t capacity, int device, ao_replay** out) {
+    ao_replay* r = new ao_replay;
+    return ao::finish_create(r, replay_create_impl(r, board, inplanes, capacity, device), out, ao_replay_destroy, "ao_replay_create: ");
+}
+
+const char* ao_replay_last_error(const ao_replay* r) { return r ? r->err.c_str() : ao::create_error<ao_replay>().c_str(); }
 
 int64_t ao_replay_size(const ao_replay* r) { return r->count; }
 int64_t ao_replay_capacity(const ao_replay* r) { return r->cap; }
@@ -188,7 +174,7 @@ static int extend_impl(ao_replay* r, const float* states, const MoveSource* mv, 
     if (r->cap < nsym) return r->fail("ao_replay_extend: capacity below one augmented sample (8 entries)");
     if (skipped > 0 && n * nsym < r->cap)
         return r->fail("ao_replay_extend_skip: the given samples do not fill the memory, so skipped ones would survive");
-    RP_HIP(r, hipSetDevice(r->device));
+    AO_HIP(r, hipSetDevice(r->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t CA = static_cast<int64_t>(r->C) * r->A;
     // Only the newest `cap` entries of this call can survive (deque(maxlen) semantics); the slots
@@ -199,51 +185,31 @@ static int extend_impl(ao_replay* r, const float* states, const MoveSource* mv, 
     const int64_t skip = std::max<int64_t>(0, total - r->cap);
     const int64_t first_smp = skip / nsym;
     const int64_t n_st = n - first_smp;
-    if (n_st > r->st_n) {
-        for (void* p : {static_cast<void*>(r->st_s), static_cast<void*>(r->st_pi), static_cast<void*>(r->st_z)})
-            if (p) hipFree(p);
-        r->st_s = nullptr; r->st_pi = nullptr; r->st_z = nullptr; r->st_n = 0;
-        RP_HIP(r, hipMalloc(&r->st_s, static_cast<size_t>(n_st) * CA * sizeof(float)));
-        RP_HIP(r, hipMalloc(&r->st_pi, static_cast<size_t>(n_st) * r->A * sizeof(double)));
-        RP_HIP(r, hipMalloc(&r->st_z, static_cast<size_t>(n_st) * sizeof(float)));
-        r->st_n = n_st;
-    }
+    const size_t stage_n = static_cast<size_t>(n_st);
+    if (r->st_s.reserve(r, stage_n * CA) || r->st_pi.reserve(r, stage_n * r->A) || r->st_z.reserve(r, stage_n)) return 1;
     if (mv) {
         if (mv->n_ep < 1 || mv->L < 1 || mv->L > r->A) return r->fail("ao_replay_extend_moves: n_episodes >= 1 and 1 <= max_len <= board * board");
         for (int64_t i = first_smp; i < n; ++i)
             if (mv->ep_of[i] < 0 || mv->ep_of[i] >= mv->n_ep || mv->ply_of[i] < 0 || mv->ply_of[i] > mv->L)
                 return r->fail("ao_replay_extend_moves: sample " + std::to_string(i) + " names an episode or a ply outside the moves given");
         const int64_t nmv = mv->n_ep * mv->L;
-        if (nmv > r->st_mv_n) {
-            if (r->st_mv) hipFree(r->st_mv);
-            r->st_mv = nullptr; r->st_mv_n = 0;
-            RP_HIP(r, hipMalloc(&r->st_mv, static_cast<size_t>(nmv) * sizeof(short)));
-            r->st_mv_n = nmv;
-        }
-        if (n_st > r->st_ep_n) {
-            if (r->st_ep) hipFree(r->st_ep);
-            if (r->st_ply) hipFree(r->st_ply);
-            r->st_ep = nullptr; r->st_ply = nullptr; r->st_ep_n = 0;
-            RP_HIP(r, hipMalloc(&r->st_ep, static_cast<size_t>(n_st) * sizeof(int)));
-            RP_HIP(r, hipMalloc(&r->st_ply, static_cast<size_t>(n_st) * sizeof(int)));
-            r->st_ep_n = n_st;
-        }
-        RP_HIP(r, hipMemcpyAsync(r->st_mv, mv->moves, static_cast<size_t>(nmv) * sizeof(short), hipMemcpyHostToDevice, s));
-        RP_HIP(r, hipMemcpyAsync(r->st_ep, mv->ep_of + first_smp, static_cast<size_t>(n_st) * sizeof(int), hipMemcpyHostToDevice, s));
-        RP_HIP(r, hipMemcpyAsync(r->st_ply, mv->ply_of + first_smp, static_cast<size_t>(n_st) * sizeof(int), hipMemcpyHostToDevice, s));
+        if (r->st_mv.reserve(r, static_cast<size_t>(nmv)) || r->st_ep.reserve(r, stage_n) || r->st_ply.reserve(r, stage_n)) return 1;
+        AO_HIP(r, hipMemcpyAsync(r->st_mv.p, mv->moves, static_cast<size_t>(nmv) * sizeof(short), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(r->st_ep.p, mv->ep_of + first_smp, static_cast<size_t>(n_st) * sizeof(int), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(r->st_ply.p, mv->ply_of + first_smp, static_cast<size_t>(n_st) * sizeof(int), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(ao::k_states_from_moves, dim3(static_cast<unsigned>(std::min<int64_t>(n_st, 65535L * 16))), dim3(128), 0, s,
-                           r->st_mv, static_cast<int>(mv->L), r->st_ep, r->st_ply, static_cast<long>(n_st), r->st_s, r->C, r->A);
+                           r->st_mv.p, static_cast<int>(mv->L), r->st_ep.p, r->st_ply.p, static_cast<long>(n_st), r->st_s.p, r->C, r->A);
     } else {
-        RP_HIP(r, hipMemcpyAsync(r->st_s, states + first_smp * CA, static_cast<size_t>(n_st) * CA * sizeof(float), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(r->st_s.p, states + first_smp * CA, static_cast<size_t>(n_st) * CA * sizeof(float), hipMemcpyHostToDevice, s));
     }
-    RP_HIP(r, hipMemcpyAsync(r->st_pi, pi + first_smp * r->A, static_cast<size_t>(n_st) * r->A * sizeof(double), hipMemcpyHostToDevice, s));
-    RP_HIP(r, hipMemcpyAsync(r->st_z, z + first_smp, static_cast<size_t>(n_st) * sizeof(float), hipMemcpyHostToDevice, s));
+    AO_HIP(r, hipMemcpyAsync(r->st_pi.p, pi + first_smp * r->A, static_cast<size_t>(n_st) * r->A * sizeof(double), hipMemcpyHostToDevice, s));
+    AO_HIP(r, hipMemcpyAsync(r->st_z.p, z + first_smp, static_cast<size_t>(n_st) * sizeof(float), hipMemcpyHostToDevice, s));
     const int64_t tail = (r->head + r->count + (skipped % r->cap) * nsym) % r->cap;  // slot of the first given entry
     const long work = static_cast<long>(std::min<int64_t>(total, r->cap + nsym)) * (r->C + 1) * r->A;
     const int block = 256;
     const int grid = static_cast<int>(std::min<long>((work + block - 1) / block, 65535L * 8));
     if (skip == 0) {
-        hipLaunchKernelGGL(ao::k_replay_write, dim3(grid), dim3(block), 0, s, r->st_s, r->st_pi, r->st_z,
+        hipLaunchKernelGGL(ao::k_replay_write, dim3(grid), dim3(block), 0, s, r->st_s.p, r->st_pi.p, r->st_z.p,
                            static_cast<long>(n), nsym, r->s_ring, r->pi_ring, r->z_ring, static_cast<long>(tail),
                            static_cast<long>(r->cap), r->C, r->B);
     } else {
@@ -252,15 +218,15 @@ static int extend_impl(ao_replay* r, const float* states, const MoveSource* mv, 
         while (k0 < total) {
             const int64_t smp0 = k0 / nsym;
             const int64_t nsmp = std::min<int64_t>(n - smp0, std::max<int64_t>(1, r->cap / nsym));
-            hipLaunchKernelGGL(ao::k_replay_write, dim3(grid), dim3(block), 0, s, r->st_s + (smp0 - first_smp) * CA,
-                               r->st_pi + (smp0 - first_smp) * r->A, r->st_z + (smp0 - first_smp), static_cast<long>(nsmp), nsym,
+            hipLaunchKernelGGL(ao::k_replay_write, dim3(grid), dim3(block), 0, s, r->st_s.p + (smp0 - first_smp) * CA,
+                               r->st_pi.p + (smp0 - first_smp) * r->A, r->st_z.p + (smp0 - first_smp), static_cast<long>(nsmp), nsym,
                                r->s_ring, r->pi_ring, r->z_ring, static_cast<long>((tail + k0) % r->cap),
                                static_cast<long>(r->cap), r->C, r->B);
             k0 += nsmp * nsym;
         }
     }
-    RP_HIP(r, hipGetLastError());
-    RP_HIP(r, hipStreamSynchronize(s));  // the caller's buffers may go away
+    AO_HIP(r, hipGetLastError());
+    AO_HIP(r, hipStreamSynchronize(s));  // the caller's buffers may go away
     const int64_t logical = (skipped + n) * nsym;
     const int64_t newcount = std::min<int64_t>(r->cap, r->count + logical);
     const int64_t dropped = r->count + logical - newcount;
@@ -289,34 +255,29 @@ int ao_replay_extend_moves(ao_replay* r, const int16_t* moves, int64_t n_episode
 int ao_replay_gather(ao_replay* r, const int64_t* idx, int64_t m, float* dev_states, float* dev_pi, float* dev_z,
                      void* stream) {
     if (m <= 0) return m == 0 ? 0 : r->fail("ao_replay_gather: negative batch size");
-    RP_HIP(r, hipSetDevice(r->device));
+    AO_HIP(r, hipSetDevice(r->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::vector<long> slots(static_cast<size_t>(m));
     for (int64_t i = 0; i < m; ++i) {
         if (idx[i] < 0 || idx[i] >= r->count) return r->fail("ao_replay_gather: index out of range");
         slots[static_cast<size_t>(i)] = static_cast<long>((r->head + idx[i]) % r->cap);
     }
-    if (m > r->st_m) {
-        if (r->st_idx) hipFree(r->st_idx);
-        r->st_idx = nullptr; r->st_m = 0;
-        RP_HIP(r, hipMalloc(&r->st_idx, static_cast<size_t>(m) * sizeof(long)));
-        r->st_m = m;
-    }
-    RP_HIP(r, hipMemcpyAsync(r->st_idx, slots.data(), static_cast<size_t>(m) * sizeof(long), hipMemcpyHostToDevice, s));
+    if (r->st_idx.reserve(r, static_cast<size_t>(m))) return 1;
+    AO_HIP(r, hipMemcpyAsync(r->st_idx.p, slots.data(), static_cast<size_t>(m) * sizeof(long), hipMemcpyHostToDevice, s));
     const long work = static_cast<long>(m) * (r->C + 1) * r->A;
     const int block = 256;
     const int grid = static_cast<int>(std::min<long>((work + block - 1) / block, 65535L * 8));
-    hipLaunchKernelGGL(ao::k_replay_gather, dim3(grid), dim3(block), 0, s, r->s_ring, r->pi_ring, r->z_ring, r->st_idx,
+    hipLaunchKernelGGL(ao::k_replay_gather, dim3(grid), dim3(block), 0, s, r->s_ring, r->pi_ring, r->z_ring, r->st_idx.p,
                        static_cast<long>(m), dev_states, dev_pi, dev_z, r->C, r->A);
-    RP_HIP(r, hipGetLastError());
-    RP_HIP(r, hipStreamSynchronize(s));  // `slots` goes away; the batch is ready for any stream
+    AO_HIP(r, hipGetLastError());
+    AO_HIP(r, hipStreamSynchronize(s));  // `slots` goes away; the batch is ready for any stream
     return 0;
 }
 
 int ao_replay_read(ao_replay* r, int64_t first, int64_t n, double* states, double* pi, double* z) {
     if (first < 0 || n < 0 || first + n > r->count) return r->fail("ao_replay_read: range outside the memory");
-    RP_HIP(r, hipSetDevice(r->device));
-    RP_HIP(r, hipDeviceSynchronize());
+    AO_HIP(r, hipSetDevice(r->device));
+    AO_HIP(r, hipDeviceSynchronize());
     const int64_t CA = static_cast<int64_t>(r->C) * r->A;
     // at most two contiguous slot ranges (the ring wraps once)
     int64_t done = 0;
@@ -325,15 +286,15 @@ int ao_replay_read(ao_replay* r, int64_t first, int64_t n, double* states, doubl
         const int64_t len = std::min<int64_t>(n - done, r->cap - slot);
         if (states) {
             std::vector<float> sb(static_cast<size_t>(len * CA));
-            RP_HIP(r, hipMemcpy(sb.data(), r->s_ring + slot * CA, sb.size() * sizeof(float), hipMemcpyDeviceToHost));
+            AO_HIP(r, hipMemcpy(sb.data(), r->s_ring + slot * CA, sb.size() * sizeof(float), hipMemcpyDeviceToHost));
             for (size_t k = 0; k < sb.size(); ++k) states[done * CA + static_cast<int64_t>(k)] = sb[k];
         }
         if (pi)
-            RP_HIP(r, hipMemcpy(pi + done * r->A, r->pi_ring + slot * r->A, sizeof(double) * r->A * len,
+            AO_HIP(r, hipMemcpy(pi + done * r->A, r->pi_ring + slot * r->A, sizeof(double) * r->A * len,
                                 hipMemcpyDeviceToHost));
         if (z) {
             std::vector<float> zb(static_cast<size_t>(len));
-            RP_HIP(r, hipMemcpy(zb.data(), r->z_ring + slot, sizeof(float) * len, hipMemcpyDeviceToHost));
+            AO_HIP(r, hipMemcpy(zb.data(), r->z_ring + slot, sizeof(float) * len, hipMemcpyDeviceToHost));
             for (int64_t k = 0; k < len; ++k) z[done + k] = zb[static_cast<size_t>(k)];
         }
         done += len;

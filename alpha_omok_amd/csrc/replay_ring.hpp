@@ -7,27 +7,17 @@
 #include <string>
 
 #include "../../include/omok_hip.h"
+#include "host_handle.hpp"
 
-struct ao_replay {
+// ao_replay_last_error(NULL) (ao::create_error<ao_replay>) speaks of this thread's failed ao_replay_create or ao_replay_snapshot_check
+struct ao_replay : ao::HandleBase {
     int B = 0, C = 0, A = 0, device = 0;
     int64_t cap = 0, head = 0, count = 0;  // deque index i lives in slot (head + i) % cap
+    ao::DevPool pool;
     float* s_ring = nullptr;
     double* pi_ring = nullptr;
     float* z_ring = nullptr;
     // staging (grow-only)
-    float* st_s = nullptr; double* st_pi = nullptr; float* st_z = nullptr; long* st_idx = nullptr;
-    int64_t st_n = 0, st_m = 0;
-    short* st_mv = nullptr; int* st_ep = nullptr; int* st_ply = nullptr;   // moves-based extend: episodes' moves, (episode, ply) per sample
-    int64_t st_mv_n = 0, st_ep_n = 0;
-    std::string err;
-    int fail(const std::string& m) { err = m; return 1; }
+    ao::DevBuf<float> st_s{&pool}; ao::DevBuf<double> st_pi{&pool}; ao::DevBuf<float> st_z{&pool}; ao::DevBuf<long> st_idx{&pool};
+    ao::DevBuf<short> st_mv{&pool}; ao::DevBuf<int> st_ep{&pool}; ao::DevBuf<int> st_ply{&pool};   // moves-based extend: episodes' moves, (episode, ply) per sample
 };
-
-// what ao_replay_last_error(NULL) returns: the failed ao_replay_create or ao_replay_snapshot_check of this thread
-inline thread_local std::string g_replay_create_error;
-
-#define RP_HIP(r, call)                                                                        \
-    do {                                                                                       \
-        hipError_t st_ = (call);                                                               \
-        if (st_ != hipSuccess) return (r)->fail(std::string(#call) + ": " + hipGetErrorString(st_)); \
-    } while (0)

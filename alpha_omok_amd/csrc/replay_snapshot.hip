@@ -148,14 +148,12 @@ __global__ __launch_bounds__(kRsBlock) void k_replay_unpack(RsRing g, RsChunk d,
 // host side
 // ----------------------------------------------------------------------------------------------
 struct RsWork {                               // device workspace of one call, freed when the call returns
+    DevPool pool;
     unsigned char* buf = nullptr;             // a chunk's packed sections
     uint32_t* off = nullptr;                  // [2][m] pioff, rawidx
     int32_t* nnz = nullptr;                   // [m] count pass
     uint8_t* ckind = nullptr;                 // [m] count pass
-    ~RsWork() {
-        for (void* p : {static_cast<void*>(buf), static_cast<void*>(off), static_cast<void*>(nnz), static_cast<void*>(ckind)})
-            if (p) hipFree(p);
-    }
+    ~RsWork() { pool.free_all(); }
 };
 
 struct RsShape {
@@ -216,25 +214,22 @@ static inline unsigned rs_grid(int64_t entries) {
 }
 
 static int rs_alloc(ao_replay* r, RsWork& ws, const RsShape& h, bool chunks) {
-    RP_HIP(r, hipMalloc(&ws.nnz, static_cast<size_t>(h.m) * sizeof(int32_t)));
-    RP_HIP(r, hipMalloc(&ws.ckind, static_cast<size_t>(h.m)));
-    if (chunks) {
-        // a chunk is closed by the entry that takes it to chunk_bytes, and holds at most m entries
-        const int64_t bytes = std::min(h.chunk_bytes + h.entry_max, h.m * h.entry_max) + 64;
-        RP_HIP(r, hipMalloc(&ws.buf, static_cast<size_t>(bytes)));
-        RP_HIP(r, hipMalloc(&ws.off, 2 * static_cast<size_t>(h.m) * sizeof(uint32_t)));
-    }
-    return 0;
+    const size_t m = static_cast<size_t>(h.m);
+    if (ws.pool.alloc(r, &ws.nnz, m) || ws.pool.alloc(r, &ws.ckind, m)) return 1;
+    if (!chunks) return 0;
+    // a chunk is closed by the entry that takes it to chunk_bytes, and holds at most m entries
+    const int64_t bytes = std::min(h.chunk_bytes + h.entry_max, h.m * h.entry_max) + 64;
+    return ws.pool.alloc(r, &ws.buf, static_cast<size_t>(bytes)) || ws.pool.alloc(r, &ws.off, 2 * m);
 }
 
 // count pass over deque entries [at, at + blk), blk <= h.m: per-entry nnz and kind on the host
 static int rs_count(ao_replay* r, const RsWork& ws, int64_t at, int64_t blk, hipStream_t s, int32_t* nnz, uint8_t* kind) {
     hipLaunchKernelGGL(k_replay_count, dim3(rs_grid(blk)), dim3(kRsBlock), 0, s, rs_ring(r), (r->head + at) % r->cap, blk, ws.nnz,
                        ws.ckind);
-    RP_HIP(r, hipGetLastError());
-    RP_HIP(r, hipMemcpyAsync(nnz, ws.nnz, static_cast<size_t>(blk) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    RP_HIP(r, hipMemcpyAsync(kind, ws.ckind, static_cast<size_t>(blk), hipMemcpyDeviceToHost, s));
-    RP_HIP(r, hipStreamSynchronize(s));
+    AO_HIP(r, hipGetLastError());
+    AO_HIP(r, hipMemcpyAsync(nnz, ws.nnz, static_cast<size_t>(blk) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    AO_HIP(r, hipMemcpyAsync(kind, ws.ckind, static_cast<size_t>(blk), hipMemcpyDeviceToHost, s));
+    AO_HIP(r, hipStreamSynchronize(s));
     return 0;
 }
 
@@ -258,7 +253,7 @@ extern "C" {
 int ao_replay_snapshot_check(const ao_replay_snapshot* snap) {
     const std::string why = ao::replay_snapshot_check(snap);
     if (why.empty()) return 0;
-    g_replay_create_error = "ao_replay_snapshot_check: " + why;
+    ao::create_error<ao_replay>() = "ao_replay_snapshot_check: " + why;
     return 1;
 }
 
@@ -266,8 +261,8 @@ int ao_replay_export_size(ao_replay* r, int64_t first, int64_t n, int64_t* pi_va
     if (first < 0 || n < 0 || first + n > r->count) return r->fail("ao_replay_export_size: range outside the memory");
     int64_t pv = 0, re = 0;
     if (n > 0) {
-        RP_HIP(r, hipSetDevice(r->device));
-        RP_HIP(r, hipDeviceSynchronize());
+        AO_HIP(r, hipSetDevice(r->device));
+        AO_HIP(r, hipDeviceSynchronize());
         const ao::RsShape h = ao::rs_shape(r, 0, n);
         ao::RsWork ws;
         if (ao::rs_alloc(r, ws, h, false)) return 1;
@@ -290,8 +285,8 @@ int ao_replay_export(ao_replay* r, int64_t first, int64_t n, ao_replay_snapshot*
     int64_t pv = 0, re = 0;
     RsWork ws;
     if (n > 0) {
-        RP_HIP(r, hipSetDevice(r->device));
-        RP_HIP(r, hipDeviceSynchronize());
+        AO_HIP(r, hipSetDevice(r->device));
+        AO_HIP(r, hipDeviceSynchronize());
         if (rs_alloc(r, ws, h, true)) return 1;
         if (rs_totals(r, ws, h, first, n, s, &pv, &re)) return 1;
     }
@@ -320,19 +315,19 @@ int ao_replay_export(ao_replay* r, int64_t first, int64_t n, ao_replay_snapshot*
             if (pi_at + npi > pv || raw_at + nraw > re) return r->fail("ao_replay_export: the memory changed during the export");
             const RsLayout l = rs_layout(h, len, npi, nraw);
             const RsChunk d = rs_chunk(ws, h, l, len, npi, nraw);
-            RP_HIP(r, hipMemcpyAsync(ws.off, off.data(), static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            RP_HIP(r, hipMemcpyAsync(ws.off + h.m, off.data() + h.m, static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            AO_HIP(r, hipMemcpyAsync(ws.off, off.data(), static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            AO_HIP(r, hipMemcpyAsync(ws.off + h.m, off.data() + h.m, static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(k_replay_pack, dim3(rs_grid(len)), dim3(kRsBlock), 0, s, rs_ring(r), d, (r->head + first + done + j) % r->cap);
-            RP_HIP(r, hipGetLastError());
+            AO_HIP(r, hipGetLastError());
             const int64_t e0 = done + j;                  // first snapshot entry of the chunk
-            RP_HIP(r, hipMemcpyAsync(snap->kind + e0, d.kind, static_cast<size_t>(len), hipMemcpyDeviceToHost, s));
-            RP_HIP(r, hipMemcpyAsync(snap->z + e0, d.z, 4 * static_cast<size_t>(len), hipMemcpyDeviceToHost, s));
-            RP_HIP(r, hipMemcpyAsync(snap->bits + e0 * h.C * h.W, d.bits, 8 * static_cast<size_t>(len) * h.C * h.W, hipMemcpyDeviceToHost, s));
-            RP_HIP(r, hipMemcpyAsync(snap->pi_mask + e0 * h.W, d.mask, 8 * static_cast<size_t>(len) * h.W, hipMemcpyDeviceToHost, s));
-            if (npi > 0) RP_HIP(r, hipMemcpyAsync(snap->pi_val + pi_at, d.pival, 8 * static_cast<size_t>(npi), hipMemcpyDeviceToHost, s));
+            AO_HIP(r, hipMemcpyAsync(snap->kind + e0, d.kind, static_cast<size_t>(len), hipMemcpyDeviceToHost, s));
+            AO_HIP(r, hipMemcpyAsync(snap->z + e0, d.z, 4 * static_cast<size_t>(len), hipMemcpyDeviceToHost, s));
+            AO_HIP(r, hipMemcpyAsync(snap->bits + e0 * h.C * h.W, d.bits, 8 * static_cast<size_t>(len) * h.C * h.W, hipMemcpyDeviceToHost, s));
+            AO_HIP(r, hipMemcpyAsync(snap->pi_mask + e0 * h.W, d.mask, 8 * static_cast<size_t>(len) * h.W, hipMemcpyDeviceToHost, s));
+            if (npi > 0) AO_HIP(r, hipMemcpyAsync(snap->pi_val + pi_at, d.pival, 8 * static_cast<size_t>(npi), hipMemcpyDeviceToHost, s));
             if (nraw > 0)
-                RP_HIP(r, hipMemcpyAsync(snap->raw + raw_at * h.C * h.A, d.raw, static_cast<size_t>(nraw) * h.raw_bytes, hipMemcpyDeviceToHost, s));
-            RP_HIP(r, hipStreamSynchronize(s));           // `off` and the workspace are free for the next chunk
+                AO_HIP(r, hipMemcpyAsync(snap->raw + raw_at * h.C * h.A, d.raw, static_cast<size_t>(nraw) * h.raw_bytes, hipMemcpyDeviceToHost, s));
+            AO_HIP(r, hipStreamSynchronize(s));           // `off` and the workspace are free for the next chunk
             pi_at += npi;
             raw_at += nraw;
             j += len;
@@ -366,7 +361,7 @@ int ao_replay_import(ao_replay* r, const ao_replay_snapshot* snap, int64_t chunk
     };
     int64_t pi_at = 0, raw_at = 0;
     for (int64_t i = 0; i < skip; ++i) { pi_at += popc(i); raw_at += snap->kind[i]; }
-    RP_HIP(r, hipSetDevice(r->device));
+    AO_HIP(r, hipSetDevice(r->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     RsWork ws;
     if (rs_alloc(r, ws, h, true)) return 1;
@@ -385,18 +380,18 @@ int ao_replay_import(ao_replay* r, const ao_replay_snapshot* snap, int64_t chunk
         }
         const RsLayout l = rs_layout(h, len, npi, nraw);
         const RsChunk d = rs_chunk(ws, h, l, len, npi, nraw);
-        RP_HIP(r, hipMemcpyAsync(ws.off, off.data(), static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        RP_HIP(r, hipMemcpyAsync(ws.off + h.m, off.data() + h.m, static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        RP_HIP(r, hipMemcpyAsync(d.kind, snap->kind + i, static_cast<size_t>(len), hipMemcpyHostToDevice, s));
-        RP_HIP(r, hipMemcpyAsync(d.z, snap->z + i, 4 * static_cast<size_t>(len), hipMemcpyHostToDevice, s));
-        RP_HIP(r, hipMemcpyAsync(d.bits, snap->bits + i * h.C * h.W, 8 * static_cast<size_t>(len) * h.C * h.W, hipMemcpyHostToDevice, s));
-        RP_HIP(r, hipMemcpyAsync(d.mask, snap->pi_mask + i * h.W, 8 * static_cast<size_t>(len) * h.W, hipMemcpyHostToDevice, s));
-        if (npi > 0) RP_HIP(r, hipMemcpyAsync(d.pival, snap->pi_val + pi_at, 8 * static_cast<size_t>(npi), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(ws.off, off.data(), static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(ws.off + h.m, off.data() + h.m, static_cast<size_t>(len) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(d.kind, snap->kind + i, static_cast<size_t>(len), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(d.z, snap->z + i, 4 * static_cast<size_t>(len), hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(d.bits, snap->bits + i * h.C * h.W, 8 * static_cast<size_t>(len) * h.C * h.W, hipMemcpyHostToDevice, s));
+        AO_HIP(r, hipMemcpyAsync(d.mask, snap->pi_mask + i * h.W, 8 * static_cast<size_t>(len) * h.W, hipMemcpyHostToDevice, s));
+        if (npi > 0) AO_HIP(r, hipMemcpyAsync(d.pival, snap->pi_val + pi_at, 8 * static_cast<size_t>(npi), hipMemcpyHostToDevice, s));
         if (nraw > 0)
-            RP_HIP(r, hipMemcpyAsync(d.raw, snap->raw + raw_at * h.C * h.A, static_cast<size_t>(nraw) * h.raw_bytes, hipMemcpyHostToDevice, s));
+            AO_HIP(r, hipMemcpyAsync(d.raw, snap->raw + raw_at * h.C * h.A, static_cast<size_t>(nraw) * h.raw_bytes, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_replay_unpack, dim3(rs_grid(len)), dim3(kRsBlock), 0, s, rs_ring(r), d, (tail + i % r->cap) % r->cap);
-        RP_HIP(r, hipGetLastError());
-        RP_HIP(r, hipStreamSynchronize(s));               // `off` and the workspace are free for the next chunk
+        AO_HIP(r, hipGetLastError());
+        AO_HIP(r, hipStreamSynchronize(s));               // `off` and the workspace are free for the next chunk
         pi_at += npi;
         raw_at += nraw;
         i += len;

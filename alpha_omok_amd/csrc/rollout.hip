@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/omok_hip.h"
+#include "host_handle.hpp"
 #include "host_rng.hpp"
 #include "tree_device.hpp"
 
@@ -495,77 +496,51 @@ __global__ __launch_bounds__(64) void k_ttt_search(TttParams p) {
 // ==============================================================================================
 // host side
 // ==============================================================================================
-struct ao_rollout {
+struct ao_rollout : ao::HandleBase {
     ao_rollout_config cfg{};
     ao::RollParams p{};
     int G = 0, A = 0;
-    std::vector<void*> allocs;
+    ao::DevPool pool;
     uint8_t* d_active = nullptr;
     std::vector<int32_t> has_gauss;
     std::vector<double> gauss;
     hipStream_t stream = nullptr;
-    std::string err;
-    int fail(const std::string& m) { err = m; return 1; }
 };
 
-static thread_local std::string g_rollout_create_error;
-
-#define RO_HIP(r, call)                                                                        \
-    do {                                                                                       \
-        hipError_t st_ = (call);                                                               \
-        if (st_ != hipSuccess) return (r)->fail(std::string(#call) + ": " + hipGetErrorString(st_)); \
-    } while (0)
-
-template <typename T>
-static int ro_alloc(ao_rollout* r, T** out, size_t count) {
-    void* q = nullptr;
-    hipError_t st = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16));
-    if (st != hipSuccess) return r->fail(std::string("hipMalloc: ") + hipGetErrorString(st));
-    r->allocs.push_back(q);
-    *out = static_cast<T*>(q);
+// ln(total_n) for 0 .. sims + 2 (np.log; ln 0 = -inf), shared by the rollout and the tic-tac-toe searches
+static int upload_log_lut(ao::HandleBase* h, ao::DevPool& pool, int sims, const double** out) {
+    std::vector<double> lut(static_cast<size_t>(sims) + 3);
+    for (size_t i = 0; i < lut.size(); ++i) lut[i] = std::log(static_cast<double>(i));
+    double* d = nullptr;
+    if (pool.alloc(h, &d, lut.size())) return 1;
+    AO_HIP(h, hipMemcpy(d, lut.data(), sizeof(double) * lut.size(), hipMemcpyHostToDevice));
+    *out = d;
     return 0;
 }
 
-extern "C" {
-
-int ao_rollout_create(const ao_rollout_config* cfg, ao_rollout** out) {
-    *out = nullptr;
+static int rollout_create_impl(ao_rollout* r, const ao_rollout_config* cfg) {
     ao_rollout_config c = *cfg;
-    if (c.board < 3 || c.board > ao::kMaxBoard || c.sims < 1 || c.games < 1 || (c.mode != 0 && c.mode != 1)) {
-        g_rollout_create_error = "ao_rollout_create: board 3..15, sims >= 1, games >= 1, mode 0 (PUCT) or 1 (UCT)";
-        return 1;
-    }
     if (c.win_mark <= 0) c.win_mark = (c.board == 3) ? 3 : 5;  // agents.py:270
     if (c.c_puct <= 0) c.c_puct = 5.0;                         // agents.py:271
-    ao_rollout* r = new ao_rollout;
     r->cfg = c;
+    if (c.board < 3 || c.board > ao::kMaxBoard || c.sims < 1 || c.games < 1 || (c.mode != 0 && c.mode != 1))
+        return r->fail("board 3..15, sims >= 1, games >= 1, mode 0 (PUCT) or 1 (UCT)");
     r->G = c.games;
     r->A = c.board * c.board;
     ao::RollParams& p = r->p;
     p.B = c.board; p.A = r->A; p.Ap = (r->A + 15) & ~15; p.win_mark = c.win_mark; p.G = c.games;
     p.cap = c.sims + 2; p.sims = c.sims; p.mode = c.mode; p.c_puct = c.c_puct;
     const size_t edges = static_cast<size_t>(p.G) * p.cap * p.Ap;
-    double* lut = nullptr;
-    bool bad = hipSetDevice(c.device) != hipSuccess || hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess;
-    bad = bad || ro_alloc(r, &p.N, edges) || ro_alloc(r, &p.W, edges) || ro_alloc(r, &p.CH, edges) ||
-          ro_alloc(r, &p.NK, static_cast<size_t>(p.G) * p.cap) || ro_alloc(r, &p.rootpos, p.G) ||
-          ro_alloc(r, &p.mt, static_cast<size_t>(p.G) * 624) || ro_alloc(r, &p.mtpos, p.G) ||
-          ro_alloc(r, &lut, c.sims + 3) || ro_alloc(r, &p.out_pi, static_cast<size_t>(p.G) * r->A) ||
-          ro_alloc(r, &p.out_stat, static_cast<size_t>(p.G) * r->A) || ro_alloc(r, &p.action, p.G) ||
-          ro_alloc(r, &p.err, p.G) || ro_alloc(r, &r->d_active, p.G);
-    if (!bad) {
-        std::vector<double> h(static_cast<size_t>(c.sims) + 3);
-        for (size_t i = 0; i < h.size(); ++i) h[i] = std::log(static_cast<double>(i));  // np.log(total_n); ln 0 = -inf
-        bad = hipMemcpy(lut, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) != hipSuccess;
-        p.log_lut = lut;
-    }
-    if (bad) {
-        g_rollout_create_error = "ao_rollout_create: " + (r->err.empty() ? std::string("HIP initialisation failed") : r->err);
-        for (void* q : r->allocs) hipFree(q);
-        if (r->stream) hipStreamDestroy(r->stream);
-        delete r;
+    ao::DevPool& pool = r->pool;
+    AO_HIP(r, hipSetDevice(c.device));
+    AO_HIP(r, hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    if (pool.alloc(r, &p.N, edges) || pool.alloc(r, &p.W, edges) || pool.alloc(r, &p.CH, edges) ||
+        pool.alloc(r, &p.NK, static_cast<size_t>(p.G) * p.cap) || pool.alloc(r, &p.rootpos, p.G) ||
+        pool.alloc(r, &p.mt, static_cast<size_t>(p.G) * 624) || pool.alloc(r, &p.mtpos, p.G) ||
+        upload_log_lut(r, pool, c.sims, &p.log_lut) || pool.alloc(r, &p.out_pi, static_cast<size_t>(p.G) * r->A) ||
+        pool.alloc(r, &p.out_stat, static_cast<size_t>(p.G) * r->A) || pool.alloc(r, &p.action, p.G) ||
+        pool.alloc(r, &p.err, p.G) || pool.alloc(r, &r->d_active, p.G))
         return 1;
-    }
     r->has_gauss.assign(p.G, 0);
     r->gauss.assign(p.G, 0.0);
     std::vector<uint32_t> mt(624);
@@ -575,26 +550,33 @@ int ao_rollout_create(const ao_rollout_config* cfg, ao_rollout** out) {
         const int32_t pos = 624;
         hipMemcpy(p.mtpos + g, &pos, sizeof(int32_t), hipMemcpyHostToDevice);
     }
-    *out = r;
     return 0;
 }
+
+extern "C" {
 
 void ao_rollout_destroy(ao_rollout* r) {
     if (!r) return;
     hipSetDevice(r->cfg.device);
-    if (r->stream) { hipStreamSynchronize(r->stream); hipStreamDestroy(r->stream); }
-    for (void* q : r->allocs) hipFree(q);
+    if (r->stream) hipStreamSynchronize(r->stream);
+    r->pool.free_all();
+    if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
 
-const char* ao_rollout_last_error(const ao_rollout* r) { return r ? r->err.c_str() : g_rollout_create_error.c_str(); }
+int ao_rollout_create(const ao_rollout_config* cfg, ao_rollout** out) {
+    ao_rollout* r = new ao_rollout;
+    return ao::finish_create(r, rollout_create_impl(r, cfg), out, ao_rollout_destroy, "ao_rollout_create: ");
+}
+
+const char* ao_rollout_last_error(const ao_rollout* r) { return r ? r->err.c_str() : ao::create_error<ao_rollout>().c_str(); }
 
 int ao_rollout_set_rng_state(ao_rollout* r, int g, const uint32_t* mt, int32_t pos, int32_t has_gauss, double gauss) {
     if (g < 0 || g >= r->G) return r->fail("game index out of range");
-    RO_HIP(r, hipSetDevice(r->cfg.device));
-    RO_HIP(r, hipMemcpyAsync(r->p.mt + static_cast<size_t>(g) * 624, mt, sizeof(uint32_t) * 624, hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipMemcpyAsync(r->p.mtpos + g, &pos, sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipStreamSynchronize(r->stream));
+    AO_HIP(r, hipSetDevice(r->cfg.device));
+    AO_HIP(r, hipMemcpyAsync(r->p.mt + static_cast<size_t>(g) * 624, mt, sizeof(uint32_t) * 624, hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipMemcpyAsync(r->p.mtpos + g, &pos, sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipStreamSynchronize(r->stream));
     r->has_gauss[g] = has_gauss;
     r->gauss[g] = gauss;
     return 0;
@@ -602,10 +584,10 @@ int ao_rollout_set_rng_state(ao_rollout* r, int g, const uint32_t* mt, int32_t p
 
 int ao_rollout_get_rng_state(ao_rollout* r, int g, uint32_t* mt, int32_t* pos, int32_t* has_gauss, double* gauss) {
     if (g < 0 || g >= r->G) return r->fail("game index out of range");
-    RO_HIP(r, hipSetDevice(r->cfg.device));
-    RO_HIP(r, hipMemcpyAsync(mt, r->p.mt + static_cast<size_t>(g) * 624, sizeof(uint32_t) * 624, hipMemcpyDeviceToHost, r->stream));
-    RO_HIP(r, hipMemcpyAsync(pos, r->p.mtpos + g, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
-    RO_HIP(r, hipStreamSynchronize(r->stream));
+    AO_HIP(r, hipSetDevice(r->cfg.device));
+    AO_HIP(r, hipMemcpyAsync(mt, r->p.mt + static_cast<size_t>(g) * 624, sizeof(uint32_t) * 624, hipMemcpyDeviceToHost, r->stream));
+    AO_HIP(r, hipMemcpyAsync(pos, r->p.mtpos + g, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+    AO_HIP(r, hipStreamSynchronize(r->stream));
     if (has_gauss) *has_gauss = r->has_gauss[g];
     if (gauss) *gauss = r->gauss[g];
     return 0;
@@ -619,7 +601,7 @@ int ao_rollout_seed(ao_rollout* r, int g, uint32_t seed) {
 
 int ao_rollout_search(ao_rollout* r, const int32_t* moves, const int32_t* nmoves, const uint8_t* active, double* pi,
                       double* stat, int32_t* action) {
-    RO_HIP(r, hipSetDevice(r->cfg.device));
+    AO_HIP(r, hipSetDevice(r->cfg.device));
     const int G = r->G, A = r->A, B = r->cfg.board;
     std::vector<ao::Pos> pos(static_cast<size_t>(G));
     std::vector<uint8_t> act(static_cast<size_t>(G), 1);
@@ -658,25 +640,19 @@ int ao_rollout_search(ao_rollout* r, const int32_t* moves, const int32_t* nmoves
         if (last_win) return r->fail("game " + std::to_string(g) + ": the root position is already won");
         s.ply = static_cast<int16_t>(n);
     }
-    RO_HIP(r, hipMemcpyAsync(r->p.rootpos, pos.data(), sizeof(ao::Pos) * G, hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipMemcpyAsync(r->d_active, act.data(), G, hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipMemsetAsync(r->p.err, 0, sizeof(int32_t) * G, r->stream));
+    AO_HIP(r, hipMemcpyAsync(r->p.rootpos, pos.data(), sizeof(ao::Pos) * G, hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipMemcpyAsync(r->d_active, act.data(), G, hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipMemsetAsync(r->p.err, 0, sizeof(int32_t) * G, r->stream));
     ao::RollParams p = r->p;
     p.active = r->d_active;
-    const int nch = (A + 63) / 64;
-    switch (nch) {
-        case 1: hipLaunchKernelGGL(ao::k_rollout_search<1>, dim3(G), dim3(64), 0, r->stream, p); break;
-        case 2: hipLaunchKernelGGL(ao::k_rollout_search<2>, dim3(G), dim3(64), 0, r->stream, p); break;
-        case 3: hipLaunchKernelGGL(ao::k_rollout_search<3>, dim3(G), dim3(64), 0, r->stream, p); break;
-        default: hipLaunchKernelGGL(ao::k_rollout_search<4>, dim3(G), dim3(64), 0, r->stream, p); break;
-    }
-    RO_HIP(r, hipGetLastError());
+    AO_DISPATCH_NCH(ao::nch_of_cells(A), hipLaunchKernelGGL(ao::k_rollout_search<NCH>, dim3(G), dim3(64), 0, r->stream, p));
+    AO_HIP(r, hipGetLastError());
     std::vector<int32_t> herr(static_cast<size_t>(G));
-    RO_HIP(r, hipMemcpyAsync(herr.data(), r->p.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
-    if (pi) RO_HIP(r, hipMemcpyAsync(pi, r->p.out_pi, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
-    if (stat) RO_HIP(r, hipMemcpyAsync(stat, r->p.out_stat, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
-    if (action) RO_HIP(r, hipMemcpyAsync(action, r->p.action, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
-    RO_HIP(r, hipStreamSynchronize(r->stream));
+    AO_HIP(r, hipMemcpyAsync(herr.data(), r->p.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
+    if (pi) AO_HIP(r, hipMemcpyAsync(pi, r->p.out_pi, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
+    if (stat) AO_HIP(r, hipMemcpyAsync(stat, r->p.out_stat, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
+    if (action) AO_HIP(r, hipMemcpyAsync(action, r->p.action, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
+    AO_HIP(r, hipStreamSynchronize(r->stream));
     for (int g = 0; g < G; ++g)
         if (herr[static_cast<size_t>(g)]) return r->fail("game " + std::to_string(g) + ": rollout search failed (error bits " + std::to_string(herr[static_cast<size_t>(g)]) + ")");
     return 0;
@@ -686,28 +662,14 @@ int ao_rollout_search(ao_rollout* r, const int32_t* moves, const int32_t* nmoves
 }  // extern "C"
 
 // ---- 1_tictactoe_MCTS/mcts_vs.py ------------------------------------------------------------------
-struct ao_ttt {
+struct ao_ttt : ao::HandleBase {
     ao_ttt_config cfg{};
     ao::TttParams p{};
     int G = 0, A = 0;
-    std::vector<void*> allocs;
+    ao::DevPool pool;
     int8_t* d_boards = nullptr; int32_t* d_turns = nullptr; uint8_t* d_active = nullptr;
     hipStream_t stream = nullptr;
-    std::string err;
-    int fail(const std::string& m) { err = m; return 1; }
 };
-
-static thread_local std::string g_ttt_create_error;
-
-template <typename T>
-static int tt_alloc(ao_ttt* r, T** out, size_t count) {
-    void* q = nullptr;
-    hipError_t st = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16));
-    if (st != hipSuccess) return r->fail(std::string("hipMalloc: ") + hipGetErrorString(st));
-    r->allocs.push_back(q);
-    *out = static_cast<T*>(q);
-    return 0;
-}
 
 // random.seed(int < 2**32): MT19937 init_by_array([seed]) (CPython Modules/_randommodule.c)
 static void py_random_seed(uint32_t* mt, uint32_t seed) {
@@ -725,75 +687,64 @@ static void py_random_seed(uint32_t* mt, uint32_t seed) {
     mt[0] = 0x80000000u;
 }
 
-extern "C" {
-
-int ao_ttt_create(const ao_ttt_config* cfg, ao_ttt** out) {
-    *out = nullptr;
+static int ttt_create_impl(ao_ttt* r, const ao_ttt_config* cfg) {
     ao_ttt_config c = *cfg;
-    if (c.board < 3 || c.board > ao::kMaxBoard || c.sims < 1 || c.games < 1) {
-        g_ttt_create_error = "ao_ttt_create: board 3..15, sims >= 1, games >= 1";
-        return 1;
-    }
     if (c.win_mark <= 0) c.win_mark = (c.board == 3) ? 3 : 5;
-    ao_ttt* r = new ao_ttt;
     r->cfg = c; r->G = c.games; r->A = c.board * c.board;
+    if (c.board < 3 || c.board > ao::kMaxBoard || c.sims < 1 || c.games < 1) return r->fail("board 3..15, sims >= 1, games >= 1");
     ao::TttParams& p = r->p;
     p.B = c.board; p.A = r->A; p.win_mark = c.win_mark; p.G = c.games; p.sims = c.sims;
     p.cap = 1 + c.sims * r->A;   // one expansion of at most A children per iteration
     const size_t nodes = static_cast<size_t>(p.G) * p.cap;
-    double* lut = nullptr;
-    bool bad = hipSetDevice(c.device) != hipSuccess || hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess;
-    bad = bad || tt_alloc(r, &p.PAR, nodes) || tt_alloc(r, &p.KID, nodes) || tt_alloc(r, &p.N, nodes) ||
-          tt_alloc(r, &p.W, nodes) || tt_alloc(r, &p.NK, nodes) || tt_alloc(r, &p.ACT, nodes) || tt_alloc(r, &p.PL, nodes) ||
-          tt_alloc(r, &p.mt, static_cast<size_t>(p.G) * 624) || tt_alloc(r, &p.mtpos, p.G) || tt_alloc(r, &lut, c.sims + 3) ||
-          tt_alloc(r, &p.out_q, static_cast<size_t>(p.G) * r->A) || tt_alloc(r, &p.out_n, static_cast<size_t>(p.G) * r->A) ||
-          tt_alloc(r, &p.action, p.G) || tt_alloc(r, &p.err, p.G) || tt_alloc(r, &r->d_boards, static_cast<size_t>(p.G) * r->A) ||
-          tt_alloc(r, &r->d_turns, p.G) || tt_alloc(r, &r->d_active, p.G);
-    if (!bad) {
-        std::vector<double> h(static_cast<size_t>(c.sims) + 3);
-        for (size_t i = 0; i < h.size(); ++i) h[i] = std::log(static_cast<double>(i));
-        bad = hipMemcpy(lut, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) != hipSuccess;
-        p.log_lut = lut;
-    }
-    if (bad) {
-        g_ttt_create_error = "ao_ttt_create: " + (r->err.empty() ? std::string("HIP initialisation failed") : r->err);
-        for (void* q : r->allocs) hipFree(q);
-        if (r->stream) hipStreamDestroy(r->stream);
-        delete r;
+    ao::DevPool& pool = r->pool;
+    AO_HIP(r, hipSetDevice(c.device));
+    AO_HIP(r, hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    if (pool.alloc(r, &p.PAR, nodes) || pool.alloc(r, &p.KID, nodes) || pool.alloc(r, &p.N, nodes) ||
+        pool.alloc(r, &p.W, nodes) || pool.alloc(r, &p.NK, nodes) || pool.alloc(r, &p.ACT, nodes) || pool.alloc(r, &p.PL, nodes) ||
+        pool.alloc(r, &p.mt, static_cast<size_t>(p.G) * 624) || pool.alloc(r, &p.mtpos, p.G) || upload_log_lut(r, pool, c.sims, &p.log_lut) ||
+        pool.alloc(r, &p.out_q, static_cast<size_t>(p.G) * r->A) || pool.alloc(r, &p.out_n, static_cast<size_t>(p.G) * r->A) ||
+        pool.alloc(r, &p.action, p.G) || pool.alloc(r, &p.err, p.G) || pool.alloc(r, &r->d_boards, static_cast<size_t>(p.G) * r->A) ||
+        pool.alloc(r, &r->d_turns, p.G) || pool.alloc(r, &r->d_active, p.G))
         return 1;
-    }
     p.boards = r->d_boards;
     p.turns = r->d_turns;
-    *out = r;
     for (int g = 0; g < p.G; ++g) ao_ttt_seed(r, g, static_cast<uint32_t>(g));
     return 0;
 }
 
+extern "C" {
+
 void ao_ttt_destroy(ao_ttt* r) {
     if (!r) return;
     hipSetDevice(r->cfg.device);
-    if (r->stream) { hipStreamSynchronize(r->stream); hipStreamDestroy(r->stream); }
-    for (void* q : r->allocs) hipFree(q);
+    if (r->stream) hipStreamSynchronize(r->stream);
+    r->pool.free_all();
+    if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
 
-const char* ao_ttt_last_error(const ao_ttt* r) { return r ? r->err.c_str() : g_ttt_create_error.c_str(); }
+int ao_ttt_create(const ao_ttt_config* cfg, ao_ttt** out) {
+    ao_ttt* r = new ao_ttt;
+    return ao::finish_create(r, ttt_create_impl(r, cfg), out, ao_ttt_destroy, "ao_ttt_create: ");
+}
+
+const char* ao_ttt_last_error(const ao_ttt* r) { return r ? r->err.c_str() : ao::create_error<ao_ttt>().c_str(); }
 
 int ao_ttt_set_rng_state(ao_ttt* r, int g, const uint32_t* mt, int32_t pos) {
     if (g < 0 || g >= r->G) return r->fail("game index out of range");
-    RO_HIP(r, hipSetDevice(r->cfg.device));
-    RO_HIP(r, hipMemcpyAsync(r->p.mt + static_cast<size_t>(g) * 624, mt, sizeof(uint32_t) * 624, hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipMemcpyAsync(r->p.mtpos + g, &pos, sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipStreamSynchronize(r->stream));
+    AO_HIP(r, hipSetDevice(r->cfg.device));
+    AO_HIP(r, hipMemcpyAsync(r->p.mt + static_cast<size_t>(g) * 624, mt, sizeof(uint32_t) * 624, hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipMemcpyAsync(r->p.mtpos + g, &pos, sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipStreamSynchronize(r->stream));
     return 0;
 }
 
 int ao_ttt_get_rng_state(ao_ttt* r, int g, uint32_t* mt, int32_t* pos) {
     if (g < 0 || g >= r->G) return r->fail("game index out of range");
-    RO_HIP(r, hipSetDevice(r->cfg.device));
-    RO_HIP(r, hipMemcpyAsync(mt, r->p.mt + static_cast<size_t>(g) * 624, sizeof(uint32_t) * 624, hipMemcpyDeviceToHost, r->stream));
-    RO_HIP(r, hipMemcpyAsync(pos, r->p.mtpos + g, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
-    RO_HIP(r, hipStreamSynchronize(r->stream));
+    AO_HIP(r, hipSetDevice(r->cfg.device));
+    AO_HIP(r, hipMemcpyAsync(mt, r->p.mt + static_cast<size_t>(g) * 624, sizeof(uint32_t) * 624, hipMemcpyDeviceToHost, r->stream));
+    AO_HIP(r, hipMemcpyAsync(pos, r->p.mtpos + g, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+    AO_HIP(r, hipStreamSynchronize(r->stream));
     return 0;
 }
 
@@ -805,7 +756,7 @@ int ao_ttt_seed(ao_ttt* r, int g, uint32_t seed) {
 
 int ao_ttt_search(ao_ttt* r, const int8_t* boards, const int32_t* turns, const uint8_t* active, double* q, double* n,
                   int32_t* action) {
-    RO_HIP(r, hipSetDevice(r->cfg.device));
+    AO_HIP(r, hipSetDevice(r->cfg.device));
     const int G = r->G, A = r->A;
     std::vector<uint8_t> act(static_cast<size_t>(G), 1);
     for (int g = 0; g < G; ++g) {
@@ -819,25 +770,20 @@ int ao_ttt_search(ao_ttt* r, const int8_t* boards, const int32_t* turns, const u
         }
         if (empty == 0) return r->fail("game " + std::to_string(g) + ": the board is full");
     }
-    RO_HIP(r, hipMemcpyAsync(r->d_boards, boards, static_cast<size_t>(G) * A, hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipMemcpyAsync(r->d_turns, turns, sizeof(int32_t) * G, hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipMemcpyAsync(r->d_active, act.data(), G, hipMemcpyHostToDevice, r->stream));
-    RO_HIP(r, hipMemsetAsync(r->p.err, 0, sizeof(int32_t) * G, r->stream));
+    AO_HIP(r, hipMemcpyAsync(r->d_boards, boards, static_cast<size_t>(G) * A, hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipMemcpyAsync(r->d_turns, turns, sizeof(int32_t) * G, hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipMemcpyAsync(r->d_active, act.data(), G, hipMemcpyHostToDevice, r->stream));
+    AO_HIP(r, hipMemsetAsync(r->p.err, 0, sizeof(int32_t) * G, r->stream));
     ao::TttParams p = r->p;
     p.active = r->d_active;
-    switch ((A + 63) / 64) {
-        case 1: hipLaunchKernelGGL(ao::k_ttt_search<1>, dim3(G), dim3(64), 0, r->stream, p); break;
-        case 2: hipLaunchKernelGGL(ao::k_ttt_search<2>, dim3(G), dim3(64), 0, r->stream, p); break;
-        case 3: hipLaunchKernelGGL(ao::k_ttt_search<3>, dim3(G), dim3(64), 0, r->stream, p); break;
-        default: hipLaunchKernelGGL(ao::k_ttt_search<4>, dim3(G), dim3(64), 0, r->stream, p); break;
-    }
-    RO_HIP(r, hipGetLastError());
+    AO_DISPATCH_NCH(ao::nch_of_cells(A), hipLaunchKernelGGL(ao::k_ttt_search<NCH>, dim3(G), dim3(64), 0, r->stream, p));
+    AO_HIP(r, hipGetLastError());
     std::vector<int32_t> herr(static_cast<size_t>(G));
-    RO_HIP(r, hipMemcpyAsync(herr.data(), r->p.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
-    if (q) RO_HIP(r, hipMemcpyAsync(q, r->p.out_q, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
-    if (n) RO_HIP(r, hipMemcpyAsync(n, r->p.out_n, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
-    if (action) RO_HIP(r, hipMemcpyAsync(action, r->p.action, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
-    RO_HIP(r, hipStreamSynchronize(r->stream));
+    AO_HIP(r, hipMemcpyAsync(herr.data(), r->p.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
+    if (q) AO_HIP(r, hipMemcpyAsync(q, r->p.out_q, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
+    if (n) AO_HIP(r, hipMemcpyAsync(n, r->p.out_n, sizeof(double) * G * A, hipMemcpyDeviceToHost, r->stream));
+    if (action) AO_HIP(r, hipMemcpyAsync(action, r->p.action, sizeof(int32_t) * G, hipMemcpyDeviceToHost, r->stream));
+    AO_HIP(r, hipStreamSynchronize(r->stream));
     for (int g = 0; g < G; ++g)
         if (herr[static_cast<size_t>(g)]) return r->fail("game " + std::to_string(g) + ": search failed (error bits " + std::to_string(herr[static_cast<size_t>(g)]) + ")");
     return 0;

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "host_handle.hpp"
 #include "tree_device.hpp"
 #include "net_device.hpp"
 
@@ -142,12 +143,7 @@ __global__ __launch_bounds__(1024) void k_step_board(TreeParams p, StepNet f, co
 
 void launch_step_board(const TreeParams& p, const StepNet& f, int rows, const int32_t* game_of_row, hipStream_t s) {
     const size_t lds = heads_lds_floats(p.A, f.planes) * sizeof(float);
-    switch ((p.A + 63) / 64) {
-        case 1: hipLaunchKernelGGL(k_step_board<1>, dim3(rows), dim3(1024), lds, s, p, f, game_of_row); break;
-        case 2: hipLaunchKernelGGL(k_step_board<2>, dim3(rows), dim3(1024), lds, s, p, f, game_of_row); break;
-        case 3: hipLaunchKernelGGL(k_step_board<3>, dim3(rows), dim3(1024), lds, s, p, f, game_of_row); break;
-        default: hipLaunchKernelGGL(k_step_board<4>, dim3(rows), dim3(1024), lds, s, p, f, game_of_row); break;
-    }
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_step_board<NCH>, dim3(rows), dim3(1024), lds, s, p, f, game_of_row));
 #ifdef AO_PROF
     if (getenv("AO_PROF_TREE")) {
         static int count = 0;

@@ -19,6 +19,7 @@
 // Arithmetic contract: fp64 PUCT evaluated left to right with no
 // FMA contraction (explicit __dmul_rn/__ddiv_rn/__dadd_rn), sqrt(total_n) from a host-built
 // table of correctly rounded values, fp32 w/q with correctly rounded add/divide.
+#include "host_handle.hpp"
 #include "tree_device.hpp"
 
 namespace ao {
@@ -484,24 +485,14 @@ __global__ void k_reset(TreeParams p, const uint8_t* mask) {
 // ----------------------------------------------------------------------------------------------
 // launchers (called from engine.hip)
 // ----------------------------------------------------------------------------------------------
-#define AO_DISPATCH_NCH(nch, ...)                    \
-    switch (nch) {                                   \
-        case 1: { constexpr int NCH = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int NCH = 2; __VA_ARGS__; } break; \
-        case 3: { constexpr int NCH = 3; __VA_ARGS__; } break; \
-        default: { constexpr int NCH = 4; __VA_ARGS__; } break; \
-    }
-
-static inline int nch_of(const TreeParams& p) { return (p.A + 63) / 64; }
-
 void launch_select(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_select<NCH>, dim3(p.G), dim3(64), 0, s, p));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_select<NCH>, dim3(p.G), dim3(64), 0, s, p));
 }
 void launch_expand_backup(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_expand_backup<NCH>, dim3(p.G), dim3(64), 0, s, p));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_expand_backup<NCH>, dim3(p.G), dim3(64), 0, s, p));
 }
 void launch_expand_select(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_expand_select<NCH>, dim3((p.G + kGamesPerWG - 1) / kGamesPerWG), dim3(64 * kGamesPerWG), 0, s, p));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_expand_select<NCH>, dim3((p.G + kGamesPerWG - 1) / kGamesPerWG), dim3(64 * kGamesPerWG), 0, s, p));
 #ifdef AO_PROF
     if (getenv("AO_PROF_TREE")) {
         static int count = 0;
@@ -546,23 +537,23 @@ __global__ __launch_bounds__(1024) void k_order(TreeParams p, int32_t* order) {
 void launch_order(const TreeParams& p, int32_t* order, hipStream_t s) { hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, s, p, order); }
 
 void launch_begin_move(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_begin_move<NCH>, dim3(p.G), dim3(64), 0, s, p));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_begin_move<NCH>, dim3(p.G), dim3(64), 0, s, p));
 }
 void launch_end_move(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_end_move<NCH>, dim3(p.G), dim3(64), 0, s, p));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_end_move<NCH>, dim3(p.G), dim3(64), 0, s, p));
 }
 static void launch_reroot(const TreeParams& p, int count, const int32_t* games, hipStream_t s) {
     const size_t lds = (2 * kRerootWaves + static_cast<size_t>(p.cap)) * 4;
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_reroot<NCH>, dim3(count), dim3(64 * kRerootWaves), lds, s, p, games));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_reroot<NCH>, dim3(count), dim3(64 * kRerootWaves), lds, s, p, games));
 }
 void launch_play(const TreeParams& p, hipStream_t s) {
     const size_t lds = 2496 + 2048;
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_play<NCH>, dim3(p.G), dim3(64), lds, s, p));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_play<NCH>, dim3(p.G), dim3(64), lds, s, p));
     launch_reroot(p, p.G, nullptr, s);
 }
 void launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
                  const int32_t* prev_known, int32_t* status_out, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of(p), hipLaunchKernelGGL(k_walk<NCH>, dim3(count), dim3(64), 0, s, p, games, extra, stride, m,
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_walk<NCH>, dim3(count), dim3(64), 0, s, p, games, extra, stride, m,
                                                    prev_known, status_out));
     launch_reroot(p, count, games, s);
 }

@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "../../include/omok_hip.h"
+#include "host_handle.hpp"
 #include "tree_device.hpp"
 
 namespace ao {
@@ -283,31 +284,24 @@ __global__ __launch_bounds__(64 * kStatWaves) void k_tree_stats(TreeParams p, co
 // ----------------------------------------------------------------------------------------------
 // launchers (called from engine.hip)
 // ----------------------------------------------------------------------------------------------
-#define AO_READ_DISPATCH_NCH(nch, ...)               \
-    switch (nch) {                                   \
-        case 1: { constexpr int NCH = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int NCH = 2; __VA_ARGS__; } break; \
-        case 3: { constexpr int NCH = 3; __VA_ARGS__; } break; \
-        default: { constexpr int NCH = 4; __VA_ARGS__; } break; \
-    }
 
 void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
                         int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s) {
     const LookupOut o{status, nchild, nwqp, c_act, c_n, c_w, c_q, c_p};
     const dim3 grid(static_cast<unsigned>((n + kReadPerWG - 1) / kReadPerWG)), block(64 * kReadPerWG);
-    AO_READ_DISPATCH_NCH((p.A + 63) / 64, hipLaunchKernelGGL(k_tree_lookup<NCH>, grid, block, 0, s, p, queries, n, stride, o));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_lookup<NCH>, grid, block, 0, s, p, queries, n, stride, o));
 }
 
 void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>((p.G + kReadPerWG - 1) / kReadPerWG)), block(64 * kReadPerWG);
-    AO_READ_DISPATCH_NCH((p.A + 63) / 64, hipLaunchKernelGGL(k_tree_pv<NCH>, grid, block, 0, s, p, mask, max_len, act, n, q, len));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_pv<NCH>, grid, block, 0, s, p, mask, max_len, act, n, q, len));
 }
 
 // non-zero: the queue of a `cap`-node arena does not fit the LDS of one workgroup -- nothing is launched
 int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s) {
     const size_t lds = (3 * kStatWaves + static_cast<size_t>(p.cap)) * 4;
     if (lds > kMaxDynLds) return 1;
-    AO_READ_DISPATCH_NCH((p.A + 63) / 64, hipLaunchKernelGGL(k_tree_stats<NCH>, dim3(p.G), dim3(64 * kStatWaves), lds, s, p, mask, out));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_stats<NCH>, dim3(p.G), dim3(64 * kStatWaves), lds, s, p, mask, out));
     return 0;
 }
 

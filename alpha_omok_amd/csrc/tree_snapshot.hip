@@ -10,6 +10,7 @@
 // Lanes run over a node's <= 225 edges in NCH chunks of 64; what steers control flow (node, level, counts) is wave-uniform.
 #include <cstdint>
 
+#include "host_handle.hpp"
 #include "tree_device.hpp"
 #include "tree_snapshot.hpp"
 
@@ -230,24 +231,17 @@ __global__ __launch_bounds__(64 * kSnapWaves) void k_tree_unpack(TreeParams p, S
 // ----------------------------------------------------------------------------------------------
 // launchers (called from engine.hip)
 // ----------------------------------------------------------------------------------------------
-#define AO_SNAP_DISPATCH_NCH(nch, ...)               \
-    switch (nch) {                                   \
-        case 1: { constexpr int NCH = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int NCH = 2; __VA_ARGS__; } break; \
-        case 3: { constexpr int NCH = 3; __VA_ARGS__; } break; \
-        default: { constexpr int NCH = 4; __VA_ARGS__; } break; \
-    }
 
 int launch_tree_pack(const TreeParams& p, const SnapDev& d, const int32_t* table, int games, hipStream_t s) {
     const size_t lds = (3 * kSnapWaves + static_cast<size_t>(p.cap)) * 4;   // k_tree_stats' rule
     if (lds > kSnapMaxDynLds) return 1;
-    AO_SNAP_DISPATCH_NCH((p.A + 63) / 64, hipLaunchKernelGGL(k_tree_pack<NCH>, dim3(games), dim3(64 * kSnapWaves), lds, s, p, d, table));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_pack<NCH>, dim3(games), dim3(64 * kSnapWaves), lds, s, p, d, table));
     return 0;
 }
 
 void launch_tree_unpack(const TreeParams& p, const SnapDev& d, const int32_t* table, const int32_t* moves, const uint32_t* mt, int games,
                         hipStream_t s) {
-    AO_SNAP_DISPATCH_NCH((p.A + 63) / 64, hipLaunchKernelGGL(k_tree_unpack<NCH>, dim3(games), dim3(64 * kSnapWaves), 0, s, p, d, table, moves, mt));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_unpack<NCH>, dim3(games), dim3(64 * kSnapWaves), 0, s, p, d, table, moves, mt));
 }
 
 }  // namespace ao
