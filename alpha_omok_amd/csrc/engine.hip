@@ -32,9 +32,10 @@ void launch_expand_select(const TreeParams& p, hipStream_t s);
 void launch_begin_move(const TreeParams& p, hipStream_t s);
 void launch_order(const TreeParams& p, int32_t* order, hipStream_t s);
 void launch_end_move(const TreeParams& p, hipStream_t s);
-void launch_play(const TreeParams& p, hipStream_t s);
-void launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
-                 const int32_t* prev_known, int32_t* status_out, hipStream_t s);
+// launch_play, launch_walk, launch_tree_stats, launch_tree_pack: non-zero = refused by walk_lds_bytes (tree_walk.hpp), nothing launched
+int launch_play(const TreeParams& p, hipStream_t s);
+int launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
+                const int32_t* prev_known, int32_t* status_out, hipStream_t s);
 void launch_reset(const TreeParams& p, const uint8_t* mask, hipStream_t s);
 // tree_readout.hip
 void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
@@ -408,6 +409,11 @@ int ao_reset(ao_engine* e, const uint8_t* mask) {
     return 0;
 }
 
+// a launcher refused by walk_lds_bytes (tree_walk.hpp); ao_create's node_cap <= 15000 keeps every engine below that bound
+static int queue_refused(ao_engine* e, const char* who) {
+    return e->fail(std::string(who) + ": the breadth-first queue of a node_cap = " + std::to_string(e->tp.cap) + " arena does not fit the LDS of a workgroup");
+}
+
 // Walks the listed games along their new ids in ONE launch (k_walk: a workgroup per listed game).
 // ids[k] / ns[k]: full move list of games[k]. Games whose new id does not extend the kept one are reset first.
 static int set_roots_impl(ao_engine* e, int count, const int32_t* games, const int32_t* const* ids, const int32_t* ns,
@@ -452,7 +458,8 @@ static int set_roots_impl(ao_engine* e, int count, const int32_t* games, const i
     int32_t* d_games = e->d_extra + static_cast<size_t>(count) * A;
     AO_HIP(e, hipMemcpyAsync(e->d_extra, h_extra, sizeof(int32_t) * (static_cast<size_t>(count) * A + 3 * static_cast<size_t>(count)),
                              hipMemcpyHostToDevice, e->stream));
-    ao::launch_walk(e->tp, count, d_games, e->d_extra, A, d_games + count, d_games + 2 * count, d_games + 3 * count, e->stream);
+    if (ao::launch_walk(e->tp, count, d_games, e->d_extra, A, d_games + count, d_games + 2 * count, d_games + 3 * count, e->stream))
+        return queue_refused(e, "ao_set_roots");
     AO_HIP(e, hipGetLastError());
     int32_t* h_st = h_pk + count;
     AO_HIP(e, hipMemcpyAsync(h_st, d_games + 3 * count, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
@@ -652,7 +659,7 @@ int ao_play(ao_engine* e, int32_t* action, int32_t* win) {
     if (!e->ended) return e->fail("ao_play must follow ao_end_move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const int G = e->G;
-    ao::launch_play(e->tp, e->stream);
+    if (ao::launch_play(e->tp, e->stream)) return queue_refused(e, "ao_play");
     int32_t* ha = e->h_i32;
     int32_t* hw = e->h_i32 + G;
     int32_t* hs = e->h_i32 + 3 * G;
@@ -1231,7 +1238,7 @@ int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
     uint8_t* d_mask = e->d_ro.p + 16 * G;
     AO_HIP(e, hipMemcpyAsync(d_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
     if (ao::launch_tree_stats(e->tp, d_mask, reinterpret_cast<int32_t*>(e->d_ro.p), e->stream))
-        return e->fail("ao_tree_stats: the breadth-first queue of a node_cap = " + std::to_string(e->tp.cap) + " arena does not fit the LDS of a workgroup");
+        return queue_refused(e, "ao_tree_stats");
     AO_HIP(e, hipGetLastError());
     AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, 16 * G, hipMemcpyDeviceToHost, e->stream));
     AO_HIP(e, hipStreamSynchronize(e->stream));
@@ -1319,7 +1326,7 @@ int ao_tree_export(ao_engine* e, const uint8_t* mask, ao_tree_snapshot* out) {
         const ao::SnapDev d = ao::snap_dev_at(e->d_ro.p, c.N, c.E);
         AO_HIP(e, hipMemcpyAsync(e->d_ro.p + tab_at, h_tab, static_cast<size_t>(c.count) * ao::kSnapRow * 4, hipMemcpyHostToDevice, e->stream));
         if (ao::launch_tree_pack(e->tp, d, reinterpret_cast<const int32_t*>(e->d_ro.p + tab_at), c.count, e->stream))
-            return e->fail("ao_tree_export: the breadth-first queue of a node_cap = " + std::to_string(e->tp.cap) + " arena does not fit the LDS of a workgroup");
+            return queue_refused(e, "ao_tree_export");
         AO_HIP(e, hipGetLastError());
         AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, ao::snap_packed_bytes(c.N, c.E), hipMemcpyDeviceToHost, e->stream));
         AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffers are reused by the next chunk

@@ -13,14 +13,16 @@
 //   k_begin_move      agents.py:93-103 (re-noise of an inherited root)
 //   k_end_move        agents.py:64-80 + utils.py:198-205 (argmax_onehot)
 //   k_play            utils.py:189-195 (get_action) + env/env_small.py:154-176,196 (step)
-//                     + re-rooting (tree reuse across moves, main.py:171)
+//                     + re-rooting (tree reuse across moves, main.py:171): k_reroot, launched behind
+//                     k_play and k_walk, on the subtree walk of tree_walk.hpp
 //   k_walk            the `root_id in self.tree` lookup of agents.py:84 for an arbitrary id
+//                     (find_edge of tree_walk.hpp per move, as k_play and k_tree_lookup)
 //
 // Arithmetic contract: fp64 PUCT evaluated left to right with no
 // FMA contraction (explicit __dmul_rn/__ddiv_rn/__dadd_rn), sqrt(total_n) from a host-built
 // table of correctly rounded values, fp32 w/q with correctly rounded add/divide.
 #include "host_handle.hpp"
-#include "tree_device.hpp"
+#include "tree_walk.hpp"
 
 namespace ao {
 
@@ -192,20 +194,18 @@ __global__ __launch_bounds__(64) void k_end_move(TreeParams p) {
 
 // ----------------------------------------------------------------------------------------------
 // re-rooting: copy the subtree of the node k_play / k_walk chose (p.pending_root) into the other arena, breadth first, so the
-// arena holds only what later searches can reach. Reads the old arena only; the BFS queue lives in LDS.
-// One workgroup of kRerootWaves waves per game. With a network that has learned something the played child keeps most of the
+// arena holds only what later searches can reach. Reads the old arena only. The walk is walk_subtree (tree_walk.hpp: one
+// workgroup of kWalkWaves waves per game, the queue in LDS, the numbering every walker shares); this kernel supplies what is done
+// with a node: copy its record to its new number. With a network that has learned something the played child keeps most of the
 // root's visits -- subtrees of one to two thousand nodes -- and a copy that takes one node per memory round trip (rounds 1 - 5:
-// one wave per game inside k_play) lasted 12.5 ms per move of 4096 games (tools/time_move_phases.py --weights ...). Here wave w
-// takes queue entry head + w: the record reads of kRerootWaves nodes are in flight together, the children's new indices come from
-// a prefix over the waves' child counts, in queue order -- the SAME numbering as the one-node-at-a-time copy, entry for entry.
+// one wave per game inside k_play) lasted 12.5 ms per move of 4096 games (tools/time_move_phases.py --weights ...). Here the
+// record reads of kWalkWaves nodes are in flight together: all six rows and the position are requested in on_node, before the
+// round's barrier -- the SAME numbering as the one-node-at-a-time copy, entry for entry.
 // ----------------------------------------------------------------------------------------------
-constexpr int kRerootWaves = 8;
-
 template <int NCH>
-__global__ __launch_bounds__(64 * kRerootWaves) void k_reroot(TreeParams p, const int32_t* games) {
+__global__ __launch_bounds__(64 * kWalkWaves) void k_reroot(TreeParams p, const int32_t* games) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    int32_t* s_cnt = reinterpret_cast<int32_t*>(s_dyn);        // [kRerootWaves] children each wave's node brings, [kRerootWaves] dropped
-    int32_t* s_old = s_cnt + 2 * kRerootWaves;                 // [cap] old index of the node that becomes new index i
+    int32_t* lds = reinterpret_cast<int32_t*>(s_dyn);
     const int g = games ? games[blockIdx.x] : blockIdx.x;
     const int pend = p.pending_root[g];
     if (pend == 0) return;                                     // (uniform over the workgroup)
@@ -213,88 +213,51 @@ __global__ __launch_bounds__(64 * kRerootWaves) void k_reroot(TreeParams p, cons
     const int w = threadIdx.x >> 6;
     const int oa = p.cur[g];
     const int na = oa ^ 1;
-    if (threadIdx.x == 0) s_old[0] = pend - 1;
-    if (lane == 0) s_cnt[kRerootWaves + w] = 0;
-    __syncthreads();
-    int tail = 1;
+    PosR m;
+    int nn[NCH];
+    uint8_t act[NCH];
+    float ww[NCH], qq[NCH];
+    double pp[NCH];
     int dropped = 0;
-    for (int head = 0; head < tail;) {
-        const int h = head + w;
-        const bool have = h < tail;                            // (wave-uniform) this round takes queue entries [head, min(head + waves, tail))
-        const int next_head = head + kRerootWaves < tail ? head + kRerootWaves : tail;
-        size_t so = 0;
-        PosR m;
-        int ch[NCH], nn[NCH];
-        uint8_t act[NCH];
-        float ww[NCH], qq[NCH];
-        double pp[NCH];
-        bool valid[NCH];
-        int cnt = 0;
-        if (have) {
-            so = node_slot(p, oa, g, s_old[h]);
-            m = pos_load(nodePos(p, so));
-            const int L = m.nchild;
+    const WalkEnd end = walk_subtree<NCH>(
+        p, g, oa, pend - 1, p.keep_max, lds,
+        [&](const WalkNode& nd, const PosR& pos) {
+            m = pos;
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const int e = lane + 64 * c;
-                valid[c] = e < L;
-                ch[c] = valid[c] ? rowCH(p, so)[e] : CH_UNVISITED;
-                nn[c] = valid[c] ? rowN(p, so)[e] : 0;
-                ww[c] = valid[c] ? rowW(p, so)[e] : 0.f;
-                qq[c] = valid[c] ? rowQ(p, so)[e] : 0.f;
-                pp[c] = valid[c] ? rowP(p, so)[e] : 0.0;
-                act[c] = valid[c] ? rowACT(p, so)[e] : 0;
-                cnt += __popcll(__ballot(valid[c] && ch[c] >= 0));
+                const bool valid = e < nd.L;
+                nn[c] = valid ? rowN(p, nd.slot)[e] : 0;
+                ww[c] = valid ? rowW(p, nd.slot)[e] : 0.f;
+                qq[c] = valid ? rowQ(p, nd.slot)[e] : 0.f;
+                pp[c] = valid ? rowP(p, nd.slot)[e] : 0.0;
+                act[c] = valid ? rowACT(p, nd.slot)[e] : 0;
             }
-        }
-        if (lane == 0) s_cnt[w] = cnt;
-        __syncthreads();
-        int base = tail, total = 0;
-#pragma unroll
-        for (int k = 0; k < kRerootWaves; ++k) {
-            const int ck = s_cnt[k];
-            if (k < w) base += ck;
-            total += ck;
-        }
-        if (have) {
-            const size_t sn = node_slot(p, na, g, h);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int e = lane + 64 * c;
-                const bool ex = valid[c] && ch[c] >= 0;
-                const uint64_t mk = __ballot(ex);
-                const int idx = base + __popcll(mk & lanes_below());
-                // A full arena (a long game whose visits keep following the played line): the breadth-first copy stops at
-                // keep_max nodes, so the next move's expansions always fit. A child subtree that is not kept becomes an
-                // unvisited child again (its statistics are forgotten); the event is counted in p.trimmed (ao_trim_stats).
-                const bool keep = ex && idx < p.keep_max;
-                const bool drop = ex && !keep;
-                if (keep) s_old[idx] = ch[c];
-                if (valid[c]) {
-                    rowCH(p, sn)[e] = keep ? idx : (drop ? CH_UNVISITED : ch[c]);
-                    rowN(p, sn)[e] = drop ? 0 : nn[c];
-                    rowW(p, sn)[e] = drop ? 0.f : ww[c];
-                    rowQ(p, sn)[e] = drop ? 0.f : qq[c];
-                    rowP(p, sn)[e] = pp[c];
-                    rowACT(p, sn)[e] = act[c];
-                }
-                dropped += __popcll(__ballot(drop));
-                base += __popcll(mk);
+        },
+        [&](const WalkNode& nd, int c, int raw, int idx, bool kept) {
+            const size_t sn = node_slot(p, na, g, nd.h);
+            const int e = lane + 64 * c;
+            // A full arena (a long game whose visits keep following the played line): the breadth-first copy stops at
+            // keep_max nodes, so the next move's expansions always fit. A child subtree that is not kept becomes an
+            // unvisited child again (its statistics are forgotten); the event is counted in p.trimmed (ao_trim_stats).
+            const bool drop = idx >= 0 && !kept;
+            if (e < nd.L) {
+                rowCH(p, sn)[e] = kept ? idx : (drop ? CH_UNVISITED : raw);
+                rowN(p, sn)[e] = drop ? 0 : nn[c];
+                rowW(p, sn)[e] = drop ? 0.f : ww[c];
+                rowQ(p, sn)[e] = drop ? 0.f : qq[c];
+                rowP(p, sn)[e] = pp[c];
+                rowACT(p, sn)[e] = act[c];
             }
-            if (lane == 0) pos_store(nodePos(p, sn), m);
-        }
-        // (indices handed out in queue order: everything below keep_max is kept, so the queue grows by what fits)
-        const int room = p.keep_max - tail;
-        tail += total < room ? total : (room > 0 ? room : 0);
-        head = next_head;
-        __syncthreads();
-    }
-    if (lane == 0 && dropped > 0) s_cnt[kRerootWaves + w] = dropped;
+            dropped += __popcll(__ballot(drop));
+            if (c == NCH - 1 && lane == 0) pos_store(nodePos(p, sn), m);
+        });
+    if (lane == 0) lds[w] = dropped;                           // (behind the walk's last barrier: the header is free)
     __syncthreads();
     if (threadIdx.x == 0) {
         int d = 0;
-        for (int k = 0; k < kRerootWaves; ++k) d += s_cnt[kRerootWaves + k];
-        p.nodes_used[g] = tail;
+        for (int k = 0; k < kWalkWaves; ++k) d += lds[k];
+        p.nodes_used[g] = end.tail;
         p.cur[g] = na;
         p.root_node[g] = 0;
         p.pending_root[g] = 0;
@@ -350,14 +313,7 @@ __global__ __launch_bounds__(64) void k_play(TreeParams p) {
     int ch = CH_UNVISITED;
     if (node >= 0) {
         const size_t slot = node_slot(p, p.cur[g], g, node);
-        const int L = nodePos(p, slot)->nchild;
-        int found = -1;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int i = lane + 64 * c;
-            const uint64_t mk = __ballot(i < L && rowACT(p, slot)[i] == action);
-            if (found < 0 && mk) found = 64 * c + __ffsll(static_cast<long long>(mk)) - 1;
-        }
+        const int found = find_edge<NCH>(p, slot, nodePos(p, slot)->nchild, action);
         if (found >= 0) ch = rowCH(p, slot)[found];
     }
     if (ch >= 0 && w == 0) {
@@ -412,14 +368,7 @@ __global__ __launch_bounds__(64) void k_walk(TreeParams p, const int32_t* games,
         bool next_known = false;
         if (node >= 0) {
             const size_t slot = node_slot(p, p.cur[g], g, node);
-            const int L = nodePos(p, slot)->nchild;
-            int found = -1;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int e = lane + 64 * c;
-                const uint64_t mk = __ballot(e < L && rowACT(p, slot)[e] == a);
-                if (found < 0 && mk) found = 64 * c + __ffsll(static_cast<long long>(mk)) - 1;
-            }
+            const int found = find_edge<NCH>(p, slot, nodePos(p, slot)->nchild, a);
             if (found >= 0) {
                 next_known = true;  // children of an expanded node are dict entries
                 const int ch = rowCH(p, slot)[found];
@@ -543,19 +492,24 @@ void launch_end_move(const TreeParams& p, hipStream_t s) {
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_end_move<NCH>, dim3(p.G), dim3(64), 0, s, p));
 }
 static void launch_reroot(const TreeParams& p, int count, const int32_t* games, hipStream_t s) {
-    const size_t lds = (2 * kRerootWaves + static_cast<size_t>(p.cap)) * 4;
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_reroot<NCH>, dim3(count), dim3(64 * kRerootWaves), lds, s, p, games));
+    const size_t lds = walk_lds_bytes(p.cap);
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_reroot<NCH>, dim3(count), dim3(64 * kWalkWaves), lds, s, p, games));
 }
-void launch_play(const TreeParams& p, hipStream_t s) {
+// launch_play / launch_walk, non-zero: the re-rooting's queue does not fit the LDS of one workgroup (walk_lds_bytes) -- nothing is launched
+int launch_play(const TreeParams& p, hipStream_t s) {
+    if (!walk_lds_bytes(p.cap)) return 1;
     const size_t lds = 2496 + 2048;
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_play<NCH>, dim3(p.G), dim3(64), lds, s, p));
     launch_reroot(p, p.G, nullptr, s);
+    return 0;
 }
-void launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
+int launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
                  const int32_t* prev_known, int32_t* status_out, hipStream_t s) {
+    if (!walk_lds_bytes(p.cap)) return 1;
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_walk<NCH>, dim3(count), dim3(64), 0, s, p, games, extra, stride, m,
                                                    prev_known, status_out));
     launch_reroot(p, count, games, s);
+    return 0;
 }
 void launch_eval_log(const int32_t* games, int n, const int32_t* row_of_game, const float* policy, const float* value, int A,
                      float* out, const int32_t* sims_done, const int32_t* leaf_status, int what, hipStream_t s) {

@@ -1,7 +1,7 @@
 // tree_readout.hip -- reading the search trees where they live: node lookup by id, principal variations and tree statistics
-// for all games in one launch each, O(result) bytes back to the host. Every kernel here is READ-ONLY on TreeParams: they are the
-// counterparts of k_walk (id -> node by ballot over ACT) and k_reroot (breadth-first walk, queue in LDS) of tree_kernels.hip
-// with the writes taken out, so a search that follows a read-out is bit for bit the search that would have run without it.
+// for all games in one launch each, O(result) bytes back to the host. Every kernel here is READ-ONLY on TreeParams, so a search
+// that follows a read-out is bit for bit the search that would have run without it. They share their steps with the kernels that
+// write (tree_walk.hpp): find_edge (id -> node, as k_walk) and walk_subtree (the breadth-first walk of k_reroot).
 //
 // Reference map (paths relative to the reference's 2_AlphaOmok/):
 //   k_tree_lookup   agents.py:52,206-210  self.tree[node_id] -> {'child', 'n', 'w', 'q', 'p'} for n ids at once. The engine keeps a
@@ -13,43 +13,17 @@
 //                                         much of the arena that subtree occupies.
 //
 // One wavefront per query / per game (k_tree_lookup, k_tree_pv: kReadPerWG of them per workgroup, nothing shared, no barrier);
-// k_tree_stats: one workgroup of kStatWaves waves per game. Lanes run over a node's <= 225 edges in NCH chunks of 64; everything
+// k_tree_stats: one workgroup of kWalkWaves waves per game. Lanes run over a node's <= 225 edges in NCH chunks of 64; everything
 // that steers control flow (game, move, edge found, child link) is wave-uniform: ballots, readfirstlane, DPP reductions.
 #include <cstdint>
 
 #include "../../include/omok_hip.h"
 #include "host_handle.hpp"
-#include "tree_device.hpp"
+#include "tree_walk.hpp"
 
 namespace ao {
 
 constexpr int kReadPerWG = 4;
-constexpr int kStatWaves = 8;
-constexpr size_t kMaxDynLds = 64 * 1024;   // dynamic LDS a launch gets without opting in to more: the same bound k_reroot lives under
-
-// a child link that can be followed: an expanded child inside the arena (anything else in a consistent tree is CH_UNVISITED / CH_TERMINAL)
-__device__ __forceinline__ bool link_ok(const TreeParams& p, int ch) { return ch >= 0 && ch < p.cap; }
-
-__device__ __forceinline__ int node_nchild(const TreeParams& p, size_t slot) {
-    const int L = pos_load(nodePos(p, slot)).nchild;
-    return L < 0 ? 0 : (L > p.A ? p.A : L);
-}
-
-// stored index of the edge of `slot` that plays `a`, -1 if there is none (an occupied or off-board cell has no edge)
-template <int NCH>
-__device__ __forceinline__ int find_edge(const TreeParams& p, size_t slot, int L, int a) {
-    const int lane = lane_id();
-    const uint8_t* rACT = rowACT(p, slot);
-    int found = -1;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int e = lane + 64 * c;
-        const int ec = e < p.Ap ? e : p.Ap - 1;
-        const uint64_t mk = __ballot(e < L && static_cast<int>(rACT[ec]) == a);
-        if (found < 0 && mk) found = 64 * c + __ffsll(static_cast<long long>(mk)) - 1;
-    }
-    return found;
-}
 
 // ----------------------------------------------------------------------------------------------
 // k_tree_lookup: query i = (game, m moves beyond that game's root). Row i of `queries`: game, m (< 0: the id does not extend
@@ -187,24 +161,22 @@ __global__ __launch_bounds__(64 * kReadPerWG) void k_tree_pv(TreeParams p, const
 }
 
 // ----------------------------------------------------------------------------------------------
-// k_tree_stats: breadth-first walk of what the root reaches, queue in LDS, wave w takes queue entry head + w (k_reroot's scheme:
-// the record reads of kStatWaves nodes are in flight together); counts are accumulated where k_reroot copies records.
+// k_tree_stats: walk_subtree (tree_walk.hpp) over what the root reaches, inside the whole arena (limit = cap); counts are
+// accumulated where k_reroot copies records.
 // mask[g]: 0 = skip the game, 1 = its root is not a key (fresh), 2 = its root is a key. out[g] = {expanded nodes reachable from
 // the root, dict entries (1 + sum of nchild over them), depth, nodes_used}; depth = the largest ply + (nchild > 0) over the
 // reachable expanded nodes (the longest key of the reference's dict, minus one: agents.py:241-250), the root's ply if the root
 // is only known, 0 without a tree. A tree that reaches more than `cap` nodes cannot exist: expanded = -1 reports it.
 // ----------------------------------------------------------------------------------------------
 template <int NCH>
-__global__ __launch_bounds__(64 * kStatWaves) void k_tree_stats(TreeParams p, const uint8_t* __restrict__ mask, int32_t* __restrict__ out) {
+__global__ __launch_bounds__(64 * kWalkWaves) void k_tree_stats(TreeParams p, const uint8_t* __restrict__ mask, int32_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    int32_t* s_cnt = reinterpret_cast<int32_t*>(s_dyn);   // [kStatWaves] children each wave's node brings, then [kStatWaves] entries, [kStatWaves] depth
-    int32_t* s_q = s_cnt + 3 * kStatWaves;                // [cap] the queue: node indices in breadth-first order
+    int32_t* lds = reinterpret_cast<int32_t*>(s_dyn);
     const int g = blockIdx.x;
     const int mk_g = mask[g];
     if (mk_g == 0) return;                                // (uniform over the workgroup)
     const int lane = lane_id();
     const int w = threadIdx.x >> 6;
-    const int arena = p.cur[g];
     const int root = p.root_node[g];
     if (!link_ok(p, root)) {
         if (threadIdx.x == 0) {
@@ -215,66 +187,24 @@ __global__ __launch_bounds__(64 * kStatWaves) void k_tree_stats(TreeParams p, co
         }
         return;
     }
-    if (threadIdx.x == 0) s_q[0] = root;
-    __syncthreads();
-    int tail = 1, entries = 0, depth = 0;
-    bool over = false;
-    for (int head = 0; head < tail;) {
-        const int h = head + w;
-        const bool have = h < tail;                       // (wave-uniform) this round takes queue entries [head, min(head + waves, tail))
-        const int next_head = head + kStatWaves < tail ? head + kStatWaves : tail;
-        int ch[NCH];
-        int cnt = 0;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) ch[c] = -1;
-        if (have) {
-            const size_t slot = node_slot(p, arena, g, s_q[h]);
-            const PosR m = pos_load(nodePos(p, slot));
-            const int L = m.nchild < 0 ? 0 : (m.nchild > p.A ? p.A : m.nchild);
-            entries += L;
-            const int d = m.ply + (L > 0 ? 1 : 0);
+    int entries = 0, depth = 0;
+    const WalkEnd end = walk_subtree<NCH>(
+        p, g, p.cur[g], root, p.cap, lds,
+        [&](const WalkNode& nd, const PosR& m) {
+            entries += nd.L;
+            const int d = m.ply + (nd.L > 0 ? 1 : 0);
             depth = d > depth ? d : depth;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int e = lane + 64 * c;
-                const int ec = e < p.Ap ? e : p.Ap - 1;
-                const int v = rowCH(p, slot)[ec];
-                ch[c] = (e < L && link_ok(p, v)) ? v : -1;
-                cnt += __popcll(__ballot(ch[c] >= 0));
-            }
-        }
-        if (lane == 0) s_cnt[w] = cnt;
-        __syncthreads();
-        int base = tail, total = 0;
-#pragma unroll
-        for (int k = 0; k < kStatWaves; ++k) {
-            const int ck = s_cnt[k];
-            if (k < w) base += ck;
-            total += ck;
-        }
-        if (have) {
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const uint64_t mk = __ballot(ch[c] >= 0);
-                const int idx = base + __popcll(mk & lanes_below());
-                if (ch[c] >= 0 && idx < p.cap) s_q[idx] = ch[c];
-                base += __popcll(mk);
-            }
-        }
-        if (tail + total > p.cap) { over = true; tail = p.cap; }
-        else tail += total;
-        head = next_head;
-        __syncthreads();
-    }
-    if (lane == 0) { s_cnt[kStatWaves + w] = entries; s_cnt[2 * kStatWaves + w] = depth; }
+        },
+        [](const WalkNode&, int, int, int, bool) {});
+    if (lane == 0) { lds[w] = entries; lds[kWalkWaves + w] = depth; }   // (behind the walk's last barrier: the header is free)
     __syncthreads();
     if (threadIdx.x == 0) {
         int en = 1, dp = 0;
-        for (int k = 0; k < kStatWaves; ++k) {
-            en += s_cnt[kStatWaves + k];
-            dp = s_cnt[2 * kStatWaves + k] > dp ? s_cnt[2 * kStatWaves + k] : dp;
+        for (int k = 0; k < kWalkWaves; ++k) {
+            en += lds[k];
+            dp = lds[kWalkWaves + k] > dp ? lds[kWalkWaves + k] : dp;
         }
-        out[4 * g + 0] = over ? -1 : tail;
+        out[4 * g + 0] = end.over ? -1 : end.tail;
         out[4 * g + 1] = en;
         out[4 * g + 2] = dp;
         out[4 * g + 3] = p.nodes_used[g];
@@ -297,11 +227,11 @@ void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_pv<NCH>, grid, block, 0, s, p, mask, max_len, act, n, q, len));
 }
 
-// non-zero: the queue of a `cap`-node arena does not fit the LDS of one workgroup -- nothing is launched
+// non-zero: the queue of a `cap`-node arena does not fit the LDS of one workgroup (walk_lds_bytes) -- nothing is launched
 int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s) {
-    const size_t lds = (3 * kStatWaves + static_cast<size_t>(p.cap)) * 4;
-    if (lds > kMaxDynLds) return 1;
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_stats<NCH>, dim3(p.G), dim3(64 * kStatWaves), lds, s, p, mask, out));
+    const size_t lds = walk_lds_bytes(p.cap);
+    if (!lds) return 1;
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_stats<NCH>, dim3(p.G), dim3(64 * kWalkWaves), lds, s, p, mask, out));
     return 0;
 }
 

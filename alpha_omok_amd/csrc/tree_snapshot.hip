@@ -1,25 +1,18 @@
 // tree_snapshot.hip -- search trees out of the arena and back in: k_tree_pack writes what a game's root reaches as the packed
 // arrays of ao_tree_snapshot (include/omok_hip.h), k_tree_unpack builds arena records and positions from them.
 //
-// k_tree_pack is k_tree_stats (tree_readout.hip) with stores to the snapshot where that kernel counts, and k_reroot
-// (tree_kernels.hip) with the snapshot in place of the other arena: one workgroup per game, the breadth-first queue in LDS,
-// wave w takes queue entry head + w, the children's numbers come from a prefix over the waves' child counts in queue order
-// -- the numbering of a re-rooting, the root node 0. It is READ-ONLY on TreeParams: a search that follows an export is bit for
+// k_tree_pack is walk_subtree (tree_walk.hpp: the walk and the numbering of a re-rooting, the root node 0) with stores to the
+// snapshot where k_reroot stores to the other arena. It is READ-ONLY on TreeParams: a search that follows an export is bit for
 // bit the search without it. k_tree_unpack is the inverse: snapshot node i becomes record i of the game's current arena.
 //
 // Lanes run over a node's <= 225 edges in NCH chunks of 64; what steers control flow (node, level, counts) is wave-uniform.
 #include <cstdint>
 
 #include "host_handle.hpp"
-#include "tree_device.hpp"
 #include "tree_snapshot.hpp"
+#include "tree_walk.hpp"
 
 namespace ao {
-
-constexpr int kSnapWaves = 8;
-constexpr size_t kSnapMaxDynLds = 64 * 1024;   // the bound k_tree_stats and k_reroot live under
-
-__device__ __forceinline__ bool snap_link_ok(const TreeParams& p, int ch) { return ch >= 0 && ch < p.cap; }
 
 // ----------------------------------------------------------------------------------------------
 // k_tree_pack: table row b = {game, first node, first edge of the game inside the chunk, nodes, edges} as the host sized them
@@ -27,88 +20,38 @@ __device__ __forceinline__ bool snap_link_ok(const TreeParams& p, int ch) { retu
 // tree that did not match would be cut off, not written past its share.
 // ----------------------------------------------------------------------------------------------
 template <int NCH>
-__global__ __launch_bounds__(64 * kSnapWaves) void k_tree_pack(TreeParams p, SnapDev d, const int32_t* __restrict__ table) {
+__global__ __launch_bounds__(64 * kWalkWaves) void k_tree_pack(TreeParams p, SnapDev d, const int32_t* __restrict__ table) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    int32_t* s_cnt = reinterpret_cast<int32_t*>(s_dyn);   // [kSnapWaves] expanded children each wave's node brings, [kSnapWaves] its edges, [kSnapWaves] unused
-    int32_t* s_q = s_cnt + 3 * kSnapWaves;                // [cap] the queue: arena index of the node that becomes snapshot node i
     const int32_t* t = table + static_cast<size_t>(blockIdx.x) * kSnapRow;
     const int g = t[0], node_off = t[1], edge_off = t[2], nodes = t[3], edges = t[4];
     if (nodes <= 0 || nodes > p.cap) return;              // (uniform over the workgroup)
     const int lane = lane_id();
-    const int w = threadIdx.x >> 6;
-    const int arena = p.cur[g];
     const int root = p.root_node[g];
-    if (!snap_link_ok(p, root)) return;
+    if (!link_ok(p, root)) return;
     if (threadIdx.x == 0) {
-        s_q[0] = root;
         d.parent[node_off] = -1;
         d.pedge[node_off] = -1;
     }
-    __syncthreads();
-    int tail = 1, ebase = 0;
-    for (int head = 0; head < tail;) {
-        const int h = head + w;
-        const bool have = h < tail;                       // (wave-uniform) this round takes queue entries [head, min(head + waves, tail))
-        const int next_head = head + kSnapWaves < tail ? head + kSnapWaves : tail;
-        size_t slot = 0;
-        int L = 0, cnt = 0;
-        int ch[NCH], raw[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) { ch[c] = -1; raw[c] = CH_UNVISITED; }
-        if (have) {
-            slot = node_slot(p, arena, g, s_q[h]);
-            const PosR m = pos_load(nodePos(p, slot));
-            L = m.nchild < 0 ? 0 : (m.nchild > p.A ? p.A : m.nchild);
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int e = lane + 64 * c;
-                const int ec = e < p.Ap ? e : p.Ap - 1;
-                const int v = rowCH(p, slot)[ec];
-                raw[c] = v;
-                ch[c] = (e < L && snap_link_ok(p, v)) ? v : -1;
-                cnt += __popcll(__ballot(ch[c] >= 0));
+    walk_subtree<NCH>(
+        p, g, p.cur[g], root, nodes, reinterpret_cast<int32_t*>(s_dyn),
+        [](const WalkNode& nd, const PosR&) { return nd.L; },   // nd.before = the node's first edge inside the game
+        [&](const WalkNode& nd, int c, int raw, int idx, bool kept) {
+            const int e = lane + 64 * c;
+            if (c == 0 && lane == 0) d.nchild[node_off + nd.h] = nd.L;    // (h < tail <= nodes)
+            if (kept) {
+                d.parent[node_off + idx] = nd.h;
+                d.pedge[node_off + idx] = e;
             }
-        }
-        if (lane == 0) { s_cnt[w] = cnt; s_cnt[kSnapWaves + w] = L; }
-        __syncthreads();
-        int base = tail, total = 0, eb = ebase, etotal = 0;
-#pragma unroll
-        for (int k = 0; k < kSnapWaves; ++k) {
-            const int ck = s_cnt[k], lk = s_cnt[kSnapWaves + k];
-            if (k < w) { base += ck; eb += lk; }
-            total += ck;
-            etotal += lk;
-        }
-        if (have) {
-            if (lane == 0) d.nchild[node_off + h] = L;    // (h < tail <= nodes)
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                const int e = lane + 64 * c;
-                const uint64_t mk = __ballot(ch[c] >= 0);
-                const int idx = base + __popcll(mk & lanes_below());
-                const bool ex = ch[c] >= 0 && idx < nodes;
-                if (ex) {
-                    s_q[idx] = ch[c];
-                    d.parent[node_off + idx] = h;
-                    d.pedge[node_off + idx] = e;
-                }
-                if (e < L && eb + e < edges) {
-                    const size_t at = static_cast<size_t>(edge_off) + eb + e;
-                    d.act[at] = rowACT(p, slot)[e];
-                    d.n[at] = rowN(p, slot)[e];
-                    d.w[at] = rowW(p, slot)[e];
-                    d.q[at] = rowQ(p, slot)[e];
-                    d.p[at] = rowP(p, slot)[e];
-                    d.child[at] = ex ? idx : (raw[c] == CH_TERMINAL ? CH_TERMINAL : CH_UNVISITED);
-                }
-                base += __popcll(mk);
+            if (e < nd.L && nd.before + e < edges) {
+                const size_t at = static_cast<size_t>(edge_off) + nd.before + e;
+                d.act[at] = rowACT(p, nd.slot)[e];
+                d.n[at] = rowN(p, nd.slot)[e];
+                d.w[at] = rowW(p, nd.slot)[e];
+                d.q[at] = rowQ(p, nd.slot)[e];
+                d.p[at] = rowP(p, nd.slot)[e];
+                d.child[at] = kept ? idx : (raw == CH_TERMINAL ? CH_TERMINAL : CH_UNVISITED);
             }
-        }
-        tail = tail + total < nodes ? tail + total : nodes;
-        ebase += etotal;
-        head = next_head;
-        __syncthreads();
-    }
+        });
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -128,8 +71,7 @@ __device__ __forceinline__ int unpack_node(const TreeParams& p, const SnapDev& d
                                            PosR m) {
     const int lane = lane_id();
     const size_t slot = node_slot(p, arena, g, i);
-    const int Lr = d.nchild[node_off + i];
-    const int L = Lr < 0 ? 0 : (Lr > p.A ? p.A : Lr);
+    const int L = clamp_nchild(p, d.nchild[node_off + i]);
     const size_t fe = static_cast<size_t>(edge_off) + d.first[node_off + i];
     int cnt = 0;
 #pragma unroll
@@ -155,9 +97,9 @@ __device__ __forceinline__ int unpack_node(const TreeParams& p, const SnapDev& d
 }
 
 template <int NCH>
-__global__ __launch_bounds__(64 * kSnapWaves) void k_tree_unpack(TreeParams p, SnapDev d, const int32_t* __restrict__ table,
+__global__ __launch_bounds__(64 * kWalkWaves) void k_tree_unpack(TreeParams p, SnapDev d, const int32_t* __restrict__ table,
                                                                  const int32_t* __restrict__ moves_all, const uint32_t* __restrict__ mt_all) {
-    __shared__ int32_t s_cnt[kSnapWaves];
+    __shared__ int32_t s_cnt[kWalkWaves];
     __shared__ int32_t s_bad;
     const int b = blockIdx.x;
     const int32_t* t = table + static_cast<size_t>(b) * kSnapRow;
@@ -166,7 +108,7 @@ __global__ __launch_bounds__(64 * kSnapWaves) void k_tree_unpack(TreeParams p, S
     const int lane = lane_id();
     const int w = threadIdx.x >> 6;
     const int arena = p.cur[g];
-    for (int i = threadIdx.x; i < 624; i += 64 * kSnapWaves) p.mt[static_cast<size_t>(g) * 624 + i] = mt_all[static_cast<size_t>(b) * 624 + i];
+    for (int i = threadIdx.x; i < 624; i += 64 * kWalkWaves) p.mt[static_cast<size_t>(g) * 624 + i] = mt_all[static_cast<size_t>(b) * 624 + i];
     if (threadIdx.x == 0) s_bad = 0;
     bool bad = false;
     int cnt = 0;
@@ -200,13 +142,13 @@ __global__ __launch_bounds__(64 * kSnapWaves) void k_tree_unpack(TreeParams p, S
     int lo = 1, hi = 1;
     if (nodes > 0) {
 #pragma unroll
-        for (int k = 0; k < kSnapWaves; ++k) hi += s_cnt[k];
+        for (int k = 0; k < kWalkWaves; ++k) hi += s_cnt[k];
     }
     hi = hi < nodes ? hi : nodes;
     __syncthreads();
     while (lo < hi) {                                      // (uniform over the workgroup) one level: nodes [lo, hi)
         cnt = 0;
-        for (int i = lo + w; i < hi; i += kSnapWaves) {    // (wave-uniform)
+        for (int i = lo + w; i < hi; i += kWalkWaves) {    // (wave-uniform)
             const int par = d.parent[node_off + i], pe = d.pedge[node_off + i];
             const int a = d.act[static_cast<size_t>(edge_off) + d.first[node_off + par] + pe];
             PosR m = pos_load(nodePos(p, node_slot(p, arena, g, par)));   // written one level up, behind a barrier
@@ -218,7 +160,7 @@ __global__ __launch_bounds__(64 * kSnapWaves) void k_tree_unpack(TreeParams p, S
         __syncthreads();                                   // the level's records are visible to the workgroup, the counts are in
         int total = 0;
 #pragma unroll
-        for (int k = 0; k < kSnapWaves; ++k) total += s_cnt[k];
+        for (int k = 0; k < kWalkWaves; ++k) total += s_cnt[k];
         lo = hi;
         hi = hi + total < nodes ? hi + total : nodes;
         __syncthreads();
@@ -233,15 +175,15 @@ __global__ __launch_bounds__(64 * kSnapWaves) void k_tree_unpack(TreeParams p, S
 // ----------------------------------------------------------------------------------------------
 
 int launch_tree_pack(const TreeParams& p, const SnapDev& d, const int32_t* table, int games, hipStream_t s) {
-    const size_t lds = (3 * kSnapWaves + static_cast<size_t>(p.cap)) * 4;   // k_tree_stats' rule
-    if (lds > kSnapMaxDynLds) return 1;
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_pack<NCH>, dim3(games), dim3(64 * kSnapWaves), lds, s, p, d, table));
+    const size_t lds = walk_lds_bytes(p.cap);
+    if (!lds) return 1;
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_pack<NCH>, dim3(games), dim3(64 * kWalkWaves), lds, s, p, d, table));
     return 0;
 }
 
 void launch_tree_unpack(const TreeParams& p, const SnapDev& d, const int32_t* table, const int32_t* moves, const uint32_t* mt, int games,
                         hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_unpack<NCH>, dim3(games), dim3(64 * kSnapWaves), 0, s, p, d, table, moves, mt));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_unpack<NCH>, dim3(games), dim3(64 * kWalkWaves), 0, s, p, d, table, moves, mt));
 }
 
 }  // namespace ao
