@@ -68,6 +68,21 @@ def test_plan_kernel_follows_batch_size_and_input_kind():
     assert plan_kernel(4, 5, 128, 9, 4096, in_kind=1, trunk_mode=2)[0].startswith("k_trunk16<9>")
 
 
+def test_plan_kernel_names_the_kernel_of_every_precision_case_at_other_plane_counts():
+    """The planner does not look at the number of input planes: every case of net_reference's input-plane block names the
+    kernel ao_net_plan_kernel answers for its shape, batch and mode (the two-product form is the same plan on fp16 weights;
+    AO_TRUNK_FMT=0 is the default format)."""
+    import net_reference as R
+    from alpha_omok_amd.engine import plan_kernel
+    from alpha_omok_amd.pvnet import native_width
+    cases = [c for c in R.CASES if c.C != 5]
+    assert {c.C for c in cases} == set(R.INPLANES)
+    for c in cases:
+        assert set(c.env) <= {"AO_TRUNK_FMT"} and c.env.get("AO_TRUNK_FMT", "0") == "0", c.id
+        name = plan_kernel(c.nb, c.C, native_width(c.planes), c.B, c.batch, in_kind=1, trunk_mode=c.mode)[0]
+        assert name.startswith(c.kernel.replace("_w16<", "<")), (c.id, name)
+
+
 def test_bench_gpus_n_refuses_without_n_devices():
     import torch
     if torch.cuda.is_available() and torch.cuda.device_count() >= 2:

@@ -10,9 +10,10 @@ float32 itself loses on that case:
     allowed: 4 x E32 for the kernels that are fp32 throughout, 16 x E32 for the split-fp16 families (net_reference.Case.mult)
 
 The bound comes from the reference, never from the kernel under test. tests/test_net_reference.py shows on the CPU that each
-of eleven small defects of the reference passes twice this bound on every case. The measured err / E32 per family and case
-is kept in profiles/r7a_forward_precision_by_family.txt; with AO_PRECISION_REPORT=<file> each case appends its figures as
-a JSON line.
+of eleven small defects of the reference, and of conv1 defects per input plane, passes twice this bound on every case. The
+measured err / E32 per family and case is kept in profiles/r7a_forward_precision_by_family.txt, that of the cases with
+another number of input planes than 5 (net_reference.INPLANES) in profiles/r17a_forward_precision_by_inplanes.txt; with
+AO_PRECISION_REPORT=<file> each case appends its figures as a JSON line.
 
 Every batch is made of boards of one pool per board size (net_reference.pool: structured boards -- empty, full, one stone in
 each corner and on each edge, float planes that are not 0/1 -- and random 0/1 planes), so one float64 evaluation of the pool
@@ -36,11 +37,11 @@ def test_kernel_family_against_float64_in_logit_space(case, monkeypatch):
     from alpha_omok_amd.pvnet import native_width, pad_state_dict
     sd = R.case_network(*case.net_key())
     m = case.boards()
-    x = torch.from_numpy(R.pool(case.B)[m]).cuda()
+    x = torch.from_numpy(R.pool(case.B, case.C)[m]).cuda()
     width = native_width(case.planes)
     for k, v in case.env.items():
         monkeypatch.setenv(k, v)
-    net = Net(case.nb, 5, width, case.B, 0)
+    net = Net(case.nb, case.C, width, case.B, 0)
     for k in case.env:
         monkeypatch.delenv(k)
     net.load_state_dict(sd if width == case.planes else pad_state_dict(sd, width))
@@ -61,13 +62,13 @@ def test_kernel_family_against_float64_in_logit_space(case, monkeypatch):
     p, v = p.cpu().double().numpy(), v.cpu().double().numpy()
     assert np.isfinite(p).all() and np.isfinite(v).all() and p.min() > 0 and np.abs(v).max() < 1
     r64, _ = R.pool_reference(*case.net_key())
-    el, ez = R.units(case.nb, case.B, case.planes, case.grid, m)
+    el, ez = R.units(case.nb, case.B, case.planes, case.grid, m, case.C)
     lp = np.log(p)
     err_l = float(np.abs(lp - lp.mean(axis=1, keepdims=True) - r64["logits"][m]).max())
     err_z = float(np.abs(np.arctanh(v) - r64["z"][m]).max())
     dp = float(np.abs(p - r64["p"][m]).max())
     dv = float(np.abs(v - r64["v"][m]).max())
-    rec = dict(id=case.id, family=case.family, kernel=name.split(" (")[0], nb=case.nb, B=case.B, planes=case.planes, batch=case.batch,
+    rec = dict(id=case.id, family=case.family, kernel=name.split(" (")[0], nb=case.nb, B=case.B, planes=case.planes, C=case.C, batch=case.batch,
                mode=case.mode, grid=case.grid, mult=case.mult, E32_l=el, E32_z=ez, err_l=err_l, err_z=err_z,
                ratio_l=err_l / el, ratio_z=err_z / ez, dp=dp, dv=dv)
     print("PRECISION " + json.dumps(rec))

@@ -1,6 +1,7 @@
 """No GPU, no compiled library: the float64 reference of tests/net_reference.py checks itself, every network and batch of
 tests/test_gpu_net_precision.py is shown to be a case on which an error can be seen, and a catalogue of small defects,
-applied to the float64 reference, is shown to pass the bound of every such case at least twice over.
+applied to the float64 reference, is shown to pass the bound of every such case at least twice over. The cases run every
+number of conv1 input planes of net_reference.INPLANES beside 5; the catalogue's conv1 defects act per input plane.
 
 The saturation of the golden-vector weights that made this necessary (float64, the batches of
 test_gpu_net.test_forward_vs_torch_fp32; `net_reference.saturation_table()`):
@@ -82,12 +83,14 @@ def test_conditioned_generator_keeps_the_wire_format_and_is_deterministic():
 NETS = sorted({c.net_key() for c in R.CASES})
 
 
-@pytest.mark.parametrize("nb,B,planes,grid", NETS, ids=["nb%d-B%d-p%d-%s" % (k[0], k[1], k[2], "w16grid" if k[3] else "w32") for k in NETS])
-def test_every_network_of_the_gpu_cases_is_conditioned(nb, B, planes, grid):
+@pytest.mark.parametrize("nb,B,planes,grid,C", NETS, ids=["nb%d-B%d-p%d-%s%s" % (k[0], k[1], k[2], "w16grid" if k[3] else "w32",
+                                                                                "" if k[4] == 5 else "-C%d" % k[4]) for k in NETS])
+def test_every_network_of_the_gpu_cases_is_conditioned(nb, B, planes, grid, C):
     """The conditions under which a forward error is visible, asserted on the float64 reference alone, on the pool every
     batch of that network is drawn from."""
-    sd = R.case_network(nb, B, planes, grid)
-    r = R.conditioning_report(sd, R.pool(B))
+    sd = R.case_network(nb, B, planes, grid, C)
+    assert sd["conv1.weight"].shape == (planes, C, 3, 3)
+    r = R.conditioning_report(sd, R.pool(B, C))
     assert 0.3 <= r["trunk_rms"] <= 4.0 and r["trunk_max"] < 100.0, r          # nowhere near the fp16 range
     assert 1.0 <= r["logit_std"] <= 1.6 and r["p_min"] >= 1e-8, r              # log p of an fp32 p is well conditioned
     assert r["z_absmax"] <= 1.5 and r["z_std"] >= 0.3, r                       # atanh of an fp32 v costs at most ~3e-7
@@ -115,7 +118,7 @@ def test_every_batch_of_the_gpu_cases_is_conditioned_and_reaches_the_edges(case)
         # (the logits are compared centred per board, so their spread is taken of the centred logits)
         assert 1.0 <= r64["logits"][m].std() <= 1.6 and r64["z"][m].std() >= 0.3, (r64["logits"][m].std(), r64["z"][m].std())
         assert len(np.unique(np.round(r64["z"][m], 6))) >= 8
-    ns = R.n_structured(case.B)
+    ns = R.n_structured(case.B, case.C)
     last = case.batch - (case.batch % 16 or 16)
     if case.batch >= 8:
         assert np.all(m[:5] < ns) and {2, 0, 3, 11} <= set(m.tolist())       # full, empty, a corner stone, float planes
@@ -128,8 +131,39 @@ def test_every_batch_of_the_gpu_cases_is_conditioned_and_reaches_the_edges(case)
         assert np.all(m[13:22] < ns)
     if case.batch > 32:
         assert np.all(m[last:] < ns) and set(range(ns)) <= set(m.tolist())
-    el, ez = R.units(case.nb, case.B, case.planes, case.grid, m)
+    el, ez = R.units(case.nb, case.B, case.planes, case.grid, m, case.C)
     assert R.E32_FLOOR <= el < 2e-5 and R.E32_FLOOR <= ez < 2e-5, (el, ez)  # the unit is fp32 rounding, not something larger
+    if case.C > 1:
+        # the colour plane C - 1 is one number per board: a conv1 that dropped it, or read it as padding, shows only if the batch
+        # holds more than one colour. From 8 boards on both 0 and 1 are there; a handful of boards has the float-plane boards'
+        # colours (0.37 ..) beside 0. The float-plane boards are in every batch.
+        x = R.pool(case.B, case.C)[m]
+        colours = set(x[:, case.C - 1, 0, 0].tolist())
+        assert np.all(x[:, case.C - 1] == x[:, case.C - 1, :1, :1])
+        assert ({0.0, 1.0} <= colours) if case.batch >= 8 else (case.batch < 2 or (len(colours) >= 2 and max(colours) > 0)), colours
+    if case.batch >= 2:
+        assert set(m.tolist()) & {ns - 3, ns - 2, ns - 1}                   # a board whose planes are neither 0 nor 1
+
+
+@pytest.mark.parametrize("B", [9, 15])
+@pytest.mark.parametrize("C", sorted(set(R.INPLANES) | {5}))
+def test_pool_has_a_stone_on_every_plane_and_no_two_planes_alike(B, C):
+    """What a swapped, dropped or doubled input plane needs to show: over the pool every stone plane 0 .. C - 2 is occupied on
+    some 0/1 board, the colour plane takes both colours, and no two planes agree on every board -- neither over the whole
+    pool nor over the boards the whole-forward defects of the catalogue are evaluated on."""
+    x = R.pool(B, C)
+    assert x.shape == (R.POOL if B <= 9 else R.WIDE_POOL, C, B, B)
+    ns = R.n_structured(B, C)
+    binary = np.array([set(np.unique(b)) <= {0.0, 1.0} for b in x])
+    assert binary[ns:].all() and not binary[ns - 3:ns].any()
+    for c in range(max(C - 1, 1)):
+        assert (x[binary, c].reshape(binary.sum(), -1).sum(axis=1) > 0).sum() >= 8, c
+    if C > 1:
+        assert {0.0, 1.0} <= set(x[binary, C - 1, 0, 0].tolist())
+    for rows in (slice(None), slice(0, SUBSET)):
+        for a in range(C):
+            for b in range(a + 1, C):
+                assert not np.array_equal(x[rows, a], x[rows, b]), (a, b)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -143,11 +177,11 @@ def _fp16(a):
     return a.astype(np.float16).astype(np.float32)
 
 
-def _defects(nb, B, planes, grid):
+def _defects(nb, B, planes, grid, C=5):
     """name -> (|d centred logits| max over moves, |dz|) per pool board (NaN where the defect was not evaluated)."""
     import torch
-    sd = R.case_network(nb, B, planes, grid)
-    x = R.pool(B)
+    sd = R.case_network(nb, B, planes, grid, C)
+    x = R.pool(B, C)
     n = len(x)
     ref = R.forward(sd, x)
     last = "layers.%d.conv2.weight" % (nb - 1)
@@ -216,6 +250,21 @@ def _defects(nb, B, planes, grid):
     def shift(s):
         s["layers.%d.bn2.bias" % (nb - 1)] = s["layers.%d.bn2.bias" % (nb - 1)] + np.float32(1e-3)
     last_block("last BatchNorm: shift off by 1e-3", shift)
+
+    # conv1, the one layer whose packing and kernel text depend on the number of input planes. A single (cout, plane, tap)
+    # weight can sit behind a dead ReLU on a small batch, so the per-plane defects span a 16-cout tile.
+    for c in range(C):
+        def plane_tap(s, c=c):
+            s["conv1.weight"][0:16, c, 0, 0] = 0
+        whole("conv1: plane %d loses tap (0, 0) in couts 0 .. 15 (a mis-indexed quad, a wrong bit)" % c, plane_tap)
+
+    def drop_last(s):
+        s["conv1.weight"][:, C - 1] = 0
+    whole("conv1: plane C - 1 dropped (a ragged last quad read as padding)", drop_last)
+    if C >= 2:
+        def swap_last(s):
+            s["conv1.weight"][:, [C - 2, C - 1]] = s["conv1.weight"][:, [C - 1, C - 2]]
+        whole("conv1: planes C - 2 and C - 1 swapped", swap_last)
     return out, ref
 
 
@@ -234,7 +283,7 @@ def test_every_defect_passes_twice_the_bound_of_every_gpu_case(case):
     defects, ref = _DEFECTS[key]
     m = case.boards()
     u = np.unique(m)
-    el, ez = R.units(case.nb, case.B, case.planes, case.grid, m)
+    el, ez = R.units(case.nb, case.B, case.planes, case.grid, m, case.C)
     bl, bz = 2 * case.mult * el, 2 * case.mult * ez
     weak = []
     for name, (dl, dz) in defects.items():
