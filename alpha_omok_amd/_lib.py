@@ -156,6 +156,8 @@ SYMBOLS = {
     "ao_positions_audit": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _u8p, _i32p, _i32p]),
     "ao_positions_forced_wins": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _u8p,
                                            _P(C.c_int16), _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "ao_positions_forced_defences": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _u8p, _u8p,
+                                               _u8p, _i32p, _i32p, _i32p, _i32p, _i32p]),
 }
 
 _lib = None

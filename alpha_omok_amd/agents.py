@@ -224,6 +224,22 @@ class ZeroAgent(Agent):
         return (int(d["result"][0]), int(d["depth"][0]), d["moves"][0].reshape(B, B).astype(bool),
                 d["line"][0, :int(d["line_len"][0])].tolist())
 
+    def get_forced_defences(self, root_id, max_depth=8, max_nodes=2000):
+        """Which moves of the side to move stop the opponent's forced win by continuous fours in the position of
+        `root_id` (PositionBatch.forced_defences)? (threat, threat_depth, safe, losing): threat 0 the opponent has no
+        forced win if the mover passes / 1 it has one / 2 the node budget ran out, threat_depth its fewest attacker moves,
+        safe bool [B, B] the empty cells after which the opponent has none -- the "must answer here" set when there is a
+        threat --, losing bool [B, B] those after which it has one (cells whose search ran out of nodes are in neither).
+        All empty on a finished game. ValueError for an id that is not a legal move list or limits outside 1..16 /
+        1..65536."""
+        from .positions import FD_LOSES, FD_SAFE
+        d = self._position_batch().forced_defences([root_id], max_depth, max_nodes)
+        if d["err"][0]:
+            raise ValueError("root_id %r is not a legal move list (err %d)" % (root_id, int(d["err"][0])))
+        B = self.board_size
+        reply = d["reply"][0].reshape(B, B)
+        return int(d["threat"][0]), int(d["threat_depth"][0]), reply == FD_SAFE, reply == FD_LOSES
+
     def get_pv_batch(self, root_ids):
         """get_pv for many ids in one call (PositionBatch.evaluate): (policy float32 [n, A], value float32 [n],
         status int32 [n] -- utils.check_win of each position, terminal ones are evaluated too --, err int32 [n]). The planes

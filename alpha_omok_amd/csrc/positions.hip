@@ -2,7 +2,7 @@
 // network's evaluation of positions the CALLER names, no tree and no game involved.
 //
 // One wavefront (64 lanes) owns one position, kPosPerWG positions per workgroup, nothing shared between them (no LDS but
-// k_forced_wins' search stack, one per wave).
+// the search stack of k_forced_wins / k_forced_defences, one per wave).
 //
 // Reference map (paths relative to /root/reference/2_AlphaOmok/):
 //   k_check_win_boards      utils.py:30-59 (check_win) on raw boards: the FULL window scan, row-major, black before white
@@ -16,6 +16,9 @@
 //                           defined through utils.py:30-59 (check_win of the board with one more stone)
 //   k_forced_wins           no counterpart: forced wins by continuous fours, a depth-first search per position over the same
 //                           winning cells (utils.forced_win of this package is the host definition)
+//   k_forced_defences, k_defence_rows  no counterpart: which replies hold against the opponent's forced win -- the same
+//                           search (fw_search) for every (position, reply) pair and for the pass, one wavefront each, then
+//                           one wavefront per position that gathers its pairs (utils.forced_defences is the host definition)
 //
 // The bitboards, pos_place, pos_occupied, win_after_move and encode_planes are the tree kernels' own (tree_device.hpp): a
 // position described here is the position the search would hold.
@@ -482,32 +485,31 @@ struct ForcedParams {
     int16_t* line;          // [n][line_stride], line_stride = 2 max_depth - 1
 };
 
-// utils.forced_win of the position of id i: iterative deepening over a depth-first search that the wave walks as ONE
-// thread of control -- every value that steers it is wave-uniform (ballots, counters, words read back from the wave's own
-// LDS stack), the 64 lanes only share the work inside winning_cells / four_cells / check_win_board. No recursion: the
-// states below are the call and return points of wins_within / four of the definition. The board is one PosR; stones are
-// toggled on the way down and up.
-template <int NCH>
-__global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) {
-    __shared__ FwWave s_wave[kPosPerWG];
-    const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
-    const int i = blockIdx.x * kPosPerWG + wv;
-    if (i >= q.n) return;
-    FwWave& W = s_wave[wv];
-    const int lane = lane_id();
-    const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
-    PosR s;
-    int end_ply;
-    const int err = replay_moves(s, q.moves + static_cast<size_t>(i) * q.stride, nm, q.A, q.B, q.win_mark, end_ply);
-    const bool ok = err == PE_OK;
-    const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
-    const int a = ok ? (nm & 1) : 0;       // the attacker
+// what a search leaves behind (the principal line stays in the wave's FwWave: line[0], its length in the last slot)
+struct FwResult {
+    int result, depth, nodes;
+    uint64_t won[kBBWords];    // the root's collection: every first move that wins within depth
+};
 
-    int result = FW_NONE, depth = 0, nodes = 0;
-    uint64_t won[kBBWords] = {0ull, 0ull, 0ull, 0ull};
+// utils.forced_win of the position `s` for the attacker `a`: iterative deepening over a depth-first search that the wave
+// walks as ONE thread of control -- every value that steers it is wave-uniform (ballots, counters, words read back from the
+// wave's own LDS stack), the 64 lanes only share the work inside winning_cells / four_cells / check_win_board. No
+// recursion: the states below are the call and return points of wins_within / four of the definition. The board is one
+// PosR; stones are toggled on the way down and up, `s` is afterwards what it was. `stones`: the stones on the board (two
+// more per level: a full board is terminal), `status`: check_win of `s`. Nothing depends on whose turn the stone count
+// says it is: the attacker moves first, whoever it is (all 64 lanes call, with wave-uniform arguments).
+template <int NCH>
+__device__ __forceinline__ void fw_search(PosR& s, int a, int stones, int status, FwWave& W, int B_in, int A, int win_mark, bool run,
+                                          int max_depth, int max_nodes, FwResult& r) {
+    const int lane = lane_id();
+    r.result = FW_NONE;
+    r.depth = 0;
+    r.nodes = 0;
+#pragma unroll
+    for (int w = 0; w < kBBWords; ++w) r.won[w] = 0ull;
     enum { ENTER, NEXT_C, NEXT_B, RETURN };
 
-    for (int D = 1; ok && result == FW_NONE && D <= q.max_depth; ++D) {
+    for (int D = 1; run && r.result == FW_NONE && D <= max_depth; ++D) {
         int L = 0, state = ENTER;
         bool yes = false;                  // what the node that RETURNs answers
         for (;;) {
@@ -515,20 +517,20 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
             // board) depends on B alone. Hoisted out of the search it would have to live in registers throughout -- some
             // 300 VGPRs at four mask words, spilling to scratch; behind a B the compiler cannot see through it is worked
             // out again at each call.
-            int B = q.B;
+            int B = B_in;
             asm volatile("" : "+s"(B));
             if (state == ENTER) {          // wins_within(P, D - L); the node's level is L <= D - 1 <= 15
-                if (nodes >= q.max_nodes) { result = FW_UNKNOWN; break; }
-                nodes += 1;
+                if (r.nodes >= max_nodes) { r.result = FW_UNKNOWN; break; }
+                r.nodes += 1;
                 yes = false;
                 state = RETURN;
                 // below the root a position cannot hold a line (the attacker's stone was no winning cell, the defender
                 // had none), it can only be full
-                const bool terminal = L == 0 ? status != 0 : nm + 2 * L >= q.A;
+                const bool terminal = L == 0 ? status != 0 : stones + 2 * L >= A;
                 if (!terminal) {
                     uint64_t mine[kBBWords], theirs[kBBWords];
-                    winning_cells<NCH>(s, a, B, q.A, q.win_mark, mine);
-                    winning_cells<NCH>(s, a ^ 1, B, q.A, q.win_mark, theirs);
+                    winning_cells<NCH>(s, a, B, A, win_mark, mine);
+                    winning_cells<NCH>(s, a ^ 1, B, A, win_mark, theirs);
                     const int n_theirs = popcount4(theirs);
                     if (popcount4(mine) > 0) {
                         yes = true;
@@ -538,11 +540,11 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
                         }
                         if (L == 0) {
 #pragma unroll
-                            for (int w = 0; w < kBBWords; ++w) won[w] = mine[w];
+                            for (int w = 0; w < kBBWords; ++w) r.won[w] = mine[w];
                         }
                     } else if (D - L > 1 && n_theirs < 2) {
                         uint64_t cand[kBBWords];
-                        four_cells<NCH>(s, a, B, q.A, q.win_mark, cand);
+                        four_cells<NCH>(s, a, B, A, win_mark, cand);
                         if (lane == 0) {
 #pragma unroll
                             for (int w = 0; w < kBBWords; ++w) W.lv[L].cand[w] = n_theirs ? cand[w] & theirs[w] : cand[w];
@@ -565,7 +567,7 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
                 // that cell -- so the four stands or falls with its forced replies
                 pos_toggle(s, a, c);
                 uint64_t rep[kBBWords];
-                winning_cells<NCH>(s, a, B, q.A, q.win_mark, rep);
+                winning_cells<NCH>(s, a, B, A, win_mark, rep);
                 wsync();                   // the reads of cand above are done before lane 0 overwrites it
                 if (lane == 0) {
 #pragma unroll
@@ -585,7 +587,7 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
                 if (b < 0) {               // every reply loses: c succeeds
                     pos_toggle(s, a, c);
                     if (L == 0) {          // the root collects and goes on
-                        mask_add(won, c);
+                        mask_add(r.won, c);
                         state = NEXT_C;
                     } else {
                         yes = true;
@@ -612,7 +614,7 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
                 pos_toggle(s, a ^ 1, b);
                 if (yes) {
                     // the line follows the first reply; the root keeps the line of its first success (min(moves))
-                    if (b == b0 && (L > 0 || popcount4(won) == 0)) {
+                    if (b == b0 && (L > 0 || popcount4(r.won) == 0)) {
                         const int len = __builtin_amdgcn_readfirstlane(static_cast<int>(W.line[L + 1][kFwLine - 1]));   // <= 2 (D - L - 1) - 1
                         const int16_t v = lane < len ? W.line[L + 1][lane] : static_cast<int16_t>(0);
                         wsync();
@@ -631,11 +633,34 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
                 }
             }
         }
-        if (result == FW_NONE && popcount4(won) > 0) {
-            result = FW_WIN;
-            depth = D;
+        if (r.result == FW_NONE && popcount4(r.won) > 0) {
+            r.result = FW_WIN;
+            r.depth = D;
         }
     }
+}
+
+// utils.forced_win of the position of id i, for its side to move
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) {
+    __shared__ FwWave s_wave[kPosPerWG];
+    const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    const int i = blockIdx.x * kPosPerWG + wv;
+    if (i >= q.n) return;
+    FwWave& W = s_wave[wv];
+    const int lane = lane_id();
+    const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
+    PosR s;
+    int end_ply;
+    const int err = replay_moves(s, q.moves + static_cast<size_t>(i) * q.stride, nm, q.A, q.B, q.win_mark, end_ply);
+    const bool ok = err == PE_OK;
+    const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
+    const int a = ok ? (nm & 1) : 0;       // the attacker
+
+    FwResult r;
+    fw_search<NCH>(s, a, nm, status, W, q.B, q.A, q.win_mark, ok, q.max_depth, q.max_nodes, r);
+    const int result = r.result, depth = r.depth, nodes = r.nodes;
+    const uint64_t (&won)[kBBWords] = r.won;
     wsync();
     const bool win = result == FW_WIN;
     const int len = win ? __builtin_amdgcn_readfirstlane(static_cast<int>(W.line[0][kFwLine - 1])) : 0;
@@ -660,6 +685,115 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_forced_wins(ForcedParams q) 
         q.line[static_cast<size_t>(i) * q.line_stride + lane] = lane < len ? W.line[0][lane] : static_cast<int16_t>(-1);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// which replies hold against a forced win (VCF defence). No reference counterpart; the definition is
+// utils.forced_defences: A + 1 searches of utils.forced_win per position, which asks utils.check_win (utils.py:30-59) and
+// nothing else -- see ao_positions_forced_defences in omok_hip.h for the text.
+// ---------------------------------------------------------------------------------------------------------------------
+enum : int { FD_NONE = 0, FD_SAFE = 1, FD_LOSES = 2, FD_UNKNOWN = 3 };
+
+struct DefenceParams {
+    const int32_t* moves;   // [n][stride]
+    const int32_t* nmoves;  // [n]
+    int n, stride, B, A, win_mark, max_depth, max_nodes;
+    // k_forced_defences -> k_defence_rows: one word per pair, [n][A + 1]; 0 for a pair without a search, else
+    // (1 + result) | depth << 2 | nodes << 8 (depth <= 16, nodes <= 65536: 25 bits)
+    uint32_t* pair;
+    // outputs, any may be null
+    uint8_t* threat_moves;                                  // [n][A]   (written by the pass's wave)
+    int32_t* status; int32_t* turn; int32_t* err;           // [n]      (the same)
+    int32_t* threat; int32_t* threat_depth; int32_t* nodes; // [n]      (k_defence_rows, as everything below)
+    uint8_t* reply; uint8_t* depth;                         // [n][A]
+    int32_t* counts;                                        // [n][4]
+};
+
+// One wavefront per pair (position i, candidate j): j < A is the mover's reply on cell j, j == A the pass; a workgroup
+// holds kPosPerWG pairs of one position. The wave replays the id, puts the mover's stone on j and runs forced_win for the
+// opponent on what stands then -- check_win of the board WITH the stone is the root's status (a stone that makes a line
+// or fills the board leaves a terminal root: no, at one node per iteration), and the board holds one stone more than the
+// id has moves. Pairs on an occupied cell, of a terminal position or of an id with an error write 0. i, j and all that
+// follows from them are wave-uniform.
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_forced_defences(DefenceParams q) {
+    __shared__ FwWave s_wave[kPosPerWG];
+    const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    const int i = blockIdx.x, j = blockIdx.y * kPosPerWG + wv;     // grid: n x ceil((A + 1) / kPosPerWG)
+    if (j > q.A) return;
+    const size_t pr = static_cast<size_t>(i) * (q.A + 1) + j;
+    const bool pass = j == q.A;
+    FwWave& W = s_wave[wv];
+    const int lane = lane_id();
+    const int nm = __builtin_amdgcn_readfirstlane(q.nmoves[i]);
+    PosR s;
+    int end_ply;
+    const int err = replay_moves(s, q.moves + static_cast<size_t>(i) * q.stride, nm, q.A, q.B, q.win_mark, end_ply);
+    const bool ok = err == PE_OK;
+    const int m = ok ? (nm & 1) : 0;       // the mover; the attacker of every search is 1 - m
+    // (a position that holds a line or is full has held one, or become full, after some move: end_ply)
+    const bool searched = ok && end_ply < 0 && (pass || !pos_occupied(s, j));
+    if (searched && !pass) pos_toggle(s, m, j);
+    // check_win of what stands now: the root of a searched pair, and for the pass also the position's own status, which is
+    // asked for even where nothing is searched (taken on every legal id, like k_forced_wins: a condition here costs registers)
+    const int status = ok ? check_win_board(s.bb[0], s.bb[1], q.B, q.win_mark) : 0;
+
+    FwResult r;
+    fw_search<NCH>(s, m ^ 1, pass ? nm : nm + 1, status, W, q.B, q.A, q.win_mark, searched, q.max_depth, q.max_nodes, r);
+    if (lane == 0)
+        q.pair[pr] = searched ? static_cast<uint32_t>(1 + r.result) | static_cast<uint32_t>(r.depth) << 2 | static_cast<uint32_t>(r.nodes) << 8 : 0u;
+    if (!pass) return;
+    if (lane == 0) {
+        if (q.status) q.status[i] = status;
+        if (q.turn) q.turn[i] = m;
+        if (q.err) q.err[i] = err;
+    }
+    if (q.threat_moves) {
+        const bool win = r.result == FW_WIN;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int cell = lane + 64 * c;
+            if (cell < q.A) q.threat_moves[static_cast<size_t>(i) * q.A + cell] = static_cast<uint8_t>(win && ((r.won[c] >> lane) & 1ull));
+        }
+    }
+}
+
+// One wavefront per position: the words of its A + 1 pairs into reply / depth [A], counts [4], nodes and the threat.
+// Ballots and integer sums only: the result does not depend on any order.
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_defence_rows(DefenceParams q) {
+    const int i = blockIdx.x * kPosPerWG + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+    if (i >= q.n) return;
+    const int lane = lane_id();
+    const uint32_t* pair = q.pair + static_cast<size_t>(i) * (q.A + 1);
+    const uint32_t pw = pair[q.A];         // the pass
+    int n_empty = 0, n_safe = 0, n_loses = 0, n_unknown = 0;
+    int nodes_l = lane == 0 ? static_cast<int>(pw >> 8) : 0;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int cell = lane + 64 * c;
+        const uint32_t w = cell < q.A ? pair[cell] : 0u;
+        const int rep = static_cast<int>(w & 3u);
+        n_empty += __popcll(__ballot(rep != FD_NONE));
+        n_safe += __popcll(__ballot(rep == FD_SAFE));
+        n_loses += __popcll(__ballot(rep == FD_LOSES));
+        n_unknown += __popcll(__ballot(rep == FD_UNKNOWN));
+        nodes_l += static_cast<int>(w >> 8);
+        if (cell < q.A) {
+            if (q.reply) q.reply[static_cast<size_t>(i) * q.A + cell] = static_cast<uint8_t>(rep);
+            if (q.depth) q.depth[static_cast<size_t>(i) * q.A + cell] = static_cast<uint8_t>((w >> 2) & 31u);
+        }
+    }
+    const int nodes = wave_sum_i(nodes_l);   // <= 226 * 65536
+    if (lane == 0) {
+        if (q.threat) q.threat[i] = pw ? static_cast<int>(pw & 3u) - 1 : 0;
+        if (q.threat_depth) q.threat_depth[i] = static_cast<int>((pw >> 2) & 31u);
+        if (q.nodes) q.nodes[i] = nodes;
+        if (q.counts) {
+            int32_t* cn = q.counts + static_cast<size_t>(i) * 4;
+            cn[0] = n_empty; cn[1] = n_safe; cn[2] = n_loses; cn[3] = n_unknown;
+        }
+    }
+}
+
 }  // namespace ao
 
 struct ao_positions : ao::HandleBase {
@@ -677,6 +811,9 @@ struct ao_positions : ao::HandleBase {
     ao::DevBuf<int32_t> d_counts{&pool};   // [cap][8]      -- allocated by the first ao_positions_audit
     ao::DevBuf<int32_t> d_forced{&pool};   // [5][cap]: result, depth, move, line_len, nodes -- these two: by the first ao_positions_forced_wins
     ao::DevBuf<int16_t> d_line{&pool};     // [cap][2 * 16 - 1]
+    ao::DevBuf<uint32_t> d_pair{&pool};    // [cap][A + 1]  -- the three below: allocated by the first ao_positions_forced_defences
+    ao::DevBuf<int32_t> d_defence{&pool};  // [3][cap]: threat, threat_depth, nodes, then counts [cap][4]
+    ao::DevBuf<uint8_t> d_depth{&pool};    // [cap][A]
     std::vector<int32_t> h_moves, h_n;
 };
 
@@ -757,6 +894,28 @@ int launch_forced(ao_positions* p, int m, int max_depth, int max_nodes) {
     q.line = p->d_line.p;
     const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
     AO_DISPATCH_NCH(ao::nch_of_cells(p->A), hipLaunchKernelGGL(ao::k_forced_wins<NCH>, grid, block, 0, p->stream, q));
+    AO_HIP(p, hipGetLastError());
+    return 0;
+}
+
+// k_forced_defences on the (A + 1) pairs of each of the m staged ids, then k_defence_rows on the ids; the outputs land in
+// d_defence, d_board (threat_moves), d_legal (reply), d_depth and d_i32
+int launch_defences(ao_positions* p, int m, int max_depth, int max_nodes) {
+    ao::DefenceParams q{};
+    const size_t cap = static_cast<size_t>(p->cap);
+    q.moves = p->d_moves; q.nmoves = p->d_n;
+    q.n = m; q.stride = p->A; q.B = p->B; q.A = p->A; q.win_mark = p->win_mark;
+    q.max_depth = max_depth; q.max_nodes = max_nodes;
+    q.pair = p->d_pair.p;
+    q.threat_moves = reinterpret_cast<uint8_t*>(p->d_board);
+    q.status = p->d_i32; q.turn = p->d_i32 + 2 * cap; q.err = p->d_i32 + 3 * cap;
+    int32_t* def = p->d_defence.p;
+    q.threat = def; q.threat_depth = def + cap; q.nodes = def + 2 * cap; q.counts = def + 3 * cap;
+    q.reply = p->d_legal; q.depth = p->d_depth.p;
+    const dim3 pair_grid(static_cast<unsigned>(m), static_cast<unsigned>((p->A + 1 + ao::kPosPerWG - 1) / ao::kPosPerWG));
+    const dim3 grid(static_cast<unsigned>((m + ao::kPosPerWG - 1) / ao::kPosPerWG)), block(64 * ao::kPosPerWG);
+    AO_DISPATCH_NCH(ao::nch_of_cells(p->A), hipLaunchKernelGGL(ao::k_forced_defences<NCH>, pair_grid, block, 0, p->stream, q);
+                    hipLaunchKernelGGL(ao::k_defence_rows<NCH>, grid, block, 0, p->stream, q));
     AO_HIP(p, hipGetLastError());
     return 0;
 }
@@ -914,6 +1073,38 @@ int ao_positions_forced_wins(ao_positions* p, const int32_t* host_moves, int32_t
             download(p, host_nodes ? host_nodes + first : nullptr, p->d_forced.p + 4 * cap, m) ||
             download(p, host_moves_mask ? host_moves_mask + first * A : nullptr, reinterpret_cast<const uint8_t*>(p->d_board), m * A) ||
             download(p, host_line ? host_line + first * lw : nullptr, p->d_line.p, m * lw) ||
+            download(p, host_status ? host_status + first : nullptr, p->d_i32, m) ||
+            download(p, host_turn ? host_turn + first : nullptr, p->d_i32 + 2 * cap, m) ||
+            download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))
+            return 1;
+        AO_HIP(p, hipStreamSynchronize(p->stream));   // the staging buffers are reused by the next chunk
+    }
+    return 0;
+}
+
+int ao_positions_forced_defences(ao_positions* p, const int32_t* host_moves, int32_t stride, const int32_t* host_n, int32_t n,
+                                 int32_t max_depth, int32_t max_nodes, int32_t* host_threat, int32_t* host_threat_depth,
+                                 uint8_t* host_threat_moves, uint8_t* host_reply, uint8_t* host_depth, int32_t* host_counts,
+                                 int32_t* host_nodes, int32_t* host_status, int32_t* host_turn, int32_t* host_err) {
+    if (n < 0 || stride < 0) return p->fail("ao_positions_forced_defences: negative position count or stride");
+    if (max_depth < 1 || max_depth > ao::kFwMaxDepth) return p->fail("ao_positions_forced_defences: max_depth must be in 1..16");
+    if (max_nodes < 1 || max_nodes > ao::kFwMaxNodes) return p->fail("ao_positions_forced_defences: max_nodes must be in 1..65536");
+    if (n == 0) return 0;
+    if (!host_n || (!host_moves && stride > 0)) return p->fail("ao_positions_forced_defences: null move buffer");
+    const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
+    AO_HIP(p, hipSetDevice(p->device));
+    if (p->d_pair.reserve(p, cap * (A + 1)) || p->d_defence.reserve(p, 7 * cap) || p->d_depth.reserve(p, cap * A)) return 1;
+    for (int64_t first = 0; first < n; first += p->cap) {
+        const int m = static_cast<int>(std::min<int64_t>(p->cap, n - first));
+        if (stage_moves(p, "ao_positions_forced_defences", host_moves, stride, host_n, first, m)) return 1;
+        if (launch_defences(p, m, max_depth, max_nodes)) return 1;
+        if (download(p, host_threat ? host_threat + first : nullptr, p->d_defence.p, m) ||
+            download(p, host_threat_depth ? host_threat_depth + first : nullptr, p->d_defence.p + cap, m) ||
+            download(p, host_nodes ? host_nodes + first : nullptr, p->d_defence.p + 2 * cap, m) ||
+            download(p, host_counts ? host_counts + first * 4 : nullptr, p->d_defence.p + 3 * cap, static_cast<size_t>(m) * 4) ||
+            download(p, host_threat_moves ? host_threat_moves + first * A : nullptr, reinterpret_cast<const uint8_t*>(p->d_board), m * A) ||
+            download(p, host_reply ? host_reply + first * A : nullptr, p->d_legal, m * A) ||
+            download(p, host_depth ? host_depth + first * A : nullptr, p->d_depth.p, m * A) ||
             download(p, host_status ? host_status + first : nullptr, p->d_i32, m) ||
             download(p, host_turn ? host_turn + first : nullptr, p->d_i32 + 2 * cap, m) ||
             download(p, host_err ? host_err + first : nullptr, p->d_i32 + 3 * cap, m))

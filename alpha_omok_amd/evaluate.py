@@ -274,3 +274,41 @@ def forced_win_summary(games, board_size, max_depth=8, max_nodes=2000, win_mark=
                          followed=int((followed & side).sum()), missed=int((forced & ~followed & side).sum()),
                          unknown=int((open_ & side & (d["result"] == P.FW_UNKNOWN)).sum()))
     return out
+
+
+def forced_defence_summary(games, board_size, max_depth=8, max_nodes=2000, win_mark=None, device=0):
+    """How the games of an evaluation dealt with the OPPONENT's forced wins by continuous fours: `games` as for
+    tactical_summary; every prefix of every game before its end goes through ONE PositionBatch.forced_defences call.
+    Returns {'black': {...}, 'white': {...}} by the side to move, each with plies (positions searched), threats (the
+    opponent would have a forced win after a pass, threat 1 with threat_depth >= 2: a threat in one is tactical_summary's
+    business), threat_unknown (that search ran out of nodes), and the threats by the move played: defended (its reply is
+    SAFE), blundered (LOSES although a SAFE cell existed), hopeless (LOSES with no SAFE and no UNKNOWN cell) and unknown
+    (the rest)."""
+    from . import positions as P
+    ids, played = [], []
+    for _, moves in games:
+        moves = [int(m) for m in moves]
+        for t in range(len(moves)):
+            ids.append(moves[:t])
+            played.append(moves[t])
+    with P.PositionBatch(board_size, win_mark=win_mark, capacity=max(1, min(len(ids), 4096)), device=device) as pb:
+        d = pb.forced_defences(ids, max_depth, max_nodes, leading_zero=False)
+    if d["err"].any():
+        raise ValueError("games hold moves that are not legal (prefixes %s)" % np.flatnonzero(d["err"]).tolist()[:8])
+    played = np.array(played, np.int64).reshape(len(ids))
+    open_ = d["status"] == 0                                              # (moves after the end of a game are not plies)
+    threat = open_ & (d["threat"] == P.FW_WIN) & (d["threat_depth"] >= 2)
+    reply = d["reply"][np.arange(len(ids)), played] if len(ids) else np.zeros(0, np.uint8)
+    n_safe, n_unknown = d["counts"][:, 1], d["counts"][:, 3]
+    defended = threat & (reply == P.FD_SAFE)
+    blundered = threat & (reply == P.FD_LOSES) & (n_safe > 0)
+    hopeless = threat & (reply == P.FD_LOSES) & (n_safe == 0) & (n_unknown == 0)
+    out = {}
+    for colour, name in enumerate(("black", "white")):
+        side = d["turn"] == colour
+        out[name] = dict(plies=int((open_ & side).sum()), threats=int((threat & side).sum()),
+                         threat_unknown=int((open_ & side & (d["threat"] == P.FW_UNKNOWN)).sum()),
+                         defended=int((defended & side).sum()), blundered=int((blundered & side).sum()),
+                         hopeless=int((hopeless & side).sum()),
+                         unknown=int((threat & ~defended & ~blundered & ~hopeless & side).sum()))
+    return out

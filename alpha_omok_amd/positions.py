@@ -26,6 +26,8 @@ WIN_AVAILABLE, WIN_TAKEN, THREAT, BLOCKED, LOST = 1, 2, 4, 8, 16
 # `result` of PositionBatch.forced_wins and the limits of its search (the same values as utils.forced_win)
 FW_NONE, FW_WIN, FW_UNKNOWN = 0, 1, 2
 FW_MAX_DEPTH, FW_MAX_NODES = 16, 65536
+# `reply` of PositionBatch.forced_defences (the same values as utils.forced_defences)
+FD_NONE, FD_SAFE, FD_LOSES, FD_UNKNOWN = 0, 1, 2, 3
 
 
 def default_win_mark(board_size):
@@ -112,6 +114,13 @@ def pack_ids(root_ids, leading_zero=True):
     for k, r in enumerate(rows):
         moves[k, :r.size] = r
     return moves, n
+
+
+def _check_limits(max_depth, max_nodes):
+    """ValueError for search limits ao_positions_forced_wins / ao_positions_forced_defences would refuse"""
+    for name, v, hi in (("max_depth", max_depth, FW_MAX_DEPTH), ("max_nodes", max_nodes, FW_MAX_NODES)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError("%s must be an integer in 1..%d, got %r" % (name, hi, v))
 
 
 class PositionBatch:
@@ -260,9 +269,7 @@ class PositionBatch:
         wins within depth), line (int16 [n, 2 max_depth - 1]: the principal line, padded with -1), line_len, nodes, and
         status, turn, err as win_cells (a terminal position has result 0; rows with err != 0 are all zero, move and line
         -1). 1 <= max_depth <= 16, 1 <= max_nodes <= 65536, ValueError otherwise: the node budget bounds the launch."""
-        for name, v, hi in (("max_depth", max_depth, FW_MAX_DEPTH), ("max_nodes", max_nodes, FW_MAX_NODES)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
-                raise ValueError("%s must be an integer in 1..%d, got %r" % (name, hi, v))
+        _check_limits(max_depth, max_nodes)
         moves, n = pack_ids(root_ids, leading_zero)
         cnt = n.shape[0]
         i32 = lambda: np.zeros(cnt, np.int32)
@@ -275,6 +282,32 @@ class PositionBatch:
             _ptr(out["moves"], C.c_uint8), _ptr(out["line"], C.c_int16), _ptr(out["line_len"], C.c_int32),
             _ptr(out["nodes"], C.c_int32), _ptr(out["status"], C.c_int32), _ptr(out["turn"], C.c_int32),
             _ptr(out["err"], C.c_int32)), "ao_positions_forced_wins")
+        return out
+
+    def forced_defences(self, root_ids, max_depth=8, max_nodes=2000, leading_zero=True):
+        """Which replies of the side to move hold against the opponent's forced win by continuous fours, one row per id;
+        utils.forced_defences is the definition: forced_wins of the position after every empty cell, and of the position
+        itself with the opponent attacking as if the mover had passed -- A + 1 searches per id, each with its own budget
+        of max_nodes, one wavefront each. dict of threat, threat_depth, threat_moves (uint8 [n, A]): result, depth and
+        moves of the opponent's search after a pass; reply (uint8 [n, A]: FD_NONE not an empty cell, FD_SAFE the opponent
+        has no forced win after a stone there -- also a stone that ends the game --, FD_LOSES it has one, FD_UNKNOWN that
+        search ran out of nodes); depth (uint8 [n, A]: the opponent's attacker moves after the reply, 0 unless LOSES);
+        counts (int32 [n, 4]: empty cells, SAFE, LOSES, UNKNOWN); nodes (the sum over the searches run); status, turn, err
+        as win_cells. A terminal position has every output but status and turn zero, and so has a row with err != 0.
+        Limits as forced_wins, ValueError otherwise."""
+        _check_limits(max_depth, max_nodes)
+        moves, n = pack_ids(root_ids, leading_zero)
+        cnt = n.shape[0]
+        i32 = lambda: np.zeros(cnt, np.int32)
+        u8 = lambda: np.zeros((cnt, self.A), np.uint8)
+        out = dict(threat=i32(), threat_depth=i32(), threat_moves=u8(), reply=u8(), depth=u8(),
+                   counts=np.zeros((cnt, 4), np.int32), nodes=i32(), status=i32(), turn=i32(), err=i32())
+        self._check(self._L.ao_positions_forced_defences(
+            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, int(max_depth), int(max_nodes),
+            _ptr(out["threat"], C.c_int32), _ptr(out["threat_depth"], C.c_int32), _ptr(out["threat_moves"], C.c_uint8),
+            _ptr(out["reply"], C.c_uint8), _ptr(out["depth"], C.c_uint8), _ptr(out["counts"], C.c_int32),
+            _ptr(out["nodes"], C.c_int32), _ptr(out["status"], C.c_int32), _ptr(out["turn"], C.c_int32),
+            _ptr(out["err"], C.c_int32)), "ao_positions_forced_defences")
         return out
 
     # -- lifetime

@@ -255,7 +255,7 @@ class WindowPosition(ArrayPosition):
         return out[0], out[1]
 
 
-def forced_win(moves, board_size, win_mark, max_depth=8, max_nodes=2000, position=WindowPosition):
+def forced_win(moves, board_size, win_mark, max_depth=8, max_nodes=2000, position=WindowPosition, attacker=None):
     """Is there a forced win by continuous fours (VCF) for the side to move in the position reached by `moves` (legal moves,
     black first)? No reference counterpart; defined through check_win / win_cells alone. The attacker a is the side to
     move, cells are always tried in ascending order, and `nodes` counts the wins_within calls of all iterations:
@@ -278,7 +278,11 @@ def forced_win(moves, board_size, win_mark, max_depth=8, max_nodes=2000, positio
     that makes the line and may be shorter than 2 depth - 1), line_len, nodes, status (check_win of the position), turn, and stats
     (host only: `block_fours` nodes at which a candidate taken from theirs succeeded, `multi_reply` fours with two or more
     replies that were tried). ValueError for an illegal move list or limits outside 1..16 / 1..65536.
-    `position`: WindowPosition (fast) or ArrayPosition (check_win / win_cells of the array, literally)."""
+    `position`: WindowPosition (fast) or ArrayPosition (check_win / win_cells of the array, literally).
+    `attacker`: None for the side to move, or 0 / 1 to name the attacker whatever the parity of `moves` -- the side that is
+    not to move is then searched as if the mover had passed; `turn` of the result is the attacker. ValueError otherwise."""
+    if attacker is not None and (isinstance(attacker, bool) or not isinstance(attacker, (int, np.integer)) or attacker not in (0, 1)):
+        raise ValueError("attacker must be None, 0 or 1, got %r" % (attacker,))
     for name, v, hi in (("max_depth", max_depth, FW_MAX_DEPTH), ("max_nodes", max_nodes, FW_MAX_NODES)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
             raise ValueError("%s must be an integer in 1..%d, got %r" % (name, hi, v))
@@ -293,7 +297,7 @@ def forced_win(moves, board_size, win_mark, max_depth=8, max_nodes=2000, positio
         if pos.board[m] != 0:
             raise ValueError("move %d is onto a stone" % m)
         pos.place(m, t % 2)
-    a = len(moves) % 2
+    a = len(moves) % 2 if attacker is None else int(attacker)
     stats = dict(block_fours=0, multi_reply=0)
     count = [0]
     won = []                                  # the root's collection
@@ -359,6 +363,43 @@ def forced_win(moves, board_size, win_mark, max_depth=8, max_nodes=2000, positio
         out.update(result=FW_UNKNOWN, nodes=max_nodes)
         return out
     out["nodes"] = count[0]
+    return out
+
+
+FD_NONE, FD_SAFE, FD_LOSES, FD_UNKNOWN = 0, 1, 2, 3     # `reply` of forced_defences / PositionBatch.forced_defences
+
+
+def forced_defences(moves, board_size, win_mark, max_depth=8, max_nodes=2000):
+    """Which replies hold against the opponent's forced win by continuous fours? For the position P after `moves` (legal
+    moves, black first) with mover m and opponent o, by forced_win alone, A + 1 searches each with its own budget of
+    max_nodes, none skipped on the strength of another one's answer:
+
+        threat, threat_depth, threat_moves: result, depth, moves of forced_win(moves, attacker=o) -- what o could do if m
+            passed.
+        for every empty cell c, r = forced_win(moves + [c]) with o to move: reply[c] = 1 + r.result, depth[c] = r.depth.
+
+    Returns a dict: threat, threat_depth, threat_moves (bool [A]), reply (uint8 [A]: FD_NONE not an empty cell, FD_SAFE the
+    reply holds -- also a c that ends the game: the position after it is terminal and forced_win says no --, FD_LOSES,
+    FD_UNKNOWN that search ran out of nodes), depth (uint8 [A], non-zero only where LOSES), counts (int32 [4]: empty cells,
+    SAFE, LOSES, UNKNOWN), nodes (the sum over all searches run), status (check_win of P), turn (m). On a terminal P every
+    output but status and turn is zero / empty: nothing is searched. Argument errors as forced_win."""
+    A = board_size * board_size
+    moves = [int(m) for m in moves]
+    first = forced_win(moves, board_size, win_mark, max_depth, max_nodes, attacker=1 - len(moves) % 2)
+    out = dict(threat=FW_NONE, threat_depth=0, threat_moves=np.zeros(A, bool), reply=np.zeros(A, np.uint8),
+               depth=np.zeros(A, np.uint8), counts=np.zeros(4, np.int32), nodes=0, status=first["status"], turn=len(moves) % 2)
+    if first["status"] != 0:
+        return out
+    out.update(threat=first["result"], threat_depth=first["depth"], threat_moves=first["moves"], nodes=first["nodes"])
+    taken = set(moves)
+    for c in range(A):
+        if c in taken:
+            continue
+        r = forced_win(moves + [c], board_size, win_mark, max_depth, max_nodes)
+        out["reply"][c] = 1 + r["result"]
+        out["depth"][c] = r["depth"]
+        out["nodes"] += r["nodes"]
+    out["counts"][:] = [A - len(moves)] + [int((out["reply"] == v).sum()) for v in (FD_SAFE, FD_LOSES, FD_UNKNOWN)]
     return out
 
 

@@ -587,6 +587,33 @@ int  ao_positions_forced_wins(ao_positions *p, const int32_t *host_moves, int32_
                               int32_t max_depth, int32_t max_nodes, int32_t *host_result, int32_t *host_depth,
                               int32_t *host_move, uint8_t *host_moves_mask, int16_t *host_line, int32_t *host_line_len,
                               int32_t *host_nodes, int32_t *host_status, int32_t *host_turn, int32_t *host_err);
+/* Which replies hold against a forced win by continuous fours, for n positions (ids as above). No reference counterpart:
+ * the definition is forced_win above, which asks utils.check_win (utils.py:30-59) and nothing else. P is the position of
+ * id i, m its side to move, o the opponent, and forced_win(Q, a) the search above on the board Q with a as the attacker
+ * (nothing in it depends on whose turn the stone count says it is). If check_win(P) != 0 every output but status and turn
+ * is zero. Otherwise
+ *   the threat         forced_win(P, o): what o could do if m passed;
+ *   for every empty c  r = forced_win(P with m on c, o); reply[c] = 1 + r.result, depth[c] = r.depth. A stone that makes
+ *                      a line or fills the board leaves a terminal position, and forced_win says no: such a reply holds.
+ * Each of the A + 1 searches has its own budget of max_nodes and none is skipped on the strength of another one's answer
+ * (no "no threat, hence all replies hold": host_nodes pins that). utils.forced_defences of the Python package is this
+ * text on the host. Limits of max_depth and max_nodes as above. Outputs (any may be NULL):
+ *   host_threat       int32 [n]     result of the threat search: 0, 1 or 2 (UNKNOWN)
+ *   host_threat_depth int32 [n]     its depth, 0 unless the threat is 1
+ *   host_threat_moves uint8 [n][A]  1 on every first move of o that wins within that depth
+ *   host_reply        uint8 [n][A]  0 NONE not an empty cell, 1 SAFE the reply holds, 2 LOSES, 3 UNKNOWN the search of
+ *                                   that reply ran out of nodes
+ *   host_depth        uint8 [n][A]  attacker moves of o's forced win after the reply; 0 unless the reply is LOSES
+ *   host_counts       int32 [n][4]  empty cells, SAFE, LOSES, UNKNOWN
+ *   host_nodes        int32 [n]     the sum of `nodes` over the searches run (at most 226 x 65536)
+ *   host_status, host_turn, host_err  int32 [n]  as ao_positions_win_cells; a position with an error has every output zeroed
+ * One wavefront per (position, reply) pair and one for the pass, each the search of ao_positions_forced_wins, then one
+ * wavefront per position gathers them: `capacity` positions, hence capacity x (A + 1) wavefronts, per launch. Chunks,
+ * staging and return value as ao_positions_from_moves; n == 0 is a no-op. */
+int  ao_positions_forced_defences(ao_positions *p, const int32_t *host_moves, int32_t stride, const int32_t *host_n, int32_t n,
+                                  int32_t max_depth, int32_t max_nodes, int32_t *host_threat, int32_t *host_threat_depth,
+                                  uint8_t *host_threat_moves, uint8_t *host_reply, uint8_t *host_depth, int32_t *host_counts,
+                                  int32_t *host_nodes, int32_t *host_status, int32_t *host_turn, int32_t *host_err);
 
 #ifdef __cplusplus
 }

@@ -59,7 +59,8 @@ def main():
     ap.add_argument("--audit", action="store_true",
                     help="add the tactical summary of every evaluation's games (evaluate.tactical_summary: wins in one available / "
                          "missed, single threats / blocks missed, lost positions, by colour) to its 'elo' log line as `tactics`, and the "
-                         "forced wins by continuous fours the games held / the mover followed (evaluate.forced_win_summary) as `forced_wins`")
+                         "forced wins by continuous fours the games held / the mover followed (evaluate.forced_win_summary) as `forced_wins`, and "
+                         "the opponent's forced wins the mover defended / walked into (evaluate.forced_defence_summary) as `forced_defences`")
     ap.add_argument("--eval-dense-until", type=int, default=0, help="evaluate after EVERY iteration up to this one (the steep part of the curve)")
     ap.add_argument("--ckpt-every", type=int, default=10)
     ap.add_argument("--max-ckpts", type=int, default=6, help="checkpoints kept on disk besides iteration 0 and final (gpurun_out is merged back up to 64 MiB)")
@@ -94,7 +95,8 @@ def main():
         if not a.audit:
             return {}
         return dict(tactics=evaluate.tactical_summary(games, a.board, device=0),
-                    forced_wins=evaluate.forced_win_summary(games, a.board, device=0))
+                    forced_wins=evaluate.forced_win_summary(games, a.board, device=0),
+                    forced_defences=evaluate.forced_defence_summary(games, a.board, device=0))
 
     def emit(rec):
         log.write(json.dumps(rec) + "\n")
