@@ -77,7 +77,11 @@ SYMBOLS = {
     "ao_set_root": (C.c_int, [_vp, C.c_int, _i32p, C.c_int32, _i32p]),
     "ao_set_roots": (C.c_int, [_vp, _u8p, _i32p, C.c_int32, _i32p, _i32p]),
     "ao_begin_move": (C.c_int, [_vp, _u8p]),
+    "ao_begin_move_opts": (C.c_int, [_vp, _u8p, _i32p, _u8p]),
     "ao_sims_left": (C.c_int, [_vp]),
+    "ao_settle": (C.c_int, [_vp, _u8p, C.c_int, _i32p]),
+    "ao_search_opts": (C.c_int, [_vp, _vp, _u8p, _i8p, _i32p, _u8p, _u8p, C.c_int32, _f64p, _f64p, _f64p]),
+    "ao_search_sims": (C.c_int, [_vp, _i32p, _u8p, _i64p, _i64p]),
     "ao_collect_leaves": (C.c_int, [_vp, _vp]),
     "ao_apply_evals": (C.c_int, [_vp, _vp, _vp]),
     "ao_end_move": (C.c_int, [_vp, _i8p, _f64p, _f64p, _f64p]),

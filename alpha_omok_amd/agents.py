@@ -123,7 +123,9 @@ class ZeroAgent(Agent):
         if self._engine is not None:
             self._engine.reset()
 
-    def get_pi(self, root_id, tau):
+    def get_pi(self, root_id, tau, sims=None, early_stop=False):
+        """sims: simulations of THIS move (1..num_mcts; None: num_mcts); early_stop=True: a tau == 0 search ends once its move is
+        decided (utils.move_decided) -- same pi and move, fewer visits in the tree the next move inherits."""
         start = time.time()
         eng = self._eng()
         st = np.random.get_state()                      # the reference's global stream
@@ -131,11 +133,12 @@ class ZeroAgent(Agent):
         status = eng.set_root(0, list(root_id)[1:])
         self.root_id = tuple(root_id)
         self.is_real_root = (status == AO_ROOT_FRESH)
-        num = self.num_mcts + 1 if self.is_real_root else self.num_mcts
+        num = (self.num_mcts if sims is None else int(sims)) + (1 if self.is_real_root else 0)
         def progress(i):
             self.message = 'simulation: {}\r'.format(i)
 
-        pi, visit, policy = self._evaluator.search(eng, self.model, tau, on_sim=progress)
+        pi, visit, policy = self._evaluator.search(eng, self.model, tau, on_sim=progress, sims=sims,
+                                                   early_stop=True if early_stop else None)
         mt, pos, has_gauss, gauss = eng.get_rng_state(0)
         np.random.set_state(('MT19937', mt, pos, has_gauss, gauss))
         self.message = 'simulation: {}\r'.format(num)

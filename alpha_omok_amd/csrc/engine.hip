@@ -37,6 +37,7 @@ int launch_play(const TreeParams& p, hipStream_t s);
 int launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
                 const int32_t* prev_known, int32_t* status_out, hipStream_t s);
 void launch_reset(const TreeParams& p, const uint8_t* mask, hipStream_t s);
+void launch_settle(const TreeParams& p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out, hipStream_t s);
 // tree_readout.hip
 void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
                         int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
@@ -96,6 +97,17 @@ struct ao_engine : ao::HandleBase {
     int32_t* h_i32 = nullptr;        // pinned [4][G]
     int sims_left = 0;
     bool in_move = false, ended = false;
+    // per-game budgets and settling (ao_begin_move_opts, ao_settle, ao_search_opts, ao_search_sims)
+    std::vector<int32_t> bonus;      // [G] 1 where this move's root was fresh (its expansion is one simulation more than the budget)
+    int64_t target_sum = 0;          // simulations the current move set out to run, over the active games
+    int64_t move_saved = 0;          // ... and how many of them settling took away
+    bool leaf_open = false;          // a selection has been launched whose leaves are not backed up yet (k_settle's `pending`)
+    uint8_t* d_settled = nullptr;    // [G] 1 where k_settle lowered the game's target in this move
+    bool settled_dirty = false;      // d_settled may hold ones
+    uint8_t* d_early = nullptr;      // [G] ao_search_opts' early_stop mask
+    int32_t* d_settle = nullptr;     // [4] k_settle's counters of one launch
+    int32_t* h_settle = nullptr;     // pinned [4]
+    int64_t settled_total = 0, saved_total = 0;
     // fp16-range recovery of ao_search: the games' MT19937 states as they were before the move (device copy), the host
     // half of the stream (legacy gauss cache), the number of recovered moves and of games searched again
     uint32_t* d_mt_backup = nullptr; int32_t* d_pos_backup = nullptr;
@@ -140,6 +152,7 @@ void ao_destroy(ao_engine* e) {
     if (e->h_out) hipHostFree(e->h_out);
     if (e->h_i32) hipHostFree(e->h_i32);
     if (e->h_live) hipHostFree(e->h_live);
+    if (e->h_settle) hipHostFree(e->h_settle);
     e->timer.destroy();
     if (e->own_stream) hipStreamDestroy(e->own_stream);
     delete e;
@@ -261,6 +274,8 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
     if (e->pool.alloc(e, &e->d_planes_u8, static_cast<size_t>(Gp) * p.u8_row) || e->pool.alloc(e, &e->d_row, 2 * static_cast<size_t>(G))) return 1;
     if (e->pool.alloc(e, &e->d_mt_backup, static_cast<size_t>(G) * 624) || e->pool.alloc(e, &e->d_pos_backup, G)) return 1;
     if (e->pool.alloc(e, &e->d_live, ao_engine::kLive) || e->pool.alloc(e, &e->d_log_games, G) || e->pool.alloc(e, &e->d_ctl, 8) || e->pool.alloc(e, &e->d_order, G)) return 1;
+    if (e->pool.alloc(e, &e->d_settled, G) || e->pool.alloc(e, &e->d_early, G) || e->pool.alloc(e, &e->d_settle, 4)) return 1;
+    AO_HIP(e, hipMemsetAsync(e->d_settled, 0, G, e->stream));
     e->order_on = !(getenv("AO_TREE_ORDER") && atoi(getenv("AO_TREE_ORDER")) == 0);
     p.order = nullptr;
     AO_HIP(e, hipMemsetAsync(e->d_row, 0, sizeof(int32_t) * 2 * G, e->stream));
@@ -292,12 +307,14 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
     AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_out), sizeof(double) * 3 * G * A, hipHostMallocDefault));
     AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_i32), sizeof(int32_t) * 4 * G, hipHostMallocDefault));
     AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_live), sizeof(unsigned) * (ao_engine::kLive + 8), hipHostMallocDefault));
+    AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_settle), sizeof(int32_t) * 4, hipHostMallocDefault));
     std::memset(e->h_noise, 0, sizeof(double) * G * Ap);
 
     e->moves.assign(G, {});
     e->status.assign(G, AO_ROOT_FRESH);
     e->over.assign(G, 0);
     e->active.assign(G, 1);
+    e->bonus.assign(G, 0);
     e->has_gauss.assign(G, 0);
     e->gauss.assign(G, 0.0);
     for (int g = 0; g < G; ++g) {
@@ -517,21 +534,37 @@ int ao_get_moves(ao_engine* e, int g, int32_t* out, int32_t* n) {
 }
 
 // ---- one move decision -----------------------------------------------------------------------
-int ao_begin_move(ao_engine* e, const uint8_t* active) {
+// sims / noise: per-game budgets and noise switches of ao_begin_move_opts (NULL = the engine's configuration)
+static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* sims, const uint8_t* noise) {
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const int G = e->G, A = e->A, Ap = e->Ap;
     ao::TreeParams& p = e->tp;
+    // nothing is touched before every value is known to be in range: a refused call leaves the engine as it was
+    for (int g = 0; g < G; ++g) {
+        if (!((active ? active[g] : 1) && !e->over[g])) continue;
+        if (sims && (sims[g] < 1 || sims[g] > e->S))
+            return e->fail("ao_begin_move_opts: game " + std::to_string(g) + ": sims " + std::to_string(sims[g]) + " is outside 1.." +
+                           std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
+        if (noise && noise[g] && !p.noise)
+            return e->fail("ao_begin_move_opts: game " + std::to_string(g) + ": noise asked for on an engine created without noise");
+    }
     int32_t* target = e->h_i32;
     int32_t* flags = e->h_i32 + G;
     int maxt = 0;
+    e->target_sum = 0;
+    e->move_saved = 0;
     for (int g = 0; g < G; ++g) {
         e->active[g] = (active ? active[g] : 1) && !e->over[g];
         target[g] = 0;
         flags[g] = 0;
+        e->bonus[g] = 0;
         if (!e->active[g]) continue;
-        target[g] = (e->status[g] == AO_ROOT_FRESH) ? e->S + 1 : e->S;  // agents.py:107-111
-        flags[g] = (p.noise && e->status[g] == AO_ROOT_EXPANDED) ? 1 : 0;
+        e->bonus[g] = (e->status[g] == AO_ROOT_FRESH) ? 1 : 0;
+        target[g] = (sims ? sims[g] : e->S) + e->bonus[g];  // agents.py:107-111
+        const bool quiet = p.noise && noise && !noise[g];   // this game, this move: as on an engine created without noise
+        flags[g] = quiet ? 2 : ((p.noise && e->status[g] == AO_ROOT_EXPANDED) ? 1 : 0);
         maxt = std::max(maxt, target[g]);
+        e->target_sum += target[g];
     }
     if (p.noise) {
         // The Dirichlet draw is the first consumer of the stream in a move in every case:
@@ -542,7 +575,7 @@ int ao_begin_move(ao_engine* e, const uint8_t* active) {
         const double alpha = e->cfg.alpha;
         auto work = [&](int g0, int g1) {
             for (int g = g0; g < g1; ++g) {
-                if (!e->active[g]) continue;
+                if (!e->active[g] || (flags[g] & 2)) continue;   // (no draw for a game without noise: its stream is not touched)
                 ao::HostMT r{e->h_mt + static_cast<size_t>(g) * 624, e->h_pos + g, &e->has_gauss[g], &e->gauss[g]};
                 const int k = A - static_cast<int>(e->moves[g].size());
                 r.dirichlet(alpha, k, e->h_noise + static_cast<size_t>(g) * Ap);
@@ -561,16 +594,81 @@ int ao_begin_move(ao_engine* e, const uint8_t* active) {
     AO_HIP(e, hipMemcpyAsync(e->d_active, e->active.data(), G, hipMemcpyHostToDevice, e->stream));
     if (e->order_on && e->row_cap > 0 && e->row_cap < G) ao::launch_order(p, e->d_order, e->stream);   // (reads the move's stats that the next line clears)
     AO_HIP(e, hipMemsetAsync(p.stats, 0, sizeof(unsigned) * 4 * G, e->stream));
+    if (e->settled_dirty) {
+        AO_HIP(e, hipMemsetAsync(e->d_settled, 0, G, e->stream));
+        e->settled_dirty = false;
+    }
     ao::launch_begin_move(p, e->stream);
     // the pinned staging buffers are reused by the next call: make sure the copies are done
     AO_HIP(e, hipStreamSynchronize(e->stream));
     e->sims_left = maxt;
     e->in_move = true;
     e->ended = false;
+    e->leaf_open = false;
     return 0;
 }
 
+int ao_begin_move(ao_engine* e, const uint8_t* active) { return begin_move_impl(e, active, nullptr, nullptr); }
+
+int ao_begin_move_opts(ao_engine* e, const uint8_t* active, const int32_t* sims, const uint8_t* noise) {
+    return begin_move_impl(e, active, sims, noise);
+}
+
 int ao_sims_left(ao_engine* e) { return e->sims_left; }
+
+// k_settle on the engine's stream, counters zeroed in front of it and copied to the pinned words behind it; settle_harvest reads
+// them once the stream has been synchronised
+static int settle_queue(ao_engine* e, const uint8_t* dmask, int stop_now) {
+    AO_HIP(e, hipMemsetAsync(e->d_settle, 0, sizeof(int32_t) * 4, e->stream));
+    ao::launch_settle(e->tp, dmask, stop_now, e->leaf_open ? 1 : 0, e->d_settled, e->d_settle, e->stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_settle, e->d_settle, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, e->stream));
+    e->settled_dirty = true;
+    return 0;
+}
+static void settle_harvest(ao_engine* e, int* unfinished, int* owed) {
+    *unfinished = e->h_settle[0];
+    *owed = e->h_settle[1];
+    e->settled_total += e->h_settle[2];
+    e->saved_total += e->h_settle[3];
+    e->move_saved += e->h_settle[3];
+}
+
+int ao_settle(ao_engine* e, const uint8_t* mask, int stop_now, int32_t* unfinished) {
+    if (!e->in_move) return e->fail("ao_settle outside ao_begin_move/ao_end_move");
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    const uint8_t* dmask = nullptr;
+    if (mask) {
+        AO_HIP(e, hipMemcpyAsync(e->d_mask, mask, e->G, hipMemcpyHostToDevice, e->stream));
+        dmask = e->d_mask;
+    }
+    if (settle_queue(e, dmask, stop_now)) return 1;
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    int left = 0, owed = 0;
+    settle_harvest(e, &left, &owed);
+    e->sims_left = owed;
+    if (unfinished) *unfinished = left;
+    return 0;
+}
+
+int ao_search_sims(ao_engine* e, int32_t* sims_run, uint8_t* settled, int64_t* settled_total, int64_t* saved_total) {
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    const int G = e->G;
+    if (sims_run) {
+        std::vector<int32_t> done(G);
+        AO_HIP(e, hipMemcpyAsync(done.data(), e->tp.sims_done, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+        AO_HIP(e, hipStreamSynchronize(e->stream));
+        for (int g = 0; g < G; ++g) sims_run[g] = e->active[g] ? std::max(0, done[g] - e->bonus[g]) : 0;
+    }
+    if (settled) {
+        AO_HIP(e, hipMemcpyAsync(settled, e->d_settled, G, hipMemcpyDeviceToHost, e->stream));
+        AO_HIP(e, hipStreamSynchronize(e->stream));
+        for (int g = 0; g < G; ++g) settled[g] = e->active[g] ? settled[g] : 0;
+    }
+    if (settled_total) *settled_total = e->settled_total;
+    if (saved_total) *saved_total = e->saved_total;
+    return 0;
+}
 
 int ao_collect_leaves(ao_engine* e, float* dev_planes_nchw) {
     if (!e->in_move) return e->fail("ao_collect_leaves outside ao_begin_move/ao_end_move");
@@ -581,6 +679,7 @@ int ao_collect_leaves(ao_engine* e, float* dev_planes_nchw) {
     else e->il_group_zeroed = -1;                // full-width write in whatever layout was planned last
     ao::launch_select(p, e->stream);
     AO_HIP(e, hipGetLastError());
+    e->leaf_open = true;
     return 0;
 }
 
@@ -593,6 +692,7 @@ int ao_apply_evals(ao_engine* e, const float* dev_policy, const float* dev_value
     ao::launch_expand_backup(p, e->stream);
     AO_HIP(e, hipGetLastError());
     if (e->sims_left > 0) --e->sims_left;
+    e->leaf_open = false;
     return 0;
 }
 
@@ -683,8 +783,17 @@ int ao_play(ao_engine* e, int32_t* action, int32_t* win) {
     return 0;
 }
 
+// what ao_search_opts adds to ao_search: per-game budgets and noise switches (ao_begin_move_opts), the games that may be settled
+// (k_settle) and how often the loop looks. All null / 0: ao_search.
+struct SearchOpts {
+    const int32_t* sims = nullptr;
+    const uint8_t* noise = nullptr;
+    const uint8_t* early_stop = nullptr;
+    int settle_every = 0;
+};
+
 static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi,
-                       double* visit, double* policy, bool may_recover) {
+                       double* visit, double* policy, bool may_recover, const SearchOpts& opts) {
     if (!net) return e->fail("ao_search: null network");
     std::string why;
     if (ao::net_check(net, e->cfg.board, e->cfg.inplanes, e->cfg.device, &why)) return e->fail("ao_search: " + why);
@@ -697,7 +806,7 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
         e->gauss_backup = e->gauss;
     }
     // the network announces the interleaved input layout it wants for a batch of G boards
-    if (ao_begin_move(e, active)) return 1;
+    if (begin_move_impl(e, active, opts.sims, opts.noise)) return 1;
     // The network runs on the ACTIVE games only. Two regimes (engine_types.hpp, TreeParams::live):
     //  * a handful of games on the per-board path with the fused per-game step: the host packs the active games to the front of
     //    the evaluation batch once per move (row_of_game / game_of_row);
@@ -770,9 +879,11 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
     p.max_levels = dynamic ? level_budget : 0;
     const bool catch_up = oversub || p.max_levels > 0;   // games may be short of their simulations after the nominal number of launches
     const int64_t rows_live_before = e->rs_rows_live;
-    int64_t sims_wanted = 0;
-    for (int g = 0; g < e->G; ++g)
-        if (e->active[g]) sims_wanted += (e->status[g] == AO_ROOT_FRESH) ? e->S + 1 : e->S;
+    // Settling (k_settle): every settle_every simulations, and in every catch-up round, the games of the early_stop mask whose move
+    // is decided get their targets lowered and the loop goes on with the largest number of simulations still owed -- or ends.
+    // Off (no mask or settle_every 0): nothing is launched and nothing is read back.
+    const bool settle_on = opts.early_stop != nullptr && opts.settle_every > 0;
+    if (settle_on) AO_HIP(e, hipMemcpyAsync(e->d_early, opts.early_stop, e->G, hipMemcpyHostToDevice, e->stream));
     unsigned sit_idx = 0;       // the window the move starts with (the host's estimate); the device takes it from there (sit_window)
     unsigned row_target = static_cast<unsigned>(cap_rows);
     if (oversub) {
@@ -871,18 +982,32 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
     static const bool launch_timing = getenv("AO_LAUNCH_TIMING") != nullptr;   // developer switch: is the simulation loop host-bound?
     const auto lt0 = std::chrono::steady_clock::now();
     const int lt_sims = e->sims_left;
+    bool all_done = false;
+    int since_settle = 0;
+    e->leaf_open = e->sims_left > 0;
     while (e->sims_left > 0 && rc == 0) {
         rc = one_sim();
         --e->sims_left;
+        if (settle_on && rc == 0 && e->sims_left > 0 && ++since_settle >= opts.settle_every) {
+            since_settle = 0;
+            int unfinished = 0, owed = 0;
+            if (settle_queue(e, e->d_early, 0)) return 1;
+            AO_HIP(e, hipStreamSynchronize(e->stream));
+            settle_harvest(e, &unfinished, &owed);
+            all_done = unfinished == 0;
+            // (without over-subscription every unfinished game advances by one simulation per launch: `owed` launches are exactly
+            // what is left; with it they are a lower bound and the catch-up rounds below find the rest)
+            e->sims_left = all_done ? 0 : std::min(e->sims_left, owed);
+        }
     }
     if (rc) return rc;
-    if (oversub && sit_idx > 0) {
+    if (oversub && sit_idx > 0 && !settle_on) {
         // a game sits out sit_idx / G of the launches: that many more launches before anyone can be done
         const int planned = static_cast<int>(std::ceil(static_cast<double>(lt_sims) * e->G / (e->G - sit_idx))) - lt_sims;
         for (int k = 0; k < planned - 8 && rc == 0; ++k) rc = one_sim();   // (a few short: the deficit rounds below find out exactly)
         if (rc) return rc;
     }
-    if (catch_up) {
+    if (catch_up && !all_done) {
         // over-subscribed: leaves that found their simulation's batch full were expanded one launch later, so some games are
         // short of their simulations. The counters say by how much; max(largest deficit, all deficits / rows per launch)
         // is a lower bound of the launches still needed -- run them, look again. The reference ALWAYS runs num_mcts simulations
@@ -903,10 +1028,12 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
         if (window_off) sit_off_forced = true;
         int stalled = 0;
         for (int round = 0; round < max_rounds; ++round) {
+            if (settle_on && settle_queue(e, e->d_early, 0)) return 1;
             AO_HIP(e, hipMemcpyAsync(h_done, e->tp.sims_done, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
             AO_HIP(e, hipMemcpyAsync(h_target, e->tp.sims_target, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
             AO_HIP(e, hipMemcpyAsync(h_err, e->tp.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
             AO_HIP(e, hipStreamSynchronize(e->stream));
+            if (settle_on) { int unfinished = 0, owed = 0; settle_harvest(e, &unfinished, &owed); }
             int64_t sum = 0;
             int mx = 0;
             bool bad = false;
@@ -932,6 +1059,7 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
         }
     }
     if (harvest_rows(launch)) return 1;
+    const int64_t sims_wanted = e->target_sum - e->move_saved;   // (the budgets actually set, less what settling took away)
     if (oversub && sims_wanted > 0)
         e->ask_frac = static_cast<double>(e->rs_rows_live - rows_live_before) / static_cast<double>(sims_wanted);
     if (launch_timing) {
@@ -983,7 +1111,7 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
         ao::net_fp16_fallback_begin(net);                // mode 2 for the repeated move
         ++e->fp16_events;
         e->fp16_games_redone += static_cast<int64_t>(games.size());
-        const int rc2 = search_impl(e, net, active, tau, pi, visit, policy, false);
+        const int rc2 = search_impl(e, net, active, tau, pi, visit, policy, false, opts);   // (same budgets, noise switches and mask)
         ao::net_fp16_fallback_end(net);                  // back to the requested mode, unless these weights did it three times
         return rc2;
     }
@@ -992,7 +1120,15 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
 
 int ao_search(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi,
               double* visit, double* policy) {
-    return search_impl(e, net, active, tau, pi, visit, policy, true);
+    return search_impl(e, net, active, tau, pi, visit, policy, true, SearchOpts{});
+}
+
+int ao_search_opts(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, const int32_t* sims, const uint8_t* noise,
+                   const uint8_t* early_stop, int32_t settle_every, double* pi, double* visit, double* policy) {
+    if (settle_every < 0) return e->fail("ao_search_opts: settle_every must be >= 0");
+    SearchOpts o;
+    o.sims = sims; o.noise = noise; o.early_stop = early_stop; o.settle_every = settle_every;
+    return search_impl(e, net, active, tau, pi, visit, policy, true, o);
 }
 
 int ao_set_row_cap(ao_engine* e, int32_t rows) {

@@ -962,7 +962,8 @@ __device__ __forceinline__ void expand_backup_game(const TreeParams& p, const in
         }
         wsync();
         const double sum = pairwise_sum_dev(s_prior, p.A);  // prior_prob.sum() (agents.py:189)
-        const bool add_noise = p.noise && status == LS_EXPAND_ROOT;  // agents.py:191-204
+        // agents.py:191-204; gflags bit 1: this game searches this move without noise (read at a root expansion only)
+        const bool add_noise = p.noise && status == LS_EXPAND_ROOT && !(p.gflags[g] & 2);
         const size_t slot = node_slot(p, arena, g, newn);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {

@@ -193,6 +193,63 @@ __global__ __launch_bounds__(64) void k_end_move(TreeParams p) {
 }
 
 // ----------------------------------------------------------------------------------------------
+// k_settle: lower the simulation target of a game whose move is decided (utils.move_decided), or of every masked game
+// (stop_now). No reference counterpart: the reference always runs num_mcts simulations. r = target - done simulations are
+// owed; every one of them adds exactly one visit to exactly one child of an expanded root, so with n1 >= n2 the two largest
+// counts of the root's child row, n1 - n2 > r means the leader is out of reach and stays the only maximum: k_end_move's
+// tau == 0 result is what the full search would have returned. The new target is done + pending -- a leaf that was selected
+// and not yet backed up (leaf_open: the host knows whether a selection is outstanding; LS_WAIT / _ROOT and LS_DESCEND are
+// such leaves too) still gets its backup, after which done == target as k_end_move asks. One read of the root's N row per
+// game; four counters per launch: out[0] active games that still owe simulations, [1] the largest number owed, [2] games
+// settled by this launch, [3] simulations that saved.
+// ----------------------------------------------------------------------------------------------
+template <int NCH>
+__global__ __launch_bounds__(64) void k_settle(TreeParams p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out) {
+    const int g = blockIdx.x;
+    const int lane = lane_id();
+    if (p.active && !p.active[g]) return;
+    const int done = p.sims_done[g];
+    int r = p.sims_target[g] - done;
+    if (r <= 0) return;                                        // finished (uniform over the wave, as every branch here)
+    const int pending = (leaf_open && p.leaf_status[g] != LS_IDLE) ? 1 : 0;
+    if (r > pending && (!mask || mask[g])) {
+        bool settle = stop_now != 0;
+        const int node = p.root_node[g];
+        if (!settle && node >= 0) {
+            const size_t slot = node_slot(p, p.cur[g], g, node);
+            const int L = nodePos(p, slot)->nchild;
+            int m1 = 0, m2 = 0;                                // the lane's two largest counts
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const int i = lane + 64 * c;
+                const int n = i < L ? rowN(p, slot)[i] : 0;
+                if (n > m1) { m2 = m1; m1 = n; }
+                else if (n > m2) m2 = n;
+            }
+            const int n1 = wave_max_i(m1);
+            const bool top = m1 == n1;
+            // a second lane at n1 is a tie; otherwise the runner-up is the leader lane's second count or another lane's first
+            const int rest = wave_max_i(top ? m2 : m1);
+            const int n2 = __popcll(__ballot(top)) > 1 ? n1 : rest;
+            settle = n1 - n2 > r;
+        }
+        if (settle) {
+            if (lane == 0) {
+                p.sims_target[g] = done + pending;
+                settled[g] = 1;
+                atomicAdd(out + 2, 1);
+                atomicAdd(out + 3, r - pending);
+            }
+            r = pending;
+        }
+    }
+    if (r > 0 && lane == 0) {
+        atomicAdd(out + 0, 1);
+        atomicMax(out + 1, r);
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
 // re-rooting: copy the subtree of the node k_play / k_walk chose (p.pending_root) into the other arena, breadth first, so the
 // arena holds only what later searches can reach. Reads the old arena only. The walk is walk_subtree (tree_walk.hpp: one
 // workgroup of kWalkWaves waves per game, the queue in LDS, the numbering every walker shares); this kernel supplies what is done
@@ -490,6 +547,9 @@ void launch_begin_move(const TreeParams& p, hipStream_t s) {
 }
 void launch_end_move(const TreeParams& p, hipStream_t s) {
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_end_move<NCH>, dim3(p.G), dim3(64), 0, s, p));
+}
+void launch_settle(const TreeParams& p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out, hipStream_t s) {
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_settle<NCH>, dim3(p.G), dim3(64), 0, s, p, mask, stop_now, leaf_open, settled, out));
 }
 static void launch_reroot(const TreeParams& p, int count, const int32_t* games, hipStream_t s) {
     const size_t lds = walk_lds_bytes(p.cap);

@@ -16,6 +16,10 @@ class EngineError(RuntimeError):
     pass
 
 
+# Engine.search(early_stop=...): simulations between two looks at whether the moves are decided
+SETTLE_EVERY = 16
+
+
 def _ptr(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
 
@@ -237,12 +241,40 @@ class Engine:
     def sync(self):
         self._check(self._L.ao_sync(self._h), "ao_sync")
 
-    def begin_move(self, active=None):
+    def _per_game(self, v, dtype):
+        return None if v is None else np.ascontiguousarray(np.broadcast_to(v, (self.G,)), dtype)
+
+    def begin_move(self, active=None, sims=None, noise=None):
+        """sims: simulations per game for this move (int or [G], 1..num_mcts), noise: per-game noise switch (bool or [G]; False
+        = this game searches this move as on a noise=False engine, stream untouched). None: the engine's configuration."""
         a = None if active is None else np.ascontiguousarray(active, np.uint8)
-        self._check(self._L.ao_begin_move(self._h, _ptr(a, C.c_uint8)), "ao_begin_move")
+        if sims is None and noise is None:
+            self._check(self._L.ao_begin_move(self._h, _ptr(a, C.c_uint8)), "ao_begin_move")
+            return
+        s, n = self._per_game(sims, np.int32), self._per_game(noise, np.uint8)
+        self._check(self._L.ao_begin_move_opts(self._h, _ptr(a, C.c_uint8), _ptr(s, C.c_int32), _ptr(n, C.c_uint8)),
+                    "ao_begin_move_opts")
 
     def sims_left(self):
         return self._L.ao_sims_left(self._h)
+
+    def settle(self, mask=None, stop=False):
+        """Inside a move: lower the target of every masked game (None: all) whose move is decided (utils.move_decided) -- or of
+        every masked game, with stop=True -- to what it has run, a pending leaf included (ao_settle). Returns the number of
+        games that still owe simulations; sims_left() then tells how many launches that takes."""
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        left = C.c_int32(0)
+        self._check(self._L.ao_settle(self._h, _ptr(m, C.c_uint8), 1 if stop else 0, C.byref(left)), "ao_settle")
+        return left.value
+
+    def sims_run(self):
+        """The last move: dict(sims int32 [G] simulations run per game in budget units, settled bool [G], settled_total and
+        saved_total: games settled / simulations saved since the engine was created) -- ao_search_sims."""
+        s, f = np.zeros(self.G, np.int32), np.zeros(self.G, np.uint8)
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.ao_search_sims(self._h, _ptr(s, C.c_int32), _ptr(f, C.c_uint8), C.byref(a), C.byref(b)),
+                    "ao_search_sims")
+        return dict(sims=s, settled=f.astype(bool), settled_total=a.value, saved_total=b.value)
 
     def collect_leaves(self, planes_ptr=None):
         self._check(self._L.ao_collect_leaves(self._h, planes_ptr), "ao_collect_leaves")
@@ -269,13 +301,27 @@ class Engine:
         return act, win
 
     # -- fused move with the native network
-    def search(self, net, tau=None, active=None):
+    def search(self, net, tau=None, active=None, sims=None, noise=None, early_stop=None, settle_every=None):
+        """sims / noise: as begin_move. early_stop: the games that may stop once their move is decided (utils.move_decided) --
+        a bool [G] mask, or True for the games with tau == 0 (the only ones whose result is the leader alone); the loop looks
+        every settle_every simulations (None: SETTLE_EVERY, 0: never). With none of them given this is ao_search."""
         t = None if tau is None else np.ascontiguousarray(np.broadcast_to(tau, (self.G,)), np.int8)
         a = None if active is None else np.ascontiguousarray(active, np.uint8)
         pi, vis, pol = self._outs()
-        self._check(self._L.ao_search(self._h, net._h, _ptr(a, C.c_uint8), _ptr(t, C.c_int8),
-                                      _ptr(pi, C.c_double), _ptr(vis, C.c_double), _ptr(pol, C.c_double)),
-                    "ao_search")
+        if early_stop is True:
+            early_stop = np.zeros(self.G, bool) if t is None else (t == 0)
+        elif early_stop is False:
+            early_stop = None
+        if sims is None and noise is None and early_stop is None:
+            self._check(self._L.ao_search(self._h, net._h, _ptr(a, C.c_uint8), _ptr(t, C.c_int8),
+                                          _ptr(pi, C.c_double), _ptr(vis, C.c_double), _ptr(pol, C.c_double)),
+                        "ao_search")
+        else:
+            s, n, m = self._per_game(sims, np.int32), self._per_game(noise, np.uint8), self._per_game(early_stop, np.uint8)
+            k = SETTLE_EVERY if settle_every is None else int(settle_every)
+            self._check(self._L.ao_search_opts(self._h, net._h, _ptr(a, C.c_uint8), _ptr(t, C.c_int8), _ptr(s, C.c_int32),
+                                               _ptr(n, C.c_uint8), _ptr(m, C.c_uint8), k, _ptr(pi, C.c_double),
+                                               _ptr(vis, C.c_double), _ptr(pol, C.c_double)), "ao_search_opts")
         ev, games = self.fp16_range_events()
         if ev != self._fp16_seen:
             import warnings

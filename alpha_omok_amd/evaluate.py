@@ -92,15 +92,20 @@ def evaluate(player, enemy, board_size, n_match=12, player_elo=1500.0, enemy_elo
     return result, (player_elo, enemy_elo)
 
 
+last_search_totals = {}      # evaluate_batched: searches, simulations asked for, searches settled and simulations saved by early stop
+
+
 class _ZeroSide:
     """One network's side of evaluate_batched: a G-game engine + evaluator; searches the masked matches at their ids."""
 
-    def __init__(self, model, sims, board_size, inplanes, G, device):
+    def __init__(self, model, sims, board_size, inplanes, G, device, early_stop=False):
         from .engine import Engine
         from .evaluator import Evaluator
         self.eng = Engine(board_size, sims, inplanes, games=G, noise=False, device=device)
         self.ev, self.model = Evaluator(device), model
         self.tau0 = np.zeros(G, np.int8)
+        self.early_stop = True if early_stop else None   # every search here has tau == 0: its result is the leader alone
+        self.sims, self.searches = sims, 0
 
     def seed(self, i, s):
         self.eng.seed(i, s)
@@ -113,7 +118,8 @@ class _ZeroSide:
 
     def search(self, ids, mask):
         self.eng.set_roots(ids, mask)
-        pi, _, _ = self.ev.search(self.eng, self.model, self.tau0, active=mask)
+        pi, _, _ = self.ev.search(self.eng, self.model, self.tau0, active=mask, early_stop=self.early_stop)
+        self.searches += int(np.count_nonzero(mask))
         return pi
 
     def close(self):
@@ -147,12 +153,14 @@ class _RolloutSide:
 
 def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mcts_enemy=None, inplanes=5, n_match=12,
                      player_elo=1500.0, enemy_elo=1500.0, seed=0, device=0, max_plies=None, monitor_model=None,
-                     n_mcts_monitor=None):
+                     n_mcts_monitor=None, early_stop=False):
     """All n_match games at once (colours swapped every game, eval_main.py:213-333). `*_model`: whatever
     ZeroAgent.model accepts (a PVNet-shaped module runs on the native forward), or 'puct' / 'uct' for the rollout
     agents (eval_main.py:68-73,106-111). With a rollout PLAYER and a `monitor_model`, the monitor ZeroAgent searches
     the same roots right after the player as Evaluator.get_action does (eval_main.py:141-144). Returns (result tally,
-    (player_elo, enemy_elo), [(win_index, moves) per match]); the ELO updates are applied in match order."""
+    (player_elo, enemy_elo), [(win_index, moves) per match]); the ELO updates are applied in match order.
+    early_stop=True: the ZeroAgent sides (both of them) end a search once its move is decided (utils.move_decided): the same move,
+    fewer simulations; the later plies then search on smaller inherited trees, so a match need not be the one full searches play."""
     n_mcts_enemy = n_mcts_player if n_mcts_enemy is None else n_mcts_enemy
     G = n_match
     win_mark = 3 if board_size == 3 else 5
@@ -160,7 +168,7 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     def make(model, sims):
         if isinstance(model, str):
             return _RolloutSide(model, sims, board_size, G, device)
-        return _ZeroSide(model, sims, board_size, inplanes, G, device)
+        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop)
 
     sides = [make(player_model, n_mcts_player), make(enemy_model, n_mcts_enemy)]
     monitor = None
@@ -203,7 +211,13 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
                 if wins[i] != 0 or (max_plies and len(ids[i]) - 1 >= max_plies):
                     running[i] = False
         ply += 1
+    last_search_totals.clear()
     for sd in sides:
+        if isinstance(sd, _ZeroSide):                                # what early stop saved, over both sides (tools/time_early_stop.py)
+            ran = sd.eng.sims_run()
+            for k, v in (('searches', sd.searches), ('simulations', sd.searches * sd.sims), ('settled', ran['settled_total']),
+                         ('saved', ran['saved_total'])):
+                last_search_totals[k] = last_search_totals.get(k, 0) + int(v)
         sd.close()
     result = {'Player': 0, 'Enemy': 0, 'Draw': 0}
     games = []

@@ -96,12 +96,21 @@ class Evaluator:
         except Exception:
             return torch.device("cpu")
 
-    def search(self, eng, model, tau, active=None, on_sim=None):
-        """Returns (pi, visit, policy) float64 [G, A]."""
+    def search(self, eng, model, tau, active=None, on_sim=None, sims=None, noise=None, early_stop=None, settle_every=None):
+        """Returns (pi, visit, policy) float64 [G, A]. sims / noise / early_stop / settle_every: Engine.search, on both paths."""
         tau = np.ascontiguousarray(np.broadcast_to(tau, (eng.G,)), np.int8)
         net = model if hasattr(model, "forward_ptr") else self.native_net(model, eng.board_size, eng.inplanes)
         if net is not None:
-            return eng.search(net, tau=tau, active=active)
+            return eng.search(net, tau=tau, active=active, sims=sims, noise=noise, early_stop=early_stop, settle_every=settle_every)
+        if early_stop is True:
+            early_stop = tau == 0
+        elif early_stop is False:
+            early_stop = None
+        if settle_every is None:
+            from .engine import SETTLE_EVERY
+            settle_every = SETTLE_EVERY
+        if early_stop is not None and settle_every <= 0:
+            early_stop = None
         import torch
         dev = torch.device("cuda", self.device)
         G, C, B, A = eng.G, eng.inplanes, eng.board_size, eng.A
@@ -113,9 +122,11 @@ class Evaluator:
         mdev = self._model_device(model)
         if hasattr(model, "eval"):
             model.eval()
-        eng.begin_move(active)
+        eng.begin_move(active, sims=sims, noise=noise)
         i = 0
         while eng.sims_left() > 0:
+            if early_stop is not None and i > 0 and i % settle_every == 0 and eng.settle(early_stop) == 0:
+                break
             i += 1
             if on_sim is not None:
                 on_sim(i)

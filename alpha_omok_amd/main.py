@@ -101,13 +101,18 @@ last_train_losses = None     # losses of the pass train_join() finished last (se
 _pool = None                 # games in flight between self_play calls (carry-over mode only)
 _terminal_share = 0.0        # terminal leaves / simulations of the last search (drives ROWS = 'auto')
 _carry_auto = False          # run() with GAMES_PER_ITER set and CARRY_OVER None
+EARLY_STOP = False           # configure(early_stop=True): a tau == 0 search stops once its move is decided (utils.move_decided)
+FAST_SIMS = None             # configure(fast_sims=N): playout-cap randomisation -- every (episode, ply) is a full search (N_MCTS simulations, noise as
+FULL_PROB = 0.25             # configured, sample recorded; probability FULL_PROB) or a fast one (N simulations, no noise, move played, no sample)
+playout_totals = {'full': 0, 'fast': 0}   # move decisions of either kind since configure() (all of them 'full' without fast_sims)
 FP16_GRID = False            # configure(fp16_grid_weights=True): the 3x3 conv weights of Agent.model are kept on the fp16 grid (see _grid_sync)
 _grid_masters = []           # ... [(parameter, fp32 master copy)]: Adam moves the master, the module holds its projection
 
 
 def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_planes=None, seed=None,
               model=None, gpu=None, noise=True, device_replay=False, node_cap=None, strict=None, reproducible=False,
-              carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None):
+              carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None,
+              early_stop=False, fast_sims=None, full_prob=0.25):
     """Build `Agent`, `Agent.model` and `optimizer` (main.py:58-85). Call instead of editing constants.
     node_cap: expanded-node capacity of a game's tree arena (0 = 16*(n_mcts+1) where 40 % of the HBM
     holds that for all games, at least 4*(n_mcts+1); -1 = grow into the free HBM);
@@ -135,11 +140,26 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     grid -- after every optimiser step the module's weights are the fp16 rounding of an fp32 master copy that Adam moves (the
     gradient is taken at the rounded weights: straight-through). Such a network runs on the TWO-product split-fp16 kernels
     (ao_net_products: a third fewer MFMAs, the same fp32-equivalent contraction). The state_dict stays the reference's wire format:
-    plain fp32 tensors whose conv entries happen to be fp16 numbers."""
+    plain fp32 tensors whose conv entries happen to be fp16 numbers.
+    early_stop=True: self-play searches with tau == 0 (from ply TAU_THRES on) stop as soon as their move is decided
+    (utils.move_decided; Engine.search(early_stop=True)): same pi, same move, a smaller tree handed to the next ply (DESIGN.md
+    section 8).
+    fast_sims=N: playout-cap randomisation. Every (episode, ply) is a FULL search with probability full_prob -- n_mcts simulations,
+    noise as configured, sample recorded -- or a FAST one: N simulations, no noise, the move is played and no sample is recorded,
+    so cur_memory / rep_memory only ever see full searches. The choice is full_search(SEED, global episode number, ply): it does
+    not depend on the slot, the rank or MAX_CONCURRENT. playout_totals counts both kinds."""
     global BOARD_SIZE, N_MCTS, N_BLOCKS, IN_PLANES, OUT_PLANES, SEED, Agent, optimizer, device
     global _engine, _evaluator, _episodes_played, rep_memory, STRICT, NODE_CAP, CARRY_OVER, _pool, OVERSUBSCRIBE, ROWS, _terminal_share
-    global OVERLAP_TRAIN, FP16_GRID
+    global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB
     train_join()
+    if fast_sims is not None and not 1 <= int(fast_sims) <= int(n_mcts or N_MCTS):
+        raise ValueError("fast_sims must be in 1..n_mcts")
+    if not 0.0 <= float(full_prob) <= 1.0:
+        raise ValueError("full_prob must be in [0, 1]")
+    EARLY_STOP = bool(early_stop)
+    FAST_SIMS = None if fast_sims is None else int(fast_sims)
+    FULL_PROB = float(full_prob)
+    playout_totals['full'] = playout_totals['fast'] = 0
     if fp16_grid_weights is not None:
         FP16_GRID = bool(fp16_grid_weights)
     if overlap_train is not None:
@@ -308,7 +328,47 @@ def _check_trim(eng):
         logging.warning(msg)
 
 
-def _check_visits(eng, vis, act, on, inherit, fp16_seen):
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x):
+    """splitmix64's output function on uint64 arrays (Steele, Lea, Flood 2014): a bijection of the 64-bit words."""
+    x = np.asarray(x, np.uint64)
+    with np.errstate(over='ignore'):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def full_search(seed, episode, ply, full_prob=None):
+    """Playout-cap randomisation: is the search at `ply` of global episode number `episode` a full one? A counter-based hash,
+    a fixed function of (seed, episode, ply) -- no stream of the engine, no np.random, nothing about slots, ranks or
+    MAX_CONCURRENT: u = top 53 bits of mix(mix(mix(seed) ^ episode) ^ ply) / 2^53, full iff u < full_prob. episode and ply may
+    be arrays (broadcast); returns a bool array of their shape."""
+    p = FULL_PROB if full_prob is None else float(full_prob)
+    e = np.asarray(episode, np.int64).astype(np.uint64)
+    q = np.asarray(ply, np.int64).astype(np.uint64)
+    h = _mix64(_mix64(_mix64(np.uint64(int(seed) & _M64)) ^ e) ^ q)
+    return (h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53 < p
+
+
+def _search_opts(eng, gids, ply, tau):
+    """What this ply's search adds to the plain one (Evaluator.search keywords) and which games record a sample (bool [G];
+    None: all). gids: global episode number per slot (anything for inactive slots)."""
+    opts = {}
+    full = None
+    if FAST_SIMS is not None:
+        full = full_search(SEED, np.maximum(gids, 0), ply)
+        opts['sims'] = np.where(full, N_MCTS, FAST_SIMS).astype(np.int32)
+        if Agent.noise:
+            opts['noise'] = full.astype(np.uint8)
+    if EARLY_STOP:
+        opts['early_stop'] = True
+    return opts, full
+
+
+def _check_visits(eng, vis, act, on, inherit, fp16_seen, sims=None):
     """configure(strict=True): every search ran ALL its simulations (agents.py:105-132) -- visit.sum() is N_MCTS for a fresh root
     and inherited + N_MCTS for a root that was a child of the last one (the child was expanded by the first
     of its n visits, so it brings n - 1). The C side already refuses to end a move that is short (ERR_SHORT); this is the same
@@ -318,19 +378,22 @@ def _check_visits(eng, vis, act, on, inherit, fp16_seen):
     if fp16_seen is None:
         fp16_seen = ev
     got = vis[on].sum(axis=1)
-    want = (inherit[on] if ev == fp16_seen else 0) + N_MCTS
+    # (sims: the simulations each game ran when the move had budgets of its own or could stop early -- never more than asked for)
+    ran = N_MCTS if sims is None else np.asarray(sims)[on]
+    want = (inherit[on] if ev == fp16_seen else 0) + ran
     if not np.array_equal(got, want):
         bad = np.flatnonzero(got != want)
         g = int(on[bad[0]])
         from .engine import EngineError
         raise EngineError("self-play: the search of game slot %d returned %d visits, %d expected (%d inherited + %d simulations); "
                           "%d of %d searches of this ply are off" % (g, int(got[bad[0]]), int(np.broadcast_to(want, got.shape)[bad[0]]),
-                                                                     int(inherit[g]) if ev == fp16_seen else 0, N_MCTS, bad.size, on.size))
+                                                                     int(inherit[g]) if ev == fp16_seen else 0,
+                                                                     int(np.broadcast_to(ran, got.shape)[bad[0]]), bad.size, on.size))
     inherit[on] = np.maximum(vis[on, act[on]] - 1, 0)
     return ev
 
 
-def _play_episodes(episodes, use_global, seed_of):
+def _play_episodes(episodes, use_global, seed_of, first_episode=0):
     """Plays the listed episodes on one engine (G = min(len, MAX_CONCURRENT) slots, finished slots refilled).
     Returns (moves [E, A] int32 (-1 padded), lengths [E], wins [E], ep_of [N], ply_of [N], pis [N, A] float64):
     E = len(episodes), rows in the order of `episodes`; the N = sum(lengths) samples sorted by (row, ply), sample i
@@ -366,7 +429,9 @@ def _play_episodes(episodes, use_global, seed_of):
         tau = (ply < TAU_THRES).astype(np.int8)           # main.py:150-153
         t_search = time.perf_counter()
         _set_rows(eng)
-        pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=active)
+        gids = first_episode + np.asarray(episodes, np.int64)[np.maximum(slot_row, 0)]
+        opts, full = _search_opts(eng, gids, ply, tau)
+        pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=active, **opts)
         _count_search(eng)
         act, win = eng.play()                             # utils.get_action + env.step
         if trace is not None:
@@ -374,9 +439,12 @@ def _play_episodes(episodes, use_global, seed_of):
         on = np.flatnonzero(active)
         if STRICT:
             _check_trim(eng)                              # (a trimmed re-rooting is reported as what it is, not as a visit mismatch)
-            fp16_seen = _check_visits(eng, vis, act, on, inherit, fp16_seen)
+            fp16_seen = _check_visits(eng, vis, act, on, inherit, fp16_seen, _sims_ran(eng, opts))
         rows = slot_row[on]
-        hist.append((rows, ply[on].copy(), pi[on]))
+        rec = on if full is None else on[full[on]]        # (a fast search plays its move and leaves no sample)
+        hist.append((slot_row[rec], ply[rec].copy(), pi[rec]))
+        playout_totals['full'] += int(rec.size)
+        playout_totals['fast'] += int(on.size - rec.size)
         moves[rows, ply[on]] = act[on]
         ply[on] += 1
         done = on[win[on] != 0]
@@ -411,6 +479,21 @@ def _play_episodes(episodes, use_global, seed_of):
     pis = np.concatenate([h[2] for h in hist])
     order = np.lexsort((plies, rows))
     return moves, lengths, wins, rows[order], plies[order], pis[order]
+
+
+def _sims_ran(eng, opts):
+    """strict mode: the simulations each game of the last search ran -- None (N_MCTS) for a plain search, the budgets of the move, or
+    what the engine reports when games could stop early (checked against the budgets: never more than asked for)."""
+    if not opts:
+        return None
+    budget = np.broadcast_to(opts.get('sims', N_MCTS), (eng.G,))
+    if 'early_stop' not in opts:
+        return budget
+    ran = eng.sims_run()['sims']
+    if (ran > budget).any():
+        from .engine import EngineError
+        raise EngineError("self-play: a search ran more simulations than its budget")
+    return ran
 
 
 class _CarryPool:
@@ -503,7 +586,8 @@ def _play_carry(first_episode, n_call, rank, world):
         tau = (pool.ply < TAU_THRES).astype(np.int8)      # main.py:150-153
         t_search = time.perf_counter()
         _set_rows(eng)
-        pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=pool.active)
+        opts, full = _search_opts(eng, pool.slot_id, pool.ply, tau)
+        pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=pool.active, **opts)
         _count_search(eng)
         act, win = eng.play()
         if trace is not None:
@@ -511,8 +595,11 @@ def _play_carry(first_episode, n_call, rank, world):
         on = np.flatnonzero(pool.active)
         if STRICT:
             _check_trim(eng)
-            pool.fp16_seen = _check_visits(eng, vis, act, on, pool.inherit, pool.fp16_seen)
-        pool.hist.append((pool.slot_id[on].copy(), pool.ply[on].copy(), pi[on]))
+            pool.fp16_seen = _check_visits(eng, vis, act, on, pool.inherit, pool.fp16_seen, _sims_ran(eng, opts))
+        rec = on if full is None else on[full[on]]        # (a fast search plays its move and leaves no sample)
+        pool.hist.append((pool.slot_id[rec].copy(), pool.ply[rec].copy(), pi[rec]))
+        playout_totals['full'] += int(rec.size)
+        playout_totals['fast'] += int(on.size - rec.size)
         pool.slot_moves[on, pool.ply[on]] = act[on]
         pool.ply[on] += 1
         done = on[win[on] != 0]
@@ -577,7 +664,7 @@ def self_play(n_selfplay, seeds=None, single_stream=False):
     t_play = time.perf_counter()
     try:
         if single_stream or (n_selfplay == 1 and seeds is None and world == 1):
-            parts = [_play_episodes([ep], True, seed_of) for ep in episodes]   # sequential, each on the global stream where the last left it
+            parts = [_play_episodes([ep], True, seed_of, first_episode) for ep in episodes]   # sequential, each on the global stream where the last left it
             moves = np.concatenate([p[0] for p in parts])
             lengths = np.concatenate([p[1] for p in parts])
             wins = np.concatenate([p[2] for p in parts])
@@ -590,7 +677,7 @@ def self_play(n_selfplay, seeds=None, single_stream=False):
                                  "an explicit seeds= list cannot be honoured")
             moves, lengths, wins, ep_of, ply_of, pis = _play_carry(first_episode, n_selfplay, rank, world)
         else:
-            moves, lengths, wins, ep_of, ply_of, pis = _play_episodes(episodes, False, seed_of)
+            moves, lengths, wins, ep_of, ply_of, pis = _play_episodes(episodes, False, seed_of, first_episode)
     except BaseException:
         # a call that did not deliver (TreeTrimmed under strict=True, an engine error, Ctrl-C) leaves nothing behind:
         # the episode numbering is where it was -- a retry plays the same episodes with the same seeds -- and the
@@ -631,7 +718,7 @@ def self_play(n_selfplay, seeds=None, single_stream=False):
         Agent.reset()
         rep_memory.extend_augmented_moves(moves, ep_of, ply_of, pis, z)
         phase_seconds['emit'] += time.perf_counter() - t_emit
-        return dict(episodes=len(episodes), moves=n_new, **trim_stats)
+        return _summary(len(episodes), n_new, lengths)
     states = utils.states_of_episodes(moves, ep_of, ply_of, BOARD_SIZE, IN_PLANES)
     n_new = states.shape[0]
     zl = z.tolist()
@@ -648,7 +735,15 @@ def self_play(n_selfplay, seeds=None, single_stream=False):
         tail = [(states[i], pis[i], zl[i]) for i in range(n_new - keep, n_new)]
         rep_memory.extend(utils.augment_dataset(tail, BOARD_SIZE))
     phase_seconds['emit'] += time.perf_counter() - t_emit
-    return dict(episodes=len(episodes), moves=int(n_new), **trim_stats)
+    return _summary(len(episodes), n_new, lengths)
+
+
+def _summary(n_episodes, n_samples, lengths):
+    """self_play's return value: `moves` counts every move decision of the call's episodes. With fast_sims only the full searches
+    leave a sample: `samples` tells them apart (without it every move decision is a sample)."""
+    if FAST_SIMS is None:
+        return dict(episodes=n_episodes, moves=int(n_samples), **trim_stats)
+    return dict(episodes=n_episodes, moves=int(np.sum(lengths)), samples=int(n_samples), **trim_stats)
 
 
 def train_batch(batch, total=None):

@@ -613,6 +613,18 @@ def argmax_onehot(pi):
     return onehot, idx
 
 
+def move_decided(visits, remaining):
+    """Is the most-visited move of a search already certain? visits: the root children's visit counts (any shape, e.g. the [A]
+    visit vector of get_pi), remaining: simulations the search still owes. Every simulation adds exactly one visit to exactly
+    one root child, so with n1 >= n2 the two largest counts (n2 = 0 with fewer than two entries) the leader cannot be caught,
+    or even tied, iff n1 - n2 > remaining: argmax_onehot of the finished search then picks it without a draw among equals.
+    No reference counterpart (the reference always runs num_mcts simulations); the device rule of k_settle is this one."""
+    v = np.sort(np.asarray(visits).reshape(-1))
+    n1 = int(v[-1]) if v.size >= 1 else 0
+    n2 = int(v[-2]) if v.size >= 2 else 0
+    return n1 - n2 > int(remaining)
+
+
 def augment_dataset(memory, board_size):
     """8 symmetries per sample in the reference's order r0, r0f, r1, r1f, ... (utils.py:226-239)."""
     out = []

@@ -100,7 +100,30 @@ int ao_set_roots(ao_engine *e, const uint8_t *host_mask, const int32_t *host_mov
  *     ao_apply_evals } -> ao_end_move
  * active[g] == 0 leaves game g untouched for this move (NULL = all games active). */
 int ao_begin_move(ao_engine *e, const uint8_t *host_active);
+/* ao_begin_move with a budget and a noise switch per game (no reference counterpart). host_sims int32 [G]: simulations of
+ * game g in this move, 1 .. ao_config.sims (the arena, the descent bounds and the catch-up loop were sized by it); a fresh
+ * root still gets one more, its own expansion. A game's search is strictly sequential, so a budget-k search is the first k
+ * simulations of the full one from the same stream. host_noise uint8 [G]: 0 on an engine created with noise means that
+ * for this game and this move there is no Dirichlet draw, the root is not re-noised and the game's MT19937 stream is not
+ * touched -- what an engine created without noise does; 1 on an engine created without noise is an error. NULL = the
+ * engine's configuration, for either array. A value out of range is an error that names the game; nothing has been
+ * changed by then and the engine stays usable. Values of inactive games are not looked at. */
+int ao_begin_move_opts(ao_engine *e, const uint8_t *host_active, const int32_t *host_sims, const uint8_t *host_noise);
+/* Launches the step-wise protocol still has to run: the largest number of simulations any active game owes. Lowered by
+ * ao_settle. */
 int ao_sims_left(ao_engine *e);
+/* Settling: lower the simulation targets of games whose move is decided, or of every masked game at once. Legal between
+ * ao_begin_move and ao_end_move only. For an active game let r = target - done be the simulations it owes, pending = 1 if
+ * a leaf was selected (ao_collect_leaves) and not yet backed up (ao_apply_evals), and n1 >= n2 the two largest visit
+ * counts among the root's children (n2 = 0 with one child). The game is DECIDED iff its root is expanded and
+ * n1 - n2 > r -- utils.move_decided(visits, remaining) in the Python package is this rule: every owed simulation adds one
+ * visit to one root child, so the leader stays the only maximum and ao_end_move's tau == 0 result is the full search's.
+ * A game with host_mask[g] != 0 (NULL = every game) that is decided, or any such game when stop_now != 0, gets
+ * target = done + pending: the pending leaf is still backed up, nothing else runs. Finished, inactive and unmasked games
+ * are left alone. Synchronises; ao_sims_left then reports the largest number still owed and *unfinished (may be NULL) the
+ * number of active games that owe anything. stop_now is how a caller ends a move early and still gets a pi from
+ * ao_end_move (see there); a game stopped before its root has a visit returns numpy's 0/0 = NaN there. */
+int ao_settle(ao_engine *e, const uint8_t *host_mask, int stop_now, int32_t *unfinished);
 /* _selection (agents.py:134-168) for every game with simulations left, + get_state_pt of the
  * leaf (utils.py:139-168). dev_planes_nchw: optional float32 [G][C][B][B] (the layout
  * Agent.model expects, agents.py:175); NULL if only the engine's own network is used. */
@@ -111,7 +134,12 @@ int ao_collect_leaves(ao_engine *e, float *dev_planes_nchw);
 int ao_apply_evals(ao_engine *e, const float *dev_policy, const float *dev_value);
 /* Tail of get_pi (agents.py:64-80): visit, policy (post-noise priors of the root children) and
  * pi = visit/visit.sum(), one-hot through utils.argmax_onehot where tau[g] == 0.
- * Outputs are host float64 [G][A]; any may be NULL. host_tau int8 [G] (NULL = all 1). */
+ * Outputs are host float64 [G][A]; any may be NULL. host_tau int8 [G] (NULL = all 1).
+ * Precondition: every active game has run exactly its target (done == target). A game that is short -- a caller that
+ * ends the move early -- makes the call fail with "search ended after d of t simulations" (no pi is built from fewer
+ * visits than asked for, the game's stream is not touched) and ends the move. The way to stop early is ao_settle with
+ * stop_now: it lowers the targets to what has been run. After a failed call the visits made so far stay in the tree: a
+ * retried move (ao_begin_move again) searches on top of them. */
 int ao_end_move(ao_engine *e, const int8_t *host_tau, double *host_pi, double *host_visit,
                 double *host_policy);
 /* utils.get_action (utils.py:189-195) on game g's stream + env step (env_small.py:154-176,196)
@@ -125,6 +153,22 @@ int ao_play(ao_engine *e, int32_t *host_action, int32_t *host_win);
  * end_move. */
 int ao_search(ao_engine *e, ao_net *net, const uint8_t *host_active, const int8_t *host_tau,
               double *host_pi, double *host_visit, double *host_policy);
+/* ao_search with the per-game budgets and noise switches of ao_begin_move_opts (host_sims, host_noise; NULL = the engine's
+ * configuration) and with settling: every settle_every simulations, and in every catch-up round of an over-subscribed
+ * search, the games with host_early_stop[g] != 0 whose move is decided (ao_settle's rule) get their targets lowered, the
+ * loop reads four counters back (a stream synchronisation) and goes on with the largest number of simulations still owed,
+ * or ends. host_early_stop NULL or settle_every 0: nothing is launched or read, the loop is ao_search's. The budgets hold
+ * in every regime of the search (the fused few-game step, rows packed per move, rows handed out per simulation) and for
+ * the move that the fp16-range recovery repeats. An early-stopped search returns the pi and the move of the full one for
+ * tau == 0 games and hands a smaller tree to the next move. */
+int ao_search_opts(ao_engine *e, ao_net *net, const uint8_t *host_active, const int8_t *host_tau, const int32_t *host_sims,
+                   const uint8_t *host_noise, const uint8_t *host_early_stop, int32_t settle_every, double *host_pi,
+                   double *host_visit, double *host_policy);
+/* The last move of the engine (either protocol), readable until the next one begins: host_sims_run int32 [G] simulations
+ * run per game in budget units (a fresh root's own expansion not counted; 0 for inactive games), host_settled uint8 [G]
+ * 1 where settling lowered the game's target; and the engine's running totals of games settled and simulations saved.
+ * Any pointer may be NULL. */
+int ao_search_sims(ao_engine *e, int32_t *host_sims_run, uint8_t *host_settled, int64_t *settled_total, int64_t *saved_total);
 
 /* ---- introspection (tests, get_visit/get_policy, del_parents prints) ---- */
 int ao_get_moves(ao_engine *e, int game, int32_t *host_moves /*[A]*/, int32_t *n);

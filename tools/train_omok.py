@@ -75,6 +75,13 @@ def main():
                     help="keep the 3x3 conv weights on the fp16 grid (main.configure(fp16_grid_weights=True): fp32 master copies in Adam, the module holds "
                          "their fp16 rounding) -- such a network runs on the two-product split-fp16 kernels (ao_net_products); the checkpoint stays a "
                          "plain fp32 state_dict the reference loads")
+    ap.add_argument("--early-stop", action="store_true",
+                    help="self-play searches with tau == 0 stop once their move is decided (main.configure(early_stop=True)): same pi and move, "
+                         "fewer simulations, smaller trees handed on")
+    ap.add_argument("--fast-sims", type=int, default=None, metavar="N",
+                    help="playout-cap randomisation (main.configure(fast_sims=N)): a ply is searched fully (--sims, noise, sample recorded) with "
+                         "probability --full-prob, else with N simulations, no noise and no sample")
+    ap.add_argument("--full-prob", type=float, default=0.25)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--resume", default=None, help="state_dict to start from")
     ap.add_argument("--save-replay", default=None, metavar="PATH",
@@ -109,7 +116,7 @@ def main():
         m.MAX_CONCURRENT = a.rows_per_sim
     m.configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, out_planes=a.planes, seed=a.seed,
                 device_replay=True, carry_over=not a.no_carry_over, oversubscribe=a.oversubscribe, rows=a.rows,
-                fp16_grid_weights=a.fp16_grid_weights)
+                fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob)
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
