@@ -82,6 +82,8 @@ SYMBOLS = {
     "ao_settle": (C.c_int, [_vp, _u8p, C.c_int, _i32p]),
     "ao_search_opts": (C.c_int, [_vp, _vp, _u8p, _i8p, _i32p, _u8p, _u8p, C.c_int32, _f64p, _f64p, _f64p]),
     "ao_search_sims": (C.c_int, [_vp, _i32p, _u8p, _i64p, _i64p]),
+    "ao_set_root_bar": (C.c_int, [_vp, _u8p]),
+    "ao_root_tactics": (C.c_int, [_vp, _u8p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _u8p, _i32p, _i32p]),
     "ao_collect_leaves": (C.c_int, [_vp, _vp]),
     "ao_apply_evals": (C.c_int, [_vp, _vp, _vp]),
     "ao_end_move": (C.c_int, [_vp, _i8p, _f64p, _f64p, _f64p]),

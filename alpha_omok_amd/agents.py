@@ -123,11 +123,23 @@ class ZeroAgent(Agent):
         if self._engine is not None:
             self._engine.reset()
 
-    def get_pi(self, root_id, tau, sims=None, early_stop=False):
+    def get_pi(self, root_id, tau, sims=None, early_stop=False, allowed=None, tactics=None):
         """sims: simulations of THIS move (1..num_mcts; None: num_mcts); early_stop=True: a tau == 0 search ends once its move is
-        decided (utils.move_decided) -- same pi and move, fewer visits in the tree the next move inherits."""
+        decided (utils.move_decided) -- same pi and move, fewer visits in the tree the next move inherits. allowed: the cells
+        that may be searched at the root, a bool [A] or a list of cells (Engine.search); tactics: True or dict(max_depth,
+        max_nodes, solved_sims) -- the forced-win solver restricts the root first (a proven win: the winning first moves; a
+        proven threat: the replies not proven to lose); last_tactics tells what it said."""
         start = time.time()
         eng = self._eng()
+        if allowed is not None:
+            a = np.asarray(allowed)
+            if a.dtype != bool or a.shape != (self.board_size ** 2,):
+                cells = np.asarray(list(allowed), np.int64).reshape(-1)
+                if cells.size and (cells.min() < 0 or cells.max() >= self.board_size ** 2):
+                    raise ValueError("allowed: a cell is off the board")
+                a = np.zeros(self.board_size ** 2, bool)
+                a[cells] = True
+            allowed = a.reshape(1, -1)
         st = np.random.get_state()                      # the reference's global stream
         eng.set_rng_state(0, st[1], st[2], st[3], st[4])
         status = eng.set_root(0, list(root_id)[1:])
@@ -138,7 +150,8 @@ class ZeroAgent(Agent):
             self.message = 'simulation: {}\r'.format(i)
 
         pi, visit, policy = self._evaluator.search(eng, self.model, tau, on_sim=progress, sims=sims,
-                                                   early_stop=True if early_stop else None)
+                                                   early_stop=True if early_stop else None, allowed=allowed, tactics=tactics)
+        self.last_tactics = eng.last_tactics()
         mt, pos, has_gauss, gauss = eng.get_rng_state(0)
         np.random.set_state(('MT19937', mt, pos, has_gauss, gauss))
         self.message = 'simulation: {}\r'.format(num)
@@ -242,6 +255,19 @@ class ZeroAgent(Agent):
         B = self.board_size
         reply = d["reply"][0].reshape(B, B)
         return int(d["threat"][0]), int(d["threat_depth"][0]), reply == FD_SAFE, reply == FD_LOSES
+
+    def get_root_tactics(self, root_id, max_depth=6, max_nodes=512):
+        """What the forced-win solver says about searching the position of `root_id` (Engine.root_tactics, utils.root_tactics
+        is the definition): (verdict, depth, allowed bool [B, B], nodes, unknown) -- verdict RT_WIN a forced win for the side
+        to move (allowed: its winning first moves), RT_DEFEND / RT_LOST the opponent threatens one (allowed: the replies not
+        proven to lose / every empty cell when all lose), RT_NONE nothing proven. The agent's root moves to `root_id`, as in
+        get_pi. ValueError for limits outside 1..16 / 1..65536."""
+        eng = self._eng()
+        eng.set_root(0, list(root_id)[1:])
+        self.root_id = tuple(root_id)
+        r = eng.root_tactics(max_depth=max_depth, max_nodes=max_nodes)
+        B = self.board_size
+        return int(r["verdict"][0]), int(r["depth"][0]), r["allowed"][0].reshape(B, B), int(r["nodes"][0]), int(r["unknown"][0])
 
     def get_pv_batch(self, root_ids):
         """get_pv for many ids in one call (PositionBatch.evaluate): (policy float32 [n, A], value float32 [n],

@@ -43,6 +43,8 @@ void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int 
                         int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
 void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s);
 int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s);
+// positions.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
+void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s);
 // net.hip
 int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, float* value,
                    hipStream_t s, int in_kind, int parts, const unsigned* live, unsigned row_cap);
@@ -108,6 +110,21 @@ struct ao_engine : ao::HandleBase {
     int32_t* d_settle = nullptr;     // [4] k_settle's counters of one launch
     int32_t* h_settle = nullptr;     // pinned [4]
     int64_t settled_total = 0, saved_total = 0;
+    // the root bar (ao_set_root_bar, ao_root_tactics with apply): what the NEXT ao_begin_move* / ao_search* is restricted to.
+    // Either the caller's masks on the host (bar_allowed / bar_has), turned into bitboards and uploaded by begin_move_impl, or
+    // bitboards that ao_root_tactics left in d_bar (bar_on_device). begin_move_impl consumes it; `used_*` is what the current
+    // move consumed, for the move the fp16-range recovery repeats.
+    uint64_t* d_bar = nullptr;              // [G][kBBWords] barred actions of the current move
+    std::vector<uint64_t> h_bar;            // staging of d_bar
+    std::vector<uint8_t> bar_allowed;       // [G][A] the caller's masks
+    std::vector<uint8_t> bar_has;           // [G] 1 where the game has a row in bar_allowed
+    bool bar_pending = false;               // some bar_has is set
+    bool bar_on_device = false;             // d_bar holds the next move's bar
+    bool bar_dirty = false;                 // a root may hold kBarQ children: the next move passes the bar array (zeros, if no game
+                                            // is barred) so that k_begin_move turns them back into unvisited children
+    std::vector<uint8_t> used_allowed, used_has;
+    bool used_pending = false, used_on_device = false;
+    bool bar_keep = false;                  // the fp16-range recovery resets its games and sets their roots again: the bar stays
     // fp16-range recovery of ao_search: the games' MT19937 states as they were before the move (device copy), the host
     // half of the stream (legacy gauss cache), the number of recovered moves and of games searched again
     uint32_t* d_mt_backup = nullptr; int32_t* d_pos_backup = nullptr;
@@ -276,6 +293,10 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
     if (e->pool.alloc(e, &e->d_live, ao_engine::kLive) || e->pool.alloc(e, &e->d_log_games, G) || e->pool.alloc(e, &e->d_ctl, 8) || e->pool.alloc(e, &e->d_order, G)) return 1;
     if (e->pool.alloc(e, &e->d_settled, G) || e->pool.alloc(e, &e->d_early, G) || e->pool.alloc(e, &e->d_settle, 4)) return 1;
     AO_HIP(e, hipMemsetAsync(e->d_settled, 0, G, e->stream));
+    if (e->pool.alloc(e, &e->d_bar, static_cast<size_t>(G) * ao::kBBWords)) return 1;
+    e->h_bar.assign(static_cast<size_t>(G) * ao::kBBWords, 0);
+    e->bar_has.assign(G, 0);
+    p.bar = nullptr;
     e->order_on = !(getenv("AO_TREE_ORDER") && atoi(getenv("AO_TREE_ORDER")) == 0);
     p.order = nullptr;
     AO_HIP(e, hipMemsetAsync(e->d_row, 0, sizeof(int32_t) * 2 * G, e->stream));
@@ -406,9 +427,67 @@ int ao_seed_all(ao_engine* e, const uint32_t* seeds) {
     return 0;
 }
 
+// ---- the root bar ----------------------------------------------------------------------------
+// The pending bar of the masked games (null: all) is dropped: their position changes (ao_play, ao_reset, ao_set_root(s)).
+static int bar_forget(ao_engine* e, const uint8_t* mask) {
+    if (e->bar_keep || (!e->bar_pending && !e->bar_on_device)) return 0;
+    bool left = false;
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    for (int g = 0; g < e->G; ++g) {
+        if (!mask || mask[g]) {
+            e->bar_has[g] = 0;
+            if (e->bar_on_device)
+                AO_HIP(e, hipMemsetAsync(e->d_bar + static_cast<size_t>(g) * ao::kBBWords, 0, sizeof(uint64_t) * ao::kBBWords, e->stream));
+        }
+        left = left || e->bar_has[g];
+    }
+    e->bar_pending = left;
+    if (!mask) e->bar_on_device = false;
+    return 0;
+}
+
+// The pending masks as bitboards of barred actions in h_bar, for the games of `act` [G]: the empty cells of a game that its row
+// does not allow (ones on stones are ignored). A row that allows none of its game's empty cells is an error that names the game;
+// *any: some game is barred from some cell.
+static int bar_build(ao_engine* e, const std::vector<uint8_t>& act, bool* any, const char* who) {
+    const int G = e->G, A = e->A;
+    *any = false;
+    std::fill(e->h_bar.begin(), e->h_bar.end(), 0ull);
+    if (!e->bar_pending) return 0;
+    std::vector<uint8_t> stone(A);
+    for (int g = 0; g < G; ++g) {
+        if (!act[g] || !e->bar_has[g]) continue;
+        std::fill(stone.begin(), stone.end(), 0);
+        for (int32_t m : e->moves[g]) stone[m] = 1;
+        const uint8_t* row = e->bar_allowed.data() + static_cast<size_t>(g) * A;
+        uint64_t* bits = e->h_bar.data() + static_cast<size_t>(g) * ao::kBBWords;
+        int open = 0, barred = 0;
+        for (int a = 0; a < A; ++a) {
+            if (stone[a]) continue;
+            if (row[a]) { ++open; continue; }
+            bits[a >> 6] |= 1ull << (a & 63);
+            ++barred;
+        }
+        if (open == 0 && barred > 0)
+            return e->fail(std::string(who) + ": game " + std::to_string(g) + ": the root bar allows no empty cell of the position");
+        *any = *any || barred > 0;
+    }
+    return 0;
+}
+
+int ao_set_root_bar(ao_engine* e, const uint8_t* allowed) {
+    if (e->in_move) return e->fail("ao_set_root_bar inside a move (between ao_begin_move and ao_end_move)");
+    e->bar_on_device = false;
+    std::fill(e->bar_has.begin(), e->bar_has.end(), allowed ? 1 : 0);
+    e->bar_pending = allowed != nullptr;
+    if (allowed) e->bar_allowed.assign(allowed, allowed + static_cast<size_t>(e->G) * e->A);
+    return 0;
+}
+
 // ---- game / tree state -----------------------------------------------------------------------
 int ao_reset(ao_engine* e, const uint8_t* mask) {
     AO_HIP(e, hipSetDevice(e->cfg.device));
+    if (bar_forget(e, mask)) return 1;
     const uint8_t* dmask = nullptr;
     if (mask) {
         AO_HIP(e, hipMemcpyAsync(e->d_mask, mask, e->G, hipMemcpyHostToDevice, e->stream));
@@ -445,6 +524,7 @@ static int set_roots_impl(ao_engine* e, int count, const int32_t* games, const i
         seen[games[k]] = 1;
         if (ns[k] < 0 || ns[k] > A) return e->fail("move list too long");
     }
+    if (bar_forget(e, seen.data())) return 1;
     // staging: [count][A] new moves, then games / counts / prev_known (device reads), then status (device writes)
     e->h_walk.assign(static_cast<size_t>(count) * A + 4 * static_cast<size_t>(count), 0);
     int32_t* h_extra = e->h_walk.data();
@@ -548,6 +628,26 @@ static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* s
         if (noise && noise[g] && !p.noise)
             return e->fail("ao_begin_move_opts: game " + std::to_string(g) + ": noise asked for on an engine created without noise");
     }
+    // the bar of this move: bitboards that ao_root_tactics left on the device, or the caller's masks (ao_set_root_bar) built here
+    const bool bar_dev = e->bar_on_device;
+    bool bar_any = false;
+    if (!bar_dev && e->bar_pending) {
+        std::vector<uint8_t> act(G);
+        for (int g = 0; g < G; ++g) act[g] = (active ? active[g] : 1) && !e->over[g];
+        if (bar_build(e, act, &bar_any, "ao_begin_move")) return 1;
+    }
+    const bool bar_pass = bar_dev || bar_any || e->bar_dirty;   // (with none of them the launches are those of an engine without bars)
+    if (bar_pass && !bar_dev) {
+        if (!bar_any) std::fill(e->h_bar.begin(), e->h_bar.end(), 0ull);
+        AO_HIP(e, hipMemcpyAsync(e->d_bar, e->h_bar.data(), sizeof(uint64_t) * e->h_bar.size(), hipMemcpyHostToDevice, e->stream));
+    }
+    p.bar = bar_pass ? e->d_bar : nullptr;
+    e->bar_dirty = bar_dev || bar_any;
+    // consumed: the bar is valid for one move (the fp16-range recovery puts `used_*` back for the move it repeats)
+    e->used_pending = e->bar_pending; e->used_on_device = bar_dev;
+    if (e->bar_pending) { e->used_allowed = e->bar_allowed; e->used_has = e->bar_has; }
+    e->bar_pending = false; e->bar_on_device = false;
+    std::fill(e->bar_has.begin(), e->bar_has.end(), 0);
     int32_t* target = e->h_i32;
     int32_t* flags = e->h_i32 + G;
     int maxt = 0;
@@ -759,6 +859,7 @@ int ao_play(ao_engine* e, int32_t* action, int32_t* win) {
     if (!e->ended) return e->fail("ao_play must follow ao_end_move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const int G = e->G;
+    if (bar_forget(e, e->active.data())) return 1;
     if (ao::launch_play(e->tp, e->stream)) return queue_refused(e, "ao_play");
     int32_t* ha = e->h_i32;
     int32_t* hw = e->h_i32 + G;
@@ -1106,8 +1207,14 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
         AO_HIP(e, hipMemcpyAsync(e->tp.mtpos, e->d_pos_backup, sizeof(int32_t) * G, hipMemcpyDeviceToDevice, e->stream));
         e->has_gauss = e->has_gauss_backup;
         e->gauss = e->gauss_backup;
-        if (ao_reset(e, mask.data())) return 1;
-        if (set_roots_impl(e, static_cast<int>(games.size()), games.data(), ids.data(), ns.data(), nullptr)) return 1;
+        // the repeated move is searched under the bar of the first attempt: what begin_move_impl consumed is pending again (the
+        // bitboards of an on-device bar are still in d_bar; k_begin_move only reads them), and resetting the games does not drop it
+        e->bar_pending = e->used_pending; e->bar_on_device = e->used_on_device;
+        if (e->used_pending) { e->bar_allowed = e->used_allowed; e->bar_has = e->used_has; }
+        e->bar_keep = true;
+        const int rc_reset = ao_reset(e, mask.data()) || set_roots_impl(e, static_cast<int>(games.size()), games.data(), ids.data(), ns.data(), nullptr);
+        e->bar_keep = false;
+        if (rc_reset) return 1;
         ao::net_fp16_fallback_begin(net);                // mode 2 for the repeated move
         ++e->fp16_events;
         e->fp16_games_redone += static_cast<int64_t>(games.size());
@@ -1386,6 +1493,52 @@ int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
     return 0;
 }
 
+// ---- the forced-win solver on the engine's own roots (positions.hip) ----------------------------
+// utils.root_tactics of every active game's root position, read where it lives (TreeParams::rootpos): no move list goes to
+// the device. apply: the bar of the next move is left on the device -- the caller's pending masks (ao_set_root_bar)
+// intersected with what the solver allows, game by game; a game whose intersection would be empty keeps the caller's.
+int ao_root_tactics(ao_engine* e, const uint8_t* active, int32_t max_depth, int32_t max_nodes, int32_t apply, int32_t* verdict,
+                    int32_t* depth, uint8_t* allowed, int32_t* nodes, int32_t* unknown) {
+    if (e->in_move) return e->fail("ao_root_tactics inside a move (between ao_begin_move and ao_end_move)");
+    if (max_depth < 1 || max_depth > 16) return e->fail("ao_root_tactics: max_depth must be in 1..16");
+    if (max_nodes < 1 || max_nodes > 65536) return e->fail("ao_root_tactics: max_nodes must be in 1..65536");
+    if (e->tp.win_mark < 3 || e->tp.win_mark > 5 || e->tp.win_mark > e->cfg.board)
+        return e->fail("ao_root_tactics: the solver needs win_mark in 3..5 and at most the board size");
+    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A);
+    std::vector<uint8_t> act(G);
+    for (size_t g = 0; g < G; ++g) act[g] = (active ? active[g] : 1) && !e->over[g];
+    bool bar_any = false;
+    if (apply && bar_build(e, act, &bar_any, "ao_root_tactics")) return 1;   // (before any device call)
+    const size_t at_stage = G * ao::kBBWords * 8, at_pair = at_stage + G * 8, at_out = at_pair + G * A * 4;
+    const size_t out_bytes = G * 16 + G * A, at_mask = at_out + out_bytes;
+    if (readout_begin(e, "ao_root_tactics", at_mask + G)) return 1;
+    ao::RootTacticsBufs b{};
+    b.won = reinterpret_cast<uint64_t*>(e->d_ro.p);
+    b.stage = reinterpret_cast<uint32_t*>(e->d_ro.p + at_stage);
+    b.pair = reinterpret_cast<uint32_t*>(e->d_ro.p + at_pair);
+    b.verdict = reinterpret_cast<int32_t*>(e->d_ro.p + at_out);
+    b.depth = b.verdict + G; b.nodes = b.depth + G; b.unknown = b.nodes + G;
+    b.allowed = e->d_ro.p + at_out + G * 16;
+    uint8_t* d_act = e->d_ro.p + at_mask;
+    AO_HIP(e, hipMemcpyAsync(d_act, act.data(), G, hipMemcpyHostToDevice, e->stream));
+    if (apply) {
+        AO_HIP(e, hipMemcpyAsync(e->d_bar, e->h_bar.data(), sizeof(uint64_t) * e->h_bar.size(), hipMemcpyHostToDevice, e->stream));
+        b.bar = e->d_bar;
+    }
+    ao::launch_root_tactics(e->tp, d_act, max_depth, max_nodes, b, e->stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p + at_out, out_bytes, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    if (apply) e->bar_on_device = true;
+    const int32_t* h = reinterpret_cast<const int32_t*>(e->h_ro.data());
+    if (verdict) std::memcpy(verdict, h, 4 * G);
+    if (depth) std::memcpy(depth, h + G, 4 * G);
+    if (nodes) std::memcpy(nodes, h + 2 * G, 4 * G);
+    if (unknown) std::memcpy(unknown, h + 3 * G, 4 * G);
+    if (allowed) std::memcpy(allowed, e->h_ro.data() + G * 16, G * A);
+    return 0;
+}
+
 // ---- tree snapshots (tree_snapshot.hip) --------------------------------------------------------
 // games of one chunk: [first, first + count) of the call's list, N nodes and E edges together
 struct SnapChunk { int first, count; size_t N, E; };
@@ -1524,6 +1677,11 @@ int ao_tree_import(ao_engine* e, const int32_t* host_games, int32_t n, const ao_
     const std::string why = ao::snapshot_check(snap);
     if (!why.empty()) return e->fail("ao_tree_import: inconsistent snapshot: " + why);
     if (n == 0) return 0;
+    // a pending bar belongs to the position it was set for; a snapshot taken after a barred move brings kBarQ children with it
+    std::vector<uint8_t> listed(G, 0);
+    for (int i = 0; i < n; ++i) listed[host_games[i]] = 1;
+    if (bar_forget(e, listed.data())) return 1;
+    for (int64_t k = 0; k < snap->edges && !e->bar_dirty; ++k) e->bar_dirty = snap->q[k] == ao::kBarQ;
     std::vector<int32_t> nodes(n), edges(n);
     for (int i = 0; i < n; ++i) {
         nodes[i] = snap->hdr[static_cast<size_t>(i) * AO_SNAP_HDR];

@@ -30,6 +30,11 @@ static_assert(sizeof(Pos) == 80, "Pos layout");
 constexpr int32_t CH_UNVISITED = -1;  // reference: child record exists with n == 0
 constexpr int32_t CH_TERMINAL = -2;   // visited child whose position ends the game
 
+// Q of a root child that is barred from this move's search (TreeParams::bar): a finite value (snapshot_check.hpp refuses
+// anything else) so far below every reachable Q + U -- Q is in [-1, 1], U >= 0 -- that the selection never picks the child
+// while any other exists. A barred child has N = 0 and W = 0. The Python package exports it as engine.BAR_Q.
+constexpr float kBarQ = -1.0e30f;
+
 // leaf status written by the select kernel for the expand/backup kernel
 // LS_WAIT / LS_WAIT_ROOT (round 5, rows handed out per simulation): the descent of this simulation is done -- path and leaf
 // position are stored -- but every row of the evaluation batch was taken (TreeParams::row_cap); the game asks again in the
@@ -121,6 +126,24 @@ struct TreeParams {
     const int8_t* tau;    // [G]
     int32_t* action; int32_t* win;  // [G]
     const uint8_t* active; // [G]
+    // Root move restriction ("the bar"): [G][kBBWords] bitboards of the ACTIONS that may not be searched at this move's roots,
+    // or null when no game of the move is barred. Read in two places only: where a root is expanded (expand_backup_game,
+    // LS_EXPAND_ROOT) and where a move begins on an expanded root (k_begin_move). The selection never looks at it: a barred
+    // child carries Q = kBarQ in the root's record.
+    const uint64_t* bar;
+};
+
+// Device buffers of ao_root_tactics (engine.hip -> launch_root_tactics, positions.hip): the forced-win solver's verdict on the
+// engine's own root positions. verdict: RT_NONE nothing proven (or a terminal / inactive game: everything zero), RT_WIN the
+// mover has a forced win, RT_DEFEND the opponent threatens one and some reply is not proven to lose, RT_LOST every reply is.
+enum : int32_t { RT_NONE = 0, RT_WIN = 1, RT_DEFEND = 2, RT_LOST = 3 };
+struct RootTacticsBufs {
+    uint64_t* won;        // [G][kBBWords] workspace: the mover's winning first moves
+    uint32_t* stage;      // [G][2]        workspace: the words of the mover's and of the opponent's search
+    uint32_t* pair;       // [G][A]        workspace: the word of every reply's search
+    int32_t* verdict; int32_t* depth; int32_t* nodes; int32_t* unknown;   // [G]
+    uint8_t* allowed;     // [G][A]
+    uint64_t* bar;        // [G][kBBWords] the caller's bar in, the bar of the move out (TreeParams::bar); or null
 };
 
 __host__ __device__ inline size_t node_slot(const TreeParams& p, int arena, int g, int node) {

@@ -965,11 +965,14 @@ __device__ __forceinline__ void expand_backup_game(const TreeParams& p, const in
         // agents.py:191-204; gflags bit 1: this game searches this move without noise (read at a root expansion only)
         const bool add_noise = p.noise && status == LS_EXPAND_ROOT && !(p.gflags[g] & 2);
         const size_t slot = node_slot(p, arena, g, newn);
+        // the bar of this move (TreeParams::bar), at a root expansion only: a barred child is born with Q = kBarQ
+        const uint64_t* bar = (p.bar && status == LS_EXPAND_ROOT) ? p.bar + static_cast<size_t>(g) * kBBWords : nullptr;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const int i = lane + 64 * c;
             if (i < L) {
                 const int a = s_ord[i];
+                const bool barred = bar && ((bar[a >> 6] >> (a & 63)) & 1ull);
                 double pr = __ddiv_rn(s_prior[a], sum);
                 if (add_noise) {
                     const double t1 = __dmul_rn(0.75, pr);
@@ -978,7 +981,7 @@ __device__ __forceinline__ void expand_backup_game(const TreeParams& p, const in
                 }
                 rowN(p, slot)[i] = 0;
                 rowW(p, slot)[i] = 0.f;
-                rowQ(p, slot)[i] = 0.f;
+                rowQ(p, slot)[i] = barred ? kBarQ : 0.f;
                 rowP(p, slot)[i] = pr;
                 rowCH(p, slot)[i] = CH_UNVISITED;
                 rowACT(p, slot)[i] = static_cast<uint8_t>(a);

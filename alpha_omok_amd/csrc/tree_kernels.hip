@@ -85,16 +85,35 @@ __global__ __launch_bounds__(64) void k_begin_move(TreeParams p) {
     if (p.active && !p.active[g]) return;
     if (lane == 0) { p.sims_done[g] = 0; p.leaf_status[g] = LS_IDLE; }   // (no leaf of an aborted move is left waiting for a row)
     const int node = p.root_node[g];
-    if (!(p.gflags[g] & 1) || node < 0) return;
+    const bool renoise = (p.gflags[g] & 1) != 0;
+    if ((!renoise && !p.bar) || node < 0) return;
     const size_t slot = node_slot(p, p.cur[g], g, node);
     const int L = nodePos(p, slot)->nchild;
+    const uint64_t* bar = p.bar ? p.bar + static_cast<size_t>(g) * kBBWords : nullptr;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int i = lane + 64 * c;
         if (i < L) {
-            const double t1 = __dmul_rn(0.75, rowP(p, slot)[i]);
-            const double t2 = __dmul_rn(0.25, p.noise_buf[static_cast<size_t>(g) * p.Ap + i]);
-            rowP(p, slot)[i] = __dadd_rn(t1, t2);
+            if (renoise) {
+                const double t1 = __dmul_rn(0.75, rowP(p, slot)[i]);
+                const double t2 = __dmul_rn(0.25, p.noise_buf[static_cast<size_t>(g) * p.Ap + i]);
+                rowP(p, slot)[i] = __dadd_rn(t1, t2);
+            }
+            // The bar on an inherited root (a fresh root gets it where it is expanded, expand_backup_game). A barred child
+            // forgets its statistics and its subtree: N = W = 0, Q = kBarQ, and CH_UNVISITED leaves what hung below it
+            // unreachable until the next re-rooting drops it. A child that carries the sentinel of an earlier search of
+            // this root and is allowed now is an unvisited child again.
+            if (bar) {
+                const int a = rowACT(p, slot)[i];
+                if ((bar[a >> 6] >> (a & 63)) & 1ull) {
+                    rowN(p, slot)[i] = 0;
+                    rowW(p, slot)[i] = 0.f;
+                    rowQ(p, slot)[i] = kBarQ;
+                    rowCH(p, slot)[i] = CH_UNVISITED;
+                } else if (rowQ(p, slot)[i] == kBarQ) {
+                    rowQ(p, slot)[i] = 0.f;
+                }
+            }
         }
     }
 }

@@ -19,6 +19,11 @@ class EngineError(RuntimeError):
 # Engine.search(early_stop=...): simulations between two looks at whether the moves are decided
 SETTLE_EVERY = 16
 
+# q of a root child that is barred from the current move (begin_move / search with allowed= or tactics=): AO_BAR_Q of
+# include/omok_hip.h, the float32 nearest to -1e30. Such a child has n == 0 and w == 0; Engine.root_children shows it.
+BAR_Q = float(np.float32(-1.0e30))
+RT_NONE, RT_WIN, RT_DEFEND, RT_LOST = 0, 1, 2, 3      # `verdict` of Engine.root_tactics / utils.root_tactics
+
 
 def _ptr(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
@@ -169,7 +174,10 @@ class Engine:
 
     def _check(self, rc, what):
         if rc:
-            raise EngineError("%s: %s" % (what, self._L.ao_last_error(self._h).decode()))
+            msg = self._L.ao_last_error(self._h).decode()
+            if "the root bar allows no empty cell" in msg:      # an argument error of allowed=, found on the host before any device call
+                raise ValueError("%s: %s" % (what, msg))
+            raise EngineError("%s: %s" % (what, msg))
 
     # -- rng
     def seed(self, game, seed):
@@ -244,10 +252,63 @@ class Engine:
     def _per_game(self, v, dtype):
         return None if v is None else np.ascontiguousarray(np.broadcast_to(v, (self.G,)), dtype)
 
-    def begin_move(self, active=None, sims=None, noise=None):
-        """sims: simulations per game for this move (int or [G], 1..num_mcts), noise: per-game noise switch (bool or [G]; False
-        = this game searches this move as on a noise=False engine, stream untouched). None: the engine's configuration."""
+    def set_root_bar(self, allowed):
+        """The root move restriction of the NEXT begin_move / search (ao_set_root_bar): allowed uint8 / bool [G, A], 1 = the
+        cell may be searched at that game's root; None clears it. What begin_move(allowed=) and search(allowed=) call."""
+        from .utils import check_allowed
+        m = check_allowed(allowed, self.G, self.A)
+        self._check(self._L.ao_set_root_bar(self._h, _ptr(m, C.c_uint8)), "ao_set_root_bar")
+
+    def root_tactics(self, active=None, max_depth=6, max_nodes=512, apply=False):
+        """utils.root_tactics of every active game's root position, solved on the device from the engine's own positions
+        (ao_root_tactics). Returns dict(verdict int32 [G]: RT_NONE / RT_WIN / RT_DEFEND / RT_LOST, depth int32 [G], allowed
+        bool [G, A], nodes int32 [G], unknown int32 [G]); inactive, ended and terminal games get zeros. apply=True: the bar
+        of the next begin_move / search is set on the device from `allowed` (intersected with a pending set_root_bar; a
+        game whose intersection is empty keeps the caller's), with no host round trip of the mask. ValueError for limits
+        outside 1..16 / 1..65536."""
+        from .positions import _check_limits
+        _check_limits(max_depth, max_nodes)
         a = None if active is None else np.ascontiguousarray(active, np.uint8)
+        G = self.G
+        v, d, n, u = (np.zeros(G, np.int32) for _ in range(4))
+        al = np.zeros((G, self.A), np.uint8)
+        self._check(self._L.ao_root_tactics(self._h, _ptr(a, C.c_uint8), int(max_depth), int(max_nodes), 1 if apply else 0,
+                                            _ptr(v, C.c_int32), _ptr(d, C.c_int32), _ptr(al, C.c_uint8), _ptr(n, C.c_int32),
+                                            _ptr(u, C.c_int32)), "ao_root_tactics")
+        return dict(verdict=v, depth=d, allowed=al.astype(bool), nodes=n, unknown=u)
+
+    def last_tactics(self):
+        """What root_tactics said in the last search(tactics=...) of this engine, or None."""
+        return getattr(self, "_last_tactics", None)
+
+    def _tactics(self, tactics, active, sims):
+        """search(tactics=): root_tactics(apply=True) for the active games; returns the per-game budgets with solved_sims
+        applied to the games with a proven win."""
+        opt = {} if tactics is True else dict(tactics)
+        unknown = set(opt) - {"max_depth", "max_nodes", "solved_sims"}
+        if unknown:
+            raise ValueError("tactics: unknown key(s) %s" % sorted(unknown))
+        k = opt.pop("solved_sims", None)
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= self.num_mcts):
+            raise ValueError("tactics: solved_sims must be an integer in 1..%d, got %r" % (self.num_mcts, k))
+        rt = self.root_tactics(active, apply=True, **opt)
+        self._last_tactics = rt
+        if k is not None and (rt["verdict"] == RT_WIN).any():
+            s = np.array(np.broadcast_to(self.num_mcts if sims is None else sims, (self.G,)), np.int32)
+            won = rt["verdict"] == RT_WIN
+            s[won] = np.minimum(s[won], int(k))
+            return s
+        return sims
+
+    def begin_move(self, active=None, sims=None, noise=None, allowed=None):
+        """sims: simulations per game for this move (int or [G], 1..num_mcts), noise: per-game noise switch (bool or [G]; False
+        = this game searches this move as on a noise=False engine, stream untouched). None: the engine's configuration.
+        allowed: uint8 / bool [G, A], the cells that may be searched at each game's root in this move (set_root_bar); a
+        barred root child gets no visit and reads q == BAR_Q in root_children. ValueError for a row of an active game that
+        allows none of its empty cells; None: no restriction."""
+        a = None if active is None else np.ascontiguousarray(active, np.uint8)
+        if allowed is not None:
+            self.set_root_bar(allowed)
         if sims is None and noise is None:
             self._check(self._L.ao_begin_move(self._h, _ptr(a, C.c_uint8)), "ao_begin_move")
             return
@@ -301,12 +362,22 @@ class Engine:
         return act, win
 
     # -- fused move with the native network
-    def search(self, net, tau=None, active=None, sims=None, noise=None, early_stop=None, settle_every=None):
-        """sims / noise: as begin_move. early_stop: the games that may stop once their move is decided (utils.move_decided) --
+    def search(self, net, tau=None, active=None, sims=None, noise=None, early_stop=None, settle_every=None, allowed=None,
+               tactics=None):
+        """sims / noise / allowed: as begin_move. early_stop: the games that may stop once their move is decided (utils.move_decided) --
         a bool [G] mask, or True for the games with tau == 0 (the only ones whose result is the leader alone); the loop looks
-        every settle_every simulations (None: SETTLE_EVERY, 0: never). With none of them given this is ao_search."""
+        every settle_every simulations (None: SETTLE_EVERY, 0: never). tactics: True or dict(max_depth, max_nodes,
+        solved_sims) -- root_tactics(apply=True) runs first for the active games: a game with a proven forced win searches
+        only its winning first moves (with solved_sims=k: at most k simulations), a game facing one only the replies not
+        proven to lose; intersected with `allowed`, and read afterwards with last_tactics(). With none of them given this
+        is ao_search."""
         t = None if tau is None else np.ascontiguousarray(np.broadcast_to(tau, (self.G,)), np.int8)
         a = None if active is None else np.ascontiguousarray(active, np.uint8)
+        if allowed is not None:
+            self.set_root_bar(allowed)
+        self._last_tactics = None
+        if tactics is not None and tactics is not False:
+            sims = self._tactics(tactics, a, sims)
         pi, vis, pol = self._outs()
         if early_stop is True:
             early_stop = np.zeros(self.G, bool) if t is None else (t == 0)
@@ -348,6 +419,10 @@ class Engine:
 
     # -- introspection
     def root_children(self, game):
+        """The root's children in stored order: dict(action int32, n, w, q, p float64), empty while the root is not expanded.
+        A child that is barred from the current move (begin_move / search with allowed= or tactics=) reads q == BAR_Q with
+        n == 0 and w == 0 -- the sentinel is what keeps the selection off it; it stays until a later move of the same root
+        allows the child again (then q == 0) or the root moves on."""
         A = self.A
         act = np.zeros(A, np.int32)
         n, w, q, p = (np.zeros(A) for _ in range(4))

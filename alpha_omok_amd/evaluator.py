@@ -96,12 +96,20 @@ class Evaluator:
         except Exception:
             return torch.device("cpu")
 
-    def search(self, eng, model, tau, active=None, on_sim=None, sims=None, noise=None, early_stop=None, settle_every=None):
-        """Returns (pi, visit, policy) float64 [G, A]. sims / noise / early_stop / settle_every: Engine.search, on both paths."""
+    def search(self, eng, model, tau, active=None, on_sim=None, sims=None, noise=None, early_stop=None, settle_every=None,
+               allowed=None, tactics=None):
+        """Returns (pi, visit, policy) float64 [G, A]. sims / noise / early_stop / settle_every / allowed / tactics:
+        Engine.search, on both paths."""
         tau = np.ascontiguousarray(np.broadcast_to(tau, (eng.G,)), np.int8)
         net = model if hasattr(model, "forward_ptr") else self.native_net(model, eng.board_size, eng.inplanes)
         if net is not None:
-            return eng.search(net, tau=tau, active=active, sims=sims, noise=noise, early_stop=early_stop, settle_every=settle_every)
+            return eng.search(net, tau=tau, active=active, sims=sims, noise=noise, early_stop=early_stop, settle_every=settle_every,
+                              allowed=allowed, tactics=tactics)
+        if allowed is not None:
+            eng.set_root_bar(allowed)
+        eng._last_tactics = None
+        if tactics is not None and tactics is not False:
+            sims = eng._tactics(tactics, None if active is None else np.ascontiguousarray(active, np.uint8), sims)
         if early_stop is True:
             early_stop = tau == 0
         elif early_stop is False:

@@ -102,6 +102,7 @@ _pool = None                 # games in flight between self_play calls (carry-ov
 _terminal_share = 0.0        # terminal leaves / simulations of the last search (drives ROWS = 'auto')
 _carry_auto = False          # run() with GAMES_PER_ITER set and CARRY_OVER None
 EARLY_STOP = False           # configure(early_stop=True): a tau == 0 search stops once its move is decided (utils.move_decided)
+TACTICS = None               # configure(tactics=True or dict): every self-play search runs Engine.search(tactics=...) -- the forced-win solver restricts the roots
 FAST_SIMS = None             # configure(fast_sims=N): playout-cap randomisation -- every (episode, ply) is a full search (N_MCTS simulations, noise as
 FULL_PROB = 0.25             # configured, sample recorded; probability FULL_PROB) or a fast one (N simulations, no noise, move played, no sample)
 playout_totals = {'full': 0, 'fast': 0}   # move decisions of either kind since configure() (all of them 'full' without fast_sims)
@@ -112,7 +113,7 @@ _grid_masters = []           # ... [(parameter, fp32 master copy)]: Adam moves t
 def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_planes=None, seed=None,
               model=None, gpu=None, noise=True, device_replay=False, node_cap=None, strict=None, reproducible=False,
               carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None,
-              early_stop=False, fast_sims=None, full_prob=0.25):
+              early_stop=False, fast_sims=None, full_prob=0.25, tactics=None):
     """Build `Agent`, `Agent.model` and `optimizer` (main.py:58-85). Call instead of editing constants.
     node_cap: expanded-node capacity of a game's tree arena (0 = 16*(n_mcts+1) where 40 % of the HBM
     holds that for all games, at least 4*(n_mcts+1); -1 = grow into the free HBM);
@@ -147,16 +148,23 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     fast_sims=N: playout-cap randomisation. Every (episode, ply) is a FULL search with probability full_prob -- n_mcts simulations,
     noise as configured, sample recorded -- or a FAST one: N simulations, no noise, the move is played and no sample is recorded,
     so cur_memory / rep_memory only ever see full searches. The choice is full_search(SEED, global episode number, ply): it does
-    not depend on the slot, the rank or MAX_CONCURRENT. playout_totals counts both kinds."""
+    not depend on the slot, the rank or MAX_CONCURRENT. playout_totals counts both kinds.
+    tactics=True or dict(max_depth, max_nodes, solved_sims): every self-play search asks the forced-win solver about its roots first
+    (Engine.search(tactics=...)): a game with a proven forced win searches only the winning first moves, a game facing one only the
+    replies not proven to lose. Off by default."""
     global BOARD_SIZE, N_MCTS, N_BLOCKS, IN_PLANES, OUT_PLANES, SEED, Agent, optimizer, device
     global _engine, _evaluator, _episodes_played, rep_memory, STRICT, NODE_CAP, CARRY_OVER, _pool, OVERSUBSCRIBE, ROWS, _terminal_share
-    global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB
+    global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS
     train_join()
     if fast_sims is not None and not 1 <= int(fast_sims) <= int(n_mcts or N_MCTS):
         raise ValueError("fast_sims must be in 1..n_mcts")
     if not 0.0 <= float(full_prob) <= 1.0:
         raise ValueError("full_prob must be in [0, 1]")
     EARLY_STOP = bool(early_stop)
+    TACTICS = tactics if tactics else None
+    if TACTICS is not None and (STRICT if strict is None else strict):
+        raise ValueError("tactics and strict=True do not go together: a barred root child forgets its inherited visits, which "
+                         "the strict visit-count check would report")
     FAST_SIMS = None if fast_sims is None else int(fast_sims)
     FULL_PROB = float(full_prob)
     playout_totals['full'] = playout_totals['fast'] = 0
@@ -365,6 +373,8 @@ def _search_opts(eng, gids, ply, tau):
             opts['noise'] = full.astype(np.uint8)
     if EARLY_STOP:
         opts['early_stop'] = True
+    if TACTICS is not None:
+        opts['tactics'] = TACTICS
     return opts, full
 
 

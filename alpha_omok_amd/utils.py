@@ -403,6 +403,88 @@ def forced_defences(moves, board_size, win_mark, max_depth=8, max_nodes=2000):
     return out
 
 
+RT_NONE, RT_WIN, RT_DEFEND, RT_LOST = 0, 1, 2, 3       # `verdict` of root_tactics / Engine.root_tactics
+
+
+def root_tactics(moves, board_size, win_mark, max_depth=6, max_nodes=512):
+    """What the forced-win solver says about searching the position P after `moves` (legal moves, black first), by
+    forced_win alone -- the host definition of Engine.root_tactics. With mover m and opponent o:
+
+        a terminal P: verdict RT_NONE, everything zero / empty, nothing searched.
+        own = forced_win(moves). own.result == FW_WIN: RT_WIN, allowed = own.moves, depth = own.depth.
+        otherwise threat = forced_win(moves, attacker=o). threat.result != FW_WIN: RT_NONE, allowed = every empty cell.
+        otherwise every empty cell c is tried as forced_defences does, r = forced_win(moves + [c]): allowed = the cells with
+            r.result != FW_WIN (a reply whose search ran out of nodes stays searchable), depth = threat.depth. Nothing
+            allowed: RT_LOST, and allowed is every empty cell again (the search is left alone when all is lost); else
+            RT_DEFEND.
+
+    Returns a dict: verdict, depth, allowed (bool [A]), nodes (the sum over the searches actually run, each with its own
+    budget of max_nodes) and unknown (bit 0 set where own ran out of nodes, bit 1 the threat's search, bit 2 any reply's).
+    The replies are searched only under a proven threat with no win of one's own: that is what makes it affordable for
+    every move of a batch of games. Argument errors as forced_win."""
+    A = board_size * board_size
+    moves = [int(m) for m in moves]
+    out = dict(verdict=RT_NONE, depth=0, allowed=np.zeros(A, bool), nodes=0, unknown=0)
+    own = forced_win(moves, board_size, win_mark, max_depth, max_nodes)
+    if own["status"] != 0:
+        return out
+    out["nodes"] = own["nodes"]
+    if own["result"] == FW_WIN:
+        out.update(verdict=RT_WIN, depth=own["depth"], allowed=own["moves"].copy())
+        return out
+    out["unknown"] |= int(own["result"] == FW_UNKNOWN)
+    empty = np.ones(A, bool)
+    empty[moves] = False
+    threat = forced_win(moves, board_size, win_mark, max_depth, max_nodes, attacker=1 - len(moves) % 2)
+    out["nodes"] += threat["nodes"]
+    out["unknown"] |= 2 * int(threat["result"] == FW_UNKNOWN)
+    out["allowed"] = empty
+    if threat["result"] != FW_WIN:
+        return out
+    holds = np.zeros(A, bool)
+    for c in np.flatnonzero(empty):
+        r = forced_win(moves + [int(c)], board_size, win_mark, max_depth, max_nodes)
+        out["nodes"] += r["nodes"]
+        out["unknown"] |= 4 * int(r["result"] == FW_UNKNOWN)
+        holds[c] = r["result"] != FW_WIN
+    out["depth"] = threat["depth"]
+    if holds.any():
+        out.update(verdict=RT_DEFEND, allowed=holds)
+    else:
+        out["verdict"] = RT_LOST
+    return out
+
+
+def check_allowed(allowed, games, cells):
+    """The `allowed` argument of Engine.begin_move / search as uint8 [games, cells] (None stays None). ValueError for
+    another shape or for values that are not 0 / 1 / bool."""
+    if allowed is None:
+        return None
+    a = np.asarray(allowed)
+    if a.shape != (games, cells):
+        raise ValueError("allowed must have shape (%d, %d), got %r" % (games, cells, a.shape))
+    if a.dtype != bool and not (np.issubdtype(a.dtype, np.integer) and ((a == 0) | (a == 1)).all()):
+        raise ValueError("allowed must be bool or 0 / 1 integers")
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def root_bar(allowed, ids, board_size):
+    """The host definition of the root move restriction: bool [G, A], True where game g's root child on that cell is
+    barred from the move -- the empty cells of the position of ids[g] (a reference id (0, a1, a2, ...)) that allowed[g]
+    does not name. Ones on occupied cells are ignored; a row that allows every empty cell bars nothing. ValueError for a
+    bad shape (check_allowed) or a row that allows none of its game's empty cells (a full board has none to allow)."""
+    A = board_size * board_size
+    a = check_allowed(allowed, len(ids), A).astype(bool)
+    bar = np.zeros_like(a)
+    for g, rid in enumerate(ids):
+        empty = np.ones(A, bool)
+        empty[list(rid)[1:]] = False
+        bar[g] = empty & ~a[g]
+        if empty.any() and not (empty & a[g]).any():
+            raise ValueError("game %d: the root bar allows no empty cell of the position" % g)
+    return bar
+
+
 def get_state_pt(node_id, board_size, channel_size):
     """Network input planes, float64 [C, B, B] (utils.py:139-168): the stones of the mover of each
     of the last C-1 plies as they stood after that ply, oldest first, then the colour plane."""

@@ -170,6 +170,37 @@ int ao_search_opts(ao_engine *e, ao_net *net, const uint8_t *host_active, const 
  * Any pointer may be NULL. */
 int ao_search_sims(ao_engine *e, int32_t *host_sims_run, uint8_t *host_settled, int64_t *settled_total, int64_t *saved_total);
 
+/* ---- root move restriction ("the bar", no reference counterpart) ----
+ * host_allowed uint8 [G][A]: 1 = the cell may be searched at game g's root in the NEXT ao_begin_move* / ao_search*; NULL
+ * clears a pending bar. That call consumes the bar: the move after it is unrestricted again. Ones on occupied cells are
+ * ignored; a row that allows every empty cell restricts nothing, and with no game restricted the move's launches are those
+ * of an engine that never heard of bars. A row of an active game that allows none of its empty cells makes the
+ * ao_begin_move* / ao_search* fail before it touches anything ("the root bar allows no empty cell"). Rows of inactive games
+ * are not looked at. The pending bar of a game is dropped when its position changes: ao_play, ao_reset, ao_set_root(s),
+ * ao_tree_import.
+ * A barred root child is never selected in that move and gets no visit: its pi and visit entries are 0, its policy entry is
+ * the prior as always. It is data in the root's record, the selection does not know about it: the child is written with
+ * q = AO_BAR_Q, n = 0, w = 0 (ao_get_root_children shows exactly that), and on a root that had been searched before it
+ * forgets its statistics and its subtree. A child that carries the sentinel and is allowed in a later move of the same
+ * root is an unvisited child again. The move that the fp16-range recovery of ao_search repeats runs under the same bar. */
+#define AO_BAR_Q (-1.0e30f)
+int ao_set_root_bar(ao_engine *e, const uint8_t *host_allowed);
+/* The forced-win solver (ao_positions_forced_wins / _forced_defences) on the engine's own root positions, read on the device:
+ * utils.root_tactics of the Python package is the definition. For every game with host_active[g] != 0 (NULL = all) that has
+ * not ended: verdict AO_RT_WIN if the mover has a forced win by continuous fours within max_depth (allowed = the winning
+ * first moves, depth = its depth); else, if the opponent has one after a pass, every empty cell is tried as a reply and
+ * allowed = the replies not proven to lose: AO_RT_DEFEND (depth = the threat's depth), or AO_RT_LOST with allowed = every
+ * empty cell when all replies lose; else AO_RT_NONE with allowed = every empty cell. nodes = the sum over the searches the
+ * definition runs, each bounded by max_nodes (1..65536; max_depth 1..16); unknown = bit 0 / 1 / 2 set where the mover's /
+ * the opponent's / a reply's search ran out of nodes (a reply whose search ran out stays allowed). Inactive, ended and
+ * terminal games get zeros. The engine's win_mark must be 3..5 and at most the board size. Outputs are host arrays, int32 [G]
+ * and uint8 [G][A]; any may be NULL. apply != 0: the bar of the next move (ao_set_root_bar) is set ON THE DEVICE to a pending
+ * bar of the caller's intersected with `allowed`, game by game; a game whose intersection holds no empty cell keeps the
+ * caller's. Fails between ao_begin_move and ao_end_move. */
+enum { AO_RT_NONE = 0, AO_RT_WIN = 1, AO_RT_DEFEND = 2, AO_RT_LOST = 3 };
+int ao_root_tactics(ao_engine *e, const uint8_t *host_active, int32_t max_depth, int32_t max_nodes, int32_t apply,
+                    int32_t *host_verdict, int32_t *host_depth, uint8_t *host_allowed, int32_t *host_nodes, int32_t *host_unknown);
+
 /* ---- introspection (tests, get_visit/get_policy, del_parents prints) ---- */
 int ao_get_moves(ao_engine *e, int game, int32_t *host_moves /*[A]*/, int32_t *n);
 /* statistics of the root's children in stored child order: action, n, w, q, p */

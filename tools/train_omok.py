@@ -78,6 +78,10 @@ def main():
     ap.add_argument("--early-stop", action="store_true",
                     help="self-play searches with tau == 0 stop once their move is decided (main.configure(early_stop=True)): same pi and move, "
                          "fewer simulations, smaller trees handed on")
+    ap.add_argument("--tactics", action="store_true",
+                    help="every self-play search asks the forced-win solver about its roots first (main.configure(tactics=True), "
+                         "Engine.search(tactics=True)): a proven forced win searches only its winning first moves, a proven threat only "
+                         "the replies not proven to lose -- what --audit counts afterwards, told to the search beforehand")
     ap.add_argument("--fast-sims", type=int, default=None, metavar="N",
                     help="playout-cap randomisation (main.configure(fast_sims=N)): a ply is searched fully (--sims, noise, sample recorded) with "
                          "probability --full-prob, else with N simulations, no noise and no sample")
@@ -116,7 +120,8 @@ def main():
         m.MAX_CONCURRENT = a.rows_per_sim
     m.configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, out_planes=a.planes, seed=a.seed,
                 device_replay=True, carry_over=not a.no_carry_over, oversubscribe=a.oversubscribe, rows=a.rows,
-                fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob)
+                fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob,
+                tactics=True if a.tactics else None)
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
