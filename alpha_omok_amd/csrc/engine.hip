@@ -23,6 +23,7 @@
 #include "host_handle.hpp"
 #include "host_rng.hpp"
 #include "snapshot_check.hpp"
+#include "tactics_limits.hpp"
 #include "tree_snapshot.hpp"
 
 namespace ao {
@@ -43,7 +44,7 @@ void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int 
                         int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
 void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s);
 int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s);
-// positions.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
+// root_tactics.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
 void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s);
 // net.hip
 int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, float* value,
@@ -1493,15 +1494,15 @@ int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
     return 0;
 }
 
-// ---- the forced-win solver on the engine's own roots (positions.hip) ----------------------------
+// ---- the forced-win solver on the engine's own roots (root_tactics.hip) -------------------------
 // utils.root_tactics of every active game's root position, read where it lives (TreeParams::rootpos): no move list goes to
 // the device. apply: the bar of the next move is left on the device -- the caller's pending masks (ao_set_root_bar)
 // intersected with what the solver allows, game by game; a game whose intersection would be empty keeps the caller's.
 int ao_root_tactics(ao_engine* e, const uint8_t* active, int32_t max_depth, int32_t max_nodes, int32_t apply, int32_t* verdict,
                     int32_t* depth, uint8_t* allowed, int32_t* nodes, int32_t* unknown) {
     if (e->in_move) return e->fail("ao_root_tactics inside a move (between ao_begin_move and ao_end_move)");
-    if (max_depth < 1 || max_depth > 16) return e->fail("ao_root_tactics: max_depth must be in 1..16");
-    if (max_nodes < 1 || max_nodes > 65536) return e->fail("ao_root_tactics: max_nodes must be in 1..65536");
+    const std::string bad_limits = ao::fw_limits_error("ao_root_tactics", max_depth, max_nodes);
+    if (!bad_limits.empty()) return e->fail(bad_limits);
     if (e->tp.win_mark < 3 || e->tp.win_mark > 5 || e->tp.win_mark > e->cfg.board)
         return e->fail("ao_root_tactics: the solver needs win_mark in 3..5 and at most the board size");
     const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A);

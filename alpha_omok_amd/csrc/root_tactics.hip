@@ -1,0 +1,157 @@
+// root_tactics.hip -- the forced-win solver on an engine's own roots (ao_root_tactics, engine.hip). No reference
+// counterpart; the definition is utils.root_tactics, which goes through utils.forced_win alone. The positions are the engine's
+// TreeParams::rootpos, read on the device: no move list is staged. Three launches: the mover's search and the opponent's
+// search after a pass (k_root_tactics_a), every reply's search for the games that stand under a proven threat with no win
+// of their own (k_root_tactics_b), and one wavefront per game that puts the words together (k_root_tactics_rows). The
+// search, its word and the search after a reply are those of the position batch (tactics_device.hpp).
+#include "host_handle.hpp"
+#include "tactics_device.hpp"
+
+namespace ao {
+
+struct RootTacticsParams {
+    const Pos* rootpos;     // [G]
+    const uint8_t* active;  // [G] or null
+    int G, B, A, win_mark, max_depth, max_nodes;
+    RootTacticsBufs b;
+};
+
+// Two wavefronts per game: role 0 searches for the mover, role 1 for the opponent as if the mover had passed -- and role 0
+// is that search with the sides exchanged: the opponent passes. Stones = popcount of the bitboards, the mover from the ply's
+// parity (what replay_moves gives for the game's id). An inactive or a terminal game is not searched: both words 0.
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_root_tactics_a(RootTacticsParams q) {
+    __shared__ FwWave s_wave[kPosPerWG];
+    const int wv = wg_wave();
+    const int k = blockIdx.x * kPosPerWG + wv;
+    const int g = k >> 1, role = k & 1;
+    if (g >= q.G) return;
+    const bool on = !q.active || __builtin_amdgcn_readfirstlane(static_cast<int>(q.active[g])) != 0;
+    PosR s = pos_load(q.rootpos + g);
+    const int stones = __builtin_amdgcn_readfirstlane(pos_stones(s));
+    const int m = __builtin_amdgcn_readfirstlane(s.ply) & 1;
+
+    FwResult r;
+    int status;
+    const uint32_t word = reply_search<NCH>(s, m ^ role ^ 1, stones, kPass, on, s_wave[wv], q.B, q.A, q.win_mark, q.max_depth, q.max_nodes,
+                                            status, r);
+    if (lane_id() == 0) {
+        q.b.stage[2 * static_cast<size_t>(g) + role] = word;
+        if (role == 0) {
+#pragma unroll
+            for (int w = 0; w < kBBWords; ++w) q.b.won[static_cast<size_t>(g) * kBBWords + w] = r.won[w];
+        }
+    }
+}
+
+// stage A left "the opponent's forced win is proven, the mover has none" for game g
+__device__ __forceinline__ bool root_under_threat(const RootTacticsParams& q, int g) {
+    const uint32_t own = q.b.stage[2 * static_cast<size_t>(g)], thr = q.b.stage[2 * static_cast<size_t>(g) + 1];
+    return own != 0u && fw_word_result(own) != FW_WIN && fw_word_result(thr) == FW_WIN;
+}
+
+// One wavefront per (game, reply cell) pair, grid G x ceil(A / kPosPerWG). A wave returns at once unless its game is under a
+// proven threat; otherwise it does what k_forced_defences does for a reply pair: the mover's stone on the cell, the
+// opponent's search on what stands then. An occupied cell writes 0.
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_root_tactics_b(RootTacticsParams q) {
+    __shared__ FwWave s_wave[kPosPerWG];
+    const int wv = wg_wave();
+    const int g = blockIdx.x, j = blockIdx.y * kPosPerWG + wv;
+    if (j >= q.A) return;
+    if (!__builtin_amdgcn_readfirstlane(static_cast<int>(root_under_threat(q, g)))) return;
+    PosR s = pos_load(q.rootpos + g);
+    const int stones = __builtin_amdgcn_readfirstlane(pos_stones(s));
+    const int m = __builtin_amdgcn_readfirstlane(s.ply) & 1;
+
+    FwResult r;
+    int status;
+    const uint32_t word = reply_search<NCH>(s, m, stones, j, true, s_wave[wv], q.B, q.A, q.win_mark, q.max_depth, q.max_nodes, status, r);
+    if (lane_id() == 0) q.b.pair[static_cast<size_t>(g) * q.A + j] = word;
+}
+
+// One wavefront per game: verdict, depth, nodes, unknown, allowed [A] and the bar of the move out of the words of its
+// searches, by utils.root_tactics' rules. `nodes` and `unknown` count the searches the host definition runs: the mover's;
+// the opponent's unless the mover wins; the replies' under a proven threat. Ballots and integer sums only: no result
+// depends on an order. The bar (in: the caller's barred actions, or zeros) becomes the caller's plus the empty cells the
+// verdict does not allow -- unless that left the game nothing to search: then it stays the caller's.
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_root_tactics_rows(RootTacticsParams q) {
+    const int g = wave_item();
+    if (g >= q.G) return;
+    const int lane = lane_id();
+    const uint32_t own = q.b.stage[2 * static_cast<size_t>(g)], thr = q.b.stage[2 * static_cast<size_t>(g) + 1];
+    const PosR s = pos_load(q.rootpos + g);
+    const bool searched = own != 0u;
+    const int own_res = fw_word_result(own), thr_res = fw_word_result(thr);
+    const bool win = searched && own_res == FW_WIN;
+    const bool threat = searched && !win && thr_res == FW_WIN;
+    int verdict = win ? RT_WIN : RT_NONE;
+    int depth = win ? fw_word_depth(own) : 0;
+    int unknown = (searched && own_res == FW_UNKNOWN) ? 1 : 0;
+    if (searched && !win && thr_res == FW_UNKNOWN) unknown |= 2;
+    int nodes_l = 0;
+    if (lane == 0 && searched) nodes_l = fw_word_nodes(own) + (win ? 0 : fw_word_nodes(thr));
+    uint64_t em[NCH], ok[NCH];             // the empty cells; the cells the verdict allows
+    int n_ok = 0;
+    bool ran_out = false;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int cell = lane + 64 * c;
+        const bool empty = cell < q.A && !(((s.bb[0][c] | s.bb[1][c]) >> lane) & 1ull);
+        em[c] = __ballot(empty);
+        const uint32_t w = (threat && cell < q.A) ? q.b.pair[static_cast<size_t>(g) * q.A + cell] : 0u;
+        const int rep = fw_word_reply(w);
+        nodes_l += fw_word_nodes(w);
+        ran_out = ran_out || __ballot(rep == FD_UNKNOWN) != 0ull;
+        const bool mine = (q.b.won[static_cast<size_t>(g) * kBBWords + c] >> lane) & 1ull;
+        ok[c] = __ballot(threat ? (rep == FD_SAFE || rep == FD_UNKNOWN) : win ? mine : empty);
+        n_ok += __popcll(ok[c]);
+    }
+    if (threat) {
+        verdict = n_ok > 0 ? RT_DEFEND : RT_LOST;
+        depth = fw_word_depth(thr);
+        if (ran_out) unknown |= 4;
+    }
+    const bool open = !searched || verdict == RT_LOST;   // nothing proven that could restrict: every empty cell (zeros where nothing was searched)
+    const int nodes = wave_sum_i(nodes_l);                // <= 227 * 65536
+    if (lane == 0) {
+        if (q.b.verdict) q.b.verdict[g] = verdict;
+        if (q.b.depth) q.b.depth[g] = depth;
+        if (q.b.nodes) q.b.nodes[g] = nodes;
+        if (q.b.unknown) q.b.unknown[g] = unknown;
+    }
+    int n_left = 0;
+    uint64_t allow[NCH], cb[NCH], nb[NCH];   // what the verdict allows; the caller's bar; the bar with the verdict's on top
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        allow[c] = open ? (searched ? em[c] : 0ull) : ok[c];
+        cb[c] = q.b.bar ? uniform64(q.b.bar[static_cast<size_t>(g) * kBBWords + c]) & em[c] : 0ull;
+        nb[c] = searched ? (cb[c] | (em[c] & ~allow[c])) : cb[c];
+        n_left += __popcll(em[c] & ~nb[c]);
+    }
+    store_cell_mask<NCH>(q.b.allowed ? q.b.allowed + static_cast<size_t>(g) * q.A : nullptr, q.A, allow, true);
+    if (q.b.bar && lane == 0) {
+        uint64_t* out = q.b.bar + static_cast<size_t>(g) * kBBWords;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) out[c] = n_left > 0 ? nb[c] : cb[c];
+#pragma unroll
+        for (int c = NCH; c < kBBWords; ++c) out[c] = 0ull;
+    }
+}
+
+void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s) {
+    RootTacticsParams q{};
+    q.rootpos = p.rootpos; q.active = active;
+    q.G = p.G; q.B = p.B; q.A = p.A; q.win_mark = p.win_mark; q.max_depth = max_depth; q.max_nodes = max_nodes;
+    q.b = b;
+    const dim3 block(64 * kPosPerWG);
+    const dim3 grid_a(static_cast<unsigned>((2 * p.G + kPosPerWG - 1) / kPosPerWG));
+    const dim3 grid_b(static_cast<unsigned>(p.G), static_cast<unsigned>((p.A + kPosPerWG - 1) / kPosPerWG));
+    const dim3 grid_r(static_cast<unsigned>((p.G + kPosPerWG - 1) / kPosPerWG));
+    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_root_tactics_a<NCH>, grid_a, block, 0, s, q);
+                    hipLaunchKernelGGL(k_root_tactics_b<NCH>, grid_b, block, 0, s, q);
+                    hipLaunchKernelGGL(k_root_tactics_rows<NCH>, grid_r, block, 0, s, q));
+}
+
+}  // namespace ao

@@ -28,6 +28,7 @@ FW_NONE, FW_WIN, FW_UNKNOWN = 0, 1, 2
 FW_MAX_DEPTH, FW_MAX_NODES = 16, 65536
 # `reply` of PositionBatch.forced_defences (the same values as utils.forced_defences)
 FD_NONE, FD_SAFE, FD_LOSES, FD_UNKNOWN = 0, 1, 2, 3
+_CTYPE = {np.int32: C.c_int32, np.uint8: C.c_uint8, np.int16: C.c_int16}   # of an output array's dtype (PositionBatch._ask)
 
 
 def default_win_mark(board_size):
@@ -232,20 +233,26 @@ class PositionBatch:
         return pol, val, status, err
 
     # -- tactics: defined through utils.check_win alone (utils.win_cells / utils.audit_moves are the host definition)
+    def _ask(self, fn, root_ids, leading_zero, outputs, *limits):
+        """The id-batch entry point `fn` with every output: `outputs` lists them as (name, shape of one row, dtype) in the
+        order of the C ABI, `limits` go between the ids and the outputs -> dict of the arrays, one row per id."""
+        moves, n = pack_ids(root_ids, leading_zero)
+        cnt = n.shape[0]
+        out = {name: np.zeros((cnt,) + shape, dtype) for name, shape, dtype in outputs}
+        self._check(getattr(self._L, fn)(
+            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, *limits,
+            *(_ptr(a, _CTYPE[a.dtype.type]) for a in out.values())), fn)
+        return out
+
     def win_cells(self, root_ids, leading_zero=True):
         """The cells that win at once, one row per id: dict of mine (uint8 [n, A], 1 where a stone of the side to move
         completes a line: check_win of the board with that stone is the mover's index), theirs (the same for the
         opponent, as if it were to move: the cells the mover must occupy), status (check_win of the position; a terminal
         position has no winning cells), turn, err (as describe; rows with err != 0 are all zero)."""
-        moves, n = pack_ids(root_ids, leading_zero)
-        cnt = n.shape[0]
-        out = dict(mine=np.zeros((cnt, self.A), np.uint8), theirs=np.zeros((cnt, self.A), np.uint8),
-                   status=np.zeros(cnt, np.int32), turn=np.zeros(cnt, np.int32), err=np.zeros(cnt, np.int32))
-        self._check(self._L.ao_positions_win_cells(
-            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, _ptr(out["mine"], C.c_uint8),
-            _ptr(out["theirs"], C.c_uint8), _ptr(out["status"], C.c_int32), _ptr(out["turn"], C.c_int32),
-            _ptr(out["err"], C.c_int32)), "ao_positions_win_cells")
-        return out
+        A = self.A
+        return self._ask("ao_positions_win_cells", root_ids, leading_zero, (
+            ("mine", (A,), np.uint8), ("theirs", (A,), np.uint8), ("status", (), np.int32), ("turn", (), np.int32),
+            ("err", (), np.int32)))
 
     def audit(self, root_ids, leading_zero=True):
         """The tactical audit of game records, one row per id: dict of flags (uint8 [n, A]: the flag byte of ply t at
@@ -253,13 +260,8 @@ class PositionBatch:
         zeros from the first terminal position on and beyond the record), counts (int32 [n, 8]: plies audited,
         WIN_AVAILABLE, wins missed, single threats, blocks missed, LOST, end_ply and status as describe), err (as
         describe; rows with err != 0 are all zero)."""
-        moves, n = pack_ids(root_ids, leading_zero)
-        cnt = n.shape[0]
-        out = dict(flags=np.zeros((cnt, self.A), np.uint8), counts=np.zeros((cnt, 8), np.int32), err=np.zeros(cnt, np.int32))
-        self._check(self._L.ao_positions_audit(
-            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, _ptr(out["flags"], C.c_uint8),
-            _ptr(out["counts"], C.c_int32), _ptr(out["err"], C.c_int32)), "ao_positions_audit")
-        return out
+        return self._ask("ao_positions_audit", root_ids, leading_zero, (
+            ("flags", (self.A,), np.uint8), ("counts", (8,), np.int32), ("err", (), np.int32)))
 
     def forced_wins(self, root_ids, max_depth=8, max_nodes=2000, leading_zero=True):
         """Forced wins by continuous fours (VCF) for the side to move, one row per id; utils.forced_win is the definition.
@@ -270,19 +272,11 @@ class PositionBatch:
         status, turn, err as win_cells (a terminal position has result 0; rows with err != 0 are all zero, move and line
         -1). 1 <= max_depth <= 16, 1 <= max_nodes <= 65536, ValueError otherwise: the node budget bounds the launch."""
         _check_limits(max_depth, max_nodes)
-        moves, n = pack_ids(root_ids, leading_zero)
-        cnt = n.shape[0]
-        i32 = lambda: np.zeros(cnt, np.int32)
-        out = dict(result=i32(), depth=i32(), move=i32(), moves=np.zeros((cnt, self.A), np.uint8),
-                   line=np.zeros((cnt, 2 * int(max_depth) - 1), np.int16), line_len=i32(), nodes=i32(), status=i32(),
-                   turn=i32(), err=i32())
-        self._check(self._L.ao_positions_forced_wins(
-            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, int(max_depth), int(max_nodes),
-            _ptr(out["result"], C.c_int32), _ptr(out["depth"], C.c_int32), _ptr(out["move"], C.c_int32),
-            _ptr(out["moves"], C.c_uint8), _ptr(out["line"], C.c_int16), _ptr(out["line_len"], C.c_int32),
-            _ptr(out["nodes"], C.c_int32), _ptr(out["status"], C.c_int32), _ptr(out["turn"], C.c_int32),
-            _ptr(out["err"], C.c_int32)), "ao_positions_forced_wins")
-        return out
+        i32 = ((), np.int32)
+        return self._ask("ao_positions_forced_wins", root_ids, leading_zero, (
+            ("result",) + i32, ("depth",) + i32, ("move",) + i32, ("moves", (self.A,), np.uint8),
+            ("line", (2 * int(max_depth) - 1,), np.int16), ("line_len",) + i32, ("nodes",) + i32, ("status",) + i32,
+            ("turn",) + i32, ("err",) + i32), int(max_depth), int(max_nodes))
 
     def forced_defences(self, root_ids, max_depth=8, max_nodes=2000, leading_zero=True):
         """Which replies of the side to move hold against the opponent's forced win by continuous fours, one row per id;
@@ -296,19 +290,11 @@ class PositionBatch:
         as win_cells. A terminal position has every output but status and turn zero, and so has a row with err != 0.
         Limits as forced_wins, ValueError otherwise."""
         _check_limits(max_depth, max_nodes)
-        moves, n = pack_ids(root_ids, leading_zero)
-        cnt = n.shape[0]
-        i32 = lambda: np.zeros(cnt, np.int32)
-        u8 = lambda: np.zeros((cnt, self.A), np.uint8)
-        out = dict(threat=i32(), threat_depth=i32(), threat_moves=u8(), reply=u8(), depth=u8(),
-                   counts=np.zeros((cnt, 4), np.int32), nodes=i32(), status=i32(), turn=i32(), err=i32())
-        self._check(self._L.ao_positions_forced_defences(
-            self._handle(), _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, int(max_depth), int(max_nodes),
-            _ptr(out["threat"], C.c_int32), _ptr(out["threat_depth"], C.c_int32), _ptr(out["threat_moves"], C.c_uint8),
-            _ptr(out["reply"], C.c_uint8), _ptr(out["depth"], C.c_uint8), _ptr(out["counts"], C.c_int32),
-            _ptr(out["nodes"], C.c_int32), _ptr(out["status"], C.c_int32), _ptr(out["turn"], C.c_int32),
-            _ptr(out["err"], C.c_int32)), "ao_positions_forced_defences")
-        return out
+        i32, u8 = ((), np.int32), ((self.A,), np.uint8)
+        return self._ask("ao_positions_forced_defences", root_ids, leading_zero, (
+            ("threat",) + i32, ("threat_depth",) + i32, ("threat_moves",) + u8, ("reply",) + u8, ("depth",) + u8,
+            ("counts", (4,), np.int32), ("nodes",) + i32, ("status",) + i32, ("turn",) + i32, ("err",) + i32),
+            int(max_depth), int(max_nodes))
 
     # -- lifetime
     def close(self):
