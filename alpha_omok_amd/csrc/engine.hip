@@ -22,43 +22,33 @@
 #include "engine_types.hpp"
 #include "host_handle.hpp"
 #include "host_rng.hpp"
+#include "launchers.hpp"
+#include "search_schedule.hpp"
 #include "snapshot_check.hpp"
 #include "tactics_limits.hpp"
 #include "tree_snapshot.hpp"
 
-namespace ao {
-void launch_select(const TreeParams& p, hipStream_t s);
-void launch_expand_backup(const TreeParams& p, hipStream_t s);
-void launch_expand_select(const TreeParams& p, hipStream_t s);
-void launch_begin_move(const TreeParams& p, hipStream_t s);
-void launch_order(const TreeParams& p, int32_t* order, hipStream_t s);
-void launch_end_move(const TreeParams& p, hipStream_t s);
-// launch_play, launch_walk, launch_tree_stats, launch_tree_pack: non-zero = refused by walk_lds_bytes (tree_walk.hpp), nothing launched
-int launch_play(const TreeParams& p, hipStream_t s);
-int launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
-                const int32_t* prev_known, int32_t* status_out, hipStream_t s);
-void launch_reset(const TreeParams& p, const uint8_t* mask, hipStream_t s);
-void launch_settle(const TreeParams& p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out, hipStream_t s);
-// tree_readout.hip
-void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
-                        int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
-void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s);
-int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s);
-// root_tactics.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
-void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s);
-// net.hip
-int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, float* value,
-                   hipStream_t s, int in_kind, int parts, const unsigned* live, unsigned row_cap);
-void launch_eval_log(const int32_t* games, int n, const int32_t* row_of_game, const float* policy, const float* value, int A,
-                     float* out, const int32_t* sims_done, const int32_t* leaf_status, int what, hipStream_t s);
-int net_step_params(ao_net* n, int boards, float* policy, float* value, StepNet* out);
-void net_fp16_fallback_begin(ao_net* n);
-int net_fp16_fallback_end(ao_net* n);
-// step_kernels.hip
-void launch_step_board(const TreeParams& p, const StepNet& f, int rows, const int32_t* game_of_row, hipStream_t s);
-void net_plan(const ao_net* n, int boards, int* group, int* nchq, int* kind);
-int net_check(const ao_net* n, int board, int inplanes, int device, std::string* why);
-}  // namespace ao
+// The developer switches of the search driver (MoveSearch below; INTEGRATION.md has the table). They have two lifetimes:
+//  * read ONCE per process, by its first search: they pick a code path for an experiment or a profile and hold for the run;
+//  * read ANEW by every search that enters the catch-up rounds: tests/test_gpu_production_loop.py sets and unsets them between
+//    the searches of one process.
+struct DevSwitches {
+    bool static_rows;     // AO_STATIC_ROWS: the per-move packing of rounds 3 - 4 everywhere
+    bool dynamic_rows;    // AO_DYNAMIC_ROWS: hand out rows per simulation without ao_set_row_cap
+    int descent_budget;   // AO_DESCENT_BUDGET (experiment): levels of a descent per launch, 0 = no bound
+    bool row_trace;       // AO_ROW_TRACE: rows asked for, launch by launch, on stderr
+    bool launch_timing;   // AO_LAUNCH_TIMING: is the simulation loop host-bound?
+    static const DevSwitches& process() {
+        static const DevSwitches s{getenv("AO_STATIC_ROWS") != nullptr, getenv("AO_DYNAMIC_ROWS") != nullptr,
+                                   getenv("AO_DESCENT_BUDGET") ? atoi(getenv("AO_DESCENT_BUDGET")) : 0,
+                                   getenv("AO_ROW_TRACE") != nullptr, getenv("AO_LAUNCH_TIMING") != nullptr};
+        return s;
+    }
+    // per search: cut the catch-up loop short (-1 = not set; tests: 0 = a short search must be an error) / run its rounds
+    // without a sit-out window from the start
+    static int catchup_rounds() { const char* v = getenv("AO_CATCHUP_ROUNDS"); return v ? atoi(v) : -1; }
+    static bool catchup_window_off() { return getenv("AO_CATCHUP_WINDOW_OFF") != nullptr; }
+};
 
 struct ao_engine : ao::HandleBase {
     ao_config cfg{};
@@ -85,7 +75,7 @@ struct ao_engine : ao::HandleBase {
     unsigned* d_ctl = nullptr;                            // [2][4] the sit-out window of the current / the next launch (tree_device.hpp, sit_window)
     int row_cap = 0;
     double ask_frac = 1.0;                                // rows asked for per simulation of a game in the last over-subscribed move (1 - terminal share)
-    int64_t rs_launches = 0, rs_rows_live = 0, rs_rows_launched = 0, rs_waits = 0;   // ao_row_stats
+    ao::RowLedger rs;                                     // ao_row_stats
     // ao_set_eval_log: what the network returned to the listed games, per simulation of the current ao_search
     int32_t* d_log_games = nullptr; int log_n = 0; float* log_dev = nullptr; int64_t log_cap = 0; int64_t log_sim = 0;
     size_t il_bytes = 0; int il_group_zeroed = -1, il_nchq_zeroed = -1;  // layout for which batch_il's padding is zero
@@ -620,9 +610,12 @@ static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* s
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const int G = e->G, A = e->A, Ap = e->Ap;
     ao::TreeParams& p = e->tp;
-    // nothing is touched before every value is known to be in range: a refused call leaves the engine as it was
+    // nothing is touched before every value is known to be in range: a refused call leaves the engine as it was (so the games of
+    // this move are worked out beside the engine and become e->active once nothing can refuse the call any more)
+    std::vector<uint8_t> act(G);
+    for (int g = 0; g < G; ++g) act[g] = (active ? active[g] : 1) && !e->over[g];
     for (int g = 0; g < G; ++g) {
-        if (!((active ? active[g] : 1) && !e->over[g])) continue;
+        if (!act[g]) continue;
         if (sims && (sims[g] < 1 || sims[g] > e->S))
             return e->fail("ao_begin_move_opts: game " + std::to_string(g) + ": sims " + std::to_string(sims[g]) + " is outside 1.." +
                            std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
@@ -632,11 +625,8 @@ static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* s
     // the bar of this move: bitboards that ao_root_tactics left on the device, or the caller's masks (ao_set_root_bar) built here
     const bool bar_dev = e->bar_on_device;
     bool bar_any = false;
-    if (!bar_dev && e->bar_pending) {
-        std::vector<uint8_t> act(G);
-        for (int g = 0; g < G; ++g) act[g] = (active ? active[g] : 1) && !e->over[g];
-        if (bar_build(e, act, &bar_any, "ao_begin_move")) return 1;
-    }
+    if (!bar_dev && e->bar_pending && bar_build(e, act, &bar_any, "ao_begin_move")) return 1;
+    e->active = act;
     const bool bar_pass = bar_dev || bar_any || e->bar_dirty;   // (with none of them the launches are those of an engine without bars)
     if (bar_pass && !bar_dev) {
         if (!bar_any) std::fill(e->h_bar.begin(), e->h_bar.end(), 0ull);
@@ -655,7 +645,6 @@ static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* s
     e->target_sum = 0;
     e->move_saved = 0;
     for (int g = 0; g < G; ++g) {
-        e->active[g] = (active ? active[g] : 1) && !e->over[g];
         target[g] = 0;
         flags[g] = 0;
         e->bonus[g] = 0;
@@ -894,160 +883,148 @@ struct SearchOpts {
     int settle_every = 0;
 };
 
-static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi,
-                       double* visit, double* policy, bool may_recover, const SearchOpts& opts) {
-    if (!net) return e->fail("ao_search: null network");
-    std::string why;
-    if (ao::net_check(net, e->cfg.board, e->cfg.inplanes, e->cfg.device, &why)) return e->fail("ao_search: " + why);
-    if (may_recover) {
-        // what the fp16-range recovery below needs to run this move again: the streams as they are NOW
-        AO_HIP(e, hipSetDevice(e->cfg.device));
-        AO_HIP(e, hipMemcpyAsync(e->d_mt_backup, e->tp.mt, sizeof(uint32_t) * 624 * e->G, hipMemcpyDeviceToDevice, e->stream));
-        AO_HIP(e, hipMemcpyAsync(e->d_pos_backup, e->tp.mtpos, sizeof(int32_t) * e->G, hipMemcpyDeviceToDevice, e->stream));
-        e->has_gauss_backup = e->has_gauss;
-        e->gauss_backup = e->gauss;
-    }
-    // the network announces the interleaved input layout it wants for a batch of G boards
-    if (begin_move_impl(e, active, opts.sims, opts.noise)) return 1;
-    // The network runs on the ACTIVE games only. Two regimes (engine_types.hpp, TreeParams::live):
-    //  * a handful of games on the per-board path with the fused per-game step: the host packs the active games to the front of
-    //    the evaluation batch once per move (row_of_game / game_of_row);
-    //  * everything else (round 5): the tree kernel hands out the rows PER SIMULATION -- a game whose new leaf needs the network takes
-    //    the next row, a terminal leaf takes none (agents.py:171-178,216-221: the reference evaluates it and throws the result
-    //    away) -- and counts them in one device word per launch that the trunk kernels read: groups without a live row exit at
-    //    once, no host read-back in the loop. With a trained network 11 - 19 % of all leaves are terminal. ao_set_row_cap bounds
-    //    the rows of one simulation BELOW the number of games (over-subscription: 5120 games on the 4096 rows = 256 groups the
-    //    resident trunk fills the chip with); a leaf that finds the batch full waits for the next launch (LS_WAIT), the loop below
-    //    runs until every game has its simulations. A game's search is strictly sequential in every regime: same bits.
-    int rows = 0;
-    e->h_row.assign(2 * static_cast<size_t>(e->G), 0);
-    for (int g = 0; g < e->G; ++g)
-        if (e->active[g]) {
-            e->h_row[e->G + rows] = g;
-            e->h_row[g] = rows++;
-        }
-    if (rows == 0) return ao_end_move(e, tau, pi, visit, policy);
-    static const bool static_rows = getenv("AO_STATIC_ROWS") != nullptr;   // developer switch: the per-move packing of rounds 3 - 4 everywhere
-    const int cap_rows = (!static_rows && e->row_cap > 0 && e->row_cap < rows) ? e->row_cap : rows;
-    int in_kind = 1;
-    ao::net_plan(net, cap_rows, &e->tp.il_group, &e->tp.nchq, &in_kind);
-    // The padding channels of the fp32 input batch (planes 5..31 of a 32-channel slab) are zero and stay zero: the
-    // encoder only writes the quads that hold planes (16 B per lane at a 2 KB stride are partial-line writes --
-    // rocprof showed 152 MB of HBM writes per launch for a 42 MB batch). A change of layout re-zeroes the buffer.
-    // The split-fp16 kernels take the planes as BITS instead (in_kind 2): one byte per cell, 81 contiguous bytes per
-    // leaf, and the fp32 batch is not written at all.
-    if (in_kind != 2 && (e->il_group_zeroed != e->tp.il_group || e->il_nchq_zeroed != e->tp.nchq)) {
-        AO_HIP(e, hipMemsetAsync(e->tp.batch_il, 0, e->il_bytes, e->stream));
-        e->il_group_zeroed = e->tp.il_group;
-        e->il_nchq_zeroed = e->tp.nchq;
-    }
-    // select | net | expand+select | net | ... | expand(+idle select): one launch fewer per simulation
-    // than the step-wise protocol, same device code (tree_device.hpp).
-    ao::TreeParams p = e->tp;
-    p.batch_nchw = nullptr;
-    p.policy = e->d_policy;
-    p.value = e->d_value;
-    p.row_of_game = e->d_row;
-    p.nchq_live = (e->cfg.inplanes + 3) / 4;
-    const float* net_in = p.batch_il;
-    if (in_kind == 2) {
-        net_in = reinterpret_cast<const float*>(e->d_planes_u8);
-        p.batch_u8 = e->d_planes_u8;
-        p.batch_il = nullptr;
-    }
-    // A few games (the per-board network path): heads, tree step and the next leaf's conv1 are ONE launch per game
-    // (k_step_board), the network is asked for the residual blocks alone -- 9 launches per simulation instead of 11.
-    ao::StepNet step{};
-    const bool fused = cap_rows == rows && ao::net_step_params(net, rows, e->d_policy, e->d_value, &step) != 0;
-    static const bool force_dynamic = getenv("AO_DYNAMIC_ROWS") != nullptr;   // developer switch: hand out rows per simulation without ao_set_row_cap
-    // (opt-in: the hand-out costs one atomic per workgroup on one word, ~11 ns each -- 10 us on top of a 20 us tree kernel when 4096
-    // descents of equal depth arrive together, profiles/r5a_row_alloc_atomics.txt; it pays when leaves are terminal)
-    const bool dynamic = !fused && !static_rows && (e->row_cap > 0 || force_dynamic);
-    if (dynamic) {
-        AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
-        p.row_cap = static_cast<unsigned>(cap_rows);
-    } else {
-        AO_HIP(e, hipMemcpyAsync(e->d_row, e->h_row.data(), sizeof(int32_t) * 2 * e->G, hipMemcpyHostToDevice, e->stream));
-    }
-    int launch = 0, harvested = 0;   // selection launches of this move so far (launch i counts its rows in slot i % kLive); slots already summed up
-    auto slot = [&](int i) -> unsigned* { return dynamic ? e->d_live + (i % ao_engine::kLive) : nullptr; };
-    // Over-subscription (more active games than rows per simulation). Every launch a window of the game indices sits out, sized so
-    // that the games that do descend ask for about cap_rows rows -- a share `ask_frac` of them does (the rest ends at terminal
-    // leaves), measured over the previous move of this engine, less three standard deviations of that binomial; the window moves on
-    // by its own length per launch (see select_game). `unfinished` = games that still need simulations.
-    const bool oversub = dynamic && cap_rows < rows;
-    p.order = (oversub && e->order_on && e->row_cap > 0 && e->row_cap < e->G) ? e->d_order : nullptr;
-    static const int level_budget = getenv("AO_DESCENT_BUDGET") ? atoi(getenv("AO_DESCENT_BUDGET")) : 0;   // experiment: levels of a descent per launch
-    p.max_levels = dynamic ? level_budget : 0;
-    const bool catch_up = oversub || p.max_levels > 0;   // games may be short of their simulations after the nominal number of launches
-    const int64_t rows_live_before = e->rs_rows_live;
-    // Settling (k_settle): every settle_every simulations, and in every catch-up round, the games of the early_stop mask whose move
-    // is decided get their targets lowered and the loop goes on with the largest number of simulations still owed -- or ends.
-    // Off (no mask or settle_every 0): nothing is launched and nothing is read back.
-    const bool settle_on = opts.early_stop != nullptr && opts.settle_every > 0;
-    if (settle_on) AO_HIP(e, hipMemcpyAsync(e->d_early, opts.early_stop, e->G, hipMemcpyHostToDevice, e->stream));
-    unsigned sit_idx = 0;       // the window the move starts with (the host's estimate); the device takes it from there (sit_window)
-    unsigned row_target = static_cast<unsigned>(cap_rows);
-    if (oversub) {
-        const double f = std::min(1.0, std::max(0.5, e->ask_frac));
-        const double slack = 2.5 * std::sqrt(static_cast<double>(cap_rows) * (1.0 - f)) + 4.0;
-        row_target = static_cast<unsigned>(std::max(1.0, cap_rows - slack));
-        const double askers = std::min<double>(rows, std::floor(row_target / f));
-        sit_idx = static_cast<unsigned>(std::lround((rows - askers) * e->G / static_cast<double>(rows)));
-        if (sit_idx >= static_cast<unsigned>(e->G)) sit_idx = static_cast<unsigned>(e->G) - 1u;
-        // the move STARTS with the window that is safe for any demand -- as many games descend as there are rows -- and the
-        // controller opens it within a handful of launches: the first descents of a move ask for more rows than its average
-        // (measured: 4741 - 4957 asked of 4096 at the average's window, ~2000 leaves per move sent waiting), and a leaf that
-        // waits costs its game a launch at the END of the move, when the batch is nearly empty
-        const double askers0 = std::min<double>(rows, row_target);
-        unsigned sit0 = static_cast<unsigned>(std::lround((rows - askers0) * e->G / static_cast<double>(rows)));
-        if (sit0 >= static_cast<unsigned>(e->G)) sit0 = static_cast<unsigned>(e->G) - 1u;
-        const float sf = static_cast<float>(sit0);
-        unsigned* init = e->h_live + ao_engine::kLive;   // (pinned; every move ends with a stream synchronisation)
-        std::memset(init, 0, 8 * sizeof(unsigned));
-        init[0] = sit0;
-        std::memcpy(&init[2], &sf, 4);
-        AO_HIP(e, hipMemcpyAsync(e->d_ctl, init, 8 * sizeof(unsigned), hipMemcpyHostToDevice, e->stream));
-    }
-    bool sit_off_forced = false;   // the catch-up loop below: nobody sits out any more
-    auto set_sit = [&](int i) {
-        p.ctl = (oversub && !sit_off_forced) ? e->d_ctl : nullptr;
+// One move of ao_search between begin_move_impl and ao_end_move: what its phases share. search_impl runs them top to bottom:
+// plan (rows and layout), run_sims (the simulations, with settling), run_planned_extra and run_catch_up (over-subscription),
+// finish (row statistics). The arithmetic of the schedule is search_schedule.hpp's.
+struct MoveSearch {
+    ao_engine* const e;
+    ao_net* const net;
+    const SearchOpts& opts;
+    const DevSwitches& dev = DevSwitches::process();
+    // ---- the plan, fixed once plan() has run
+    int rows = 0, cap_rows = 0;    // active games; rows of one network launch: ao_set_row_cap's, or one per active game
+    int in_kind = 1;               // the input the network wants (net_plan): 2 = bit planes, otherwise the interleaved fp32 batch
+    const float* net_in = nullptr;
+    ao::TreeParams p{};            // the move's copy of e->tp; live, ctl, ctl_cur, live_prev and row_target change per launch
+    ao::StepNet step{};            // the fused per-game step (k_step_board)
+    bool fused = false;            // a few games on the per-board path: heads, tree step and the next leaf's conv1 are one launch per game
+    bool dynamic = false, oversub = false;   // the tree kernel hands out the rows per simulation; ... and there are fewer of them than active games
+    bool catch_up = false;         // games may be short of their simulations after the nominal number of launches
+    bool settle_on = false;        // k_settle runs every opts.settle_every simulations and in every catch-up round
+    ao::SitWindow win{};           // over-subscription: the sit-out window the move starts with (the device takes it from there, sit_window)
+    int64_t rows_live_before = 0;  // e->rs.rows_live when the move began (ask_frac)
+    // ---- progress
+    int launch = 0, harvested = 0; // selection launches of this move so far (launch i counts its rows in slot i % kLive); slots already summed up
+    bool first_sim = true;
+    bool sit_off = false, all_done = false;   // the catch-up rounds have switched the window off: nobody sits out any more; settling found no unfinished game
+    int nominal_sims = 0;          // e->sims_left when the loop began
+    std::chrono::steady_clock::time_point t0;   // ... and the time (AO_LAUNCH_TIMING)
+
+    unsigned* slot(int i) const { return dynamic ? e->d_live + (i % ao_engine::kLive) : nullptr; }
+    void set_sit(int i) {
+        p.ctl = (oversub && !sit_off) ? e->d_ctl : nullptr;
         p.ctl_cur = i & 1;
         p.live_prev = (oversub && i > 0 && i % ao_engine::kLive != 0) ? slot(i - 1) : nullptr;   // (the ring was zeroed at a wrap: no demand reading for that launch)
-        p.row_target = row_target;
-    };
+        p.row_target = win.row_target;
+    }
+
+    int plan() {
+        // The network runs on the ACTIVE games only. Two regimes (engine_types.hpp, TreeParams::live):
+        //  * a handful of games on the per-board path with the fused per-game step: the host packs the active games to the front of
+        //    the evaluation batch once per move (row_of_game / game_of_row);
+        //  * everything else (round 5): the tree kernel hands out the rows PER SIMULATION -- a game whose new leaf needs the network takes
+        //    the next row, a terminal leaf takes none (agents.py:171-178,216-221: the reference evaluates it and throws the result
+        //    away) -- and counts them in one device word per launch that the trunk kernels read: groups without a live row exit at
+        //    once, no host read-back in the loop. With a trained network 11 - 19 % of all leaves are terminal. ao_set_row_cap bounds
+        //    the rows of one simulation BELOW the number of games (over-subscription: 5120 games on the 4096 rows = 256 groups the
+        //    resident trunk fills the chip with); a leaf that finds the batch full waits for the next launch (LS_WAIT), the catch-up
+        //    rounds run until every game has its simulations. A game's search is strictly sequential in every regime: same bits.
+        e->h_row.assign(2 * static_cast<size_t>(e->G), 0);
+        for (int g = 0; g < e->G; ++g)
+            if (e->active[g]) {
+                e->h_row[e->G + rows] = g;
+                e->h_row[g] = rows++;
+            }
+        if (rows == 0) return 0;
+        cap_rows = (!dev.static_rows && e->row_cap > 0 && e->row_cap < rows) ? e->row_cap : rows;
+        // the network announces the interleaved input layout it wants for a batch of cap_rows boards
+        ao::net_plan(net, cap_rows, &e->tp.il_group, &e->tp.nchq, &in_kind);
+        // The padding channels of the fp32 input batch (planes 5..31 of a 32-channel slab) are zero and stay zero: the
+        // encoder only writes the quads that hold planes (16 B per lane at a 2 KB stride are partial-line writes --
+        // rocprof showed 152 MB of HBM writes per launch for a 42 MB batch). A change of layout re-zeroes the buffer.
+        // The split-fp16 kernels take the planes as BITS instead (in_kind 2): one byte per cell, 81 contiguous bytes per
+        // leaf, and the fp32 batch is not written at all.
+        if (in_kind != 2 && (e->il_group_zeroed != e->tp.il_group || e->il_nchq_zeroed != e->tp.nchq)) {
+            AO_HIP(e, hipMemsetAsync(e->tp.batch_il, 0, e->il_bytes, e->stream));
+            e->il_group_zeroed = e->tp.il_group;
+            e->il_nchq_zeroed = e->tp.nchq;
+        }
+        // select | net | expand+select | net | ... | expand(+idle select): one launch fewer per simulation
+        // than the step-wise protocol, same device code (tree_device.hpp).
+        p = e->tp;
+        p.batch_nchw = nullptr;
+        p.policy = e->d_policy;
+        p.value = e->d_value;
+        p.row_of_game = e->d_row;
+        p.nchq_live = (e->cfg.inplanes + 3) / 4;
+        net_in = p.batch_il;
+        if (in_kind == 2) {
+            net_in = reinterpret_cast<const float*>(e->d_planes_u8);
+            p.batch_u8 = e->d_planes_u8;
+            p.batch_il = nullptr;
+        }
+        // A few games (the per-board network path): heads, tree step and the next leaf's conv1 are ONE launch per game
+        // (k_step_board), the network is asked for the residual blocks alone -- 9 launches per simulation instead of 11.
+        fused = cap_rows == rows && ao::net_step_params(net, rows, e->d_policy, e->d_value, &step) != 0;
+        // (AO_DYNAMIC_ROWS is opt-in: the hand-out costs one atomic per workgroup on one word, ~11 ns each -- 10 us on top of a 20 us tree
+        // kernel when 4096 descents of equal depth arrive together, profiles/r5a_row_alloc_atomics.txt; it pays when leaves are terminal)
+        dynamic = !fused && !dev.static_rows && (e->row_cap > 0 || dev.dynamic_rows);
+        if (dynamic) {
+            AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
+            p.row_cap = static_cast<unsigned>(cap_rows);
+        } else {
+            AO_HIP(e, hipMemcpyAsync(e->d_row, e->h_row.data(), sizeof(int32_t) * 2 * e->G, hipMemcpyHostToDevice, e->stream));
+        }
+        oversub = dynamic && cap_rows < rows;   // more active games than rows per simulation: search_schedule.hpp, SitWindow
+        p.order = (oversub && e->order_on && e->row_cap > 0 && e->row_cap < e->G) ? e->d_order : nullptr;
+        p.max_levels = dynamic ? dev.descent_budget : 0;
+        catch_up = oversub || p.max_levels > 0;
+        rows_live_before = e->rs.rows_live;
+        // Settling (k_settle): every settle_every simulations, and in every catch-up round, the games of the early_stop mask whose move
+        // is decided get their targets lowered and the loop goes on with the largest number of simulations still owed -- or ends.
+        // Off (no mask or settle_every 0): nothing is launched and nothing is read back.
+        settle_on = opts.early_stop != nullptr && opts.settle_every > 0;
+        if (settle_on) AO_HIP(e, hipMemcpyAsync(e->d_early, opts.early_stop, e->G, hipMemcpyHostToDevice, e->stream));
+        win.row_target = static_cast<unsigned>(cap_rows);
+        if (oversub) {
+            win = ao::sit_window(rows, e->G, cap_rows, e->ask_frac);
+            const float sf = static_cast<float>(win.sit0);
+            unsigned* init = e->h_live + ao_engine::kLive;   // (pinned; every move ends with a stream synchronisation)
+            std::memset(init, 0, 8 * sizeof(unsigned));
+            init[0] = win.sit0;
+            std::memcpy(&init[2], &sf, 4);
+            AO_HIP(e, hipMemcpyAsync(e->d_ctl, init, 8 * sizeof(unsigned), hipMemcpyHostToDevice, e->stream));
+        }
+        return 0;
+    }
+
     // sums up the row counters of the selection launches [harvested, upto) -- each of them was followed by a network launch
-    auto harvest_rows = [&](int upto) -> int {
+    int harvest_rows(int upto) {
         if (!dynamic || upto <= harvested) return 0;
         AO_HIP(e, hipMemcpyAsync(e->h_live, e->d_live, sizeof(unsigned) * ao_engine::kLive, hipMemcpyDeviceToHost, e->stream));
         AO_HIP(e, hipStreamSynchronize(e->stream));
-        static const bool row_trace = getenv("AO_ROW_TRACE") != nullptr;   // developer switch: rows asked for, launch by launch
-        if (row_trace) {
+        if (dev.row_trace) {
             fprintf(stderr, "AO_ROW_TRACE %d active games, %d rows, launches %d..%d, rows asked for:", rows, cap_rows, harvested, upto - 1);
             for (int i = harvested; i < upto; ++i) fprintf(stderr, " %u", e->h_live[i % ao_engine::kLive]);
             fprintf(stderr, "\n");
         }
-        for (int i = harvested; i < upto; ++i) {
-            const int64_t want = e->h_live[i % ao_engine::kLive];
-            e->rs_rows_live += std::min<int64_t>(want, cap_rows);
-            e->rs_waits += std::max<int64_t>(want - cap_rows, 0);
-            e->rs_rows_launched += cap_rows;
-            ++e->rs_launches;
-        }
+        for (int i = harvested; i < upto; ++i) e->rs.add(e->h_live[i % ao_engine::kLive], cap_rows);
         harvested = upto;
         return 0;
-    };
+    }
+
     // what: 1 = policy + value, 2 = simulation count + leaf status (the fused step computes the heads AND moves on to the next leaf
     // in one kernel: the two halves of a record are taken on either side of it)
-    auto log_evals = [&](int what) {
+    void log_evals(int what) {
         if (e->log_n > 0 && (e->log_sim + 1) * e->log_n * (e->A + 3) <= e->log_cap) {
             ao::launch_eval_log(e->d_log_games, e->log_n, e->d_row, e->d_policy, e->d_value, e->A,
                                 e->log_dev + e->log_sim * e->log_n * (e->A + 3), e->tp.sims_done, e->tp.leaf_status, what, e->stream);
             if (what & 1) ++e->log_sim;
         }
-    };
-    bool first_sim = true;
-    auto one_sim = [&]() -> int {
+    }
+
+    // the one place that queues a network launch followed by a tree launch
+    int one_sim() {
         if (ao::net_forward_il(net, net_in, cap_rows, e->d_policy, e->d_value, e->stream, in_kind, fused ? (first_sim ? 3 : 2) : 7,
                                slot(launch), static_cast<unsigned>(cap_rows)))
             return e->fail(std::string("network forward failed: ") + ao_net_last_error(net));
@@ -1071,65 +1048,64 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
         if (timed) e->timer.end(e->stream);
         AO_HIP(e, hipGetLastError());
         return 0;
-    };
-    if (e->sims_left > 0) {
-        p.live = slot(0);
-        set_sit(0);
-        ao::launch_select(p, e->stream);
-        AO_HIP(e, hipGetLastError());
     }
+
+    // the first selection, then e->sims_left simulations; with settling the loop looks every opts.settle_every of them
     // (Replaying the per-simulation launch sequence as a HIP graph was measured and is slower than
     // eager launches here: 71.7 vs 65.7 us per simulation for one game)
-    int rc = 0;
-    static const bool launch_timing = getenv("AO_LAUNCH_TIMING") != nullptr;   // developer switch: is the simulation loop host-bound?
-    const auto lt0 = std::chrono::steady_clock::now();
-    const int lt_sims = e->sims_left;
-    bool all_done = false;
-    int since_settle = 0;
-    e->leaf_open = e->sims_left > 0;
-    while (e->sims_left > 0 && rc == 0) {
-        rc = one_sim();
-        --e->sims_left;
-        if (settle_on && rc == 0 && e->sims_left > 0 && ++since_settle >= opts.settle_every) {
-            since_settle = 0;
-            int unfinished = 0, owed = 0;
-            if (settle_queue(e, e->d_early, 0)) return 1;
-            AO_HIP(e, hipStreamSynchronize(e->stream));
-            settle_harvest(e, &unfinished, &owed);
-            all_done = unfinished == 0;
-            // (without over-subscription every unfinished game advances by one simulation per launch: `owed` launches are exactly
-            // what is left; with it they are a lower bound and the catch-up rounds below find the rest)
-            e->sims_left = all_done ? 0 : std::min(e->sims_left, owed);
+    int run_sims() {
+        if (e->sims_left > 0) {
+            p.live = slot(0);
+            set_sit(0);
+            ao::launch_select(p, e->stream);
+            AO_HIP(e, hipGetLastError());
         }
+        t0 = std::chrono::steady_clock::now();
+        nominal_sims = e->sims_left;
+        int since_settle = 0;
+        e->leaf_open = e->sims_left > 0;
+        while (e->sims_left > 0) {
+            const int rc = one_sim();
+            --e->sims_left;
+            if (rc) return 1;
+            if (settle_on && e->sims_left > 0 && ++since_settle >= opts.settle_every) {
+                since_settle = 0;
+                int unfinished = 0, owed = 0;
+                if (settle_queue(e, e->d_early, 0)) return 1;
+                AO_HIP(e, hipStreamSynchronize(e->stream));
+                settle_harvest(e, &unfinished, &owed);
+                all_done = unfinished == 0;
+                // (without over-subscription every unfinished game advances by one simulation per launch: `owed` launches are exactly
+                // what is left; with it they are a lower bound and the catch-up rounds find the rest)
+                e->sims_left = all_done ? 0 : std::min(e->sims_left, owed);
+            }
+        }
+        return 0;
     }
-    if (rc) return rc;
-    if (oversub && sit_idx > 0 && !settle_on) {
-        // a game sits out sit_idx / G of the launches: that many more launches before anyone can be done
-        const int planned = static_cast<int>(std::ceil(static_cast<double>(lt_sims) * e->G / (e->G - sit_idx))) - lt_sims;
-        for (int k = 0; k < planned - 8 && rc == 0; ++k) rc = one_sim();   // (a few short: the deficit rounds below find out exactly)
-        if (rc) return rc;
+
+    // over-subscribed, without settling: the launches that the sit-out window costs every game
+    int run_planned_extra() {
+        if (!(oversub && win.sit_idx > 0 && !settle_on)) return 0;
+        const int extra = ao::planned_extra_launches(nominal_sims, e->G, win.sit_idx);
+        for (int k = 0; k < extra; ++k)
+            if (one_sim()) return 1;
+        return 0;
     }
-    if (catch_up && !all_done) {
-        // over-subscribed: leaves that found their simulation's batch full were expanded one launch later, so some games are
-        // short of their simulations. The counters say by how much; max(largest deficit, all deficits / rows per launch)
-        // is a lower bound of the launches still needed -- run them, look again. The reference ALWAYS runs num_mcts simulations
-        // (agents.py:105-132), so the loop ends in exactly two ways: every active game has its simulations, or an error. A round
-        // without progress is not a stall yet -- a leaf that waited takes its row in one launch and is expanded by the next, and a
-        // game may have sat out the only launch of the round -- so the sit-out window is switched OFF first (nobody sits out, and
-        // every round runs two launches at least); two more rounds without progress after that are a real stall. Whatever is still
-        // short when the loop ends is reported by k_end_move (ERR_SHORT) -- no result is built from fewer visits than asked for.
+
+    // Leaves that found their simulation's batch full were expanded one launch later, so some games are short of their
+    // simulations: rounds of launches by the rule of search_schedule.hpp's CatchUp. The reference ALWAYS runs num_mcts
+    // simulations (agents.py:105-132), so the loop ends in exactly two ways: every active game has its simulations, or an
+    // error. Whatever is still short when it ends is reported by k_end_move (ERR_SHORT) -- no result is built from fewer
+    // visits than asked for.
+    int run_catch_up() {
+        if (!catch_up || all_done) return 0;
         const int G = e->G;
         int32_t* h_done = e->h_i32;
         int32_t* h_target = e->h_i32 + G;
         int32_t* h_err = e->h_i32 + 2 * G;
-        int64_t last_sum = -1;
-        const char* dev_env = getenv("AO_CATCHUP_ROUNDS");   // developer switch, read per search: cut the loop short (tests: 0 = a short search must be an error)
-        const int dev_rounds = dev_env ? atoi(dev_env) : -1;
-        const int max_rounds = dev_rounds >= 0 ? dev_rounds : 4 * (e->S + 2);
-        bool window_off = getenv("AO_CATCHUP_WINDOW_OFF") != nullptr;   // developer switch (tests): the catch-up rounds run without a sit-out window from the start
-        if (window_off) sit_off_forced = true;
-        int stalled = 0;
-        for (int round = 0; round < max_rounds; ++round) {
+        ao::CatchUp rule(cap_rows, e->S, DevSwitches::catchup_rounds(), DevSwitches::catchup_window_off());
+        sit_off = rule.window_off;
+        while (rule.open()) {
             if (settle_on && settle_queue(e, e->d_early, 0)) return 1;
             AO_HIP(e, hipMemcpyAsync(h_done, e->tp.sims_done, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
             AO_HIP(e, hipMemcpyAsync(h_target, e->tp.sims_target, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
@@ -1145,84 +1121,108 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
                 const int d = h_target[g] - h_done[g];
                 if (d > 0) { sum += d; mx = std::max(mx, d); }
             }
-            if (mx == 0 || bad) break;                      // done / a per-game error (reported by ao_end_move)
-            if (sum == last_sum && p.max_levels == 0) {     // (with a level budget a round may pass without a finished simulation)
-                if (!window_off) window_off = true;
-                else if (++stalled >= 2) break;             // a real stall: ao_end_move names the games
-            } else {
-                stalled = 0;
-            }
-            last_sum = sum;
-            if (window_off) sit_off_forced = true;
-            int extra = static_cast<int>(std::max<int64_t>(mx, (sum + cap_rows - 1) / cap_rows));
-            if (window_off) extra = std::max(extra, 2);
-            for (int k = 0; k < extra && rc == 0; ++k) rc = one_sim();
-            if (rc) return rc;
+            const int extra = rule.next(sum, mx, bad, p.max_levels != 0);
+            if (extra == 0) break;
+            sit_off = rule.window_off;
+            for (int k = 0; k < extra; ++k)
+                if (one_sim()) return 1;
         }
+        return 0;
     }
-    if (harvest_rows(launch)) return 1;
-    const int64_t sims_wanted = e->target_sum - e->move_saved;   // (the budgets actually set, less what settling took away)
-    if (oversub && sims_wanted > 0)
-        e->ask_frac = static_cast<double>(e->rs_rows_live - rows_live_before) / static_cast<double>(sims_wanted);
-    if (launch_timing) {
-        const auto lt1 = std::chrono::steady_clock::now();
-        (void)hipStreamSynchronize(e->stream);
-        const auto lt2 = std::chrono::steady_clock::now();
-        fprintf(stderr, "AO_LAUNCH_TIMING %d simulations: launches enqueued in %.1f us each, stream drained %.1f us after the last enqueue\n", lt_sims,
-                std::chrono::duration<double, std::micro>(lt1 - lt0).count() / (lt_sims > 0 ? lt_sims : 1),
-                std::chrono::duration<double, std::micro>(lt2 - lt1).count());
+
+    // the row statistics of the move, and the share of its simulations that asked for a row: the next move's window
+    int finish() {
+        if (harvest_rows(launch)) return 1;
+        const int64_t sims_wanted = e->target_sum - e->move_saved;   // (the budgets actually set, less what settling took away)
+        if (oversub && sims_wanted > 0)
+            e->ask_frac = static_cast<double>(e->rs.rows_live - rows_live_before) / static_cast<double>(sims_wanted);
+        if (dev.launch_timing) {
+            const auto lt1 = std::chrono::steady_clock::now();
+            (void)hipStreamSynchronize(e->stream);
+            const auto lt2 = std::chrono::steady_clock::now();
+            fprintf(stderr, "AO_LAUNCH_TIMING %d simulations: launches enqueued in %.1f us each, stream drained %.1f us after the last enqueue\n", nominal_sims,
+                    std::chrono::duration<double, std::micro>(lt1 - t0).count() / (nominal_sims > 0 ? nominal_sims : 1),
+                    std::chrono::duration<double, std::micro>(lt2 - lt1).count());
+        }
+        return 0;
     }
-    // The split-fp16 trunk clamps activations beyond the fp16 range and reports it: the evaluations of such a move are
-    // not the fp32-equivalent ones the engine promises (checked before the per-game errors: clamped evaluations are what
-    // makes priors degenerate). The move is then searched AGAIN, transparently, on the fp32-MFMA trunk: the games of this
-    // move get their pre-move MT19937 streams back and FRESH trees at their current positions (ao_set_roots semantics:
-    // what the search inherited from earlier moves is forgotten -- the one deviation from the reference, which would
-    // have searched on top of its inherited counts), the caller gets a result instead of an exception and the event is
-    // counted (ao_fp16_range_events; the Python layer turns it into a warning). The network returns to its requested
-    // mode afterwards; from the third event of the SAME weights on (counted per network object since its last
-    // ao_net_finalize) it stays on the fp32-MFMA trunk -- a checkpoint that keeps leaving the range would otherwise search
-    // every move twice -- until new weights are loaded or ao_net_set_mode is called.
+};
+
+static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi, double* visit, double* policy,
+                       bool may_recover, const SearchOpts& opts);
+
+// The split-fp16 trunk clamps activations beyond the fp16 range and reports it: the evaluations of such a move are
+// not the fp32-equivalent ones the engine promises (checked before the per-game errors: clamped evaluations are what
+// makes priors degenerate). The move is then searched AGAIN, transparently, on the fp32-MFMA trunk: the games of this
+// move get their pre-move MT19937 streams back and FRESH trees at their current positions (ao_set_roots semantics:
+// what the search inherited from earlier moves is forgotten -- the one deviation from the reference, which would
+// have searched on top of its inherited counts), the caller gets a result instead of an exception and the event is
+// counted (ao_fp16_range_events; the Python layer turns it into a warning). The network returns to its requested
+// mode afterwards; from the third event of the SAME weights on (counted per network object since its last
+// ao_net_finalize) it stays on the fp32-MFMA trunk -- a checkpoint that keeps leaving the range would otherwise search
+// every move twice -- until new weights are loaded or ao_net_set_mode is called.
+static int recover_fp16_range(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi, double* visit,
+                              double* policy, bool may_recover, const SearchOpts& opts) {
+    (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
+    (void)hipStreamSynchronize(e->stream);
+    e->in_move = false;
+    e->ended = false;
+    if (!may_recover)
+        return e->fail("ao_search: an activation left the fp16 range (|x| > 65504) in the split-fp16 trunk during the repeated move");
+    const int G = e->G;
+    std::vector<uint8_t> mask(G, 0);
+    std::vector<int32_t> games, ns;
+    std::vector<std::vector<int32_t>> saved;
+    for (int g = 0; g < G; ++g) {
+        if (!e->active[g]) continue;
+        mask[g] = 1;
+        games.push_back(g);
+        saved.push_back(e->moves[g]);
+        ns.push_back(static_cast<int32_t>(e->moves[g].size()));
+    }
+    std::vector<const int32_t*> ids;
+    for (auto& m : saved) ids.push_back(m.data());
+    AO_HIP(e, hipMemcpyAsync(e->tp.mt, e->d_mt_backup, sizeof(uint32_t) * 624 * G, hipMemcpyDeviceToDevice, e->stream));
+    AO_HIP(e, hipMemcpyAsync(e->tp.mtpos, e->d_pos_backup, sizeof(int32_t) * G, hipMemcpyDeviceToDevice, e->stream));
+    e->has_gauss = e->has_gauss_backup;
+    e->gauss = e->gauss_backup;
+    // the repeated move is searched under the bar of the first attempt: what begin_move_impl consumed is pending again (the
+    // bitboards of an on-device bar are still in d_bar; k_begin_move only reads them), and resetting the games does not drop it
+    e->bar_pending = e->used_pending; e->bar_on_device = e->used_on_device;
+    if (e->used_pending) { e->bar_allowed = e->used_allowed; e->bar_has = e->used_has; }
+    e->bar_keep = true;
+    const int rc_reset = ao_reset(e, mask.data()) || set_roots_impl(e, static_cast<int>(games.size()), games.data(), ids.data(), ns.data(), nullptr);
+    e->bar_keep = false;
+    if (rc_reset) return 1;
+    ao::net_fp16_fallback_begin(net);                // mode 2 for the repeated move
+    ++e->fp16_events;
+    e->fp16_games_redone += static_cast<int64_t>(games.size());
+    const int rc = search_impl(e, net, active, tau, pi, visit, policy, false, opts);   // (same budgets, noise switches and mask)
+    ao::net_fp16_fallback_end(net);                  // back to the requested mode, unless these weights did it three times
+    return rc;
+}
+
+static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi, double* visit, double* policy,
+                       bool may_recover, const SearchOpts& opts) {
+    if (!net) return e->fail("ao_search: null network");
+    std::string why;
+    if (ao::net_check(net, e->cfg.board, e->cfg.inplanes, e->cfg.device, &why)) return e->fail("ao_search: " + why);
+    if (may_recover) {
+        // what recover_fp16_range needs to run this move again: the streams as they are NOW
+        AO_HIP(e, hipSetDevice(e->cfg.device));
+        AO_HIP(e, hipMemcpyAsync(e->d_mt_backup, e->tp.mt, sizeof(uint32_t) * 624 * e->G, hipMemcpyDeviceToDevice, e->stream));
+        AO_HIP(e, hipMemcpyAsync(e->d_pos_backup, e->tp.mtpos, sizeof(int32_t) * e->G, hipMemcpyDeviceToDevice, e->stream));
+        e->has_gauss_backup = e->has_gauss;
+        e->gauss_backup = e->gauss;
+    }
+    if (begin_move_impl(e, active, opts.sims, opts.noise)) return 1;
+    MoveSearch m{e, net, opts};
+    if (m.plan()) return 1;
+    if (m.rows == 0) return ao_end_move(e, tau, pi, visit, policy);
+    if (m.run_sims() || m.run_planned_extra() || m.run_catch_up() || m.finish()) return 1;
     int32_t nflags = 0;
     if (ao_net_status(net, e->stream, &nflags, 1)) return e->fail(std::string("ao_net_status: ") + ao_net_last_error(net));
-    if (nflags & AO_NET_FP16_RANGE) {
-        (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
-        (void)hipStreamSynchronize(e->stream);
-        e->in_move = false;
-        e->ended = false;
-        if (!may_recover)
-            return e->fail("ao_search: an activation left the fp16 range (|x| > 65504) in the split-fp16 trunk during the repeated move");
-        const int G = e->G;
-        std::vector<uint8_t> mask(G, 0);
-        std::vector<int32_t> games, ns;
-        std::vector<std::vector<int32_t>> saved;
-        for (int g = 0; g < G; ++g) {
-            if (!e->active[g]) continue;
-            mask[g] = 1;
-            games.push_back(g);
-            saved.push_back(e->moves[g]);
-            ns.push_back(static_cast<int32_t>(e->moves[g].size()));
-        }
-        std::vector<const int32_t*> ids;
-        for (auto& m : saved) ids.push_back(m.data());
-        AO_HIP(e, hipMemcpyAsync(e->tp.mt, e->d_mt_backup, sizeof(uint32_t) * 624 * G, hipMemcpyDeviceToDevice, e->stream));
-        AO_HIP(e, hipMemcpyAsync(e->tp.mtpos, e->d_pos_backup, sizeof(int32_t) * G, hipMemcpyDeviceToDevice, e->stream));
-        e->has_gauss = e->has_gauss_backup;
-        e->gauss = e->gauss_backup;
-        // the repeated move is searched under the bar of the first attempt: what begin_move_impl consumed is pending again (the
-        // bitboards of an on-device bar are still in d_bar; k_begin_move only reads them), and resetting the games does not drop it
-        e->bar_pending = e->used_pending; e->bar_on_device = e->used_on_device;
-        if (e->used_pending) { e->bar_allowed = e->used_allowed; e->bar_has = e->used_has; }
-        e->bar_keep = true;
-        const int rc_reset = ao_reset(e, mask.data()) || set_roots_impl(e, static_cast<int>(games.size()), games.data(), ids.data(), ns.data(), nullptr);
-        e->bar_keep = false;
-        if (rc_reset) return 1;
-        ao::net_fp16_fallback_begin(net);                // mode 2 for the repeated move
-        ++e->fp16_events;
-        e->fp16_games_redone += static_cast<int64_t>(games.size());
-        const int rc2 = search_impl(e, net, active, tau, pi, visit, policy, false, opts);   // (same budgets, noise switches and mask)
-        ao::net_fp16_fallback_end(net);                  // back to the requested mode, unless these weights did it three times
-        return rc2;
-    }
+    if (nflags & AO_NET_FP16_RANGE) return recover_fp16_range(e, net, active, tau, pi, visit, policy, may_recover, opts);
     return ao_end_move(e, tau, pi, visit, policy);
 }
 
@@ -1247,10 +1247,10 @@ int ao_set_row_cap(ao_engine* e, int32_t rows) {
 }
 
 int ao_row_stats(ao_engine* e, int64_t* launches, int64_t* rows_live, int64_t* rows_launched, int64_t* waits) {
-    if (launches) *launches = e->rs_launches;
-    if (rows_live) *rows_live = e->rs_rows_live;
-    if (rows_launched) *rows_launched = e->rs_rows_launched;
-    if (waits) *waits = e->rs_waits;
+    if (launches) *launches = e->rs.launches;
+    if (rows_live) *rows_live = e->rs.rows_live;
+    if (rows_launched) *rows_launched = e->rs.rows_launched;
+    if (waits) *waits = e->rs.waits;
     return 0;
 }
 

@@ -1,0 +1,47 @@
+// launchers.hpp -- the host entry points that one translation unit defines and another calls: the kernel launchers of the tree,
+// read-out, root-tactics and step kernels and the network's internal interface. Included by the callers AND by every file that
+// defines one of them, so that a changed signature is a compile error where it changes and never a second overload.
+// (tree_snapshot.hpp declares launch_tree_pack / launch_tree_unpack beside the chunk layout they take.)
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "../../include/omok_hip.h"
+#include "engine_types.hpp"
+
+namespace ao {
+// tree_kernels.hip
+void launch_select(const TreeParams& p, hipStream_t s);
+void launch_expand_backup(const TreeParams& p, hipStream_t s);
+void launch_expand_select(const TreeParams& p, hipStream_t s);
+void launch_begin_move(const TreeParams& p, hipStream_t s);
+void launch_order(const TreeParams& p, int32_t* order, hipStream_t s);
+void launch_end_move(const TreeParams& p, hipStream_t s);
+// launch_play, launch_walk, launch_tree_stats, launch_tree_pack: non-zero = refused by walk_lds_bytes (tree_walk.hpp), nothing launched
+int launch_play(const TreeParams& p, hipStream_t s);
+int launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
+                const int32_t* prev_known, int32_t* status_out, hipStream_t s);
+void launch_reset(const TreeParams& p, const uint8_t* mask, hipStream_t s);
+void launch_settle(const TreeParams& p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out, hipStream_t s);
+void launch_eval_log(const int32_t* games, int n, const int32_t* row_of_game, const float* policy, const float* value, int A,
+                     float* out, const int32_t* sims_done, const int32_t* leaf_status, int what, hipStream_t s);
+// tree_readout.hip
+void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
+                        int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
+void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s);
+int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s);
+// root_tactics.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
+void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s);
+// step_kernels.hip
+void launch_step_board(const TreeParams& p, const StepNet& f, int rows, const int32_t* game_of_row, hipStream_t s);
+// net.hip
+int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, float* value,
+                   hipStream_t s, int in_kind, int parts, const unsigned* live, unsigned row_cap);
+int net_step_params(ao_net* n, int boards, float* policy, float* value, StepNet* out);
+void net_fp16_fallback_begin(ao_net* n);
+int net_fp16_fallback_end(ao_net* n);
+void net_plan(const ao_net* n, int boards, int* group, int* nchq, int* kind);
+int net_check(const ao_net* n, int board, int inplanes, int device, std::string* why);
+}  // namespace ao

@@ -19,6 +19,7 @@
 #include "../../include/omok_hip.h"
 #include "engine_types.hpp"
 #include "host_handle.hpp"
+#include "launchers.hpp"
 #include "net_device.hpp"
 #include "net_common.hpp"
 #include "net_trunk_f32.hpp"

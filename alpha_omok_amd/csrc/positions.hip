@@ -33,11 +33,10 @@
 
 #include "../../include/omok_hip.h"
 #include "host_handle.hpp"
+#include "launchers.hpp"
 #include "tactics_device.hpp"
 
 namespace ao {
-
-int net_check(const ao_net* n, int board, int inplanes, int device, std::string* why);   // net.hip
 
 // per-position error codes (ao_positions_from_moves)
 enum : int32_t { PE_OK = 0, PE_RANGE = 1, PE_OCCUPIED = 2, PE_LENGTH = 3 };

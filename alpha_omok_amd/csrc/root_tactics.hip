@@ -5,6 +5,7 @@
 // of their own (k_root_tactics_b), and one wavefront per game that puts the words together (k_root_tactics_rows). The
 // search, its word and the search after a reply are those of the position batch (tactics_device.hpp).
 #include "host_handle.hpp"
+#include "launchers.hpp"
 #include "tactics_device.hpp"
 
 namespace ao {

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "host_handle.hpp"
+#include "launchers.hpp"
 #include "tree_device.hpp"
 #include "net_device.hpp"
 

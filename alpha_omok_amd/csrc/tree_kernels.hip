@@ -22,6 +22,7 @@
 // FMA contraction (explicit __dmul_rn/__ddiv_rn/__dadd_rn), sqrt(total_n) from a host-built
 // table of correctly rounded values, fp32 w/q with correctly rounded add/divide.
 #include "host_handle.hpp"
+#include "launchers.hpp"
 #include "tree_walk.hpp"
 
 namespace ao {

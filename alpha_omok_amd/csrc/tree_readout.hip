@@ -19,6 +19,7 @@
 
 #include "../../include/omok_hip.h"
 #include "host_handle.hpp"
+#include "launchers.hpp"
 #include "tree_walk.hpp"
 
 namespace ao {
