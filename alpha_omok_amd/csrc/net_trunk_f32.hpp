@@ -344,8 +344,14 @@ __device__ __forceinline__ void trunk_layer(const float4* __restrict__ src, floa
 // wave per board: policy_fc + softmax, value_fc1 + ReLU + value_fc2 + tanh.
 // H16: 1 = the activations are in the split-fp16 layout of k_trunk16h (x = high half + low half), 2 = its 3-byte form
 // (fp16 high half + one low byte, kPairBytes(1) in net_trunk_h16.hpp), 0 = fp32
+// hand2 / hand1 (H16 = 1 only, null otherwise): board rows BW-2 and BW-1 of the final tensor are not in `act` but in these LDS
+// row buffers, left there by the last trunk layer in the layout of its stores (2 KB per (cell, 32-channel block): high
+// fragment, low fragment). They fill the dynamic LDS that s_w3 / s_h alias, so their cells go first -- one cell per thread,
+// the 1x1 conv weights straight from global memory (the same numbers in the same fmaf order), the three sums kept in
+// registers -- and only behind a barrier are s_w3 and s_h written.
 template <int BW, int H16 = 0, typename Args = TrunkArgs>
-__device__ __forceinline__ void trunk_heads(const Args& a, const float4* act, size_t gbase, int grp) {
+__device__ __forceinline__ void trunk_heads(const Args& a, const float4* act, size_t gbase, int grp, const uint4* hand2 = nullptr,
+                                            const uint4* hand1 = nullptr) {
     constexpr int A = BW * BW;
     constexpr int GB = 16;
     constexpr int NA = (A + 63) / 64;
@@ -354,73 +360,98 @@ __device__ __forceinline__ void trunk_heads(const Args& a, const float4* act, si
     const int tid = threadIdx.x, nthreads = blockDim.x;
     float* s_w3 = s_heads;              // [3][planes]
     float* s_h = s_w3 + 3 * planes;     // [16 boards][3][A]
-    for (int i = tid; i < 3 * planes; i += nthreads) s_w3[i] = a.w3[i];
-    __syncthreads();
-    if (H16 != 0) {
-        // split-fp16 layouts: a lane's 8 channels of one (cell, 32-channel block, oct) are ONE 16-byte slot of the high
-        // fragment (+ 16 / 8 bytes of the low one). All slots of two blocks are requested before the first is used: written
-        // quad by quad this loop was a chain of 32 dependent round trips per cell to data that has mostly left L2 by
-        // now (0.10 M of the launch's 2.75 M cycles, profiles/r3a_trunk16h_bytes_ko.txt).
-        const int b = tid & 15;
-        const int nblk = CQ >> 3;
-        for (int cell = tid >> 4; cell < A; cell += nthreads >> 4) {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-            constexpr int CB = 4;   // blocks in flight (the split-fp16 kernels are built for 128 planes = 4 blocks)
-            for (int c0 = 0; c0 < nblk; c0 += CB) {
-                uint4 hv[CB][4], lv[CB][4];
+    // split-fp16 layouts: a lane's 8 channels of one (cell, 32-channel block, oct) are ONE 16-byte slot of the high
+    // fragment (+ 16 / 8 bytes of the low one). All slots of two blocks are requested before the first is used: written
+    // quad by quad this loop was a chain of 32 dependent round trips per cell to data that has mostly left L2 by
+    // now (0.10 M of the launch's 2.75 M cycles, profiles/r3a_trunk16h_bytes_ko.txt).
+    // slot(c, oc, hv, lv): fetches the slot of block c, oct oc; w: the [3][planes] weights of the 1x1 convs
+    const int nblk = CQ >> 3;
+    auto cell_sums = [&](auto&& slot, const float* w, float& a0, float& a1, float& a2) {
+        constexpr int CB = 4;   // blocks in flight (the split-fp16 kernels are built for 128 planes = 4 blocks)
+        for (int c0 = 0; c0 < nblk; c0 += CB) {
+            uint4 hv[CB][4], lv[CB][4];
 #pragma unroll
-                for (int cb = 0; cb < CB; ++cb)
+            for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-                    for (int oc = 0; oc < 4; ++oc) {
-                        const int c = c0 + cb < nblk ? c0 + cb : nblk - 1;
-                        const char* base = reinterpret_cast<const char*>(act) +
-                                           ((gbase + cell) * nblk + c) * (H16 == 2 ? 1536 : 2048) + (oc * 16 + b) * 16;
-                        hv[cb][oc] = *reinterpret_cast<const uint4*>(base);
+                for (int oc = 0; oc < 4; ++oc) slot(c0 + cb < nblk ? c0 + cb : nblk - 1, oc, hv[cb][oc], lv[cb][oc]);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                if (c0 + cb >= nblk) continue;
+#pragma unroll
+                for (int oc = 0; oc < 4; ++oc) {
+                    const unsigned hw[4] = {hv[cb][oc].x, hv[cb][oc].y, hv[cb][oc].z, hv[cb][oc].w};
+                    const unsigned lw[4] = {lv[cb][oc].x, lv[cb][oc].y, lv[cb][oc].z, lv[cb][oc].w};
+                    float x[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const unsigned hb = (hw[k >> 1] >> (16 * (k & 1))) & 0xffffu;
                         if (H16 == 2) {
-                            const uint2 t = *reinterpret_cast<const uint2*>(base + 1024 - (oc * 16 + b) * 8);
-                            lv[cb][oc] = make_uint4(t.x, t.y, 0u, 0u);
+                            const unsigned t = (hb << 8) | ((lw[k >> 2] >> (8 * (k & 3))) & 0xffu);
+                            x[k] = __uint_as_float(t ? (t << 5) + 0x38000000u : 0u);
                         } else {
-                            lv[cb][oc] = *reinterpret_cast<const uint4*>(base + 1024);
+                            const unsigned lb = (lw[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                            x[k] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<unsigned short>(hb))) +
+                                   static_cast<float>(__builtin_bit_cast(_Float16, static_cast<unsigned short>(lb)));
                         }
                     }
+                    const int ch = ((c0 + cb) * 4 + oc) * 8;   // first channel of this slot
+                    const float* w0 = w + ch;
+                    const float* w1 = w + planes + ch;
+                    const float* w2 = w + 2 * planes + ch;
 #pragma unroll
-                for (int cb = 0; cb < CB; ++cb) {
-                    if (c0 + cb >= nblk) continue;
-#pragma unroll
-                    for (int oc = 0; oc < 4; ++oc) {
-                        const unsigned hw[4] = {hv[cb][oc].x, hv[cb][oc].y, hv[cb][oc].z, hv[cb][oc].w};
-                        const unsigned lw[4] = {lv[cb][oc].x, lv[cb][oc].y, lv[cb][oc].z, lv[cb][oc].w};
-                        float x[8];
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            const unsigned hb = (hw[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-                            if (H16 == 2) {
-                                const unsigned t = (hb << 8) | ((lw[k >> 2] >> (8 * (k & 3))) & 0xffu);
-                                x[k] = __uint_as_float(t ? (t << 5) + 0x38000000u : 0u);
-                            } else {
-                                const unsigned lb = (lw[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-                                x[k] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<unsigned short>(hb))) +
-                                       static_cast<float>(__builtin_bit_cast(_Float16, static_cast<unsigned short>(lb)));
-                            }
-                        }
-                        const int ch = ((c0 + cb) * 4 + oc) * 8;   // first channel of this slot
-                        const float* w0 = s_w3 + ch;
-                        const float* w1 = s_w3 + planes + ch;
-                        const float* w2 = s_w3 + 2 * planes + ch;
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            a0 = fmaf(x[k], w0[k], a0);
-                            a1 = fmaf(x[k], w1[k], a1);
-                            a2 = fmaf(x[k], w2[k], a2);
-                        }
+                    for (int k = 0; k < 8; ++k) {
+                        a0 = fmaf(x[k], w0[k], a0);
+                        a1 = fmaf(x[k], w1[k], a1);
+                        a2 = fmaf(x[k], w2[k], a2);
                     }
                 }
             }
+        }
+    };
+    const bool handed = H16 == 1 && hand2 != nullptr;   // (uniform)
+    const bool mine = handed && (tid >> 4) < 2 * BW;    // this thread owns (cell A - 2 BW + (tid >> 4), board tid & 15)
+    float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+    if (handed) {
+        if (mine) {
+            const int hc = tid >> 4, i = hc < BW ? hc : hc - BW;
+            const char* row = reinterpret_cast<const char*>(hc < BW ? hand2 : hand1);
+            cell_sums([&](int c, int oc, uint4& hv, uint4& lv) {
+                const char* base = row + (i * nblk + c) * 2048 + (oc * 16 + (tid & 15)) * 16;
+                hv = *reinterpret_cast<const uint4*>(base);
+                lv = *reinterpret_cast<const uint4*>(base + 1024);
+            }, a.w3, m0, m1, m2);
+        }
+        __syncthreads();   // the handed rows are consumed: s_w3 / s_h may overwrite them
+    }
+    for (int i = tid; i < 3 * planes; i += nthreads) s_w3[i] = a.w3[i];
+    __syncthreads();
+    if (H16 != 0) {
+        const int b = tid & 15;
+        const int ncell = handed ? A - 2 * BW : A;   // cells whose activations are in `act`
+        for (int cell = tid >> 4; cell < ncell; cell += nthreads >> 4) {
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+            cell_sums([&](int c, int oc, uint4& hv, uint4& lv) {
+                const char* base = reinterpret_cast<const char*>(act) +
+                                   ((gbase + cell) * nblk + c) * (H16 == 2 ? 1536 : 2048) + (oc * 16 + b) * 16;
+                hv = *reinterpret_cast<const uint4*>(base);
+                if (H16 == 2) {
+                    const uint2 t = *reinterpret_cast<const uint2*>(base + 1024 - (oc * 16 + b) * 8);
+                    lv = make_uint4(t.x, t.y, 0u, 0u);
+                } else {
+                    lv = *reinterpret_cast<const uint4*>(base + 1024);
+                }
+            }, s_w3, a0, a1, a2);
             // s_h is [3A][16 boards] here: the FC sweeps below read the 16 boards of an input index as four 16-byte
             // broadcasts instead of sixteen 4-byte ones (the sweeps were LDS-instruction bound: ~60 k of the heads' 88 k cycles)
             s_h[(cell) * GB + b] = fmaxf(fmaf(a0, a.sc3[0], a.sh3[0]), 0.f);
             s_h[(A + cell) * GB + b] = fmaxf(fmaf(a1, a.sc3[1], a.sh3[1]), 0.f);
             s_h[(2 * A + cell) * GB + b] = fmaxf(fmaf(a2, a.sc3[2], a.sh3[2]), 0.f);
+        }
+        if (mine) {
+            const int cell = A - 2 * BW + (tid >> 4);
+            s_h[(cell) * GB + b] = fmaxf(fmaf(m0, a.sc3[0], a.sh3[0]), 0.f);
+            s_h[(A + cell) * GB + b] = fmaxf(fmaf(m1, a.sc3[1], a.sh3[1]), 0.f);
+            s_h[(2 * A + cell) * GB + b] = fmaxf(fmaf(m2, a.sc3[2], a.sh3[2]), 0.f);
         }
     } else {
         const int b = tid & 15;

@@ -181,18 +181,30 @@ template <int BW, int NC32, int NCI, int KIND, int FMT = 0, bool W16 = false>
 struct TrunkHLayerFn {
 static __device__ __forceinline__ void run(const void* src, uint4* dst, const TrunkHLayer& L, const bool RES, uint4* s_x,
                                            int tile, int lane, unsigned long long* prof, const bool flip,
-                                           unsigned* s_cnt, const unsigned rows_before, const bool hand_next, const int par) {
+                                           unsigned* s_cnt, const unsigned rows_before, const bool hand_next, const int par,
+                                           const bool to_heads = false) {
     constexpr bool FIRST = KIND != 0;
     constexpr bool BITS = KIND == 2;
     // Hand-off of the layer boundary through LDS (see the row-buffer life cycle below). hand_next: another resident layer
     // follows this one and takes its first two input rows from the row buffers; HANDED: the previous layer left this layer's
     // input rows 0 and 1 there (every trunk layer of the 4-byte format: conv1 and each trunk layer hand off whenever a layer
-    // follows). par: which row buffer holds input row 0 (always 0 for an odd board width). The 3-byte format (FMT 1) keeps
-    // expanded fragments in LDS that differ from what it stores and stays on the HBM round trip; the knock-out builds too,
-    // so that they keep measuring what their notes say.
+    // follows). to_heads: this is the LAST trunk layer and the reader of the handed rows is trunk_heads, the only reader of the
+    // final tensor: the two rows are handed over in the same way and, although this is a block's output, not stored. par:
+    // which row buffer holds input row 0 (always 0 for an odd board width). The 3-byte format (FMT 1) keeps expanded fragments
+    // in LDS that differ from what it stores and stays on the HBM round trip; the knock-out builds too, so that they keep
+    // measuring what their notes say.
     constexpr bool HAND = FMT == 0 && AO_KO == 0;
     constexpr bool HANDED = HAND && !FIRST;
     static_assert(!HAND || NC32 >= 2, "conv1's hand-off assumes that its own row buffers lie inside the next layer's buffer 0");
+    // conv1 on bit planes as ONE pass over an LDS-resident board (RES1): the high-half fragments of all BW*BW cells (1 KB
+    // each; bit planes have no low half, none is staged) are built once behind one barrier, then every wave runs all rows'
+    // slabs and epilogues on its own -- no row barrier, no drain of the epilogue's stores per row (they must have landed at
+    // the layer boundary only, which waits for them). The resident board overlaps BOTH hand-off targets, so one more barrier
+    // stands between a wave's last read and its two handed rows: three barriers per layer beside the boundary's, whatever BW.
+    // The 3-byte format, the knock-out builds and the measured-neutral conv1 / barrier variants keep the row loop.
+    constexpr bool RES1 = BITS && HAND && !AO_CONV1_SPLIT && !AO_SPLIT_BARRIER;
+    static_assert(!RES1 || (BW >= 2 && BW * BW <= 2 * BW * NC32 * 2),
+                  "conv1's resident board (BW*BW high-half fragments) lies inside the two row buffers of the next layer");
     // flip: this layer walks the board from the LAST row to the first (logical row y = physical row BW-1-y, tap rows
     // mirrored). Layers alternate direction, so a layer starts with the rows the previous one wrote last: the first two
     // are handed over in LDS (HAND), the third is still in L2 / the Infinity Cache -- instead of the ones that left the
@@ -225,15 +237,22 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
     // SIMD computes meanwhile)
     // (conv1 has a single 32-channel block: its 9 x 2 fragments are simply loaded once)
     half8 wA[2][3], wB[2][3], wres[2][FIRST ? 9 : 1];
-    auto load_w = [&](int slab, half8 (&W)[2][3]) {
+    // issued (wave-uniform): false for a slab whose MFMAs are skipped because its output row falls off the board (the first
+    // input row's yo == -1 slab, the last row's yo == BW slab, in LOGICAL rows, so in either direction) and for the prefetch
+    // past the layer's last row. Its loads are then sent with a per-lane offset beyond the descriptor's range: a buffer
+    // load out of range returns zeros without a request to the cache, and the number of loads in flight -- what the waits
+    // in front of the MFMAs count -- is the same on every path (a branch around the loads would make every wait for a
+    // slab's weights cover the prefetch behind it as well).
+    auto load_w = [&](int slab, half8 (&W)[2][3], bool issued = true) {
         if (FIRST) return;
         if (AO_KO == 1 && slab > 2) return;
         const int c = (slab / 3) % NCI, dy = slab % 3;
+        const int voff = (AO_KO != 0 || issued) ? lane16 : 0x40000000;
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
             const int ub = ((((flip ? 2 - dy : dy) * 3 + dx) * NCI + c) * NT + tile) * 1024;
-            W[0][dx] = buf_ld_h8(rs_wh, lane16, ub);
-            if (!W16) W[1][dx] = buf_ld_h8(rs_wl, lane16, ub);
+            W[0][dx] = buf_ld_h8(rs_wh, voff, ub);
+            if (!W16) W[1][dx] = buf_ld_h8(rs_wl, voff, ub);
         }
     };
     if (FIRST) {
@@ -348,7 +367,7 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
                     u32x2* hp = reinterpret_cast<u32x2*>(reinterpret_cast<char*>(hx) + (i * NC32 + (tile >> 1)) * 2048 + out_voff);
                     hp[0] = __builtin_bit_cast(u32x2, hh);
                     hp[128] = __builtin_bit_cast(u32x2, hl);   // the low fragment, 1024 bytes on
-                    if (!RES && !FIRST) continue;
+                    if ((!RES && !FIRST) || to_heads) continue;
                 }
                 buf_st_h4(hh, rs_dst, out_voff, ob);
                 if (AO_KO == 10 || AO_KO == 12) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(u32x2, hl)[0], rs_dst, out_voff >> 1, ob + 1024, AO_AUX_ST);
@@ -414,6 +433,9 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
     // LDS writes, and stages its row 2 in its first iteration (row 1 is there already). For an even BW the two rows land
     // in swapped buffers, which the next layer is told through par. conv1's own buffers (one 32-channel block) lie inside
     // the next layer's buffer 0, so it hands row BW-2 to buffer 1 and row BW-1, after its last read, to buffer 0.
+    // (conv1 on its resident board, RES1, reads neither buffer as such: the board spans both, and the one barrier in front of
+    // its hand-off epilogues is what frees them.) A last layer that hands its two rows to the heads does so exactly as to a next
+    // layer; trunk_heads finds row BW-1 in the buffer `par` would name next and row BW-2 in the other one.
     const int po = (BW & 1) ? 0 : par;
     uint4* const hand2 = s_x + static_cast<size_t>(FIRST ? 1 : (BW + po) & 1) * NFRO * 64;       // output row BW-2
     uint4* const hand1 = s_x + static_cast<size_t>(FIRST ? 0 : (BW - 1 + po) & 1) * NFRO * 64;   // output row BW-1
@@ -424,7 +446,27 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
     AO_T(t_a1);
     // (all loads of the wave in flight at once: written as a loop over f the compiler emits load, wait, LDS write
     // per fragment -- nine serial HBM round trips, 10 us per layer)
-    if (FIRST) {
+    if (RES1) {
+        // the whole board: wave w builds the fragments of cells w, w + NT, ... (all byte loads first, then the LDS writes)
+        constexpr int KC = (A + NT - 1) / NT;
+        unsigned pb[KC];
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const int cell = tile + NT * k;
+            pb[k] = cell < A ? __builtin_amdgcn_raw_buffer_load_b8(rs_src, b * kPlaneRow(BW) + cell, 0, 0) : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const int cell = tile + NT * k;
+            if (cell < A) {
+                half8 h;
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    h[q] = (kq == 0 && ((pb[k] >> q) & 1u)) ? static_cast<_Float16>(1.0f) : static_cast<_Float16>(0.0f);
+                s_x[cell * 64 + lane] = __builtin_bit_cast(uint4, h);
+            }
+        }
+    } else if (FIRST) {
 #pragma unroll
         for (int k = 0; k < (NFR + NT - 1) / NT; ++k) {
             const int f = tile + NT * k;
@@ -462,17 +504,26 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
 
     for (int yi = 0; yi < BW; ++yi) {
         AO_T(t_r0);
-        const uint4* xs = s_x + static_cast<size_t>((yi + po) & 1) * NFR * 64;       // this row
+        const uint4* xs = RES1 ? s_x + static_cast<size_t>(yi) * BW * 64             // this row of the resident board
+                               : s_x + static_cast<size_t>((yi + po) & 1) * NFR * 64;   // this row
+        // fragment (cell xi, block c, half sp) of this row; the resident board holds one high-half fragment per cell
+        auto xfrag = [&](int xi, int c, int sp) {
+            return __builtin_bit_cast(half8, xs[(RES1 ? xi : (xi * NCI + c) * NSP + sp) * 64 + lane]);
+        };
         uint4* xn = s_x + static_cast<size_t>((yi + 1 + po) & 1) * NFR * 64;       // next row's buffer
         const int yn = yi + 1;                                                  // next input row
-        const bool stage_next = yn < BW && !(HANDED && yi == 0);                // (uniform) the last row has none; row 1 was handed over
+        const bool stage_next = !RES1 && yn < BW && !(HANDED && yi == 0);       // (uniform) the last row has none; row 1 was handed over
 #pragma unroll
         for (int slab = 0; slab < NB; ++slab) {
             const int c = slab / 3, dy = slab % 3;
             // (NB is even for the trunk layers: the buffer parity carries over from one row to the next)
             half8 (&w)[2][3] = (slab & 1) ? wB : wA;
             half8 (&wn)[2][3] = (slab & 1) ? wA : wB;
-            load_w(slab + 1, wn);
+            {
+                // the slab these weights are for: (row yi, slab + 1) or (row yi + 1, slab 0)
+                const int ty = slab + 1 < NB ? yi : yi + 1, tyo = ty + 1 - (slab + 1) % 3;
+                load_w(slab + 1, wn, ty < BW && tyo >= 0 && tyo < BW);
+            }
             if (!stage_next) {
                 // nothing to stage in this iteration
             } else if (dy == 1 && !AO_KO_NOSTAGE && FMT == 1 && !FIRST) {
@@ -518,14 +569,14 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
             }
             const int yo = yi + 1 - dy;
             if (yo >= 0 && yo < BW) {   // (uniform)
-                half8 xh = __builtin_bit_cast(half8, xs[((0 * NCI + c) * NSP + 0) * 64 + lane]);
-                half8 xl = __builtin_bit_cast(half8, xs[((0 * NCI + c) * NSP + 1) * 64 + lane]);
+                half8 xh = xfrag(0, c, 0);
+                half8 xl = RES1 ? xh : xfrag(0, c, 1);   // (resident board: no low halves, the xl * wh product is not issued)
 #pragma unroll
                 for (int xi = 0; xi < BW; ++xi) {
                     half8 nh = xh, nl = xl;
                     if (xi + 1 < BW && AO_KO != 2) {
-                        nh = __builtin_bit_cast(half8, xs[(((xi + 1) * NCI + c) * NSP + 0) * 64 + lane]);
-                        nl = __builtin_bit_cast(half8, xs[(((xi + 1) * NCI + c) * NSP + 1) * 64 + lane]);
+                        nh = xfrag(xi + 1, c, 0);
+                        nl = RES1 ? nh : xfrag(xi + 1, c, 1);
                     }
                     // input cell (yi, xi) feeds output row yo at cells xi-dx+1: xh*wh, xh*wl, xl*wh, ordered so that
                     // consecutive MFMAs hit different accumulators
@@ -556,8 +607,13 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
         row_arrive(s_cnt, lane);
 #endif
         if (yi >= 1 && (!AO_KO_NOEPI || (AO_KO == 4 && yi == 1))) {
-            if (HAND && hand_next && yi == BW - 1) epilogue(yi - 1, kHand, hand2);
-            else epilogue(yi - 1, kStore, nullptr);
+            if (HAND && hand_next && yi == BW - 1) {
+                // resident board: this wave has read its last fragment; the handed rows overwrite the board once all have
+                if (RES1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                epilogue(yi - 1, kHand, hand2);
+            } else {
+                epilogue(yi - 1, kStore, nullptr);
+            }
         }
         else if (yi >= 1 && (AO_KO == 14 || AO_KO == 15)) {
             // (no epilogue, but the row's accumulators stay "used": without a consumer the compiler deletes the MFMAs that
@@ -579,7 +635,9 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
         if ((yi + 1 < BW || (HAND && hand_next)) && AO_KO != 9) row_wait(s_cnt, static_cast<unsigned>(NT) * (rows_before + static_cast<unsigned>(yi) + 1u));
 #else
         // next row staged by all waves (LDS-direct loads count in vmcnt), this row's buffer free
-        if (AO_KO == 9) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        // (not for the resident board of conv1: nothing is staged between its rows)
+        if (RES1) {}
+        else if (AO_KO == 9) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #endif
         AO_T(t_r3);
@@ -879,16 +937,25 @@ __device__ __forceinline__ void trunk16h_body(const TrunkHArgs& a) {
 #ifdef AO_PROF
     for (int k = 0; k < 12; ++k) prof[k] = 0;
 #endif
+    // The last trunk layer hands its last two output rows to the heads in the LDS row buffers (4-byte format, at least one
+    // ResBlock; the last layer is a block's second conv and never flipped, so these are board rows BW-2 and BW-1)
+    static_assert(2 * BW * 16 <= NC32 * 2 * 64, "trunk_heads gives every (cell, board) of the two handed rows a thread of its own");
+    const bool to_heads = FMT == 0 && AO_KO == 0 && a.nlayers > 1;
     int par = 0;   // the row buffer in which the previous layer left this layer's input row 0 (see TrunkHLayerFn, hand-off)
     for (int l = 1; l < a.nlayers; ++l) {
         // l odd: first conv of a ResBlock (x -> t); l even: second conv (t -> x, + x in place)
         const bool second = (l & 1) == 0;
         TrunkHLayerFn<BW, NC32, NC32, 0, FMT, W16>::run(second ? bufB : bufA, second ? bufA : bufB, a.layers[l], second, s_x, tile, lane, pp,
-                                             (l & 1) != 0, s_cnt, static_cast<unsigned>(l) * BW, l + 1 < a.nlayers, par);
+                                             (l & 1) != 0, s_cnt, static_cast<unsigned>(l) * BW, l + 1 < a.nlayers || to_heads, par,
+                                             to_heads && l + 1 == a.nlayers);
         par = (par + BW - 1) & 1;
     }
     AO_T(t2);
-    if (AO_KO != 8) trunk_heads<BW, FMT == 1 ? 2 : 1>(a, reinterpret_cast<const float4*>(a.bufA), static_cast<size_t>(grp) * A, grp);
+    // (par: the buffer in which a further layer would find its input row 0 = the last layer's output row BW-1)
+    constexpr size_t kRowQ = static_cast<size_t>(BW) * NC32 * 2 * 64;
+    if (AO_KO != 8)
+        trunk_heads<BW, FMT == 1 ? 2 : 1>(a, reinterpret_cast<const float4*>(a.bufA), static_cast<size_t>(grp) * A, grp,
+                                          to_heads ? s_x + (par ^ 1) * kRowQ : nullptr, to_heads ? s_x + par * kRowQ : nullptr);
 #ifdef AO_PROF
     AO_T(t3);
     prof[5] = t3 - t2;
