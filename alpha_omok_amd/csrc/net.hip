@@ -28,6 +28,7 @@
 #include "net_board_h16.hpp"
 #include "net_small.hpp"
 #include "net_w16.hpp"
+#include "net_f16.hpp"
 
 
 // ==============================================================================================
@@ -98,6 +99,9 @@ struct ao_net : ao::HandleBase {
     // found out by ao_net_finalize, per export. products_req: 0 = use it when the weights allow, 3 = always three (ao_net_products)
     bool w16 = false;
     int products_req = 0;
+    // The opt-in fp16 forward (ao_net_precision; net_f16.hip): AO_NET_PRECISION_FP16 = the batches planned onto the resident trunk
+    // or k_boardh run its ONE-product form. Belongs to the net like products_req, survives ao_net_finalize, independent of it.
+    int precision_req = AO_NET_PRECISION_FP32;
     int trunk_fmt = -1;                            // activation format inside the resident split-fp16 trunk (kPairBytes): 0 = two fp16 halves (default), 1 = fp16 high half + one low byte (AO_TRUNK_FMT=1)
 };
 
@@ -149,6 +153,9 @@ static bool h16_supported(const ao_net* n) {
 // k_row16hk, the per-board path's k_conv_cells_h, k_boardh; what is left -- conv1 of the per-layer and per-board paths, k_layer16hk<B, 2> --
 // keeps its three products: on such weights the same bits)
 static bool two_products(const ao_net* n) { return n->w16 && n->products_req != 3; }
+// the one-product kernels run where the resident trunk / k_boardh are planned (modes 0 and 5; mode 6 never plans them, and under the
+// fp16-range fallback the net is on mode 2)
+static bool fp16_forward(const ao_net* n) { return n->precision_req == AO_NET_PRECISION_FP16 && h16_supported(n); }
 
 namespace ao {
 
@@ -605,7 +612,9 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             // (the kernel deals boards to workgroups in rounds of 8 groups -- a group's 16 boards on one XCD --, so the grid covers whole rounds)
             const dim3 grid(std::min((boards + 127) / 128 * 128, n->num_cu)), block(512);
             if (n->timing) n->timer.begin(s);
-            if (two_products(n)) {
+            if (fp16_forward(n)) {
+                AO_HIP(n, ao::launch_boardh_f16(n->device, n->B, bits, grid, s, a));
+            } else if (two_products(n)) {
                 AO_HIP(n, ao::launch_boardh_w16(n->device, n->B, bits, grid, s, a));
             } else
             switch (n->B) {
@@ -663,7 +672,10 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             a.layers[l].ovf = n->d_status;
         }
         if (n->timing) n->timer.begin(s);
-        if (two_products(n) && n->trunk_fmt != 1) {
+        if (fp16_forward(n)) {   // (AO_TRUNK_FMT is a choice between two fp32-equivalent formats: it does not apply)
+            if (n->B > 9) return n->fail("split-fp16 trunk: board larger than 9x9");
+            AO_HIP(n, ao::launch_trunk16h_f16(n->device, n->B, in_kind, groups, s, a));
+        } else if (two_products(n) && n->trunk_fmt != 1) {
             if (n->B > 9) return n->fail("split-fp16 trunk: board larger than 9x9");
             AO_HIP(n, ao::launch_trunk16h_w16(n->device, n->B, in_kind, groups, s, a));
         } else
@@ -1195,8 +1207,10 @@ static void dominant_name(const ao_net* n, int boards, int in_kind, std::string*
              ", waves split the contraction by input block, partial tiles exchanged through LDS)";
         f = conv;
     } else if (group == 16 && mode == 5 && board_resident(n, boards)) {
-        nm = std::string(two_products(n) ? "k_boardh_w16<" : "k_boardh<") + bw + (in_kind == 2 ? ", 2" : ", 1") + "> (" + (in_kind == 2 ? "conv1 + " : "") + std::to_string(2 * n->nb) +
-             " 3x3 convs in one launch as split-fp16 MFMA 16x16x32 (" + (two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate): "
+        const bool one = fp16_forward(n);
+        nm = std::string(one ? "k_boardh_f16<" : two_products(n) ? "k_boardh_w16<" : "k_boardh<") + bw + (in_kind == 2 ? ", 2" : ", 1") + "> (" + (in_kind == 2 ? "conv1 + " : "") + std::to_string(2 * n->nb) +
+             " 3x3 convs in one launch as " + (one ? "fp16" : "split-fp16") + " MFMA 16x16x32 (" +
+             (one ? "1 product: the opt-in fp16 forward, activations rounded once to fp16" : two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate): "
              "a workgroup = one board resident in LDS through all layers, the row's cells as the MFMA N dimension, column shifts as DPP row shifts)";
         f = 2.0 * n->nb * 2.0 * n->A * 9.0 * n->planes * n->planes * boards + (in_kind == 2 ? 2.0 * n->A * 9.0 * n->C * n->planes * boards : 0.0);
     } else if (group == 16 && mode == 5 && (layers_only(n) || !(n->B <= 9 && ((boards + 15) / 16 >= 192 || n->force_resident)))) {
@@ -1205,10 +1219,13 @@ static void dominant_name(const ao_net* n, int boards, int in_kind, std::string*
              "16-board groups x row chunks x column tiles)";
         f = conv;
     } else if (group == 16 && mode == 5) {
-        const bool two = two_products(n) && n->trunk_fmt != 1;
-        nm = std::string(in_kind == 2 ? "k_trunk16hb" : "k_trunk16h") + (two ? "_w16<" : "<") + bw + ", 4, " + std::to_string(n->trunk_fmt) + "> (conv1 + " +
-             std::to_string(2 * n->nb) + " 3x3 convs as split-fp16 MFMA 16x16x32 (" + (two ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate) + heads, one resident "
-             "launch; activations between layers as " + (n->trunk_fmt == 1 ? "fp16 high half + one low byte" : "two fp16 halves") + ")";
+        const bool one = fp16_forward(n);
+        const bool two = !one && two_products(n) && n->trunk_fmt != 1;
+        const int fmt = one ? 0 : n->trunk_fmt;
+        nm = std::string(in_kind == 2 ? "k_trunk16hb" : "k_trunk16h") + (one ? "_f16<" : two ? "_w16<" : "<") + bw + ", 4, " + std::to_string(fmt) + "> (conv1 + " +
+             std::to_string(2 * n->nb) + " 3x3 convs as " + (one ? "fp16" : "split-fp16") + " MFMA 16x16x32 (" +
+             (one ? "1 product: the opt-in fp16 forward" : two ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate) + heads, one resident "
+             "launch; activations between layers as " + (one ? "one fp16" : fmt == 1 ? "fp16 high half + one low byte" : "two fp16 halves") + ")";
         f = conv1 + 2.0 * n->nb * conv;
     } else if (group == 16) {
         nm = "k_trunk16<" + bw + "> (conv1 + " + std::to_string(2 * n->nb) + " 3x3 convs, one launch, fp32 MFMA 16x16x4)";
@@ -1234,6 +1251,17 @@ int ao_net_products(ao_net* n, int32_t request, int32_t* in_force, int32_t* weig
     if (request != -1) n->products_req = request;
     if (in_force) *in_force = two_products(n) ? 2 : 3;
     if (weights_fp16) *weights_fp16 = n->w16 ? 1 : 0;
+    return 0;
+}
+
+int ao_net_precision(ao_net* n, int32_t request, int32_t* in_force, int32_t* supported) {
+    if (request != -1 && request != AO_NET_PRECISION_FP32 && request != AO_NET_PRECISION_FP16)
+        return n->fail("ao_net_precision: request must be -1 (query), 0 (AO_NET_PRECISION_FP32) or 1 (AO_NET_PRECISION_FP16)");
+    if (request == AO_NET_PRECISION_FP16 && !h16_supported(n))
+        return n->fail("ao_net_precision: the fp16 forward needs a network the split-fp16 kernels cover (128 planes, at least one ResBlock)");
+    if (request != -1) n->precision_req = request;
+    if (in_force) *in_force = n->precision_req;
+    if (supported) *supported = h16_supported(n) ? 1 : 0;
     return 0;
 }
 

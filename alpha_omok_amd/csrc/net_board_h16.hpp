@@ -29,6 +29,8 @@
 //     workgroup -- run inside this kernel by heads_board_dev the heads cost 70 us per board): 23 launches become 2.
 // Same arithmetic family as the other split-fp16 kernels (3 products per multiply-add, fp32 accumulate, weights pre-scaled by a
 // power of two per layer); the summation order over taps / blocks differs, so results agree to fp32 rounding, not bit for bit.
+// Besides the three- and two-product forms (k_boardh, k_boardh_w16) there is the one-product form of the OPT-IN fp16 forward
+// (k_boardh_f16, net_f16.hip; ao_net_precision): plain fp16 operands, every activation rounded once to fp16 -- see boardh_body, NPROD.
 #pragma once
 
 // Timing knock-outs (-DAO_BKO=n, WRONG RESULTS, experiment builds only: AO_BUILD_TAG): 1 no DPP shifts (every tap column reads the
@@ -70,8 +72,15 @@ __device__ __forceinline__ half8 dpp_shift_h8(const half8 v) {
 // takes any float planes) and its output is gathered from the group layout
 // W16: the conv weights are fp16 numbers (zero low halves): two products per multiply-add, no low weight fragments (36 registers
 // less) -- see TrunkHLayerFn
-template <int BW, int IN, bool W16>
+// NPROD (products per multiply-add, as in TrunkHLayerFn): 3, 2 (W16) or 1 -- the opt-in fp16 forward (ao_net_precision, launched from
+// net_f16.hip): xh * wh alone. No low weight fragments, no low activation fragment is read, shifted or written (the low slots of
+// the board in LDS stay unused); every activation is rounded once to fp16 after ReLU and clamp, and the ResBlock input kept in
+// registers (xres) and the values fed to the head 1x1 convs are that rounded number. The IN 1 gather reads the high halves of
+// conv1's output alone (conv1 itself ran as k_layer16h, which has no one-product form: all its products, then one rounding).
+template <int BW, int IN, int NPROD>
 __device__ __forceinline__ void boardh_body(const BoardHArgs& a) {
+    constexpr bool W16 = NPROD <= 2, F16 = NPROD == 1;
+    static_assert(!F16 || AO_BKO == 0, "the one-product form has no knock-out builds");
     static_assert(BW >= 10 && BW <= 15, "rows are padded to 16 cells and need at least one zero pad");
     __shared__ uint8_t s_pl[256];                  // IN 2: the board's plane bytes
     __shared__ __attribute__((aligned(16))) float s_w3[384];
@@ -165,11 +174,13 @@ __device__ __forceinline__ void boardh_body(const BoardHArgs& a) {
                         const float v = n < BW ? fminf(fmaxf(f[k], 0.f), 65504.f) : 0.f;
                         hh[k] = static_cast<_Float16>(v);
                         hl[k] = static_cast<_Float16>(v - static_cast<float>(hh[k]));
+                        if (F16) xres[y][k] = static_cast<float>(hh[k]);
+                        else
                         if (AO_BKO != 6) xres[y][k] = static_cast<float>(hh[k]) + static_cast<float>(hl[k]);   // (what the gather of IN 1 reconstructs)
                     }
                     char* frag = reinterpret_cast<char*>(s_x + ((y * NCI + (tile >> 1)) * 2) * 64);
                     *reinterpret_cast<half4*>(frag + out_off) = hh;
-                    *reinterpret_cast<half4*>(frag + 1024 + out_off) = hl;
+                    if (!F16) *reinterpret_cast<half4*>(frag + 1024 + out_off) = hl;
                 }
             }
         } else {
@@ -181,19 +192,21 @@ __device__ __forceinline__ void boardh_body(const BoardHArgs& a) {
                 if (n < BW) {
                     const char* p = gact + (static_cast<size_t>(row * BW + n) * NCI + kb) * 2048u + (kq * 16 + bslot) * 16;
                     vh = *reinterpret_cast<const uint4*>(p);
-                    vl = *reinterpret_cast<const uint4*>(p + 1024);
+                    if (!F16) vl = *reinterpret_cast<const uint4*>(p + 1024);
                 }
                 s_x[(f * 2 + 0) * 64 + lane] = vh;
-                s_x[(f * 2 + 1) * 64 + lane] = vl;
+                if (!F16) s_x[(f * 2 + 1) * 64 + lane] = vl;
             }
 #pragma unroll
             for (int y = 0; y < BW; ++y) {   // x = xh + xl of conv1's output, this wave's cout tile in D-operand order
                 xres[y] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (n < BW && AO_BKO != 5 && AO_BKO != 6) {
                     const char* p = gact + (static_cast<size_t>(y * BW + n) * NCI + (tile >> 1)) * 2048u + (((tile & 1) * 2 + (kq >> 1)) * 16 + bslot) * 16 + (kq & 1) * 8;
-                    const half4 hh = *reinterpret_cast<const half4*>(p), hl = *reinterpret_cast<const half4*>(p + 1024);
+                    const half4 hh = *reinterpret_cast<const half4*>(p);
+                    half4 hl = {};
+                    if (!F16) hl = *reinterpret_cast<const half4*>(p + 1024);
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) xres[y][c] = static_cast<float>(hh[c]) + static_cast<float>(hl[c]);
+                    for (int c = 0; c < 4; ++c) xres[y][c] = F16 ? static_cast<float>(hh[c]) : static_cast<float>(hh[c]) + static_cast<float>(hl[c]);
                 }
             }
         }
@@ -232,15 +245,16 @@ __device__ __forceinline__ void boardh_body(const BoardHArgs& a) {
                 for (int r = 0; r < BW; ++r) {
                     half8 xh[3], xl[3];
                     xh[1] = __builtin_bit_cast(half8, s_x[((r * NCI + kb) * 2 + 0) * 64 + lane]);
-                    xl[1] = __builtin_bit_cast(half8, s_x[((r * NCI + kb) * 2 + 1) * 64 + lane]);
+                    if (!F16) xl[1] = __builtin_bit_cast(half8, s_x[((r * NCI + kb) * 2 + 1) * 64 + lane]);
                     // tap column kx reads input cell (output cell + kx - 1): kx = 0 from the lane below, kx = 2 from the lane above
                     xh[0] = AO_BKO == 1 ? xh[1] : dpp_shift_h8<kDppRowShr1>(xh[1]);
-                    xl[0] = AO_BKO == 1 ? xl[1] : dpp_shift_h8<kDppRowShr1>(xl[1]);
+                    if (!F16) xl[0] = AO_BKO == 1 ? xl[1] : dpp_shift_h8<kDppRowShr1>(xl[1]);
                     xh[2] = AO_BKO == 1 ? xh[1] : dpp_shift_h8<kDppRowShl1>(xh[1]);
-                    xl[2] = AO_BKO == 1 ? xl[1] : dpp_shift_h8<kDppRowShl1>(xl[1]);
+                    if (!F16) xl[2] = AO_BKO == 1 ? xl[1] : dpp_shift_h8<kDppRowShl1>(xl[1]);
 #pragma unroll
                     for (int pr = 0; pr < 3; ++pr) {          // products xh*wh, xh*wl, xl*wh
                         if (W16 && pr == 1) continue;         // (wl == 0)
+                        if (F16 && pr == 2) continue;         // (fp16 forward: the activation operand is its high half alone)
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx) {
 #pragma unroll
@@ -280,6 +294,7 @@ __device__ __forceinline__ void boardh_body(const BoardHArgs& a) {
                     v[c] = n < BW ? fminf(fmaxf(f[c], 0.f), 65504.f) : 0.f;   // ReLU, fp16-range clamp (reported), zero pad cell
                     hh[c] = static_cast<_Float16>(v[c]);
                     hl[c] = static_cast<_Float16>(v[c] - static_cast<float>(hh[c]));
+                    if (F16) v[c] = static_cast<float>(hh[c]);   // what the heads and the next block's residual read: the stored fp16
                 }
                 if (last) {
                     // The trunk's output never leaves the chip (round 6; it was 118 MB of fp32 NHWC per launch of 1024 boards for a
@@ -307,7 +322,7 @@ __device__ __forceinline__ void boardh_body(const BoardHArgs& a) {
                 }
                 char* frag = reinterpret_cast<char*>(s_x + ((y * NCI + (tile >> 1)) * 2) * 64);
                 *reinterpret_cast<half4*>(frag + out_off) = hh;
-                *reinterpret_cast<half4*>(frag + 1024 + out_off) = hl;
+                if (!F16) *reinterpret_cast<half4*>(frag + 1024 + out_off) = hl;
                 if (second && AO_BKO != 6) xres[y] = f32x4{v[0], v[1], v[2], v[3]};   // the next block's input
             }
             __syncthreads();
@@ -329,11 +344,15 @@ __device__ __forceinline__ void boardh_body(const BoardHArgs& a) {
 
 template <int BW, int IN>
 __global__ __launch_bounds__(512, 1) void k_boardh(BoardHArgs a) {
-    boardh_body<BW, IN, false>(a);
+    boardh_body<BW, IN, 3>(a);
 }
 template <int BW, int IN>
 __global__ __launch_bounds__(512, 1) void k_boardh_w16(BoardHArgs a) {   // launched from net_w16.hip
-    boardh_body<BW, IN, true>(a);
+    boardh_body<BW, IN, 2>(a);
+}
+template <int BW, int IN>
+__global__ __launch_bounds__(512, 1) void k_boardh_f16(BoardHArgs a) {   // the one-product form, launched from net_f16.hip
+    boardh_body<BW, IN, 1>(a);
 }
 
 }  // namespace ao

@@ -343,8 +343,9 @@ __device__ __forceinline__ void trunk_layer(const float4* __restrict__ src, floa
 // 1x1 convs + BN + ReLU into LDS (flatten order c*A + cell, as the reference's .view), then one
 // wave per board: policy_fc + softmax, value_fc1 + ReLU + value_fc2 + tanh.
 // H16: 1 = the activations are in the split-fp16 layout of k_trunk16h (x = high half + low half), 2 = its 3-byte form
-// (fp16 high half + one low byte, kPairBytes(1) in net_trunk_h16.hpp), 0 = fp32
-// hand2 / hand1 (H16 = 1 only, null otherwise): board rows BW-2 and BW-1 of the final tensor are not in `act` but in these LDS
+// (fp16 high half + one low byte, kPairBytes(1) in net_trunk_h16.hpp), 0 = fp32, 3 = the layout of 1 with the HIGH half alone
+// (the one-product fp16 forward: the activation is one fp16, the low slot of a pair was never written and is not read)
+// hand2 / hand1 (H16 = 1 and 3 only, null otherwise): board rows BW-2 and BW-1 of the final tensor are not in `act` but in these LDS
 // row buffers, left there by the last trunk layer in the layout of its stores (2 KB per (cell, 32-channel block): high
 // fragment, low fragment). They fill the dynamic LDS that s_w3 / s_h alias, so their cells go first -- one cell per thread,
 // the 1x1 conv weights straight from global memory (the same numbers in the same fmaf order), the three sums kept in
@@ -385,7 +386,9 @@ __device__ __forceinline__ void trunk_heads(const Args& a, const float4* act, si
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
                         const unsigned hb = (hw[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-                        if (H16 == 2) {
+                        if (H16 == 3) {
+                            x[k] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<unsigned short>(hb)));
+                        } else if (H16 == 2) {
                             const unsigned t = (hb << 8) | ((lw[k >> 2] >> (8 * (k & 3))) & 0xffu);
                             x[k] = __uint_as_float(t ? (t << 5) + 0x38000000u : 0u);
                         } else {
@@ -408,7 +411,7 @@ __device__ __forceinline__ void trunk_heads(const Args& a, const float4* act, si
             }
         }
     };
-    const bool handed = H16 == 1 && hand2 != nullptr;   // (uniform)
+    const bool handed = (H16 == 1 || H16 == 3) && hand2 != nullptr;   // (uniform)
     const bool mine = handed && (tid >> 4) < 2 * BW;    // this thread owns (cell A - 2 BW + (tid >> 4), board tid & 15)
     float m0 = 0.f, m1 = 0.f, m2 = 0.f;
     if (handed) {
@@ -418,7 +421,7 @@ __device__ __forceinline__ void trunk_heads(const Args& a, const float4* act, si
             cell_sums([&](int c, int oc, uint4& hv, uint4& lv) {
                 const char* base = row + (i * nblk + c) * 2048 + (oc * 16 + (tid & 15)) * 16;
                 hv = *reinterpret_cast<const uint4*>(base);
-                lv = *reinterpret_cast<const uint4*>(base + 1024);
+                if (H16 != 3) lv = *reinterpret_cast<const uint4*>(base + 1024);
             }, a.w3, m0, m1, m2);
         }
         __syncthreads();   // the handed rows are consumed: s_w3 / s_h may overwrite them
@@ -434,7 +437,9 @@ __device__ __forceinline__ void trunk_heads(const Args& a, const float4* act, si
                 const char* base = reinterpret_cast<const char*>(act) +
                                    ((gbase + cell) * nblk + c) * (H16 == 2 ? 1536 : 2048) + (oc * 16 + b) * 16;
                 hv = *reinterpret_cast<const uint4*>(base);
-                if (H16 == 2) {
+                if (H16 == 3) {
+                    // (no low half)
+                } else if (H16 == 2) {
                     const uint2 t = *reinterpret_cast<const uint2*>(base + 1024 - (oc * 16 + b) * 8);
                     lv = make_uint4(t.x, t.y, 0u, 0u);
                 } else {

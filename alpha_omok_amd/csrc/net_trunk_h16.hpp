@@ -1,6 +1,10 @@
 // net_trunk_h16.hpp -- the conv stack with the fp32 contraction carried by fp16 MFMAs on split operands:
 // k_trunk16h (group-resident) and k_layer16h (per layer). Included by net.hip after net_trunk_f32.hpp
 // (trunk_heads is shared).
+// Products per multiply-add (TrunkHLayerFn, NPROD): 3 = the fp32-equivalent contraction xh*wh + xh*wl + xl*wh on any fp32 weights,
+// 2 = the same bits when the weights are fp16 numbers (net_w16.hip), 1 = the OPT-IN fp16 forward of the resident trunk
+// (k_trunk16h_f16 / k_trunk16hb_f16, net_f16.hip; ao_net_precision): xh*wh alone, one fp16 per stored activation, not
+// fp32-equivalent. The per-layer kernels below (k_layer16h) have the forms 3 and 2 only.
 #pragma once
 
 #include <type_traits>
@@ -177,8 +181,18 @@ __device__ __forceinline__ unsigned lo8_word(float vs) {   // vs: scaled, clampe
 // bits as the three-product form on such weights (an MFMA on a zero operand leaves its accumulator as it was), a third fewer
 // MFMAs on a power-limited kernel and no low-half weight loads. ao_net_finalize finds out (net.hip, Net::w16); checkpoints get
 // there by keeping their conv weights on the fp16 grid (tools/train_omok.py --fp16-grid-weights).
-template <int BW, int NC32, int NCI, int KIND, int FMT = 0, bool W16 = false>
+// NPROD = 1, the opt-in fp16 forward (ao_net_precision, launched from net_f16.hip): ONE product, xh * wh. The weight operand is the
+// high half alone (fp16(w * 2^s), whatever the weights), every activation is rounded once to fp16 (to nearest even, after ReLU
+// and clamp) and everything downstream -- the next conv, the block's residual add, the heads -- reads that rounded value. The LDS
+// and HBM geometry is the one of the split forms (2 KB per (cell, block) pair, hand-off rows, par, flip order, conv1's resident
+// board), with the low slot of every pair UNUSED: it is never staged, stored, handed over or read. Float planes of conv1 that
+// are not fp16 numbers are rounded to nearest (load_planes(., 0)); the engine's 0 / 1 planes are taken as they are.
+template <int BW, int NC32, int NCI, int KIND, int FMT = 0, int NPROD = 3>
 struct TrunkHLayerFn {
+static_assert(NPROD >= 1 && NPROD <= 3, "products per multiply-add: 3 (any fp32 weights), 2 (weights on the fp16 grid), 1 (fp16 forward)");
+static constexpr bool W16 = NPROD <= 2;   // no xh * wl product, no low weight halves
+static constexpr bool F16 = NPROD == 1;   // no xl * wh product either, no low activation halves anywhere
+static_assert(!F16 || (FMT == 0 && AO_KO == 0 && !AO_CONV1_SPLIT), "the one-product form exists for the 4-byte geometry only");
 static __device__ __forceinline__ void run(const void* src, uint4* dst, const TrunkHLayer& L, const bool RES, uint4* s_x,
                                            int tile, int lane, unsigned long long* prof, const bool flip,
                                            unsigned* s_cnt, const unsigned rows_before, const bool hand_next, const int par,
@@ -318,7 +332,7 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
                     } else if (AO_KO == 10 || AO_KO == 12) {
                         const unsigned u = __builtin_amdgcn_raw_buffer_load_b32(rs_dst, out_voff >> 1, ob + 1024, AO_AUX_RES);
                         rl[k] = __builtin_bit_cast(half4, u32x2{u, u});
-                    } else {
+                    } else if (!F16) {
                         rl[k] = buf_ld_h4(rs_dst, out_voff, ob + 1024);
                     }
                 }
@@ -336,6 +350,9 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             f[r] += lo8_scaled((hb[r >> 1] >> (16 * (r & 1))) & 0xffffu, (rb[k] >> (8 * r)) & 0xffu);
+                    } else if (F16) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) f[r] += static_cast<float>(rh[k][r]);   // the block's input as it was stored: one fp16
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) f[r] += static_cast<float>(rh[k][r]) + static_cast<float>(rl[k][r]);
@@ -360,16 +377,17 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
                     // BatchNorm-ed residual tower produces) finite instead of turning the board into inf / NaN; the
                     // event is reported through L.ovf (ao_net_status), the result of such a forward is not fp32-equivalent
                     const float v = fminf(fmaxf(f[r], 0.f), 65504.f);
-                    hh[r] = static_cast<_Float16>(v);
-                    hl[r] = static_cast<_Float16>(v - static_cast<float>(hh[r]));
+                    hh[r] = static_cast<_Float16>(v);   // (round to nearest even: in the one-product form this IS the activation)
+                    if (!F16) hl[r] = static_cast<_Float16>(v - static_cast<float>(hh[r]));
                 }
                 if (HO) {
                     u32x2* hp = reinterpret_cast<u32x2*>(reinterpret_cast<char*>(hx) + (i * NC32 + (tile >> 1)) * 2048 + out_voff);
                     hp[0] = __builtin_bit_cast(u32x2, hh);
-                    hp[128] = __builtin_bit_cast(u32x2, hl);   // the low fragment, 1024 bytes on
+                    if (!F16) hp[128] = __builtin_bit_cast(u32x2, hl);   // the low fragment, 1024 bytes on
                     if ((!RES && !FIRST) || to_heads) continue;
                 }
                 buf_st_h4(hh, rs_dst, out_voff, ob);
+                if (F16) continue;   // (no low half exists)
                 if (AO_KO == 10 || AO_KO == 12) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(u32x2, hl)[0], rs_dst, out_voff >> 1, ob + 1024, AO_AUX_ST);
                 else
                 buf_st_h4(hl, rs_dst, out_voff, ob + 1024);
@@ -470,7 +488,7 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
 #pragma unroll
         for (int k = 0; k < (NFR + NT - 1) / NT; ++k) {
             const int f = tile + NT * k;
-            if (f < NFR) s_x[f * 64 + lane] = __builtin_bit_cast(uint4, load_planes(f >> 1, f & 1));
+            if (f < NFR && !(F16 && (f & 1))) s_x[f * 64 + lane] = __builtin_bit_cast(uint4, load_planes(f >> 1, f & 1));
         }
     } else if (HANDED) {
         // input rows 0 and 1 are in the row buffers already
@@ -553,6 +571,19 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
                         }
                     }
                 }
+            } else if (dy == 1 && F16) {
+                // one product: the HIGH fragments of the next row alone (fragment 2p of pair p), a share of this wave's pairs per block
+                constexpr int KP = ((NPAIR + NT - 1) / NT + NCI - 1) / NCI;
+#pragma unroll
+                for (int k = 0; k < KP; ++k) {
+                    const int p = tile + NT * (c * KP + k);
+                    if (p < NPAIR) {
+                        if (FIRST) xn[2 * p * 64 + lane] = __builtin_bit_cast(uint4, load_planes(yn * BW + p, 0));
+                        else
+                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, (__attribute__((address_space(3))) void*)(xn + 2 * p * 64),
+                                                                     16, lane16, (py(yn) * NFR + 2 * p) * 1024, 0, AO_AUX_STAGE);
+                    }
+                }
             } else if (dy == 1 && (!AO_KO_NOSTAGE || FIRST)) {
                 // next input row into LDS, a share per block (always-executed slab)
 #pragma unroll
@@ -570,13 +601,13 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
             const int yo = yi + 1 - dy;
             if (yo >= 0 && yo < BW) {   // (uniform)
                 half8 xh = xfrag(0, c, 0);
-                half8 xl = RES1 ? xh : xfrag(0, c, 1);   // (resident board: no low halves, the xl * wh product is not issued)
+                half8 xl = (RES1 || F16) ? xh : xfrag(0, c, 1);   // (resident board / one product: no low halves, the xl * wh product is not issued)
 #pragma unroll
                 for (int xi = 0; xi < BW; ++xi) {
                     half8 nh = xh, nl = xl;
                     if (xi + 1 < BW && AO_KO != 2) {
                         nh = xfrag(xi + 1, c, 0);
-                        nl = RES1 ? nh : xfrag(xi + 1, c, 1);
+                        nl = (RES1 || F16) ? nh : xfrag(xi + 1, c, 1);
                     }
                     // input cell (yi, xi) feeds output row yo at cells xi-dx+1: xh*wh, xh*wl, xl*wh, ordered so that
                     // consecutive MFMAs hit different accumulators
@@ -584,6 +615,7 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
                     for (int pr = 0; pr < NPR; ++pr) {
                         if (BITS && pr == 2) continue;   // bit planes are 0 / 1: their low halves are zero, no xl * wh product
                         if (W16 && pr == 1) continue;    // fp16 weights: their low halves are zero, no xh * wl product
+                        if (F16 && pr == 2) continue;    // fp16 forward: the activation operand is its high half alone
 #pragma unroll
                         for (int dx = 0; dx < 3; ++dx) {
                             const int i = xi - dx + 1;
@@ -901,7 +933,7 @@ __global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_layer16h_w16(LayerHArgs a)
     layer16h_body<BW, XT, NC32, KIND, true>(a);
 }
 
-template <int BW, int NC32, int INK, int FMT, bool W16 = false>   // INK: 1 fp32 plane batch, 2 bit planes (see trunk_h_layer); FMT: see kPairBytes
+template <int BW, int NC32, int INK, int FMT, int NPROD = 3>   // NPROD: see TrunkHLayerFn; INK: 1 fp32 plane batch, 2 bit planes (see trunk_h_layer); FMT: see kPairBytes
 __device__ __forceinline__ void trunk16h_body(const TrunkHArgs& a) {
     static_assert(FMT == 0 || AO_SPLIT_BARRIER == 0, "the split row barrier is implemented for the 4-byte format only");
     constexpr int A = BW * BW;
@@ -923,10 +955,10 @@ __device__ __forceinline__ void trunk16h_body(const TrunkHArgs& a) {
     // conv1: fp32 planes -> x
     AO_T(t0);
     if (INK == 2)
-        TrunkHLayerFn<BW, NC32, 1, 2, FMT, W16>::run(reinterpret_cast<const uint8_t*>(a.in0) + static_cast<size_t>(grp) * 16 * kPlaneRow(BW), bufA,
+        TrunkHLayerFn<BW, NC32, 1, 2, FMT, NPROD>::run(reinterpret_cast<const uint8_t*>(a.in0) + static_cast<size_t>(grp) * 16 * kPlaneRow(BW), bufA,
                                       a.layers[0], false, s_x, tile, lane, pp, false, s_cnt, 0u, a.nlayers > 1, 0);
     else
-        TrunkHLayerFn<BW, NC32, 1, 1, FMT, W16>::run(a.in0 + static_cast<size_t>(grp) * A * 8 * 16, bufA, a.layers[0], false, s_x, tile, lane, pp, false,
+        TrunkHLayerFn<BW, NC32, 1, 1, FMT, NPROD>::run(a.in0 + static_cast<size_t>(grp) * A * 8 * 16, bufA, a.layers[0], false, s_x, tile, lane, pp, false,
                                       s_cnt, 0u, a.nlayers > 1, 0);
     AO_T(t1);
     if (ko_fill) {   // data-like LDS rows for the trunk layers, never refreshed (see AO_KO)
@@ -945,7 +977,7 @@ __device__ __forceinline__ void trunk16h_body(const TrunkHArgs& a) {
     for (int l = 1; l < a.nlayers; ++l) {
         // l odd: first conv of a ResBlock (x -> t); l even: second conv (t -> x, + x in place)
         const bool second = (l & 1) == 0;
-        TrunkHLayerFn<BW, NC32, NC32, 0, FMT, W16>::run(second ? bufB : bufA, second ? bufA : bufB, a.layers[l], second, s_x, tile, lane, pp,
+        TrunkHLayerFn<BW, NC32, NC32, 0, FMT, NPROD>::run(second ? bufB : bufA, second ? bufA : bufB, a.layers[l], second, s_x, tile, lane, pp,
                                              (l & 1) != 0, s_cnt, static_cast<unsigned>(l) * BW, l + 1 < a.nlayers || to_heads, par,
                                              to_heads && l + 1 == a.nlayers);
         par = (par + BW - 1) & 1;
@@ -954,7 +986,7 @@ __device__ __forceinline__ void trunk16h_body(const TrunkHArgs& a) {
     // (par: the buffer in which a further layer would find its input row 0 = the last layer's output row BW-1)
     constexpr size_t kRowQ = static_cast<size_t>(BW) * NC32 * 2 * 64;
     if (AO_KO != 8)
-        trunk_heads<BW, FMT == 1 ? 2 : 1>(a, reinterpret_cast<const float4*>(a.bufA), static_cast<size_t>(grp) * A, grp,
+        trunk_heads<BW, FMT == 1 ? 2 : NPROD == 1 ? 3 : 1>(a, reinterpret_cast<const float4*>(a.bufA), static_cast<size_t>(grp) * A, grp,
                                           to_heads ? s_x + (par ^ 1) * kRowQ : nullptr, to_heads ? s_x + par * kRowQ : nullptr);
 #ifdef AO_PROF
     AO_T(t3);
@@ -978,11 +1010,20 @@ __global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_trunk16hb(TrunkHArgs a) {
 // the two-product forms (see TrunkHLayerFn, W16): launched from net_w16.hip
 template <int BW, int NC32, int FMT>
 __global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_trunk16h_w16(TrunkHArgs a) {
-    trunk16h_body<BW, NC32, 1, FMT, true>(a);
+    trunk16h_body<BW, NC32, 1, FMT, 2>(a);
 }
 template <int BW, int NC32, int FMT>
 __global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_trunk16hb_w16(TrunkHArgs a) {
-    trunk16h_body<BW, NC32, 2, FMT, true>(a);
+    trunk16h_body<BW, NC32, 2, FMT, 2>(a);
+}
+// the one-product forms (the opt-in fp16 forward, see TrunkHLayerFn, NPROD = 1): launched from net_f16.hip
+template <int BW, int NC32, int FMT>
+__global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_trunk16h_f16(TrunkHArgs a) {
+    trunk16h_body<BW, NC32, 1, FMT, 1>(a);
+}
+template <int BW, int NC32, int FMT>
+__global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_trunk16hb_f16(TrunkHArgs a) {
+    trunk16h_body<BW, NC32, 2, FMT, 1>(a);
 }
 
 }  // namespace ao

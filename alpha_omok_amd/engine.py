@@ -126,6 +126,20 @@ class Net:
         self._check(self._L.ao_net_products(self._h, int(request), C.byref(a), C.byref(b)), "ao_net_products")
         return a.value, bool(b.value)
 
+    PRECISIONS = ("fp32", "fp16")       # AO_NET_PRECISION_FP32 / AO_NET_PRECISION_FP16
+
+    def precision(self, request=None):
+        """"fp32" (the default: every forward fp32-equivalent) or "fp16" (the opt-in plain-fp16 forward: one MFMA product per
+        multiply-add, activations rounded once to fp16, on the batches planned onto the resident / board-resident trunk) --
+        ao_net_precision. request: None = query, or either string. Belongs to this Net and survives load_state_dict; "fp16" on a
+        network the split-fp16 kernels do not cover raises EngineError."""
+        if request is not None and request not in self.PRECISIONS:
+            raise ValueError("precision must be 'fp32' or 'fp16', not %r" % (request,))
+        a, b = C.c_int32(0), C.c_int32(0)
+        req = -1 if request is None else self.PRECISIONS.index(request)
+        self._check(self._L.ao_net_precision(self._h, req, C.byref(a), C.byref(b)), "ao_net_precision")
+        return self.PRECISIONS[a.value]
+
     def dominant_kernel(self, boards):
         """(name, algorithmic FLOPs per launch) of the kernel conv_timing() measures."""
         buf = C.create_string_buffer(256)

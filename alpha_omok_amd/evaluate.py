@@ -98,11 +98,13 @@ last_search_totals = {}      # evaluate_batched: searches, simulations asked for
 class _ZeroSide:
     """One network's side of evaluate_batched: a G-game engine + evaluator; searches the masked matches at their ids."""
 
-    def __init__(self, model, sims, board_size, inplanes, G, device, early_stop=False, tactics=None):
+    def __init__(self, model, sims, board_size, inplanes, G, device, early_stop=False, tactics=None, forward_precision=None):
         from .engine import Engine
         from .evaluator import Evaluator
         self.eng = Engine(board_size, sims, inplanes, games=G, noise=False, device=device)
         self.ev, self.model = Evaluator(device), model
+        if forward_precision is not None:
+            self.ev.net_precision = forward_precision    # Net.precision of this side's exported network ("fp16": the opt-in one-product forward)
         self.tau0 = np.zeros(G, np.int8)
         self.early_stop = True if early_stop else None   # every search here has tau == 0: its result is the leader alone
         self.tactics = tactics if tactics else None      # Engine.search(tactics=): the forced-win solver restricts every root first
@@ -154,7 +156,7 @@ class _RolloutSide:
 
 def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mcts_enemy=None, inplanes=5, n_match=12,
                      player_elo=1500.0, enemy_elo=1500.0, seed=0, device=0, max_plies=None, monitor_model=None,
-                     n_mcts_monitor=None, early_stop=False, tactics=None):
+                     n_mcts_monitor=None, early_stop=False, tactics=None, forward_precision=None):
     """All n_match games at once (colours swapped every game, eval_main.py:213-333). `*_model`: whatever
     ZeroAgent.model accepts (a PVNet-shaped module runs on the native forward), or 'puct' / 'uct' for the rollout
     agents (eval_main.py:68-73,106-111). With a rollout PLAYER and a `monitor_model`, the monitor ZeroAgent searches
@@ -163,7 +165,13 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     early_stop=True: the ZeroAgent sides (both of them) end a search once its move is decided (utils.move_decided): the same move,
     fewer simulations; the later plies then search on smaller inherited trees, so a match need not be the one full searches play.
     tactics: Engine.search(tactics=) for the ZeroAgent sides -- True or a dict for both, or a pair (player's, enemy's) with None for
-    a side that searches plainly, so that the switch's strength can be measured against the same network without it."""
+    a side that searches plainly, so that the switch's strength can be measured against the same network without it.
+    forward_precision: "fp32" / "fp16" (Net.precision of the exported networks of the ZeroAgent sides) for both, or a pair (player's,
+    enemy's); None leaves the default. A side given as an engine.Net keeps the precision it was set to."""
+    if forward_precision is None or isinstance(forward_precision, str):
+        forward_precision = (forward_precision, forward_precision)
+    if len(forward_precision) != 2 or any(p not in (None, "fp32", "fp16") for p in forward_precision):
+        raise ValueError("forward_precision: 'fp32', 'fp16' or a pair (player, enemy) of them")
     n_mcts_enemy = n_mcts_player if n_mcts_enemy is None else n_mcts_enemy
     G = n_match
     win_mark = 3 if board_size == 3 else 5
@@ -172,12 +180,13 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     if len(side_tactics) != 2:
         raise ValueError("tactics: one value for both sides or a pair (player, enemy)")
 
-    def make(model, sims, tac):
+    def make(model, sims, tac, prec):
         if isinstance(model, str):
             return _RolloutSide(model, sims, board_size, G, device)
-        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac)
+        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac, prec)
 
-    sides = [make(player_model, n_mcts_player, side_tactics[0]), make(enemy_model, n_mcts_enemy, side_tactics[1])]
+    sides = [make(player_model, n_mcts_player, side_tactics[0], forward_precision[0]),
+             make(enemy_model, n_mcts_enemy, side_tactics[1], forward_precision[1])]
     monitor = None
     if monitor_model is not None and isinstance(player_model, str):
         monitor = _ZeroSide(monitor_model, n_mcts_monitor or n_mcts_enemy, board_size, inplanes, G, device)

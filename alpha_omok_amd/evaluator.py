@@ -23,6 +23,7 @@ class Evaluator:
         self._warned_width = False
         self._frozen = False   # freeze(): searches keep the weights exported last, whatever happens to the module (main.train_async)
         self.strict_native = False   # True: a PVNet the native forward cannot take raises instead of running on its torch module
+        self.net_precision = "fp32"   # Net.precision of the exported network ("fp16": the opt-in one-product forward; main.configure(forward_precision=))
         self.net_mode = 0      # ao_net_set_mode of the exported network (6: one kernel family for every batch size)
 
     def native_net(self, model, board_size, inplanes):
@@ -60,6 +61,7 @@ class Evaluator:
             sd = model.state_dict()
             self._net.load_state_dict(sd if width == cfg[2] else pvnet.pad_state_dict(sd, width))
             self._net.set_mode(self.net_mode)             # after every export, 0 included: an fp16-range fallback of the OLD weights ends here
+            self._net.precision(self.net_precision)       # (the library keeps it across exports; a Net built anew starts on "fp32")
             self._key = (cfg, version)
             try:
                 self._ref = weakref.ref(model)

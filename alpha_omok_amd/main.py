@@ -113,7 +113,7 @@ _grid_masters = []           # ... [(parameter, fp32 master copy)]: Adam moves t
 def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_planes=None, seed=None,
               model=None, gpu=None, noise=True, device_replay=False, node_cap=None, strict=None, reproducible=False,
               carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None,
-              early_stop=False, fast_sims=None, full_prob=0.25, tactics=None):
+              early_stop=False, fast_sims=None, full_prob=0.25, tactics=None, forward_precision="fp32"):
     """Build `Agent`, `Agent.model` and `optimizer` (main.py:58-85). Call instead of editing constants.
     node_cap: expanded-node capacity of a game's tree arena (0 = 16*(n_mcts+1) where 40 % of the HBM
     holds that for all games, at least 4*(n_mcts+1); -1 = grow into the free HBM);
@@ -151,10 +151,20 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     not depend on the slot, the rank or MAX_CONCURRENT. playout_totals counts both kinds.
     tactics=True or dict(max_depth, max_nodes, solved_sims): every self-play search asks the forced-win solver about its roots first
     (Engine.search(tactics=...)): a game with a proven forced win searches only the winning first moves, a game facing one only the
-    replies not proven to lose. Off by default."""
+    replies not proven to lose. Off by default.
+    forward_precision="fp16": the exported network's searches run the opt-in plain-fp16 forward (Net.precision, ao_net_precision:
+    one MFMA product per multiply-add, activations rounded once to fp16) wherever the resident / board-resident trunk is planned;
+    training is untouched (the module trains in torch fp32). A position's evaluation then depends on which kernel its batch is
+    planned onto (about 5e-3 in a logit), so it cannot be combined with reproducible=True. Needs a network the split-fp16 kernels
+    cover (128 planes, at least one block); "fp32" (the default) is everything as before."""
     global BOARD_SIZE, N_MCTS, N_BLOCKS, IN_PLANES, OUT_PLANES, SEED, Agent, optimizer, device
     global _engine, _evaluator, _episodes_played, rep_memory, STRICT, NODE_CAP, CARRY_OVER, _pool, OVERSUBSCRIBE, ROWS, _terminal_share
     global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS
+    if forward_precision not in ("fp32", "fp16"):
+        raise ValueError("forward_precision must be 'fp32' or 'fp16', not %r" % (forward_precision,))
+    if forward_precision == "fp16" and reproducible:
+        raise ValueError("forward_precision='fp16' and reproducible=True do not go together: under the fp16 forward a position's "
+                         "evaluation depends on which kernel its batch is planned onto")
     train_join()
     if fast_sims is not None and not 1 <= int(fast_sims) <= int(n_mcts or N_MCTS):
         raise ValueError("fast_sims must be in 1..n_mcts")
@@ -218,6 +228,8 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     _engine = None
     _evaluator = Evaluator(gpu)
     _evaluator.net_mode = 6 if reproducible else 0
+    _evaluator.net_precision = forward_precision
+    Agent._evaluator.net_precision = forward_precision    # (the agent's own searches: get_pi, analysis)
     _episodes_played = 0
     if device_replay:
         from .replay import DeviceReplay
@@ -1206,9 +1218,11 @@ if __name__ == '__main__':
     ap.add_argument('--oversubscribe', type=float, default=None, help='game slots per row of the evaluation batch (1.25 with a trained network)')
     ap.add_argument('--overlap-train', action='store_true', help='train beside the next iteration\'s games (train_async)')
     ap.add_argument('--fp16-grid-weights', action='store_true', help='keep the 3x3 conv weights on the fp16 grid: two-product split-fp16 kernels (configure)')
+    ap.add_argument('--fp16-forward', action='store_true', help='searches run the opt-in plain-fp16 forward: one MFMA product per multiply-add (configure(forward_precision="fp16"))')
     a = ap.parse_args()
     parallel.init_from_env()
     GAMES_PER_ITER, TRAIN_STEPS = a.games_per_iter, a.train_steps
     configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, device_replay=a.device_replay, oversubscribe=a.oversubscribe,
-              overlap_train=a.overlap_train, fp16_grid_weights=a.fp16_grid_weights)
+              overlap_train=a.overlap_train, fp16_grid_weights=a.fp16_grid_weights,
+              forward_precision="fp16" if a.fp16_forward else "fp32")
     run(a.iters, a.model, a.dataset, a.selfplay)

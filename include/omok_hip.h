@@ -411,6 +411,26 @@ int  ao_net_conv_timing(ao_net *n, int enable, double *ms_total, int64_t *launch
  * weights_fp16: 1 when the loaded weights qualify. A checkpoint gets there by keeping its conv weights on the fp16 grid
  * (tools/train_omok.py --fp16-grid-weights); nothing else about the state_dict changes. */
 int  ao_net_products(ao_net *n, int32_t request, int32_t *in_force, int32_t *weights_fp16);
+/* Precision of the network forward. AO_NET_PRECISION_FP32 (the default) is everything described above: fp32-equivalent, within
+ * 1e-4 of model.py:76-104. AO_NET_PRECISION_FP16 is the opt-in plain-fp16 forward: the operands of every 3x3 conv of the trunk
+ * are fp16 -- the weight fp16(w * 2^s) (the high half the library packs anyway), the activation rounded ONCE to fp16, to nearest
+ * even, after ReLU and the clamp at 65504 -- with fp32 accumulation: one MFMA product per multiply-add and one fp16 per stored
+ * activation. BatchNorm, the residual add, ReLU, the clamp and the heads stay fp32; the next conv, the block's residual add and the
+ * heads all read the rounded activation. Float input planes that are not fp16 numbers are rounded to nearest by the resident
+ * trunk and taken with all their bits by conv1 in front of the board-resident trunk (the engine's 0/1 planes are exact either way).
+ * request: -1 = query only, AO_NET_PRECISION_FP32, AO_NET_PRECISION_FP16. in_force: the setting; supported: 1 for networks the
+ * split-fp16 kernels cover (128 planes, at least one ResBlock) -- AO_NET_PRECISION_FP16 on any other network is an error. The
+ * setting belongs to the ao_net, survives ao_net_finalize and is independent of ao_net_products, which keeps answering for the
+ * fp32-equivalent kernels.
+ * What runs: exactly the batches that modes 0 / 5 plan onto the resident trunk (boards up to 9x9, >= 192 groups of 16) or the
+ * board-resident trunk (wider boards, >= 64 boards) run that kernel's one-product form (k_trunk16h_f16 / k_trunk16hb_f16 /
+ * k_boardh_f16; ao_net_dominant_kernel names it). Every other batch size and mode runs the fp32-equivalent kernel it runs
+ * anyway -- more accurate, never less. CONSEQUENCE: under AO_NET_PRECISION_FP16 a position's evaluation depends on which kernel
+ * its batch is planned onto, to about 5e-3 in a logit; mode 6 (one arithmetic for every batch size) therefore plans no
+ * one-product kernel and must not be combined with it. The fp16-range event is reported as ever (AO_NET_FP16_RANGE), and
+ * ao_search's recovery on the fp32-MFMA trunk (mode 2) is unchanged. */
+enum { AO_NET_PRECISION_FP32 = 0, AO_NET_PRECISION_FP16 = 1 };
+int  ao_net_precision(ao_net *n, int32_t request, int32_t *in_force, int32_t *supported);
 /* name and algorithmic FLOPs per launch (2*MAC, zero padding counted) of the kernel the timing
  * refers to, for a batch of `boards` positions. */
 int  ao_net_dominant_kernel(ao_net *n, int boards, char *name, int name_cap, double *flop_per_launch);

@@ -75,6 +75,10 @@ def main():
                     help="keep the 3x3 conv weights on the fp16 grid (main.configure(fp16_grid_weights=True): fp32 master copies in Adam, the module holds "
                          "their fp16 rounding) -- such a network runs on the two-product split-fp16 kernels (ao_net_products); the checkpoint stays a "
                          "plain fp32 state_dict the reference loads")
+    ap.add_argument("--fp16-forward", action="store_true",
+                    help="self-play and evaluation searches run the opt-in plain-fp16 forward (main.configure(forward_precision='fp16'), "
+                         "Net.precision): one MFMA product per multiply-add on the batches planned onto the resident trunk; training stays "
+                         "torch fp32")
     ap.add_argument("--early-stop", action="store_true",
                     help="self-play searches with tau == 0 stop once their move is decided (main.configure(early_stop=True)): same pi and move, "
                          "fewer simulations, smaller trees handed on")
@@ -121,7 +125,7 @@ def main():
     m.configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, out_planes=a.planes, seed=a.seed,
                 device_replay=True, carry_over=not a.no_carry_over, oversubscribe=a.oversubscribe, rows=a.rows,
                 fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob,
-                tactics=True if a.tactics else None)
+                tactics=True if a.tactics else None, forward_precision="fp16" if a.fp16_forward else "fp32")
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
