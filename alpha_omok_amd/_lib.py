@@ -43,6 +43,19 @@ class AoReplaySnapshot(C.Structure):
                 ("pi_mask", C.POINTER(C.c_uint64)), ("pi_val", C.POINTER(C.c_double)), ("raw", C.POINTER(C.c_float))]
 
 
+class AoRollOpts(C.Structure):
+    """ao_roll_opts of include/omok_hip.h."""
+    _fields_ = [("active", C.POINTER(C.c_uint8)), ("tau_plies", C.POINTER(C.c_int32)), ("sims", C.POINTER(C.c_int32)),
+                ("sims_stride", C.c_int32), ("noise", C.POINTER(C.c_uint8)), ("noise_stride", C.c_int32),
+                ("early_stop", C.c_int32), ("turn_every", C.c_int32), ("want_visit", C.c_int32), ("want_policy", C.c_int32)]
+
+
+class AoRollRecords(C.Structure):
+    """ao_roll_records of include/omok_hip.h: a count + pointers to caller-owned host arrays of capacity G."""
+    _fields_ = [("count", C.c_int32)] + [(k, C.POINTER(C.c_int32)) for k in ("game", "ply", "action", "win", "tau", "sims", "settled")] + \
+               [(k, C.POINTER(C.c_double)) for k in ("pi", "visit", "policy")]
+
+
 class AoRolloutConfig(C.Structure):
     _fields_ = [("board", C.c_int32), ("win_mark", C.c_int32), ("sims", C.c_int32), ("games", C.c_int32),
                 ("mode", C.c_int32), ("device", C.c_int32), ("c_puct", C.c_double)]
@@ -82,6 +95,12 @@ SYMBOLS = {
     "ao_settle": (C.c_int, [_vp, _u8p, C.c_int, _i32p]),
     "ao_search_opts": (C.c_int, [_vp, _vp, _u8p, _i8p, _i32p, _u8p, _u8p, C.c_int32, _f64p, _f64p, _f64p]),
     "ao_search_sims": (C.c_int, [_vp, _i32p, _u8p, _i64p, _i64p]),
+    "ao_roll_begin": (C.c_int, [_vp, _vp, _P(AoRollOpts)]),
+    "ao_roll_run": (C.c_int, [_vp, C.c_int64, _P(AoRollRecords)]),
+    "ao_roll_join": (C.c_int, [_vp, _P(AoRollOpts)]),
+    "ao_roll_drain": (C.c_int, [_vp]),
+    "ao_roll_end": (C.c_int, [_vp]),
+    "ao_roll_stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p]),
     "ao_set_root_bar": (C.c_int, [_vp, _u8p]),
     "ao_root_tactics": (C.c_int, [_vp, _u8p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _u8p, _i32p, _i32p]),
     "ao_collect_leaves": (C.c_int, [_vp, _vp]),

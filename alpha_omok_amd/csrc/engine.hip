@@ -23,6 +23,7 @@
 #include "host_handle.hpp"
 #include "host_rng.hpp"
 #include "launchers.hpp"
+#include "roll_schedule.hpp"
 #include "search_schedule.hpp"
 #include "snapshot_check.hpp"
 #include "tactics_limits.hpp"
@@ -48,6 +49,31 @@ struct DevSwitches {
     // without a sit-out window from the start
     static int catchup_rounds() { const char* v = getenv("AO_CATCHUP_ROUNDS"); return v ? atoi(v) : -1; }
     static bool catchup_window_off() { return getenv("AO_CATCHUP_WINDOW_OFF") != nullptr; }
+};
+
+// The rolling search (ao_roll_*, at the end of this file): what lives from ao_roll_begin to ao_roll_end. The rules are
+// roll_schedule.hpp's, the kernels roll.hip's.
+struct RollState {
+    bool open = false, draining = false;
+    ao_net* net = nullptr;
+    bool early = false, want_visit = false, want_policy = false;
+    ao::RollCadence cad;
+    bool look_pending = false;            // a look's counters have not been read yet
+    std::vector<uint8_t> in_move;         // [G]
+    int n_in_move = 0;
+    std::vector<int32_t> tau_plies;       // [G], empty: tau 1 always
+    std::vector<int32_t> sims; int sims_stride = 0;      // [G][stride] budgets by ply, empty: ao_config.sims
+    std::vector<uint8_t> noise; int noise_stride = 0;    // [G][stride] noise switches by ply, empty: the engine's
+    // the launch plan: always rows per simulation (MoveSearch::plan's `dynamic`), no sit-out window, no launch order
+    int cap_rows = 0, in_kind = 1;
+    const float* net_in = nullptr;
+    ao::TreeParams p{};
+    int64_t launch = 0, harvested = 0;    // selection launches of the roll; row counters already summed up
+    // compact buffers of a turn, allocated by the first roll of the engine: [G] games, [G][kRollItem], [G][kRollRec], [3][G][A], [G][Ap]
+    int32_t* d_games = nullptr; int32_t* d_items = nullptr; int32_t* d_rec = nullptr; double* d_out = nullptr; double* d_noise = nullptr;
+    int32_t* h_i32 = nullptr;             // pinned: [4][G] done, target, leaf status, error words; [G] games; [G][kRollItem]; [G][kRollRec]
+    // ao_roll_stats
+    int64_t turns = 0, games_turned = 0, bytes = 0, last_games = 0, last_bytes = 0;
 };
 
 struct ao_engine : ao::HandleBase {
@@ -127,7 +153,20 @@ struct ao_engine : ao::HandleBase {
     std::vector<unsigned char> h_ro;
     // HIP-event timing of the per-simulation tree kernel (k_expand_select) on the launch stream (ao_tree_timing)
     ao::EventTimer timer{256};
+    RollState roll;
 };
+
+// Inside an open roll the engine's games move on their own clocks: everything that begins, ends or steps a move of the whole
+// engine, moves roots or reads trees in bulk is refused until ao_roll_end.
+static int roll_refuses(ao_engine* e, const char* who) {
+    if (!e->roll.open) return 0;
+    return e->fail(std::string(who) + ": a roll is open (ao_roll_begin ... ao_roll_end); drain it (ao_roll_drain, ao_roll_run) and close it with ao_roll_end first");
+}
+// ... and what touches single games is refused for a game that is in a move of the roll
+static int roll_refuses_game(ao_engine* e, const char* who, int g) {
+    if (!e->roll.open || !e->roll.in_move[g]) return 0;
+    return e->fail(std::string(who) + ": game " + std::to_string(g) + " is in a move of the open roll");
+}
 
 extern "C" {
 
@@ -161,6 +200,7 @@ void ao_destroy(ao_engine* e) {
     if (e->h_i32) hipHostFree(e->h_i32);
     if (e->h_live) hipHostFree(e->h_live);
     if (e->h_settle) hipHostFree(e->h_settle);
+    if (e->roll.h_i32) hipHostFree(e->roll.h_i32);
     e->timer.destroy();
     if (e->own_stream) hipStreamDestroy(e->own_stream);
     delete e;
@@ -353,6 +393,7 @@ int ao_create(const ao_config* cfg, ao_engine** out) {
 int ao_set_rng_state(ao_engine* e, int g, const uint32_t* mt, int32_t pos, int32_t has_gauss, double gauss) {
     if (g < 0 || g >= e->G) return e->fail("game index out of range");
     if (e->in_move) return e->fail("ao_set_rng_state / ao_seed inside a move (the move's Dirichlet draw has already consumed the old stream)");
+    if (roll_refuses_game(e, "ao_set_rng_state / ao_seed", g)) return 1;
     AO_HIP(e, hipSetDevice(e->cfg.device));
     AO_HIP(e, hipMemcpyAsync(e->tp.mt + static_cast<size_t>(g) * 624, mt, sizeof(uint32_t) * 624,
                              hipMemcpyHostToDevice, e->stream));
@@ -387,6 +428,8 @@ int ao_seed_games(ao_engine* e, const int32_t* games, const uint32_t* seeds, int
     if (e->in_move) return e->fail("ao_seed_games inside a move");
     for (int k = 0; k < n; ++k)
         if (games[k] < 0 || games[k] >= e->G) return e->fail("ao_seed_games: game index out of range");
+    for (int k = 0; k < n; ++k)
+        if (roll_refuses_game(e, "ao_seed_games", games[k])) return 1;
     AO_HIP(e, hipStreamSynchronize(e->stream));   // (the pinned staging rows are free)
     for (int k = 0; k < n; ++k) {
         const int g = games[k];
@@ -404,6 +447,8 @@ int ao_seed_games(ao_engine* e, const int32_t* games, const uint32_t* seeds, int
 
 int ao_seed_all(ao_engine* e, const uint32_t* seeds) {
     if (e->in_move) return e->fail("ao_seed_all inside a move");
+    for (int g = 0; g < e->G; ++g)
+        if (roll_refuses_game(e, "ao_seed_all", g)) return 1;
     AO_HIP(e, hipSetDevice(e->cfg.device));
     AO_HIP(e, hipStreamSynchronize(e->stream));
     for (int g = 0; g < e->G; ++g) {
@@ -467,6 +512,7 @@ static int bar_build(ao_engine* e, const std::vector<uint8_t>& act, bool* any, c
 }
 
 int ao_set_root_bar(ao_engine* e, const uint8_t* allowed) {
+    if (roll_refuses(e, "ao_set_root_bar")) return 1;
     if (e->in_move) return e->fail("ao_set_root_bar inside a move (between ao_begin_move and ao_end_move)");
     e->bar_on_device = false;
     std::fill(e->bar_has.begin(), e->bar_has.end(), allowed ? 1 : 0);
@@ -477,6 +523,8 @@ int ao_set_root_bar(ao_engine* e, const uint8_t* allowed) {
 
 // ---- game / tree state -----------------------------------------------------------------------
 int ao_reset(ao_engine* e, const uint8_t* mask) {
+    for (int g = 0; g < e->G; ++g)
+        if ((!mask || mask[g]) && roll_refuses_game(e, "ao_reset", g)) return 1;
     AO_HIP(e, hipSetDevice(e->cfg.device));
     if (bar_forget(e, mask)) return 1;
     const uint8_t* dmask = nullptr;
@@ -505,6 +553,7 @@ static int queue_refused(ao_engine* e, const char* who) {
 // ids[k] / ns[k]: full move list of games[k]. Games whose new id does not extend the kept one are reset first.
 static int set_roots_impl(ao_engine* e, int count, const int32_t* games, const int32_t* const* ids, const int32_t* ns,
                           int32_t* status) {
+    if (roll_refuses(e, "ao_set_root(s)")) return 1;
     AO_HIP(e, hipSetDevice(e->cfg.device));
     if (count <= 0) return 0;
     const int G = e->G, A = e->A;
@@ -607,6 +656,7 @@ int ao_get_moves(ao_engine* e, int g, int32_t* out, int32_t* n) {
 // ---- one move decision -----------------------------------------------------------------------
 // sims / noise: per-game budgets and noise switches of ao_begin_move_opts (NULL = the engine's configuration)
 static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* sims, const uint8_t* noise) {
+    if (roll_refuses(e, "ao_begin_move")) return 1;
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const int G = e->G, A = e->A, Ap = e->Ap;
     ao::TreeParams& p = e->tp;
@@ -725,6 +775,7 @@ static void settle_harvest(ao_engine* e, int* unfinished, int* owed) {
 }
 
 int ao_settle(ao_engine* e, const uint8_t* mask, int stop_now, int32_t* unfinished) {
+    if (roll_refuses(e, "ao_settle")) return 1;
     if (!e->in_move) return e->fail("ao_settle outside ao_begin_move/ao_end_move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const uint8_t* dmask = nullptr;
@@ -761,6 +812,7 @@ int ao_search_sims(ao_engine* e, int32_t* sims_run, uint8_t* settled, int64_t* s
 }
 
 int ao_collect_leaves(ao_engine* e, float* dev_planes_nchw) {
+    if (roll_refuses(e, "ao_collect_leaves")) return 1;
     if (!e->in_move) return e->fail("ao_collect_leaves outside ao_begin_move/ao_end_move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     ao::TreeParams p = e->tp;
@@ -774,6 +826,7 @@ int ao_collect_leaves(ao_engine* e, float* dev_planes_nchw) {
 }
 
 int ao_apply_evals(ao_engine* e, const float* dev_policy, const float* dev_value) {
+    if (roll_refuses(e, "ao_apply_evals")) return 1;
     if (!e->in_move) return e->fail("ao_apply_evals outside ao_begin_move/ao_end_move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     ao::TreeParams p = e->tp;
@@ -786,10 +839,9 @@ int ao_apply_evals(ao_engine* e, const float* dev_policy, const float* dev_value
     return 0;
 }
 
-static int check_game_errors(ao_engine* e) {
-    int32_t* herr = e->h_i32 + 2 * e->G;
-    AO_HIP(e, hipMemcpyAsync(herr, e->tp.err, sizeof(int32_t) * e->G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
+// herr [G]: the games' error words as just read from the device. The first game with one fails the call with a message that
+// names it; the words are cleared and no move is in flight afterwards.
+static int report_game_errors(ao_engine* e, const int32_t* herr) {
     for (int g = 0; g < e->G; ++g) {
         if (!herr[g]) continue;
         std::string m = "game " + std::to_string(g) + ":";
@@ -817,7 +869,15 @@ static int check_game_errors(ao_engine* e) {
     return 0;
 }
 
+static int check_game_errors(ao_engine* e) {
+    int32_t* herr = e->h_i32 + 2 * e->G;
+    AO_HIP(e, hipMemcpyAsync(herr, e->tp.err, sizeof(int32_t) * e->G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    return report_game_errors(e, herr);
+}
+
 int ao_end_move(ao_engine* e, const int8_t* tau, double* pi, double* visit, double* policy) {
+    if (roll_refuses(e, "ao_end_move")) return 1;
     if (!e->in_move) return e->fail("ao_end_move without ao_begin_move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const int G = e->G, A = e->A;
@@ -846,6 +906,7 @@ int ao_end_move(ao_engine* e, const int8_t* tau, double* pi, double* visit, doub
 }
 
 int ao_play(ao_engine* e, int32_t* action, int32_t* win) {
+    if (roll_refuses(e, "ao_play")) return 1;
     if (!e->ended) return e->fail("ao_play must follow ao_end_move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     const int G = e->G;
@@ -1204,6 +1265,7 @@ static int recover_fp16_range(ao_engine* e, ao_net* net, const uint8_t* active, 
 
 static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi, double* visit, double* policy,
                        bool may_recover, const SearchOpts& opts) {
+    if (roll_refuses(e, "ao_search")) return 1;
     if (!net) return e->fail("ao_search: null network");
     std::string why;
     if (ao::net_check(net, e->cfg.board, e->cfg.inplanes, e->cfg.device, &why)) return e->fail("ao_search: " + why);
@@ -1240,6 +1302,7 @@ int ao_search_opts(ao_engine* e, ao_net* net, const uint8_t* active, const int8_
 }
 
 int ao_set_row_cap(ao_engine* e, int32_t rows) {
+    if (roll_refuses(e, "ao_set_row_cap")) return 1;
     if (rows < 0) return e->fail("ao_set_row_cap: negative");
     if (e->in_move) return e->fail("ao_set_row_cap inside a move");
     e->row_cap = rows;
@@ -1255,6 +1318,7 @@ int ao_row_stats(ao_engine* e, int64_t* launches, int64_t* rows_live, int64_t* r
 }
 
 int ao_set_eval_log(ao_engine* e, const int32_t* games, int32_t n, float* dev_log, int64_t capacity_floats) {
+    if (roll_refuses(e, "ao_set_eval_log")) return 1;
     if (n < 0 || n > e->G) return e->fail("ao_set_eval_log: bad game count");
     if (e->in_move) return e->fail("ao_set_eval_log inside a move");
     AO_HIP(e, hipSetDevice(e->cfg.device));
@@ -1500,6 +1564,7 @@ int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
 // intersected with what the solver allows, game by game; a game whose intersection would be empty keeps the caller's.
 int ao_root_tactics(ao_engine* e, const uint8_t* active, int32_t max_depth, int32_t max_nodes, int32_t apply, int32_t* verdict,
                     int32_t* depth, uint8_t* allowed, int32_t* nodes, int32_t* unknown) {
+    if (roll_refuses(e, "ao_root_tactics")) return 1;
     if (e->in_move) return e->fail("ao_root_tactics inside a move (between ao_begin_move and ao_end_move)");
     const std::string bad_limits = ao::fw_limits_error("ao_root_tactics", max_depth, max_nodes);
     if (!bad_limits.empty()) return e->fail(bad_limits);
@@ -1570,6 +1635,7 @@ static size_t snap_chunk_bytes(const SnapChunk& c, int A, bool import) {
 }
 
 int ao_tree_export(ao_engine* e, const uint8_t* mask, ao_tree_snapshot* out) {
+    if (roll_refuses(e, "ao_tree_export")) return 1;
     if (e->in_move) return e->fail("ao_tree_export inside a move (between ao_begin_move and ao_end_move)");
     if (!out) return e->fail("ao_tree_export: null snapshot");
     const int G = e->G, A = e->A;
@@ -1661,6 +1727,7 @@ int ao_tree_snapshot_check(const ao_tree_snapshot* snap) {
 }
 
 int ao_tree_import(ao_engine* e, const int32_t* host_games, int32_t n, const ao_tree_snapshot* snap) {
+    if (roll_refuses(e, "ao_tree_import")) return 1;
     if (e->in_move) return e->fail("ao_tree_import inside a move (between ao_begin_move and ao_end_move)");
     if (!snap || (n > 0 && !host_games)) return e->fail("ao_tree_import: null argument");
     if (n != snap->games) return e->fail("ao_tree_import: " + std::to_string(n) + " games listed, the snapshot holds " + std::to_string(snap->games));
@@ -1796,6 +1863,469 @@ int ao_search_stats(ao_engine* e, int64_t* levels, int64_t* ties, int64_t* termi
     if (ties) *ties = static_cast<int64_t>(h[1]);
     if (terminal) *terminal = static_cast<int64_t>(h[2]);
     if (evaluated) *evaluated = static_cast<int64_t>(h[3]);
+    return 0;
+}
+
+// ---- the rolling search ------------------------------------------------------------------------
+// ao_search moves every game of the engine through one move per call: the launch loop of a move lasts until its LAST game has its
+// simulations. Here the launch loop never stops for a move: every turn_every launches the games that have their simulations are
+// TURNED -- move ended and played (k_roll_turn, k_reroot), the next one begun (k_roll_begin) -- while the others are mid-search
+// in the same launches. A game's search stays strictly sequential: the records equal ao_search + ao_play of that game to the bit.
+// Which games turn, what their next move is, when a run returns and the order of looks, launches and turns: roll_schedule.hpp.
+static void roll_count(ao_engine* e, size_t bytes) { e->roll.bytes += static_cast<int64_t>(bytes); }
+
+// every way out of a roll, the failures included: no game is in a move and the engine is between moves
+static void roll_close(ao_engine* e) {
+    RollState& r = e->roll;
+    r.open = false;
+    r.draining = false;
+    std::fill(r.in_move.begin(), r.in_move.end(), 0);
+    r.n_in_move = 0;
+    e->in_move = false;
+    e->ended = false;
+}
+
+// what a failure inside the loop leaves behind: error words cleared, the roll closed (check_game_errors does the same for its own)
+static int roll_fail(ao_engine* e, const std::string& m) {
+    (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
+    (void)hipStreamSynchronize(e->stream);
+    roll_close(e);
+    return e->fail(m);
+}
+
+static unsigned* roll_slot(ao_engine* e, int64_t i) { return e->d_live + (i % ao_engine::kLive); }
+
+// sums up the row counters of the selection launches [harvested, upto): each of them was followed by a network launch. Copies
+// those words only; synchronises.
+static int roll_harvest_rows(ao_engine* e, int64_t upto) {
+    RollState& r = e->roll;
+    if (upto <= r.harvested) return 0;
+    const int64_t first = r.harvested % ao_engine::kLive, count = upto - r.harvested;   // (count <= kLive: the ring is harvested where it wraps)
+    const int64_t head = std::min<int64_t>(count, ao_engine::kLive - first);
+    AO_HIP(e, hipMemcpyAsync(e->h_live + first, e->d_live + first, sizeof(unsigned) * head, hipMemcpyDeviceToHost, e->stream));
+    if (count > head) AO_HIP(e, hipMemcpyAsync(e->h_live, e->d_live, sizeof(unsigned) * (count - head), hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    roll_count(e, sizeof(unsigned) * count);
+    for (int64_t i = r.harvested; i < upto; ++i) e->rs.add(e->h_live[i % ao_engine::kLive], r.cap_rows);
+    r.harvested = upto;
+    return 0;
+}
+
+// the move a game would begin now (roll_schedule.hpp), from the roll's tables and the host mirrors
+static ao::RollMove roll_move_of(const ao_engine* e, int g, int ply) {
+    const RollState& r = e->roll;
+    return ao::roll_next_move(ply, r.tau_plies.empty() ? -1 : r.tau_plies[g],
+                              r.sims.empty() ? nullptr : r.sims.data() + static_cast<size_t>(g) * r.sims_stride, r.sims_stride,
+                              r.noise.empty() ? nullptr : r.noise.data() + static_cast<size_t>(g) * r.noise_stride, r.noise_stride,
+                              e->tp.noise != 0, e->S, e->status[g]);
+}
+
+// Takes the per-game fields of `o` for the games of `act` into the roll's tables -- after every column of theirs has been found in
+// range: a refused call has touched nothing. fresh: the tables of a roll that begins (what an earlier roll left is dropped).
+static int roll_take_tables(ao_engine* e, const ao_roll_opts* o, const std::vector<uint8_t>& act, bool fresh, const char* who) {
+    RollState& r = e->roll;
+    const int G = e->G;
+    if (o->sims && o->sims_stride < 1) return e->fail(std::string(who) + ": sims_stride must be >= 1");
+    if (o->noise && o->noise_stride < 1) return e->fail(std::string(who) + ": noise_stride must be >= 1");
+    if (!fresh && o->sims && !r.sims.empty() && o->sims_stride != r.sims_stride) return e->fail(std::string(who) + ": sims_stride differs from the open roll's");
+    if (!fresh && o->noise && !r.noise.empty() && o->noise_stride != r.noise_stride) return e->fail(std::string(who) + ": noise_stride differs from the open roll's");
+    for (int g = 0; g < G; ++g) {
+        if (!act[g]) continue;
+        const int cols = std::max(o->sims ? o->sims_stride : 1, o->noise ? o->noise_stride : 1);
+        for (int c = 0; c < cols; ++c) {
+            const ao::RollMove m = ao::roll_next_move(c, -1, o->sims ? o->sims + static_cast<size_t>(g) * o->sims_stride : nullptr, o->sims_stride,
+                                                      o->noise ? o->noise + static_cast<size_t>(g) * o->noise_stride : nullptr, o->noise_stride,
+                                                      e->tp.noise != 0, e->S, AO_ROOT_EXPANDED);
+            if (m.refuse == 1)
+                return e->fail(std::string(who) + ": game " + std::to_string(g) + ": sims " + std::to_string(m.budget) + " at ply " + std::to_string(c) +
+                               " is outside 1.." + std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
+            if (m.refuse == 2)
+                return e->fail(std::string(who) + ": game " + std::to_string(g) + ": noise asked for on an engine created without noise");
+        }
+    }
+    if (fresh) {
+        r.tau_plies.clear(); r.sims.clear(); r.noise.clear();
+        r.sims_stride = r.noise_stride = 0;
+    }
+    if (o->tau_plies && r.tau_plies.empty()) r.tau_plies.assign(G, -1);
+    if (o->sims && r.sims.empty()) { r.sims_stride = o->sims_stride; r.sims.assign(static_cast<size_t>(G) * r.sims_stride, e->S); }
+    if (o->noise && r.noise.empty()) { r.noise_stride = o->noise_stride; r.noise.assign(static_cast<size_t>(G) * r.noise_stride, e->tp.noise ? 1 : 0); }
+    for (int g = 0; g < G; ++g) {
+        if (!act[g]) continue;
+        if (o->tau_plies) r.tau_plies[g] = std::max(o->tau_plies[g], 0);
+        if (o->sims) std::copy(o->sims + static_cast<size_t>(g) * r.sims_stride, o->sims + static_cast<size_t>(g + 1) * r.sims_stride, r.sims.begin() + static_cast<size_t>(g) * r.sims_stride);
+        if (o->noise) std::copy(o->noise + static_cast<size_t>(g) * r.noise_stride, o->noise + static_cast<size_t>(g + 1) * r.noise_stride, r.noise.begin() + static_cast<size_t>(g) * r.noise_stride);
+    }
+    return 0;
+}
+
+// Begins the next move of the listed games (not in a move, not over). rows: where game games[k]'s stream lies in the compact
+// staging rows (h_mt / h_pos, gathered by the turn that just played it), or null: the streams are gathered here. The Dirichlet
+// draw of the games that search with noise is the host's (host_rng.hpp), on the pool; everything travels in compact rows.
+static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, const int32_t* rows) {
+    RollState& r = e->roll;
+    const int n = static_cast<int>(games.size()), G = e->G, A = e->A, Ap = e->Ap;
+    if (n == 0) return 0;
+    int32_t* h_games = r.h_i32 + 4 * static_cast<size_t>(G);
+    int32_t* h_items = h_games + G;
+    std::vector<ao::RollMove> mv(n);
+    bool any_draw = false;
+    for (int k = 0; k < n; ++k) {
+        mv[k] = roll_move_of(e, games[k], static_cast<int>(e->moves[games[k]].size()));
+        any_draw = any_draw || mv[k].draw;
+    }
+    if (!rows) {
+        AO_HIP(e, hipStreamSynchronize(e->stream));   // (the pinned staging rows are free)
+        if (any_draw) {
+            std::copy(games.begin(), games.end(), h_games);
+            AO_HIP(e, hipMemcpyAsync(r.d_games, h_games, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
+            ao::launch_roll_gather(e->tp, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
+            AO_HIP(e, hipGetLastError());
+            AO_HIP(e, hipMemcpyAsync(e->h_mt, e->d_mt_backup, sizeof(uint32_t) * 624 * n, hipMemcpyDeviceToHost, e->stream));
+            AO_HIP(e, hipMemcpyAsync(e->h_pos, e->d_pos_backup, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+            AO_HIP(e, hipStreamSynchronize(e->stream));
+            roll_count(e, static_cast<size_t>(n) * (4 + 624 * 4 + 4));
+        }
+    }
+    int nrows = 0;   // staging rows in use: [0, nrows)
+    for (int k = 0; k < n; ++k) {
+        const int g = games[k];
+        const int row = rows ? rows[k] : k;
+        int32_t* it = h_items + static_cast<size_t>(k) * ao::kRollItem;
+        it[0] = g; it[1] = mv[k].target; it[2] = mv[k].gflags; it[3] = mv[k].tau;
+        it[4] = (r.early && mv[k].tau == 0) ? 1 : 0;
+        it[5] = mv[k].draw ? row : -1;
+        if (mv[k].draw) nrows = std::max(nrows, row + 1);
+    }
+    if (any_draw) {
+        const double alpha = e->cfg.alpha;
+        auto work = [&](int k0, int k1) {
+            for (int k = k0; k < k1; ++k) {
+                if (!mv[k].draw) continue;   // (no draw for a game without noise: its stream is not touched)
+                const int g = games[k];
+                const size_t row = static_cast<size_t>(rows ? rows[k] : k);
+                ao::HostMT rng{e->h_mt + row * 624, e->h_pos + row, &e->has_gauss[g], &e->gauss[g]};
+                rng.dirichlet(alpha, A - static_cast<int>(e->moves[g].size()), e->h_noise + row * Ap);
+            }
+        };
+        if (n < 64) work(0, n);
+        else ao::HostPool::get().run(n, 16, work);
+        AO_HIP(e, hipMemcpyAsync(e->d_mt_backup, e->h_mt, sizeof(uint32_t) * 624 * nrows, hipMemcpyHostToDevice, e->stream));
+        AO_HIP(e, hipMemcpyAsync(e->d_pos_backup, e->h_pos, sizeof(int32_t) * nrows, hipMemcpyHostToDevice, e->stream));
+        AO_HIP(e, hipMemcpyAsync(r.d_noise, e->h_noise, sizeof(double) * Ap * nrows, hipMemcpyHostToDevice, e->stream));
+        roll_count(e, static_cast<size_t>(nrows) * (624 * 4 + 4 + sizeof(double) * Ap));
+    }
+    AO_HIP(e, hipMemcpyAsync(r.d_items, h_items, sizeof(int32_t) * ao::kRollItem * n, hipMemcpyHostToDevice, e->stream));
+    roll_count(e, sizeof(int32_t) * ao::kRollItem * n);
+    ao::launch_roll_begin(r.p, r.d_items, n, e->d_mt_backup, e->d_pos_backup, r.d_noise, e->d_tau, e->d_active, e->d_settled, e->d_early, e->stream);
+    AO_HIP(e, hipGetLastError());
+    e->settled_dirty = true;
+    for (int k = 0; k < n; ++k) {
+        const int g = games[k];
+        e->bonus[g] = (e->status[g] == AO_ROOT_FRESH) ? 1 : 0;
+        e->active[g] = 1;
+        r.in_move[g] = 1;
+        ++r.n_in_move;
+    }
+    return 0;
+}
+
+// the games of a begin / join: listed (null: all), not over; a listed game that is in a move already is refused by name
+static int roll_listed(ao_engine* e, const uint8_t* active, std::vector<uint8_t>* act, const char* who) {
+    act->assign(e->G, 0);
+    for (int g = 0; g < e->G; ++g) {
+        if ((active && !active[g]) || e->over[g]) continue;
+        if (e->roll.open && e->roll.in_move[g]) {
+            if (active) return e->fail(std::string(who) + ": game " + std::to_string(g) + " is in a move already");
+            continue;
+        }
+        (*act)[g] = 1;
+    }
+    return 0;
+}
+
+int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
+    RollState& r = e->roll;
+    if (roll_refuses(e, "ao_roll_begin")) return 1;
+    if (e->in_move) return e->fail("ao_roll_begin inside a move (between ao_begin_move and ao_end_move)");
+    if (!net || !o) return e->fail("ao_roll_begin: null argument");
+    if (e->bar_pending || e->bar_on_device) return e->fail("ao_roll_begin: a root bar is pending (ao_set_root_bar / ao_root_tactics with apply): the rolling search has no root bar");
+    if (e->log_n > 0) return e->fail("ao_roll_begin: an eval log is set (ao_set_eval_log): the rolling search does not feed it");
+    if (o->turn_every < 1) return e->fail("ao_roll_begin: turn_every must be >= 1");
+    std::string why;
+    if (ao::net_check(net, e->cfg.board, e->cfg.inplanes, e->cfg.device, &why)) return e->fail("ao_roll_begin: " + why);
+    // (every turn re-roots: the bound is fixed per engine, so it is checked here, where the call can still be refused)
+    if (!ao::reroot_fits(e->tp)) return queue_refused(e, "ao_roll_begin");
+    const int G = e->G, A = e->A;
+    std::vector<uint8_t> act;
+    if (roll_listed(e, o->active, &act, "ao_roll_begin")) return 1;
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    if (!r.h_i32) {   // the compact buffers of the engine's first roll (a failed allocation refuses the call; what it got stays in the pool)
+        if (e->pool.alloc(e, &r.d_games, G) || e->pool.alloc(e, &r.d_items, static_cast<size_t>(G) * ao::kRollItem) ||
+            e->pool.alloc(e, &r.d_rec, static_cast<size_t>(G) * ao::kRollRec) || e->pool.alloc(e, &r.d_out, 3 * static_cast<size_t>(G) * A) ||
+            e->pool.alloc(e, &r.d_noise, static_cast<size_t>(G) * e->Ap))
+            return 1;
+        AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&r.h_i32), sizeof(int32_t) * G * (5 + ao::kRollItem + ao::kRollRec), hipHostMallocDefault));
+    }
+    if (roll_take_tables(e, o, act, true, "ao_roll_begin")) return 1;
+    // nothing can refuse the call any more
+    r.in_move.assign(G, 0);
+    r.net = net;
+    r.early = o->early_stop != 0;
+    r.want_visit = o->want_visit != 0;
+    r.want_policy = o->want_policy != 0;
+    r.cad = ao::RollCadence{};
+    r.cad.turn_every = o->turn_every;
+    r.cad.early = r.early;
+    r.look_pending = false;
+    r.n_in_move = 0;
+    r.draining = false;
+    r.launch = r.harvested = 0;
+    // the plan: MoveSearch::plan's rows-per-simulation path for every G, the batch bounded by ao_set_row_cap
+    r.cap_rows = (e->row_cap > 0 && e->row_cap < G) ? e->row_cap : G;
+    ao::net_plan(net, r.cap_rows, &e->tp.il_group, &e->tp.nchq, &r.in_kind);
+    if (r.in_kind != 2 && (e->il_group_zeroed != e->tp.il_group || e->il_nchq_zeroed != e->tp.nchq)) {
+        AO_HIP(e, hipMemsetAsync(e->tp.batch_il, 0, e->il_bytes, e->stream));
+        e->il_group_zeroed = e->tp.il_group;
+        e->il_nchq_zeroed = e->tp.nchq;
+    }
+    ao::TreeParams& p = r.p;
+    p = e->tp;
+    p.batch_nchw = nullptr;
+    p.policy = e->d_policy;
+    p.value = e->d_value;
+    p.row_of_game = e->d_row;
+    p.nchq_live = (e->cfg.inplanes + 3) / 4;
+    r.net_in = p.batch_il;
+    if (r.in_kind == 2) {
+        r.net_in = reinterpret_cast<const float*>(e->d_planes_u8);
+        p.batch_u8 = e->d_planes_u8;
+        p.batch_il = nullptr;
+    }
+    p.row_cap = static_cast<unsigned>(r.cap_rows);
+    p.row_target = p.row_cap;
+    p.ctl = nullptr; p.live_prev = nullptr; p.order = nullptr; p.max_levels = 0;
+    // (a root may still hold kBarQ children of an earlier barred move: an all-zero bar turns them back where a move begins)
+    p.bar = nullptr;
+    if (e->bar_dirty) {
+        AO_HIP(e, hipMemsetAsync(e->d_bar, 0, sizeof(uint64_t) * e->h_bar.size(), e->stream));
+        p.bar = e->d_bar;
+    }
+    AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
+    AO_HIP(e, hipMemsetAsync(e->d_active, 0, G, e->stream));
+    AO_HIP(e, hipMemsetAsync(e->d_early, 0, G, e->stream));
+    AO_HIP(e, hipMemsetAsync(e->d_settled, 0, G, e->stream));
+    AO_HIP(e, hipMemsetAsync(p.stats, 0, sizeof(unsigned) * 4 * G, e->stream));
+    std::fill(e->active.begin(), e->active.end(), 0);
+    r.open = true;
+    std::vector<int32_t> games;
+    for (int g = 0; g < G; ++g)
+        if (act[g]) games.push_back(g);
+    if (roll_begin_games(e, games, nullptr)) { roll_close(e); return 1; }
+    p.live = roll_slot(e, 0);
+    ao::launch_select(p, e->stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int ao_roll_join(ao_engine* e, const ao_roll_opts* o) {
+    RollState& r = e->roll;
+    if (!r.open) return e->fail("ao_roll_join: no roll is open");
+    if (!o) return e->fail("ao_roll_join: null argument");
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    std::vector<uint8_t> act;
+    if (roll_listed(e, o->active, &act, "ao_roll_join")) return 1;
+    if (roll_take_tables(e, o, act, false, "ao_roll_join")) return 1;
+    std::vector<int32_t> games;
+    for (int g = 0; g < e->G; ++g)
+        if (act[g]) games.push_back(g);
+    // (a joined game has LS_IDLE: the next launch's expansion half does nothing for it, its selection half starts simulation 0)
+    if (roll_begin_games(e, games, nullptr)) return roll_fail(e, e->err);
+    return 0;
+}
+
+int ao_roll_drain(ao_engine* e) {
+    if (!e->roll.open) return e->fail("ao_roll_drain: no roll is open");
+    e->roll.draining = true;
+    return 0;
+}
+
+// one launch of the loop: the network on the rows the last selection handed out, then expansion + backup and the next selection
+static int roll_launch(ao_engine* e) {
+    RollState& r = e->roll;
+    if (ao::net_forward_il(r.net, r.net_in, r.cap_rows, e->d_policy, e->d_value, e->stream, r.in_kind, 7, roll_slot(e, r.launch),
+                           static_cast<unsigned>(r.cap_rows)))
+        return roll_fail(e, std::string("ao_roll_run: network forward failed: ") + ao_net_last_error(r.net));
+    const bool timed = e->timer.tick();   // (see ao_tree_timing)
+    if (timed) e->timer.begin(e->stream);
+    ++r.launch;
+    if (r.launch % ao_engine::kLive == 0) {   // the counter ring wraps: sum it up, zero it
+        if (roll_harvest_rows(e, r.launch)) return 1;
+        AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
+    }
+    r.p.live = roll_slot(e, r.launch);
+    ao::launch_expand_select(r.p, e->stream);
+    if (timed) e->timer.end(e->stream);
+    AO_HIP(e, hipGetLastError());
+    return 0;
+}
+
+// the look: k_settle over the early-stop games (tau == 0 moves) that have run a simulation of their move; a leaf is under way
+static int roll_look(ao_engine* e) {
+    RollState& r = e->roll;
+    ao::launch_roll_mask(r.p, e->d_early, e->d_mask, e->stream);
+    AO_HIP(e, hipMemsetAsync(e->d_settle, 0, sizeof(int32_t) * 4, e->stream));
+    ao::launch_settle(r.p, e->d_mask, 0, 1, e->d_settled, e->d_settle, e->stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_settle, e->d_settle, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, e->stream));
+    roll_count(e, sizeof(int32_t) * 4);
+    r.look_pending = true;
+    return 0;
+}
+
+// A turn. Reads the network's status word and the games' words first: on either kind of error no game is turned.
+static int roll_turn(ao_engine* e, ao_roll_records* out) {
+    RollState& r = e->roll;
+    const int G = e->G, A = e->A;
+    const int64_t bytes0 = r.bytes;
+    int32_t nflags = 0;
+    if (ao_net_status(r.net, e->stream, &nflags, 1)) return roll_fail(e, std::string("ao_roll_run: ao_net_status: ") + ao_net_last_error(r.net));
+    if (nflags & AO_NET_FP16_RANGE)
+        return roll_fail(e, "ao_roll_run: AO_NET_FP16_RANGE: an activation left the fp16 range (|x| > 65504) in the split-fp16 trunk; the rolling search does not "
+                            "repeat moves on the fp32-MFMA trunk (ao_search does). No game was turned, the roll is closed");
+    int32_t* h_done = r.h_i32;
+    int32_t* h_target = h_done + G;
+    int32_t* h_leaf = h_target + G;
+    int32_t* h_err = h_leaf + G;
+    int32_t* h_games = h_err + G;
+    int32_t* h_rec = h_games + G + static_cast<size_t>(G) * ao::kRollItem;
+    AO_HIP(e, hipMemcpyAsync(h_done, e->tp.sims_done, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipMemcpyAsync(h_target, e->tp.sims_target, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipMemcpyAsync(h_leaf, e->tp.leaf_status, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipMemcpyAsync(h_err, e->tp.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+    roll_count(e, sizeof(int32_t) * 4 * G);
+    if (roll_harvest_rows(e, r.launch)) return 1;
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    if (r.look_pending) {
+        int unfinished = 0, owed = 0;
+        settle_harvest(e, &unfinished, &owed);
+        r.look_pending = false;
+    }
+    if (report_game_errors(e, h_err)) { roll_close(e); return 1; }
+    int n = 0;
+    for (int g = 0; g < G; ++g)
+        if (ao::roll_turns(r.in_move[g] != 0, h_done[g], h_target[g], h_leaf[g] == ao::LS_IDLE)) h_games[n++] = g;
+    ++r.turns;
+    r.last_games = n;
+    out->count = 0;
+    if (n == 0) { r.last_bytes = r.bytes - bytes0; return 0; }
+    const size_t nA = static_cast<size_t>(n) * A;
+    double* d_pi = r.d_out;
+    double* d_visit = r.want_visit ? r.d_out + nA : nullptr;
+    double* d_policy = r.want_policy ? r.d_out + 2 * nA : nullptr;
+    AO_HIP(e, hipMemcpyAsync(r.d_games, h_games, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
+    ao::launch_roll_turn(r.p, r.d_games, n, e->d_active, e->d_settled, r.d_rec, d_pi, d_visit, d_policy, e->stream);
+    (void)ao::launch_reroot(r.p, n, r.d_games, e->stream);   // (cannot refuse: ao_roll_begin checked reroot_fits)
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(h_rec, r.d_rec, sizeof(int32_t) * ao::kRollRec * n, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipMemcpyAsync(e->h_out, d_pi, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
+    if (d_visit) AO_HIP(e, hipMemcpyAsync(e->h_out + nA, d_visit, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
+    if (d_policy) AO_HIP(e, hipMemcpyAsync(e->h_out + 2 * nA, d_policy, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
+    roll_count(e, sizeof(int32_t) * (1 + ao::kRollRec) * n + sizeof(double) * nA * (1 + (d_visit ? 1 : 0) + (d_policy ? 1 : 0)));
+    const bool gather = e->tp.noise != 0 && !r.draining;   // the streams of the played games, for the draws of their next moves
+    if (gather) {
+        ao::launch_roll_gather(r.p, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
+        AO_HIP(e, hipGetLastError());
+        AO_HIP(e, hipMemcpyAsync(e->h_mt, e->d_mt_backup, sizeof(uint32_t) * 624 * n, hipMemcpyDeviceToHost, e->stream));
+        AO_HIP(e, hipMemcpyAsync(e->h_pos, e->d_pos_backup, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+        roll_count(e, static_cast<size_t>(n) * (624 * 4 + 4));
+    }
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    // The turned games' error words came back in their records (ERR_SHORT, ERR_BAD_MOVE): no second [G]-wide read. Any of them
+    // fails the call as ao_end_move / ao_play would, before a host mirror is touched; the roll is closed.
+    bool bad = false;
+    for (int b = 0; b < n; ++b) {
+        const int32_t* rec = h_rec + static_cast<size_t>(b) * ao::kRollRec;
+        h_err[rec[0]] = rec[7];   // (h_err was all zero: report_game_errors passed it above)
+        bad = bad || rec[7] != 0;
+    }
+    if (bad && report_game_errors(e, h_err)) { roll_close(e); return 1; }
+    std::vector<int32_t> next, next_rows;
+    for (int b = 0; b < n; ++b) {
+        const int32_t* rec = h_rec + static_cast<size_t>(b) * ao::kRollRec;
+        const int g = rec[0];
+        out->game[b] = g;
+        out->ply[b] = static_cast<int32_t>(e->moves[g].size());
+        out->action[b] = rec[1];
+        out->win[b] = rec[2];
+        out->tau[b] = rec[3];
+        out->sims[b] = std::max(0, rec[4] - e->bonus[g]);
+        out->settled[b] = rec[5];
+        e->moves[g].push_back(rec[1]);
+        e->status[g] = rec[6];
+        e->over[g] = rec[2];
+        e->active[g] = 0;
+        r.in_move[g] = 0;
+        --r.n_in_move;
+        if (ao::roll_begins_next(rec[2], r.draining)) { next.push_back(g); next_rows.push_back(b); }
+    }
+    std::memcpy(out->pi, e->h_out, sizeof(double) * nA);
+    if (out->visit && d_visit) std::memcpy(out->visit, e->h_out + nA, sizeof(double) * nA);
+    if (out->policy && d_policy) std::memcpy(out->policy, e->h_out + 2 * nA, sizeof(double) * nA);
+    out->count = n;
+    r.games_turned += n;
+    if (roll_begin_games(e, next, gather ? next_rows.data() : nullptr)) return roll_fail(e, e->err);
+    r.last_bytes = r.bytes - bytes0;
+    return 0;
+}
+
+int ao_roll_run(ao_engine* e, int64_t max_launches, ao_roll_records* out) {
+    RollState& r = e->roll;
+    if (!r.open) return e->fail("ao_roll_run: no roll is open");
+    if (!out || !out->game || !out->ply || !out->action || !out->win || !out->tau || !out->sims || !out->settled || !out->pi)
+        return e->fail("ao_roll_run: null record array");
+    if (max_launches < 0) return e->fail("ao_roll_run: max_launches must be >= 0");
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    out->count = 0;
+    int64_t launches = 0;
+    if (ao::roll_run_returns(0, r.n_in_move, launches, max_launches)) return 0;
+    for (;;) {
+        switch (r.cad.next()) {
+        case ao::ROLL_TURN:
+            if (roll_turn(e, out)) return 1;
+            if (ao::roll_run_returns(out->count, r.n_in_move, launches, max_launches)) return 0;
+            break;
+        case ao::ROLL_LOOK:
+            if (roll_look(e)) return 1;
+            break;
+        case ao::ROLL_LAUNCH:
+            if (roll_launch(e)) return 1;
+            ++launches;
+            if (!r.cad.turn_due() && ao::roll_run_returns(0, r.n_in_move, launches, max_launches)) return 0;
+            break;
+        }
+    }
+}
+
+int ao_roll_end(ao_engine* e) {
+    RollState& r = e->roll;
+    if (!r.open) return e->fail("ao_roll_end: no roll is open");
+    if (r.n_in_move > 0)
+        return e->fail("ao_roll_end: " + std::to_string(r.n_in_move) + " game(s) are still in a move (ao_roll_drain, then ao_roll_run until nothing is)");
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    if (roll_harvest_rows(e, r.launch)) return 1;
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    roll_close(e);
+    return 0;
+}
+
+int ao_roll_stats(ao_engine* e, int64_t* turns, int64_t* games_turned, int64_t* bytes, int64_t* last_games, int64_t* last_bytes) {
+    if (turns) *turns = e->roll.turns;
+    if (games_turned) *games_turned = e->roll.games_turned;
+    if (bytes) *bytes = e->roll.bytes;
+    if (last_games) *last_games = e->roll.last_games;
+    if (last_bytes) *last_bytes = e->roll.last_bytes;
     return 0;
 }
 

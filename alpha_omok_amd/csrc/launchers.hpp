@@ -23,10 +23,21 @@ void launch_end_move(const TreeParams& p, hipStream_t s);
 int launch_play(const TreeParams& p, hipStream_t s);
 int launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
                 const int32_t* prev_known, int32_t* status_out, hipStream_t s);
+int launch_reroot(const TreeParams& p, int count, const int32_t* games, hipStream_t s);   // k_reroot for the listed games (null: all p.G)
+bool reroot_fits(const TreeParams& p);   // false: launch_reroot / launch_play / launch_walk would refuse (the queue of a p.cap arena does not fit the LDS)
 void launch_reset(const TreeParams& p, const uint8_t* mask, hipStream_t s);
 void launch_settle(const TreeParams& p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out, hipStream_t s);
 void launch_eval_log(const int32_t* games, int n, const int32_t* row_of_game, const float* policy, const float* value, int A,
                      float* out, const int32_t* sims_done, const int32_t* leaf_status, int what, hipStream_t s);
+// roll.hip: a turn of the rolling search for a compact list of n games (one wave per listed game)
+constexpr int kRollRec = 8;    // words of a turn record: game, action (-1: short of its simulations), win, tau, simulations done, settled, AO_ROOT_* of the new root, the game's error word behind the turn (0: none)
+constexpr int kRollItem = 6;   // words of a begin item: game, target, gflags, tau, settle mask, row of its stream and noise in the compact buffers (-1: no draw)
+void launch_roll_turn(const TreeParams& p, const int32_t* games, int n, uint8_t* active, const uint8_t* settled, int32_t* rec, double* rec_pi,
+                      double* rec_visit, double* rec_policy, hipStream_t s);
+void launch_roll_gather(const TreeParams& p, const int32_t* games, int n, uint32_t* out_mt, int32_t* out_pos, hipStream_t s);
+void launch_roll_begin(const TreeParams& p, const int32_t* items, int n, const uint32_t* in_mt, const int32_t* in_pos, const double* in_noise,
+                       int8_t* tau, uint8_t* active, uint8_t* settled, uint8_t* early, hipStream_t s);
+void launch_roll_mask(const TreeParams& p, const uint8_t* early, uint8_t* out, hipStream_t s);
 // tree_readout.hip
 void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
                         int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);

@@ -1,0 +1,73 @@
+// roll_schedule.hpp -- the host rules of the rolling search (engine.hip, the ao_roll_* driver): which games are turned (their move
+// ended, played, the next one begun) while the others go on searching, what a turned game's next move is, when a run call
+// returns, what draining means, and in which order looks, launches and turns follow each other. No HIP, no engine: plain C++17,
+// tested on the host (tests/host/roll_schedule_main.cpp).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+
+namespace ao {
+
+// ---- who turns ------------------------------------------------------------------------------------------------------------------
+// A game is turned when it is in a move, has run exactly its target and has no leaf under way (a settled game's pending leaf is
+// backed up by the launch behind the look, after which done == target). done != target in a turned game would be ERR_SHORT.
+inline bool roll_turns(bool in_move, int done, int target, bool leaf_idle) { return in_move && leaf_idle && done == target; }
+
+// ---- the next move of a game ----------------------------------------------------------------------------------------------------
+// the column of a by-ply table row of `stride` entries: plies beyond the table read its last column
+inline int roll_ply_column(int ply, int stride) { return std::min(ply, stride - 1); }
+
+// refuse: 0 the move can begin; 1 the budget is outside 1..S; 2 noise asked for on an engine created without noise
+struct RollMove { int tau, budget, target, gflags, draw, refuse; };
+
+// ply: moves on the board; tau_plies: tau is 1 for the first tau_plies moves of the game (negative: always); sims_row /
+// noise_row: the game's rows of the by-ply tables (null: the engine's S / the engine's noise); root_status: AO_ROOT_* of the
+// position (0 fresh, 1 known, 2 expanded). target counts a fresh root's own expansion; gflags are TreeParams::gflags (bit 0:
+// re-noise the inherited root when the move begins, bit 1: no noise at this move's root); draw: the game's stream pays for a
+// Dirichlet draw before the move.
+inline RollMove roll_next_move(int ply, int tau_plies, const int32_t* sims_row, int sims_stride, const uint8_t* noise_row,
+                               int noise_stride, bool engine_noise, int S, int root_status) {
+    RollMove m{};
+    m.tau = (tau_plies < 0 || ply < tau_plies) ? 1 : 0;
+    m.budget = sims_row ? sims_row[roll_ply_column(ply, sims_stride)] : S;
+    const bool wants = noise_row ? noise_row[roll_ply_column(ply, noise_stride)] != 0 : engine_noise;
+    if (m.budget < 1 || m.budget > S) m.refuse = 1;
+    else if (wants && !engine_noise) m.refuse = 2;
+    m.target = m.budget + (root_status == 0 ? 1 : 0);
+    const bool quiet = engine_noise && !wants;      // this game, this move: as on an engine created without noise
+    m.gflags = quiet ? 2 : ((engine_noise && root_status == 2) ? 1 : 0);
+    m.draw = (engine_noise && !quiet) ? 1 : 0;
+    return m;
+}
+
+// ---- drain ----------------------------------------------------------------------------------------------------------------------
+// a turned game begins another move unless its game is over or the roll is draining
+inline bool roll_begins_next(int win, bool draining) { return win == 0 && !draining; }
+
+// ---- when a run call returns ----------------------------------------------------------------------------------------------------
+// asked behind every turn (records: what it produced) and behind every launch that no turn follows (records = 0):
+// at least one record; nothing in a move any more; the launch bound (0: none) is spent
+inline bool roll_run_returns(int records, int in_move, int64_t launches, int64_t max_launches) {
+    return records > 0 || in_move == 0 || (max_launches > 0 && launches >= max_launches);
+}
+
+// ---- look / launch / turn -------------------------------------------------------------------------------------------------------
+// A period is turn_every launches and one turn. With early stop the look (k_settle) stands in front of the period's LAST launch:
+// that launch backs up the leaf a settled game still had under way, the turn behind it ends the game's move and begins the next,
+// and the launch after the turn selects the new move's first leaf -- a settled game idles in no launch.
+enum RollStep { ROLL_LAUNCH = 0, ROLL_LOOK = 1, ROLL_TURN = 2 };
+struct RollCadence {
+    int turn_every = 1;
+    bool early = false;
+    int since = 0;         // launches since the last turn
+    bool looked = false;   // this period's look has been queued
+    bool turn_due() const { return since >= turn_every; }
+    RollStep next() {      // the next step, taken
+        if (turn_due()) { since = 0; looked = false; return ROLL_TURN; }
+        if (early && !looked && since == turn_every - 1) { looked = true; return ROLL_LOOK; }
+        ++since;
+        return ROLL_LAUNCH;
+    }
+};
+
+}  // namespace ao

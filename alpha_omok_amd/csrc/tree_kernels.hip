@@ -15,6 +15,8 @@
 //   k_play            utils.py:189-195 (get_action) + env/env_small.py:154-176,196 (step)
 //                     + re-rooting (tree reuse across moves, main.py:171): k_reroot, launched behind
 //                     k_play and k_walk, on the subtree walk of tree_walk.hpp
+//                     (the bodies of k_begin_move, k_end_move and k_play are functions of ONE game in move_device.hpp:
+//                     the rolling search's turn, roll.hip, calls the same ones for a compact list of games)
 //   k_walk            the `root_id in self.tree` lookup of agents.py:84 for an arbitrary id
 //                     (find_edge of tree_walk.hpp per move, as k_play and k_tree_lookup)
 //
@@ -23,6 +25,7 @@
 // table of correctly rounded values, fp32 w/q with correctly rounded add/divide.
 #include "host_handle.hpp"
 #include "launchers.hpp"
+#include "move_device.hpp"
 #include "tree_walk.hpp"
 
 namespace ao {
@@ -82,41 +85,8 @@ __global__ __launch_bounds__(64 * kGamesPerWG) void k_expand_select(TreeParams p
 template <int NCH>
 __global__ __launch_bounds__(64) void k_begin_move(TreeParams p) {
     const int g = blockIdx.x;
-    const int lane = lane_id();
     if (p.active && !p.active[g]) return;
-    if (lane == 0) { p.sims_done[g] = 0; p.leaf_status[g] = LS_IDLE; }   // (no leaf of an aborted move is left waiting for a row)
-    const int node = p.root_node[g];
-    const bool renoise = (p.gflags[g] & 1) != 0;
-    if ((!renoise && !p.bar) || node < 0) return;
-    const size_t slot = node_slot(p, p.cur[g], g, node);
-    const int L = nodePos(p, slot)->nchild;
-    const uint64_t* bar = p.bar ? p.bar + static_cast<size_t>(g) * kBBWords : nullptr;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int i = lane + 64 * c;
-        if (i < L) {
-            if (renoise) {
-                const double t1 = __dmul_rn(0.75, rowP(p, slot)[i]);
-                const double t2 = __dmul_rn(0.25, p.noise_buf[static_cast<size_t>(g) * p.Ap + i]);
-                rowP(p, slot)[i] = __dadd_rn(t1, t2);
-            }
-            // The bar on an inherited root (a fresh root gets it where it is expanded, expand_backup_game). A barred child
-            // forgets its statistics and its subtree: N = W = 0, Q = kBarQ, and CH_UNVISITED leaves what hung below it
-            // unreachable until the next re-rooting drops it. A child that carries the sentinel of an earlier search of
-            // this root and is allowed now is an unvisited child again.
-            if (bar) {
-                const int a = rowACT(p, slot)[i];
-                if ((bar[a >> 6] >> (a & 63)) & 1ull) {
-                    rowN(p, slot)[i] = 0;
-                    rowW(p, slot)[i] = 0.f;
-                    rowQ(p, slot)[i] = kBarQ;
-                    rowCH(p, slot)[i] = CH_UNVISITED;
-                } else if (rowQ(p, slot)[i] == kBarQ) {
-                    rowQ(p, slot)[i] = 0.f;
-                }
-            }
-        }
-    }
+    begin_move_game<NCH>(p, g, (p.gflags[g] & 1) != 0);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -128,88 +98,10 @@ __global__ __launch_bounds__(64) void k_end_move(TreeParams p) {
     __shared__ int s_vis[256];
     __shared__ double s_pol[256];
     const int g = blockIdx.x;
-    const int lane = lane_id();
     if (p.active && !p.active[g]) return;
-    // The reference's search always runs its num_mcts simulations (agents.py:105-132): a game that is short of them -- a caller that
-    // ends the move early, an over-subscribed search that left its catch-up loop -- gets an error word instead of a pi, and its
-    // stream is not touched.
-    if (p.sims_done[g] != p.sims_target[g]) {
-        if (lane == 0) atomicOr(&p.err[g], ERR_SHORT);
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int a = lane + 64 * c;
-        if (a < p.A) { s_vis[a] = 0; s_pol[a] = 0.0; }
-    }
-    __syncthreads();
-    const int node = p.root_node[g];
-    int tot = 0;
-    if (node >= 0) {
-        const size_t slot = node_slot(p, p.cur[g], g, node);
-        const int L = nodePos(p, slot)->nchild;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int i = lane + 64 * c;
-            if (i < L) {
-                const int a = rowACT(p, slot)[i];
-                const int n = rowN(p, slot)[i];
-                s_vis[a] = n;
-                s_pol[a] = rowP(p, slot)[i];
-                tot += n;
-            }
-        }
-    }
-    tot = wave_sum_i(tot);
-    __syncthreads();
-    const double total = static_cast<double>(tot);
-    double pi[NCH];
-    int vmax = -1;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int a = lane + 64 * c;
-        pi[c] = 0.0;
-        if (a < p.A) {
-            pi[c] = __ddiv_rn(static_cast<double>(s_vis[a]), total);  // visit / visit.sum()
-            vmax = s_vis[a] > vmax ? s_vis[a] : vmax;
-            if (p.out_visit) p.out_visit[static_cast<size_t>(g) * p.A + a] = static_cast<double>(s_vis[a]);
-            if (p.out_policy) p.out_policy[static_cast<size_t>(g) * p.A + a] = s_pol[a];
-        }
-    }
-    const int tau = p.tau ? p.tau[g] : 1;
-    if (tau == 0) {
-        // utils.argmax_onehot: np.argwhere(pi == pi.max()) in ascending action order.
-        // Equal pi <=> equal visit count (same divisor), so compare the exact integers.
-        vmax = wave_max_i(vmax);
-        MtDev mt;
-        mt.open(p.mt + static_cast<size_t>(g) * 624, p.mtpos + g, s_mt);
-        uint64_t tm[NCH];
-        int k = 0;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int a = lane + 64 * c;
-            tm[c] = __ballot(a < p.A && s_vis[a] == vmax);
-            k += __popcll(tm[c]);
-        }
-        int r = mt.below(k);
-        int pick = -1;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int cnt = __popcll(tm[c]);
-            if (pick < 0) {
-                if (r < cnt) pick = 64 * c + nth_set_bit(tm[c], r);
-                else r -= cnt;
-            }
-        }
-        mt.close();
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) pi[c] = (lane + 64 * c == pick) ? 1.0 : 0.0;
-    }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int a = lane + 64 * c;
-        if (a < p.A) p.out_pi[static_cast<size_t>(g) * p.A + a] = pi[c];
-    }
+    const size_t row = static_cast<size_t>(g) * p.A;
+    (void)end_move_game<NCH>(p, g, p.tau ? p.tau[g] : 1, nullptr, s_mt, s_vis, s_pol, p.out_pi + row, p.out_visit ? p.out_visit + row : nullptr,
+                             p.out_policy ? p.out_policy + row : nullptr, nullptr);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -354,68 +246,8 @@ __global__ __launch_bounds__(64) void k_play(TreeParams p) {
     uint32_t* s_mt = reinterpret_cast<uint32_t*>(s_dyn);             // 624 * 4 = 2496 B
     double* s_cdf = reinterpret_cast<double*>(s_dyn + 2496);         // 256 * 8 = 2048 B
     const int g = blockIdx.x;
-    const int lane = lane_id();
     if (p.active && !p.active[g]) return;
-    MtDev mt;
-    mt.open(p.mt + static_cast<size_t>(g) * 624, p.mtpos + g, s_mt);
-    // cdf = pi.cumsum() (sequential fp64); cdf /= cdf[-1]; searchsorted(cdf, u, 'right')
-    if (lane == 0) {
-        double s = 0.0;
-        for (int a = 0; a < p.A; ++a) {
-            const double x = p.out_pi[static_cast<size_t>(g) * p.A + a];
-            s = (a == 0) ? x : __dadd_rn(s, x);
-            s_cdf[a] = s;
-        }
-    }
-    __syncthreads();
-    const double last = s_cdf[p.A - 1];
-    const double u = mt.next_double();
-    mt.close();
-    int action = -1;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int a = lane + 64 * c;
-        const bool gt = (a < p.A) && (__ddiv_rn(s_cdf[a], last) > u);
-        const uint64_t mk = __ballot(gt);
-        if (action < 0 && mk) action = 64 * c + __ffsll(static_cast<long long>(mk)) - 1;
-    }
-    if (action < 0) action = p.A - 1;  // pi == NaN (no visits): numpy would return A here
-    // env.step: place the stone, flip the turn, check_win (env_small.py:154-176,196)
-    PosR rp = pos_load(p.rootpos + g);
-    const bool occupied = pos_occupied(rp, action);
-    pos_place(rp, action);
-    const int w = win_after_move(rp, action, p.B, p.win_mark);
-    // tree reuse: the chosen child becomes the root (main.py:171 -> agents.py:84)
-    const int node = p.root_node[g];
-    int ch = CH_UNVISITED;
-    if (node >= 0) {
-        const size_t slot = node_slot(p, p.cur[g], g, node);
-        const int found = find_edge<NCH>(p, slot, nodePos(p, slot)->nchild, action);
-        if (found >= 0) ch = rowCH(p, slot)[found];
-    }
-    if (ch >= 0 && w == 0) {
-        // The arena is compacted (k_reroot, launched right behind this kernel: the subtree copied into the other arena) only when
-        // the next search might not fit behind what is in it: nodes_used <= keep_max = cap - sims - 1 leaves room for every
-        // expansion of the next move, so the root just moves to the child and the unreachable nodes stay where they are until a
-        // later move needs the room. Same trees, same trims (a subtree above keep_max nodes implies nodes_used above it), a
-        // copy every (cap - subtree) / sims moves instead of every move.
-        if (lane == 0) {
-            if (p.nodes_used[g] <= p.keep_max && !p.compact_always) p.root_node[g] = ch;
-            else p.pending_root[g] = ch + 1;
-        }
-    } else if (lane == 0) {
-        p.nodes_used[g] = 0;
-        p.root_node[g] = -1;
-    }
-    if (lane == 0) {
-        rp.nchild = 0;
-        pos_store(p.rootpos + g, rp);
-        p.action[g] = action;
-        p.win[g] = w;
-        // the new root is a record of the reference's dict iff its parent was expanded
-        p.rstatus[g] = (ch >= 0 && w == 0) ? 2 : ((node >= 0) ? 1 : 0);
-        if (occupied) atomicOr(&p.err[g], ERR_BAD_MOVE);
-    }
+    (void)play_game<NCH>(p, g, p.out_pi + static_cast<size_t>(g) * p.A, nullptr, s_mt, s_cdf);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -571,9 +403,12 @@ void launch_end_move(const TreeParams& p, hipStream_t s) {
 void launch_settle(const TreeParams& p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out, hipStream_t s) {
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_settle<NCH>, dim3(p.G), dim3(64), 0, s, p, mask, stop_now, leaf_open, settled, out));
 }
-static void launch_reroot(const TreeParams& p, int count, const int32_t* games, hipStream_t s) {
+bool reroot_fits(const TreeParams& p) { return walk_lds_bytes(p.cap) != 0; }
+int launch_reroot(const TreeParams& p, int count, const int32_t* games, hipStream_t s) {
+    if (!walk_lds_bytes(p.cap)) return 1;
     const size_t lds = walk_lds_bytes(p.cap);
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_reroot<NCH>, dim3(count), dim3(64 * kWalkWaves), lds, s, p, games));
+    return 0;
 }
 // launch_play / launch_walk, non-zero: the re-rooting's queue does not fit the LDS of one workgroup (walk_lds_bytes) -- nothing is launched
 int launch_play(const TreeParams& p, hipStream_t s) {

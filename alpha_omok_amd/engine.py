@@ -419,6 +419,85 @@ class Engine:
             self._fp16_seen, self._fp16_games_seen = ev, games
         return pi, vis, pol
 
+    # -- rolling search: every game moves on its own clock inside one launch loop (ao_roll_*)
+    def _by_ply(self, v, dtype):
+        """None, a scalar, [G] or [G, P] -> a contiguous [G, P] table by ply (the last column holds for every later ply)."""
+        if v is None:
+            return None
+        a = np.asarray(v)
+        if a.ndim == 2 and a.shape[0] == self.G and a.shape[1] >= 1:
+            return np.ascontiguousarray(a, dtype)
+        if a.ndim > 1:
+            raise ValueError("expected a scalar, [G] or [G, P], got shape %r" % (a.shape,))
+        return np.ascontiguousarray(np.broadcast_to(a, (self.G,)).reshape(self.G, 1), dtype)
+
+    def _roll_opts(self, active, tau_plies, sims, noise, early_stop=False, turn_every=None, visit=False, policy=False):
+        keep = (None if active is None else np.ascontiguousarray(active, np.uint8), self._per_game(tau_plies, np.int32),
+                self._by_ply(sims, np.int32), self._by_ply(noise, np.uint8))
+        a, t, s, n = keep
+        o = _lib.AoRollOpts(active=_ptr(a, C.c_uint8), tau_plies=_ptr(t, C.c_int32), sims=_ptr(s, C.c_int32),
+                            sims_stride=0 if s is None else s.shape[1], noise=_ptr(n, C.c_uint8),
+                            noise_stride=0 if n is None else n.shape[1], early_stop=1 if early_stop else 0,
+                            turn_every=SETTLE_EVERY if turn_every is None else int(turn_every),
+                            want_visit=1 if visit else 0, want_policy=1 if policy else 0)
+        return o, keep                                   # (the struct holds pointers into `keep`: the caller keeps it until the call returns)
+
+    def roll_begin(self, net, active=None, tau_plies=None, sims=None, noise=None, early_stop=False, turn_every=None,
+                   visit=False, policy=False):
+        """Opens a rolling search on `net` (ao_roll_begin): the listed games (None: all that are not over) begin a move and
+        from then on every game ends its move, plays and begins the next one on its own clock, turn_every launches apart
+        (None: SETTLE_EVERY), while the others go on searching. tau_plies: int or [G], tau is 1 while fewer moves than that
+        are on the board (None: always); sims / noise: budgets and noise switches by ply, a scalar, [G] or [G, P] (a ply
+        beyond P reads the last column); early_stop: tau == 0 moves stop once decided; visit / policy: roll_run returns
+        them. Until roll_end, begin_move / search / end_move / play / set_root(s) / export_trees ... raise EngineError."""
+        o, keep = self._roll_opts(active, tau_plies, sims, noise, early_stop, turn_every, visit, policy)
+        self._check(self._L.ao_roll_begin(self._h, net._h, C.byref(o)), "ao_roll_begin")
+        self._roll_buf = self._roll_buffers(visit, policy)
+
+    def _roll_buffers(self, visit=False, policy=False):
+        G, A = self.G, self.A
+        return dict({k: np.zeros(G, np.int32) for k in ("game", "ply", "action", "win", "tau", "sims", "settled")},
+                    pi=np.zeros((G, A)), visit=np.zeros((G, A)) if visit else None, policy=np.zeros((G, A)) if policy else None)
+
+    def roll_run(self, max_launches=0):
+        """Runs the loop until a turn has produced a record, nothing is in a move, or max_launches launches are spent (0: no
+        bound) -- ao_roll_run. Returns a dict of arrays cut to the record count, one entry per game that ended a move: game,
+        ply (moves on the board before it), action, win, tau, sims (simulations run, budget units), settled (bool), pi
+        [n, A], and visit / policy [n, A] where roll_begin asked for them. A game with win != 0 is over; every other one is
+        already searching its next move (unless draining)."""
+        b = getattr(self, "_roll_buf", None) or self._roll_buffers()
+        rec = _lib.AoRollRecords(count=0, pi=_ptr(b["pi"], C.c_double), visit=_ptr(b["visit"], C.c_double),
+                                 policy=_ptr(b["policy"], C.c_double),
+                                 **{k: _ptr(b[k], C.c_int32) for k in ("game", "ply", "action", "win", "tau", "sims", "settled")})
+        self._check(self._L.ao_roll_run(self._h, int(max_launches), C.byref(rec)), "ao_roll_run")
+        n = rec.count
+        out = {k: b[k][:n].copy() for k in ("game", "ply", "action", "win", "tau", "sims", "pi")}
+        out["settled"] = b["settled"][:n].astype(bool)
+        for k in ("visit", "policy"):
+            if b[k] is not None:
+                out[k] = b[k][:n].copy()
+        return out
+
+    def roll_join(self, active=None, tau_plies=None, sims=None, noise=None):
+        """Games that are not in a move (a slot refilled by reset + seed_games) begin one and join the running loop
+        (ao_roll_join); tau_plies / sims / noise replace the listed games' rows, shapes as at roll_begin."""
+        o, keep = self._roll_opts(active, tau_plies, sims, noise)
+        self._check(self._L.ao_roll_join(self._h, C.byref(o)), "ao_roll_join")
+
+    def roll_drain(self):
+        """From now on no turned game begins another move; roll_run returns records until nothing is in a move."""
+        self._check(self._L.ao_roll_drain(self._h), "ao_roll_drain")
+
+    def roll_end(self):
+        """Closes the roll (ao_roll_end); EngineError while any game is in a move. The engine is between moves afterwards."""
+        self._check(self._L.ao_roll_end(self._h), "ao_roll_end")
+
+    def roll_stats(self):
+        """dict(turns, games_turned, bytes, last_games, last_bytes): host traffic of the turns (ao_roll_stats)."""
+        v = [C.c_int64(0) for _ in range(5)]
+        self._check(self._L.ao_roll_stats(self._h, *[C.byref(x) for x in v]), "ao_roll_stats")
+        return dict(zip(("turns", "games_turned", "bytes", "last_games", "last_bytes"), (x.value for x in v)))
+
     def fp16_range_events(self):
         """(moves ao_search repeated on the fp32-MFMA trunk, games searched again) since the engine was created."""
         a, b = C.c_int64(0), C.c_int64(0)

@@ -86,7 +86,7 @@ trim_stats = {'subtrees_dropped': 0, 'reroots_trimmed': 0}   # cumulative since 
 # simulations of all searches (levels / (evaluated + terminal) = mean selection depth)
 phase_seconds = {'play': 0.0, 'emit': 0.0, 'train_wait': 0.0}   # cumulative since configure(): self_play's wall time inside the searches / building and
                              # appending the samples / waiting for an overlapped training pass (train_join) before the samples are appended
-search_totals = {'levels': 0, 'ties': 0, 'terminal': 0, 'evaluated': 0, 'searches': 0}
+search_totals = {'levels': 0, 'ties': 0, 'terminal': 0, 'evaluated': 0, 'searches': 0}   # 'searches': engine-wide search calls; under configure(rolling=True): runs of the roll that returned records (a run turns some games, not every game one ply)
 CARRY_OVER = None            # configure(carry_over=True): slots freed at the end of one self_play call start the NEXT call's episodes
                              # (None = automatic: on inside run() when GAMES_PER_ITER is set, off otherwise)
 DEVICE_STATES = True         # with configure(device_replay=True): the samples' state planes are built on the device from the move lists
@@ -94,7 +94,7 @@ DEVICE_STATES = True         # with configure(device_replay=True): the samples' 
 CARRY_CALLS = 2              # ... of at most this many calls ahead
 OVERLAP_TRAIN = False        # configure(overlap_train=True): run() trains on a worker thread + side stream WHILE the next iteration's games are
                              # played (train_async / train_join); 'serial' = the same deferred schedule without the thread (tests)
-played_ahead = [0]           # carry-over + overlapped training: searches made for LATER calls' games while a call that was complete waited for the pass
+played_ahead = [0]           # carry-over + overlapped training: searches made for LATER calls' games while a call that was complete waited for the pass (rolling: runs of the roll, as 'searches' above)
 _train_job = None            # the training pass in flight (train_async): dict(thread, plan, n_epochs, losses, error, done)
 _train_stream = None
 last_train_losses = None     # losses of the pass train_join() finished last (self_play joins silently)
@@ -106,6 +106,9 @@ TACTICS = None               # configure(tactics=True or dict): every self-play 
 FAST_SIMS = None             # configure(fast_sims=N): playout-cap randomisation -- every (episode, ply) is a full search (N_MCTS simulations, noise as
 FULL_PROB = 0.25             # configured, sample recorded; probability FULL_PROB) or a fast one (N simulations, no noise, move played, no sample)
 playout_totals = {'full': 0, 'fast': 0}   # move decisions of either kind since configure() (all of them 'full' without fast_sims)
+ROLLING = False              # configure(rolling=True): self-play runs ONE rolling search per call (Engine.roll_*): every game ends its move, plays and
+TURN_EVERY = None            # begins the next on its own clock, looked at every TURN_EVERY launches (None: engine.SETTLE_EVERY), instead of search + play per ply
+roll_sims_log = None         # a list: the rolling loop appends (global episode number, ply, simulations run, settled) per move decision (tests, tools)
 FP16_GRID = False            # configure(fp16_grid_weights=True): the 3x3 conv weights of Agent.model are kept on the fp16 grid (see _grid_sync)
 _grid_masters = []           # ... [(parameter, fp32 master copy)]: Adam moves the master, the module holds its projection
 
@@ -113,7 +116,8 @@ _grid_masters = []           # ... [(parameter, fp32 master copy)]: Adam moves t
 def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_planes=None, seed=None,
               model=None, gpu=None, noise=True, device_replay=False, node_cap=None, strict=None, reproducible=False,
               carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None,
-              early_stop=False, fast_sims=None, full_prob=0.25, tactics=None, forward_precision="fp32"):
+              early_stop=False, fast_sims=None, full_prob=0.25, tactics=None, forward_precision="fp32", rolling=False,
+              turn_every=None):
     """Build `Agent`, `Agent.model` and `optimizer` (main.py:58-85). Call instead of editing constants.
     node_cap: expanded-node capacity of a game's tree arena (0 = 16*(n_mcts+1) where 40 % of the HBM
     holds that for all games, at least 4*(n_mcts+1); -1 = grow into the free HBM);
@@ -156,10 +160,26 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     one MFMA product per multiply-add, activations rounded once to fp16) wherever the resident / board-resident trunk is planned;
     training is untouched (the module trains in torch fp32). A position's evaluation then depends on which kernel its batch is
     planned onto (about 5e-3 in a logit), so it cannot be combined with reproducible=True. Needs a network the split-fp16 kernels
-    cover (128 planes, at least one block); "fp32" (the default) is everything as before."""
+    cover (128 planes, at least one block); "fp32" (the default) is everything as before.
+    rolling=True: a self_play call is ONE rolling search (Engine.roll_begin ... roll_end) instead of search + play per ply: the launch
+    loop never stops for a move boundary, every turn_every launches (None: engine.SETTLE_EVERY) the games that have their simulations
+    end their move, play and begin the next one, finished slots are refilled and join the running loop. Every game's search is the
+    same strictly sequential one, so with reproducible=True an episode is bit for bit the episode of rolling=False. Combines with
+    early_stop, fast_sims / full_prob, oversubscribe, carry_over, overlap_train, fp16_grid_weights, forward_precision and
+    reproducible; not with tactics= (the rolling search has no root bar), and it needs a model with a native form."""
     global BOARD_SIZE, N_MCTS, N_BLOCKS, IN_PLANES, OUT_PLANES, SEED, Agent, optimizer, device
     global _engine, _evaluator, _episodes_played, rep_memory, STRICT, NODE_CAP, CARRY_OVER, _pool, OVERSUBSCRIBE, ROWS, _terminal_share
-    global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS
+    global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS, ROLLING, TURN_EVERY
+    if rolling and tactics:
+        raise ValueError("rolling=True and tactics= do not go together: the rolling search has no root bar")
+    if turn_every is not None and int(turn_every) < 1:
+        raise ValueError("turn_every must be >= 1")
+    if rolling and model is not None and not hasattr(model, "forward_ptr"):
+        from . import pvnet as _pv
+        cfg = _pv.looks_like_pvnet(model)
+        if cfg is None or not _pv.native_supported(cfg[2]) or cfg[3] != (board_size or BOARD_SIZE) or cfg[1] != (in_planes or IN_PLANES):
+            raise ValueError("rolling=True needs a model with a native form (a PVNet the MFMA forward covers, or an engine.Net): the "
+                             "rolling search runs on the native network only")
     if forward_precision not in ("fp32", "fp16"):
         raise ValueError("forward_precision must be 'fp32' or 'fp16', not %r" % (forward_precision,))
     if forward_precision == "fp16" and reproducible:
@@ -171,6 +191,8 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     if not 0.0 <= float(full_prob) <= 1.0:
         raise ValueError("full_prob must be in [0, 1]")
     EARLY_STOP = bool(early_stop)
+    ROLLING = bool(rolling)
+    TURN_EVERY = None if turn_every is None else int(turn_every)
     TACTICS = tactics if tactics else None
     if TACTICS is not None and (STRICT if strict is None else strict):
         raise ValueError("tactics and strict=True do not go together: a barred root child forgets its inherited visits, which "
@@ -415,6 +437,90 @@ def _check_visits(eng, vis, act, on, inherit, fp16_seen, sims=None):
     return ev
 
 
+def _roll_tables(gids):
+    """configure(rolling=True): the playout-cap tables of the listed episodes by ply -- budgets int32 [n, A] and noise switches
+    uint8 [n, A] (None on an agent without noise) from full_search(SEED, episode, ply) for plies 0..A-1; (None, None) without
+    fast_sims. gids < 0 (idle slots) read as episode 0: their rows are never used."""
+    if FAST_SIMS is None:
+        return None, None
+    A = BOARD_SIZE * BOARD_SIZE
+    full = full_search(SEED, np.maximum(np.asarray(gids, np.int64), 0)[:, None], np.arange(A, dtype=np.int64)[None, :])
+    return np.where(full, N_MCTS, FAST_SIMS).astype(np.int32), (full.astype(np.uint8) if Agent.noise else None)
+
+
+def _roll_play(eng, gid, ply, active, inherit, sample, moved, finish, start, stop, trace):
+    """configure(rolling=True): the one loop _play_episodes and _play_carry share in place of search + play per ply. gid / ply /
+    active / inherit: per slot, the global episode number, the moves played, 1 while the slot's game runs, and (strict) the visits
+    its next root brings along -- updated in place. Callbacks, whole arrays each: sample(slots, plies, pi) for the records that
+    leave a sample; moved(slots, plies, actions); finish(slots, wins) for the games that ended; start(slots) -> uint8 [G] mask of
+    the slots it reset, seeded and gave a new episode (gid, ply, active set); stop() -> True once the call has what it wants:
+    the roll drains, so the games still running end their current move and stay in flight between moves."""
+    net = Agent.model if hasattr(Agent.model, "forward_ptr") else _evaluator.native_net(Agent.model, eng.board_size, eng.inplanes)
+    if net is None:
+        raise ValueError("rolling=True needs a model with a native form: the rolling search runs on the native network only")
+    _set_rows(eng)
+    sims, noise = _roll_tables(gid)
+    budget = (lambda g, p: N_MCTS) if sims is None else (lambda g, p: sims[g, np.minimum(p, sims.shape[1] - 1)])
+    eng.roll_begin(net, active=active, tau_plies=TAU_THRES, sims=sims, noise=noise, early_stop=EARLY_STOP, turn_every=TURN_EVERY,
+                   visit=STRICT)
+    draining = False
+    try:
+        while True:
+            t_run = time.perf_counter()
+            if not draining and stop():
+                eng.roll_drain()
+                draining = True
+            r = eng.roll_run()
+            on = r['game'].astype(np.int64)
+            if on.size == 0:
+                break                                         # (nothing is in a move any more)
+            if trace is not None:
+                trace.append((int(on.size), time.perf_counter() - t_run))
+            search_totals['searches'] += 1
+            at = r['ply'].astype(np.int64)
+            assert np.array_equal(at, ply[on])
+            full = np.ones(on.size, bool) if sims is None else full_search(SEED, np.maximum(gid[on], 0), at)
+            if STRICT:
+                _check_trim(eng)
+                got, want = r['visit'].sum(axis=1), inherit[on] + r['sims']
+                if not np.array_equal(got, want) or (r['sims'] > budget(on, at)).any():
+                    from .engine import EngineError
+                    bad = int(np.flatnonzero((got != want) | (r['sims'] > budget(on, at)))[0])
+                    raise EngineError("self-play: the rolling search of game slot %d returned %d visits at ply %d, %d expected (%d inherited "
+                                      "+ %d simulations)" % (on[bad], int(got[bad]), at[bad], int(want[bad]), int(inherit[on[bad]]), int(r['sims'][bad])))
+                inherit[on] = np.maximum(r['visit'][np.arange(on.size), r['action']] - 1, 0).astype(np.int64)
+            if roll_sims_log is not None:
+                roll_sims_log.extend(zip(gid[on].tolist(), at.tolist(), r['sims'].tolist(), r['settled'].tolist()))
+            sample(on[full], at[full], r['pi'][full])          # (a fast search plays its move and leaves no sample)
+            playout_totals['full'] += int(full.sum())
+            playout_totals['fast'] += int(on.size - full.sum())
+            moved(on, at, r['action'])
+            ply[on] += 1
+            done = on[r['win'] != 0]
+            if done.size:
+                finish(done, r['win'][r['win'] != 0])
+                active[done] = 0
+                inherit[done] = 0
+                mask = start(done)
+                if mask.any() and not draining:
+                    gs = np.flatnonzero(mask)
+                    if sims is not None:
+                        s1, n1 = _roll_tables(gid[gs])
+                        sims[gs] = s1
+                        if noise is not None:
+                            noise[gs] = n1
+                    eng.roll_join(active=mask, tau_plies=TAU_THRES, sims=sims, noise=noise)
+    except BaseException:
+        release_engine()                                      # (a roll that failed is closed by the library; anything else leaves it open)
+        raise
+    eng.roll_end()
+    st = eng.search_stats()
+    for k in ('levels', 'ties', 'terminal', 'evaluated'):
+        search_totals[k] += st[k]
+    global _terminal_share
+    _terminal_share = st['terminal'] / max(st['terminal'] + st['evaluated'], 1)
+
+
 def _play_episodes(episodes, use_global, seed_of, first_episode=0):
     """Plays the listed episodes on one engine (G = min(len, MAX_CONCURRENT) slots, finished slots refilled).
     Returns (moves [E, A] int32 (-1 padded), lengths [E], wins [E], ep_of [N], ply_of [N], pis [N, A] float64):
@@ -447,48 +553,80 @@ def _play_episodes(episodes, use_global, seed_of, first_episode=0):
     inherit = np.zeros(G, np.int64)                       # strict mode: visits the next root of each slot brings along
     fp16_seen = eng.fp16_range_events()[0]
     trace = [] if os.environ.get("AO_SELFPLAY_TRACE") else None   # (active games, seconds) per search, for tools/time_self_play.py
-    while active.any():
-        tau = (ply < TAU_THRES).astype(np.int8)           # main.py:150-153
-        t_search = time.perf_counter()
-        _set_rows(eng)
-        gids = first_episode + np.asarray(episodes, np.int64)[np.maximum(slot_row, 0)]
-        opts, full = _search_opts(eng, gids, ply, tau)
-        pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=active, **opts)
-        _count_search(eng)
-        act, win = eng.play()                             # utils.get_action + env.step
-        if trace is not None:
-            trace.append((int(active.sum()), time.perf_counter() - t_search))
-        on = np.flatnonzero(active)
-        if STRICT:
-            _check_trim(eng)                              # (a trimmed re-rooting is reported as what it is, not as a visit mismatch)
-            fp16_seen = _check_visits(eng, vis, act, on, inherit, fp16_seen, _sims_ran(eng, opts))
-        rows = slot_row[on]
-        rec = on if full is None else on[full[on]]        # (a fast search plays its move and leaves no sample)
-        hist.append((slot_row[rec], ply[rec].copy(), pi[rec]))
-        playout_totals['full'] += int(rec.size)
-        playout_totals['fast'] += int(on.size - rec.size)
-        moves[rows, ply[on]] = act[on]
-        ply[on] += 1
-        done = on[win[on] != 0]
-        if done.size:
-            r = slot_row[done]
-            lengths[r] = ply[done]
-            wins[r] = win[done]
+    if ROLLING:
+        gid = first_episode + np.asarray(episodes, np.int64)[slot_row]
+
+        def finish(done, win):
+            lengths[slot_row[done]] = ply[done]
+            wins[slot_row[done]] = win
+
+        def start(done):
+            nonlocal next_row
             refill = np.zeros(G, np.uint8)
-            for g in done:                                # finished games only
+            for g in done:
+                ply[g] = 0
                 if next_row < E:
                     refill[g] = 1
                     slot_row[g] = next_row
+                    gid[g] = first_episode + episodes[next_row]
                     next_row += 1
                 else:
-                    active[g] = 0
                     slot_row[g] = -1
-                ply[g] = 0
-                inherit[g] = 0
             if refill.any():
                 eng.reset(refill)                         # Agent.reset() (main.py:248)
                 gs = np.flatnonzero(refill)
                 eng.seed_games(gs, [seed_of(episodes[slot_row[g]]) for g in gs])
+                active[gs] = 1
+            return refill
+
+        def moved(on, at, act):
+            moves[slot_row[on], at] = act
+
+        _roll_play(eng, gid, ply, active, inherit, lambda on, at, pi: hist.append((slot_row[on], at, pi)), moved, finish, start,
+                   lambda: False, trace)
+    else:
+        while active.any():
+            tau = (ply < TAU_THRES).astype(np.int8)           # main.py:150-153
+            t_search = time.perf_counter()
+            _set_rows(eng)
+            gids = first_episode + np.asarray(episodes, np.int64)[np.maximum(slot_row, 0)]
+            opts, full = _search_opts(eng, gids, ply, tau)
+            pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=active, **opts)
+            _count_search(eng)
+            act, win = eng.play()                             # utils.get_action + env.step
+            if trace is not None:
+                trace.append((int(active.sum()), time.perf_counter() - t_search))
+            on = np.flatnonzero(active)
+            if STRICT:
+                _check_trim(eng)                              # (a trimmed re-rooting is reported as what it is, not as a visit mismatch)
+                fp16_seen = _check_visits(eng, vis, act, on, inherit, fp16_seen, _sims_ran(eng, opts))
+            rows = slot_row[on]
+            rec = on if full is None else on[full[on]]        # (a fast search plays its move and leaves no sample)
+            hist.append((slot_row[rec], ply[rec].copy(), pi[rec]))
+            playout_totals['full'] += int(rec.size)
+            playout_totals['fast'] += int(on.size - rec.size)
+            moves[rows, ply[on]] = act[on]
+            ply[on] += 1
+            done = on[win[on] != 0]
+            if done.size:
+                r = slot_row[done]
+                lengths[r] = ply[done]
+                wins[r] = win[done]
+                refill = np.zeros(G, np.uint8)
+                for g in done:                                # finished games only
+                    if next_row < E:
+                        refill[g] = 1
+                        slot_row[g] = next_row
+                        next_row += 1
+                    else:
+                        active[g] = 0
+                        slot_row[g] = -1
+                    ply[g] = 0
+                    inherit[g] = 0
+                if refill.any():
+                    eng.reset(refill)                         # Agent.reset() (main.py:248)
+                    gs = np.flatnonzero(refill)
+                    eng.seed_games(gs, [seed_of(episodes[slot_row[g]]) for g in gs])
     _check_trim(eng)
     if trace is not None:
         last_trace[:] = trace
@@ -600,39 +738,72 @@ def _play_carry(first_episode, n_call, rank, world):
         job = _train_job
         return job is not None and job['thread'] is not None and job['thread'].is_alive()
 
-    while todo or (pass_running() and pool.active.any()):
-        if not todo:
-            played_ahead[0] += 1
-        if not pool.active.any():
+    if ROLLING:
+        if todo and not pool.active.any():
             raise RuntimeError("carry-over self-play: episodes %r are neither in flight nor finished" % sorted(todo)[:8])
-        tau = (pool.ply < TAU_THRES).astype(np.int8)      # main.py:150-153
-        t_search = time.perf_counter()
-        _set_rows(eng)
-        opts, full = _search_opts(eng, pool.slot_id, pool.ply, tau)
-        pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=pool.active, **opts)
-        _count_search(eng)
-        act, win = eng.play()
-        if trace is not None:
-            trace.append((int(pool.active.sum()), time.perf_counter() - t_search))
-        on = np.flatnonzero(pool.active)
-        if STRICT:
-            _check_trim(eng)
-            pool.fp16_seen = _check_visits(eng, vis, act, on, pool.inherit, pool.fp16_seen, _sims_ran(eng, opts))
-        rec = on if full is None else on[full[on]]        # (a fast search plays its move and leaves no sample)
-        pool.hist.append((pool.slot_id[rec].copy(), pool.ply[rec].copy(), pi[rec]))
-        playout_totals['full'] += int(rec.size)
-        playout_totals['fast'] += int(on.size - rec.size)
-        pool.slot_moves[on, pool.ply[on]] = act[on]
-        pool.ply[on] += 1
-        done = on[win[on] != 0]
-        if done.size:
-            for g in done:                                # finished games only
+
+        def finish(done, win):
+            for g, w in zip(done, win):
+                g = int(g)
                 gid = int(pool.slot_id[g])
-                pool.finished[gid] = (pool.slot_moves[g].copy(), int(pool.ply[g]), int(win[g]))
+                pool.finished[gid] = (pool.slot_moves[g].copy(), int(pool.ply[g]), int(w))
                 todo.discard(gid)
                 pool.slot_id[g] = -1
+
+        def restart(done):
+            before = pool.active.copy()
+            before[done] = 0
             pool.active[done] = 0
             start(done)
+            return (pool.active != before).astype(np.uint8)
+
+        def moved(on, at, act):
+            pool.slot_moves[on, at] = act
+
+        def sample(on, at, pi):
+            pool.hist.append((pool.slot_id[on].copy(), at, pi))
+
+        def stop():
+            if not todo and pass_running():
+                played_ahead[0] += 1                      # (a run of the loop beyond what the call asked for)
+            return not (todo or pass_running())
+
+        if todo or (pass_running() and pool.active.any()):
+            _roll_play(eng, pool.slot_id, pool.ply, pool.active, pool.inherit, sample, moved, finish, restart, stop, trace)
+    else:
+        while todo or (pass_running() and pool.active.any()):
+            if not todo:
+                played_ahead[0] += 1
+            if not pool.active.any():
+                raise RuntimeError("carry-over self-play: episodes %r are neither in flight nor finished" % sorted(todo)[:8])
+            tau = (pool.ply < TAU_THRES).astype(np.int8)      # main.py:150-153
+            t_search = time.perf_counter()
+            _set_rows(eng)
+            opts, full = _search_opts(eng, pool.slot_id, pool.ply, tau)
+            pi, vis, _ = _evaluator.search(eng, Agent.model, tau, active=pool.active, **opts)
+            _count_search(eng)
+            act, win = eng.play()
+            if trace is not None:
+                trace.append((int(pool.active.sum()), time.perf_counter() - t_search))
+            on = np.flatnonzero(pool.active)
+            if STRICT:
+                _check_trim(eng)
+                pool.fp16_seen = _check_visits(eng, vis, act, on, pool.inherit, pool.fp16_seen, _sims_ran(eng, opts))
+            rec = on if full is None else on[full[on]]        # (a fast search plays its move and leaves no sample)
+            pool.hist.append((pool.slot_id[rec].copy(), pool.ply[rec].copy(), pi[rec]))
+            playout_totals['full'] += int(rec.size)
+            playout_totals['fast'] += int(on.size - rec.size)
+            pool.slot_moves[on, pool.ply[on]] = act[on]
+            pool.ply[on] += 1
+            done = on[win[on] != 0]
+            if done.size:
+                for g in done:                                # finished games only
+                    gid = int(pool.slot_id[g])
+                    pool.finished[gid] = (pool.slot_moves[g].copy(), int(pool.ply[g]), int(win[g]))
+                    todo.discard(gid)
+                    pool.slot_id[g] = -1
+                pool.active[done] = 0
+                start(done)
     _check_trim(eng)
     if trace is not None:
         last_trace[:] = trace
@@ -1219,10 +1390,12 @@ if __name__ == '__main__':
     ap.add_argument('--overlap-train', action='store_true', help='train beside the next iteration\'s games (train_async)')
     ap.add_argument('--fp16-grid-weights', action='store_true', help='keep the 3x3 conv weights on the fp16 grid: two-product split-fp16 kernels (configure)')
     ap.add_argument('--fp16-forward', action='store_true', help='searches run the opt-in plain-fp16 forward: one MFMA product per multiply-add (configure(forward_precision="fp16"))')
+    ap.add_argument('--rolling', action='store_true', help='self-play as one rolling search per call: every game moves on its own clock (configure(rolling=True))')
+    ap.add_argument('--turn-every', type=int, default=None, metavar='N', help='with --rolling: launches between two turns (default: engine.SETTLE_EVERY)')
     a = ap.parse_args()
     parallel.init_from_env()
     GAMES_PER_ITER, TRAIN_STEPS = a.games_per_iter, a.train_steps
     configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, device_replay=a.device_replay, oversubscribe=a.oversubscribe,
               overlap_train=a.overlap_train, fp16_grid_weights=a.fp16_grid_weights,
-              forward_precision="fp16" if a.fp16_forward else "fp32")
+              forward_precision="fp16" if a.fp16_forward else "fp32", rolling=a.rolling, turn_every=a.turn_every)
     run(a.iters, a.model, a.dataset, a.selfplay)

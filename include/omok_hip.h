@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define AO_ABI_VERSION 2   /* 2: ao_config.arena_fraction (round 6) */
+#define AO_ABI_VERSION 2   /* 2: ao_config.arena_fraction (round 6); entry points added since (ao_roll_*) change no existing layout */
 
 typedef struct ao_engine ao_engine; /* search engine: G games                       */
 typedef struct ao_net ao_net;       /* policy/value ResNet (model.py PVNet) weights  */
@@ -110,7 +110,10 @@ int ao_begin_move(ao_engine *e, const uint8_t *host_active);
  * changed by then and the engine stays usable. Values of inactive games are not looked at. */
 int ao_begin_move_opts(ao_engine *e, const uint8_t *host_active, const int32_t *host_sims, const uint8_t *host_noise);
 /* Launches the step-wise protocol still has to run: the largest number of simulations any active game owes. Lowered by
- * ao_settle. */
+ * ao_settle. ao_end_move's precondition is stated in these terms: every active game has done == target, which the step-wise
+ * protocol reaches after exactly this many ao_collect_leaves / ao_apply_evals pairs; a game that is not there gets the error
+ * word ERR_SHORT from k_end_move and the call fails (see ao_end_move). The rolling search (ao_roll_run) relies on the same
+ * rule from the other side: it turns a game only when it has read done == target for it. */
 int ao_sims_left(ao_engine *e);
 /* Settling: lower the simulation targets of games whose move is decided, or of every masked game at once. Legal between
  * ao_begin_move and ao_end_move only. For an active game let r = target - done be the simulations it owes, pending = 1 if
@@ -169,6 +172,74 @@ int ao_search_opts(ao_engine *e, ao_net *net, const uint8_t *host_active, const 
  * 1 where settling lowered the game's target; and the engine's running totals of games settled and simulations saved.
  * Any pointer may be NULL. */
 int ao_search_sims(ao_engine *e, int32_t *host_sims_run, uint8_t *host_settled, int64_t *settled_total, int64_t *saved_total);
+
+/* ---- rolling search (no reference counterpart) ---- every game moves on its own clock inside one launch loop.
+ * ao_search searches one move of every game per call: its loop lasts until the LAST game has its simulations, then all games
+ * end the move, play and begin the next one together. A ROLL keeps the launch loop running (select | net | expand + select |
+ * net | ..., always on the rows-per-simulation path, the batch bounded by ao_set_row_cap) and every turn_every launches TURNS
+ * the games that have their simulations: end of move, play, re-root, and the begin of the game's next move, for a compact
+ * list of games, in O(listed games) work and host traffic; the other games are mid-search in the same launches. A game's
+ * search stays strictly sequential, so each record is, to the bit, what ao_search_opts + ao_play return for that game's ply
+ * from the same stream, budget and noise switch (pi, visit, policy, action, win, and the stream afterwards).
+ * Protocol: ao_roll_begin -> repeat ao_roll_run (records come back as games turn; refill finished slots with ao_reset(mask),
+ * ao_seed_games, ao_roll_join) -> ao_roll_drain -> ao_roll_run until nothing is in a move -> ao_roll_end.
+ * Inside an open roll ao_begin_move*, ao_search*, ao_end_move, ao_play, ao_settle, ao_collect_leaves, ao_apply_evals,
+ * ao_set_root(s), ao_set_root_bar, ao_set_row_cap, ao_set_eval_log, ao_tree_export, ao_tree_import and ao_root_tactics fail
+ * with a message that says a roll is open; ao_reset, ao_seed*, ao_set_rng_state fail, naming the game, for a game that is in
+ * a move, and work for the others. The tree read-outs (ao_tree_lookup, ao_tree_pv, ao_tree_stats, ao_get_root_children)
+ * stay legal between ao_roll_run calls; ao_destroy is legal at any time. ao_search_sims' totals, ao_row_stats,
+ * ao_trim_stats and ao_search_stats keep counting. */
+typedef struct ao_roll_opts {
+    const uint8_t *active;     /* [G] the games that begin a move; NULL = every game that is not over                        */
+    const int32_t *tau_plies;  /* [G] tau = 1 while ply < tau_plies[g] (ply: moves on the board), else 0; NULL = tau 1 always */
+    const int32_t *sims;       /* [G][sims_stride] budget by ply: column min(ply, sims_stride - 1); NULL = ao_config.sims     */
+    int32_t sims_stride;
+    const uint8_t *noise;      /* [G][noise_stride] noise switch by ply, looked up the same way; NULL = the engine's          */
+    int32_t noise_stride;
+    int32_t early_stop;        /* != 0: a look (ao_settle's rule, pending leaf counted) settles decided tau == 0 moves         */
+    int32_t turn_every;        /* >= 1: launches between two turns                                                            */
+    int32_t want_visit;        /* != 0: the records carry visit / policy                                                      */
+    int32_t want_policy;
+} ao_roll_opts;
+/* Records of one ao_roll_run, caller-owned arrays of capacity G (a game turns at most once per turn): entry b < count is
+ * game[b]'s move at ply[b] (moves on the board before it): action, win (0 playing, 1 black, 2 white, 3 draw), the tau it
+ * was decided with, sims = simulations run in budget units (done - bonus, as ao_search_sims reports them), settled = 1
+ * where a look lowered its target, pi [b][A], and visit / policy [b][A] where asked for (either may be NULL). */
+typedef struct ao_roll_records {
+    int32_t count;
+    int32_t *game, *ply, *action, *win, *tau, *sims, *settled;
+    double *pi, *visit, *policy;
+} ao_roll_records;
+/* Opens a roll on `net`: begins a move for every listed game and queues the first selection. Refused, with nothing touched:
+ * inside a move or an open roll, with a pending root bar, with an eval log set, on a network that does not fit the engine,
+ * turn_every < 1, or a budget outside 1..ao_config.sims / a noise switch on an engine without noise anywhere in a listed
+ * game's table rows (the message names the game). */
+int ao_roll_begin(ao_engine *e, ao_net *net, const ao_roll_opts *opts);
+/* Runs the loop until a turn has produced at least one record, nothing is in a move, or max_launches launches of this call
+ * are spent (0 = no bound). out->count may be 0. A game whose record has win != 0 is over and takes no further part; every
+ * other turned game is already searching its next move, unless the roll is draining. Order of steps with early_stop, per
+ * period of turn_every launches: turn_every - 1 launches, the look, one launch (it backs up the leaf a settled game still had
+ * under way), the turn. At every turn the network's status word and the games' error words are read BEFORE any game is
+ * turned: AO_NET_FP16_RANGE fails the call with a message that names it (there is no transparent repeat on the fp32-MFMA
+ * trunk under rolling), a per-game error fails it as ao_end_move / ao_play would; either way no game is turned in that turn,
+ * the error words are cleared, the roll is closed and the engine is outside any move. */
+int ao_roll_run(ao_engine *e, int64_t max_launches, ao_roll_records *out);
+/* Games that are not in a move (listed in opts->active; NULL = all that are not over) begin one and join the running loop;
+ * only the per-game fields of opts are read (tau_plies, the sims / noise rows; strides as at ao_roll_begin) and replace the
+ * listed games' rows. Typical: a slot refilled by ao_reset(mask) + ao_seed_games. A listed game that is in a move is refused. */
+int ao_roll_join(ao_engine *e, const ao_roll_opts *opts);
+/* From now on no turned game begins another move; ao_roll_run keeps returning records until nothing is in a move. */
+int ao_roll_drain(ao_engine *e);
+/* Closes the roll. Refused, naming how many games are affected, while any game is in a move. Afterwards the engine is
+ * exactly between moves, as after ao_play: moves, root status, over flags, streams and the Gaussian cache of the host
+ * draws; ao_search, ao_tree_export, ao_set_roots and the rest work again. */
+int ao_roll_end(ao_engine *e);
+/* Host traffic of the turns: turns taken, games turned, bytes copied between host and device by turns, looks and begins
+ * since the engine was created, and the games / bytes of the LAST turn. Every copy a turn makes is counted. A turn's bytes
+ * are 16 per game of the engine (the four words it decides from: simulations done, target, leaf status, error word) plus a
+ * few KB per game it turns; the turned games' error words come back in their records -- never a second [G]-wide read, and
+ * never a [G]-wide copy of pi, visit, policy or the streams. */
+int ao_roll_stats(ao_engine *e, int64_t *turns, int64_t *games_turned, int64_t *bytes, int64_t *last_games, int64_t *last_bytes);
 
 /* ---- root move restriction ("the bar", no reference counterpart) ----
  * host_allowed uint8 [G][A]: 1 = the cell may be searched at game g's root in the NEXT ao_begin_move* / ao_search*; NULL

@@ -90,6 +90,10 @@ def main():
                     help="playout-cap randomisation (main.configure(fast_sims=N)): a ply is searched fully (--sims, noise, sample recorded) with "
                          "probability --full-prob, else with N simulations, no noise and no sample")
     ap.add_argument("--full-prob", type=float, default=0.25)
+    ap.add_argument("--rolling", action="store_true",
+                    help="self-play as one rolling search per call (main.configure(rolling=True)): every game ends its move, plays and begins "
+                         "the next one on its own clock inside one launch loop; not with --tactics")
+    ap.add_argument("--turn-every", type=int, default=None, metavar="N", help="with --rolling: launches between two turns (default: engine.SETTLE_EVERY)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--resume", default=None, help="state_dict to start from")
     ap.add_argument("--save-replay", default=None, metavar="PATH",
@@ -125,7 +129,8 @@ def main():
     m.configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, out_planes=a.planes, seed=a.seed,
                 device_replay=True, carry_over=not a.no_carry_over, oversubscribe=a.oversubscribe, rows=a.rows,
                 fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob,
-                tactics=True if a.tactics else None, forward_precision="fp16" if a.fp16_forward else "fp32")
+                tactics=True if a.tactics else None, forward_precision="fp16" if a.fp16_forward else "fp32", rolling=a.rolling,
+                turn_every=a.turn_every)
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
