@@ -100,7 +100,8 @@ struct ao_net : ao::HandleBase {
     bool w16 = false;
     int products_req = 0;
     // The opt-in fp16 forward (ao_net_precision; net_f16.hip): AO_NET_PRECISION_FP16 = the batches planned onto the resident trunk
-    // or k_boardh run its ONE-product form. Belongs to the net like products_req, survives ao_net_finalize, independent of it.
+    // or k_boardh run its ONE-product form; AO_NET_PRECISION_FP16_ALL = those, and every other batch as k_layer16h_f16
+    // (net_f16_layers.hip). Belongs to the net like products_req, survives ao_net_finalize, independent of it.
     int precision_req = AO_NET_PRECISION_FP32;
     int trunk_fmt = -1;                            // activation format inside the resident split-fp16 trunk (kPairBytes): 0 = two fp16 halves (default), 1 = fp16 high half + one low byte (AO_TRUNK_FMT=1)
 };
@@ -155,7 +156,10 @@ static bool h16_supported(const ao_net* n) {
 static bool two_products(const ao_net* n) { return n->w16 && n->products_req != 3; }
 // the one-product kernels run where the resident trunk / k_boardh are planned (modes 0 and 5; mode 6 never plans them, and under the
 // fp16-range fallback the net is on mode 2)
-static bool fp16_forward(const ao_net* n) { return n->precision_req == AO_NET_PRECISION_FP16 && h16_supported(n); }
+static bool fp16_forward(const ao_net* n) { return n->precision_req != AO_NET_PRECISION_FP32 && h16_supported(n); }
+// AO_NET_PRECISION_FP16_ALL: every OTHER batch of modes 0 / 5 / 6 runs the one-product per-layer kernel (k_layer16h_f16, conv1
+// included) -- k_layer16hk, k_row16hk and the per-board path are not planned, as under layers_only()
+static bool fp16_all(const ao_net* n) { return n->precision_req == AO_NET_PRECISION_FP16_ALL && h16_supported(n); }
 
 namespace ao {
 
@@ -185,7 +189,9 @@ static int pick_mode(const ao_net* n, int boards, int* nch_out) {
         const long cells = static_cast<long>(boards) * n->A;
         // (end of round 3, with the activations split once at staging and the fused per-game step: 9x9 per-board vs per-layer
         // 841 vs 653 move-decisions/s at 64 games, 983 vs 960 at 96, 1076 vs 1281 at 128; 15x15 equal at 24 games, 581 vs 816 at 36)
-        if (h16_supported(n)) mode = cells <= (n->B > 9 ? 5400 : n->B >= 4 ? n->perboard_cells : 7776) ? 3 : 5;
+        // (fp16-all: the per-board path has no one-product form, its batches take the per-layer kernel; net_plan follows -- group
+        // 16, bit planes for C <= 8 -- and the engine re-plans per search and at roll_begin)
+        if (h16_supported(n)) mode = (!fp16_all(n) && cells <= (n->B > 9 ? 5400 : n->B >= 4 ? n->perboard_cells : 7776)) ? 3 : 5;
         else mode = cells <= 13000 ? 3 : (g16 >= 192 ? 2 : 4);
     }
     if (mode == 2 && (1 + 2 * n->nb > kMaxTrunkLayers)) mode = 4;
@@ -340,7 +346,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
     // (tools/time_move_phases.py --events); with a stride only every n-th forward is timed -- the mean is the same estimate
     n->timing = n->timer.tick();
     int group = 32, nchq = 0, nch = 1;
-    bool heads_h16 = false;   // the separate head kernels read the split-fp16 layout
+    int heads_h16 = 0;   // the separate head kernels read the split-fp16 layout: 1 both halves, 2 the high half alone (k_head_conv)
     net_plan(n, boards, &group, &nchq, nullptr);
     const int mode = pick_mode(n, boards, &nch);
     if (in_kind == 2 && !(mode == 5 && n->C <= 8)) return n->fail("bit planes handed to a kernel that takes the fp32 batch");
@@ -473,8 +479,10 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
         // medium batches of boards up to 9x9: the trunk convs split a group by cout pairs over four workgroups whose
         // waves split the contraction (net_layer_ksplit.hpp); conv1 stays with k_layer16h. Never in mode 6 (one
         // arithmetic for every batch size).
-        const int ks = (!layers_only(n) && n->B >= 4 && n->B <= 9 && groups >= n->ksplit_min) ? (groups <= n->ksplit_max ? 4 : groups <= n->ksplit_max2 ? 2 : 0) : 0;
-        const bool rowk = !layers_only(n) && n->B >= 4 && n->B <= 9 && groups >= n->rowk_min && groups <= n->rowk_max;
+        // Never under fp16-all either: the one-product form exists for k_layer16h alone.
+        const bool f16l = fp16_all(n) && !board_resident(n, boards);   // every layer of this batch, conv1 included, as k_layer16h_f16
+        const int ks = (!layers_only(n) && !f16l && n->B >= 4 && n->B <= 9 && groups >= n->ksplit_min) ? (groups <= n->ksplit_max ? 4 : groups <= n->ksplit_max2 ? 2 : 0) : 0;
+        const bool rowk = !layers_only(n) && !f16l && n->B >= 4 && n->B <= 9 && groups >= n->rowk_min && groups <= n->rowk_max;
         const bool ksplit = ks != 0 || rowk;
         auto layer_k = [&](int l) -> int {
             LayerHArgs a;
@@ -552,6 +560,11 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
             const dim3 grid(groups * nchh * nxt), block(512);
             const bool timed = n->timing && l > 0;
             if (timed) n->timer.begin(s);
+            if (f16l) {
+                AO_HIP(n, ao::launch_layer16h_f16(n->device, n->B, xt, l > 0 ? 0 : in_kind == 2 ? 2 : 1, grid, s, a));
+                if (timed) n->timer.end(s);
+                return 0;
+            }
             if (l > 0 && two_products(n)) {
                 AO_HIP(n, ao::launch_layer16h_w16(n->device, n->B, xt, grid, s, a));
                 if (timed) n->timer.end(s);
@@ -648,7 +661,7 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
                 if (layer(l)) return 1;
         }
         AO_HIP(n, hipGetLastError());
-        heads_h16 = true;   // k_head_conv<true> / k_head_fc below
+        heads_h16 = f16l ? 2 : 1;   // k_head_conv<1> (k_head_conv<2> behind the one-product layers: the high halves alone) / k_head_fc below
     } else if (group == 16 && mode == 5) {
         // split-fp16 resident trunk: one launch carries every 16-board group through conv1 (fp32 planes converted
         // while they are staged), the ResBlocks and the heads
@@ -791,12 +804,16 @@ int net_forward_il(ao_net* n, const float* in_il, int boards, float* policy, flo
     }
     const int ppb = 256 / group;
     const int nchunk = (n->A + ppb - 1) / ppb;
-    if (heads_h16)
-        hipLaunchKernelGGL(k_head_conv<true>, dim3(groups * nchunk), dim3(256), 3 * n->planes * sizeof(float), s,
+    if (heads_h16 == 2)
+        hipLaunchKernelGGL(k_head_conv<2>, dim3(groups * nchunk), dim3(256), 3 * n->planes * sizeof(float), s,
+                           reinterpret_cast<const float4*>(n->act_x), n->head_w3, n->head_sc3, n->head_sh3, n->hbuf,
+                           n->A, n->CQ, group);
+    else if (heads_h16)
+        hipLaunchKernelGGL(k_head_conv<1>, dim3(groups * nchunk), dim3(256), 3 * n->planes * sizeof(float), s,
                            reinterpret_cast<const float4*>(n->act_x), n->head_w3, n->head_sc3, n->head_sh3, n->hbuf,
                            n->A, n->CQ, group);
     else
-        hipLaunchKernelGGL(k_head_conv<false>, dim3(groups * nchunk), dim3(256), 3 * n->planes * sizeof(float), s,
+        hipLaunchKernelGGL(k_head_conv<0>, dim3(groups * nchunk), dim3(256), 3 * n->planes * sizeof(float), s,
                            reinterpret_cast<const float4*>(n->act_x), n->head_w3, n->head_sc3, n->head_sh3, n->hbuf,
                            n->A, n->CQ, group);
     const size_t lds = (static_cast<size_t>(4) * n->A + n->planes + 8) * sizeof(float);
@@ -1191,13 +1208,13 @@ static void dominant_name(const ao_net* n, int boards, int in_kind, std::string*
     } else if (group == 16 && mode == 4) {
         nm = "k_layer16<" + bw + "> (one 3x3 conv per launch, 16-board groups x row chunks, fp32 MFMA 16x16x4)";
         f = conv;
-    } else if (group == 16 && mode == 5 && !layers_only(n) && !n->force_resident && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->rowk_min &&
+    } else if (group == 16 && mode == 5 && !layers_only(n) && !fp16_all(n) && !n->force_resident && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->rowk_min &&
                (boards + 15) / 16 <= n->rowk_max) {
         nm = std::string(two_products(n) ? "k_row16hk_w16<" : "k_row16hk<") + bw + "> (one 3x3 conv per launch as split-fp16 MFMA 16x16x32 (" +
              (two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate): one workgroup per "
              "16-board group x output row x cout pair, waves split the contraction by input block, partial tiles exchanged through LDS)";
         f = conv;
-    } else if (group == 16 && mode == 5 && !layers_only(n) && !n->force_resident && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->ksplit_min &&
+    } else if (group == 16 && mode == 5 && !layers_only(n) && !fp16_all(n) && !n->force_resident && n->B >= 4 && n->B <= 9 && (boards + 15) / 16 >= n->ksplit_min &&
                (boards + 15) / 16 <= std::max(n->ksplit_max, n->ksplit_max2)) {
         const bool four = (boards + 15) / 16 <= n->ksplit_max;
         const bool two = two_products(n) && four;
@@ -1213,6 +1230,11 @@ static void dominant_name(const ao_net* n, int boards, int in_kind, std::string*
              (one ? "1 product: the opt-in fp16 forward, activations rounded once to fp16" : two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate): "
              "a workgroup = one board resident in LDS through all layers, the row's cells as the MFMA N dimension, column shifts as DPP row shifts)";
         f = 2.0 * n->nb * 2.0 * n->A * 9.0 * n->planes * n->planes * boards + (in_kind == 2 ? 2.0 * n->A * 9.0 * n->C * n->planes * boards : 0.0);
+    } else if (group == 16 && mode == 5 && fp16_all(n) && (layers_only(n) || !(n->B <= 9 && ((boards + 15) / 16 >= 192 || n->force_resident)))) {
+        nm = "k_layer16h_f16<" + bw + "> (one 3x3 conv per launch as fp16 MFMA 16x16x32 (1 product: the opt-in fp16 forward, "
+             "activations rounded once to fp16, fp32 accumulate), conv1 on " + (in_kind == 2 ? "bit planes (KIND 2)" : "float planes (KIND 1)") +
+             ", 16-board groups x row chunks x column tiles)";
+        f = conv;
     } else if (group == 16 && mode == 5 && (layers_only(n) || !(n->B <= 9 && ((boards + 15) / 16 >= 192 || n->force_resident)))) {
         nm = std::string(two_products(n) ? "k_layer16h_w16<" : "k_layer16h<") + bw + "> (one 3x3 conv per launch as split-fp16 MFMA 16x16x32 (" +
              (two_products(n) ? "2 products: the conv weights are fp16 numbers" : "3 products") + ", fp32 accumulate), "
@@ -1255,9 +1277,9 @@ int ao_net_products(ao_net* n, int32_t request, int32_t* in_force, int32_t* weig
 }
 
 int ao_net_precision(ao_net* n, int32_t request, int32_t* in_force, int32_t* supported) {
-    if (request != -1 && request != AO_NET_PRECISION_FP32 && request != AO_NET_PRECISION_FP16)
-        return n->fail("ao_net_precision: request must be -1 (query), 0 (AO_NET_PRECISION_FP32) or 1 (AO_NET_PRECISION_FP16)");
-    if (request == AO_NET_PRECISION_FP16 && !h16_supported(n))
+    if (request != -1 && request != AO_NET_PRECISION_FP32 && request != AO_NET_PRECISION_FP16 && request != AO_NET_PRECISION_FP16_ALL)
+        return n->fail("ao_net_precision: request must be -1 (query), 0 (AO_NET_PRECISION_FP32), 1 (AO_NET_PRECISION_FP16) or 2 (AO_NET_PRECISION_FP16_ALL)");
+    if ((request == AO_NET_PRECISION_FP16 || request == AO_NET_PRECISION_FP16_ALL) && !h16_supported(n))
         return n->fail("ao_net_precision: the fp16 forward needs a network the split-fp16 kernels cover (128 planes, at least one ResBlock)");
     if (request != -1) n->precision_req = request;
     if (in_force) *in_force = n->precision_req;

@@ -10,10 +10,14 @@ namespace ao {
 
 struct TrunkHArgs;
 struct BoardHArgs;
+struct LayerHArgs;
 
 // resident trunk (k_trunk16h_f16 / k_trunk16hb_f16<B, 4, 0>), boards 3 .. 9; in_kind 2 = bit planes
 hipError_t launch_trunk16h_f16(int device, int B, int in_kind, int groups, hipStream_t s, const TrunkHArgs& a);
 // board-resident trunk (k_boardh_f16<B, 1 | 2>), boards 10 .. 15
 hipError_t launch_boardh_f16(int device, int B, bool bits, dim3 grid, hipStream_t s, const BoardHArgs& a);
+// per-layer kernel (k_layer16h_f16<B, XT, 4, kind>, net_f16_layers.hip), boards 3 .. 15: XT = B up to 9, xt = 5 or 4 above; kind 0 a
+// trunk layer, 1 conv1 on the fp32 plane batch, 2 conv1 on bit planes. AO_NET_PRECISION_FP16_ALL only.
+hipError_t launch_layer16h_f16(int device, int B, int xt, int kind, dim3 grid, hipStream_t s, const LayerHArgs& a);
 
 }  // namespace ao

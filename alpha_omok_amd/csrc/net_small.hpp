@@ -77,8 +77,10 @@ __global__ __launch_bounds__(64 * 12, 1) void k_conv_cells_h_w16(const float4* _
 
 // 1x1 convs of both heads (model.py:37,56) + their BatchNorm + ReLU.
 // hbuf[board][3][A]: channel 0,1 = policy head, 2 = value head.
-// H16: `in` is in the split-fp16 layout of the k_trunk16h / k_layer16h kernels (GB = 16)
-template <bool H16>
+// H16 != 0: `in` is in the split-fp16 layout of the k_trunk16h / k_layer16h kernels (GB = 16); 1 = x is the sum of its two halves,
+// 2 = the high half alone: behind the one-product layers (k_layer16h_f16) the low slots are unused and hold whatever an earlier
+// default forward of the same net left there
+template <int H16>
 __global__ __launch_bounds__(256) void k_head_conv(const float4* __restrict__ in, const float* __restrict__ w3,
                                                    const float* __restrict__ sc3, const float* __restrict__ sh3,
                                                    float* __restrict__ hbuf, int A, int CQ, int GB) {
@@ -101,9 +103,13 @@ __global__ __launch_bounds__(256) void k_head_conv(const float4* __restrict__ in
                                ((((static_cast<size_t>(grp) * A + pos) * (CQ >> 3) + (cq >> 3)) * 2) * 64 + ((cq & 7) >> 1) * 16 + b) * 16 +
                                (cq & 1) * 8;
             const half4 hh = *reinterpret_cast<const half4*>(base);
+            if (H16 == 2) {
+                x = make_float4(static_cast<float>(hh[0]), static_cast<float>(hh[1]), static_cast<float>(hh[2]), static_cast<float>(hh[3]));
+            } else {
             const half4 hl = *reinterpret_cast<const half4*>(base + 1024);
             x = make_float4(static_cast<float>(hh[0]) + static_cast<float>(hl[0]), static_cast<float>(hh[1]) + static_cast<float>(hl[1]),
                             static_cast<float>(hh[2]) + static_cast<float>(hl[2]), static_cast<float>(hh[3]) + static_cast<float>(hl[3]));
+            }
         } else {
             x = xp[static_cast<size_t>(cq) * GB];
         }

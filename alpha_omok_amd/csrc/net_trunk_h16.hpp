@@ -2,9 +2,9 @@
 // k_trunk16h (group-resident) and k_layer16h (per layer). Included by net.hip after net_trunk_f32.hpp
 // (trunk_heads is shared).
 // Products per multiply-add (TrunkHLayerFn, NPROD): 3 = the fp32-equivalent contraction xh*wh + xh*wl + xl*wh on any fp32 weights,
-// 2 = the same bits when the weights are fp16 numbers (net_w16.hip), 1 = the OPT-IN fp16 forward of the resident trunk
-// (k_trunk16h_f16 / k_trunk16hb_f16, net_f16.hip; ao_net_precision): xh*wh alone, one fp16 per stored activation, not
-// fp32-equivalent. The per-layer kernels below (k_layer16h) have the forms 3 and 2 only.
+// 2 = the same bits when the weights are fp16 numbers (net_w16.hip), 1 = the OPT-IN fp16 forward (ao_net_precision): xh*wh
+// alone, one fp16 per stored activation, not fp32-equivalent -- the resident trunk as k_trunk16h_f16 / k_trunk16hb_f16
+// (net_f16.hip), the per-layer kernel as k_layer16h_f16 (net_f16_layers.hip; AO_NET_PRECISION_FP16_ALL only).
 #pragma once
 
 #include <type_traits>
@@ -698,9 +698,17 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
 // plus one halo column on each side = 7 cells = 56 KB, two of them 112 KB). Halo columns that fall off the
 // board are staged as zeros, so the MFMA stream needs no per-column conditions; halo rows are handled by the
 // slab conditions (uniform per row) exactly as in the fp32 row-chunk kernel.
-template <int BW, int XT, int NC32, int NCI, int KIND, bool W16 = false>
+// NPROD as in TrunkHLayerFn: 3 / 2 the fp32-equivalent forms, 1 the one-product form of the fp16 forward at every batch size
+// (ao_net_precision(AO_NET_PRECISION_FP16_ALL); k_layer16h_f16, launched from net_f16_layers.hip): xh * wh alone, no low weight
+// halves loaded, no low activation half staged, read as a residual, computed or stored; the epilogue stores half(v), the
+// hardware's round to nearest even. Same LDS / HBM geometry, the low slot of every pair unused.
+template <int BW, int XT, int NC32, int NCI, int KIND, int NPROD = 3>
 __device__ __forceinline__ void trunk_h_layer_tile(const void* src, uint4* dst, const TrunkHLayer& L, const bool RES,
                                                    uint4* s_x, int tile, int lane, int x0, int yb, int ye) {
+    static_assert(NPROD >= 1 && NPROD <= 3, "products per multiply-add: 3 (any fp32 weights), 2 (weights on the fp16 grid), 1 (fp16 forward)");
+    constexpr bool W16 = NPROD <= 2;   // no xh * wl product, no low weight halves
+    constexpr bool F16 = NPROD == 1;   // no xl * wh product either, no low activation halves anywhere
+    static_assert(!F16 || (AO_KO == 0 && !AO_CONV1_SPLIT), "the one-product form is no timing experiment");
     constexpr bool FIRST = KIND != 0;
     constexpr bool BITS = KIND == 2;
     constexpr int A = BW * BW;
@@ -763,6 +771,27 @@ __device__ __forceinline__ void trunk_h_layer_tile(const void* src, uint4* dst, 
     };
     // stage this wave's share of input row y into row buffer `xb`
     auto stage = [&](int y, uint4* xb) {
+        if (F16) {
+            // one product: the HIGH fragment of every staged pair alone (fragment 2p of pair p), pairs dealt over the waves
+            constexpr int NPAIR = NFR / 2;
+#pragma unroll
+            for (int k = 0; k < (NPAIR + NT - 1) / NT; ++k) {
+                const int p = tile + NT * k;   // staged pair: (cell j, block c)
+                if (p < NPAIR) {
+                    const int j = p / NCI, c = p - j * NCI;
+                    const int xin = HALO ? x0 - 1 + j : j;
+                    if (xin < 0 || xin >= BW) {
+                        xb[2 * p * 64 + lane] = make_uint4(0, 0, 0, 0);
+                    } else if (FIRST) {
+                        xb[2 * p * 64 + lane] = __builtin_bit_cast(uint4, load_planes(y * BW + xin, 0));
+                    } else {
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, (__attribute__((address_space(3))) void*)(xb + 2 * p * 64), 16,
+                                                                 lane16, ((y * BW + xin) * NCI + c) * 2048, 0, AO_AUX_STAGE);
+                    }
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < (NFR + NT - 1) / NT; ++k) {
             const int f = tile + NT * k;   // staged fragment: (cell j, block c, half)
@@ -795,7 +824,7 @@ __device__ __forceinline__ void trunk_h_layer_tile(const void* src, uint4* dst, 
                 const int xo = x0 + i < BW ? x0 + i : BW - 1;
                 const int ob = (((yo * BW + xo) * NC32 + (tile >> 1)) * 2) * 1024;
                 rh[i] = buf_ld_h4(rs_dst, out_voff, ob);
-                rl[i] = buf_ld_h4(rs_dst, out_voff, ob + 1024);
+                if (!F16) rl[i] = buf_ld_h4(rs_dst, out_voff, ob + 1024);
             }
         }
 #pragma unroll
@@ -804,7 +833,10 @@ __device__ __forceinline__ void trunk_h_layer_tile(const void* src, uint4* dst, 
             const f32x4 c = acc[0][i];
             float f[4] = {fmaf(c[0], sc.x, sh.x), fmaf(c[1], sc.y, sh.y), fmaf(c[2], sc.z, sh.z), fmaf(c[3], sc.w, sh.w)};
             const int ob = (((yo * BW + x0 + i) * NC32 + (tile >> 1)) * 2) * 1024;
-            if (RES) {
+            if (RES && F16) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) f[r] += static_cast<float>(rh[i][r]);   // the block's input as it was stored: one fp16
+            } else if (RES) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) f[r] += static_cast<float>(rh[i][r]) + static_cast<float>(rl[i][r]);
             }
@@ -813,11 +845,11 @@ __device__ __forceinline__ void trunk_h_layer_tile(const void* src, uint4* dst, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float v = fminf(fmaxf(f[r], 0.f), 65504.f);
-                hh[r] = static_cast<_Float16>(v);
-                hl[r] = static_cast<_Float16>(v - static_cast<float>(hh[r]));
+                hh[r] = static_cast<_Float16>(v);   // (round to nearest even: in the one-product form this IS the activation)
+                if (!F16) hl[r] = static_cast<_Float16>(v - static_cast<float>(hh[r]));
             }
             buf_st_h4(hh, rs_dst, out_voff, ob);
-            buf_st_h4(hl, rs_dst, out_voff, ob + 1024);
+            if (!F16) buf_st_h4(hl, rs_dst, out_voff, ob + 1024);
         }
     };
 
@@ -843,18 +875,19 @@ __device__ __forceinline__ void trunk_h_layer_tile(const void* src, uint4* dst, 
             const int yo = yi + 1 - dy;
             if (yo >= yb && yo < ye) {   // (uniform)
                 half8 xh = __builtin_bit_cast(half8, xs[((0 * NCI + c) * NSP + 0) * 64 + lane]);
-                half8 xl = __builtin_bit_cast(half8, xs[((0 * NCI + c) * NSP + 1) * 64 + lane]);
+                half8 xl = F16 ? xh : __builtin_bit_cast(half8, xs[((0 * NCI + c) * NSP + 1) * 64 + lane]);   // (one product: no low halves in LDS)
 #pragma unroll
                 for (int j = 0; j < NX; ++j) {
                     half8 nh = xh, nl = xl;
                     if (j + 1 < NX) {
                         nh = __builtin_bit_cast(half8, xs[(((j + 1) * NCI + c) * NSP + 0) * 64 + lane]);
-                        nl = __builtin_bit_cast(half8, xs[(((j + 1) * NCI + c) * NSP + 1) * 64 + lane]);
+                        nl = F16 ? nh : __builtin_bit_cast(half8, xs[(((j + 1) * NCI + c) * NSP + 1) * 64 + lane]);
                     }
 #pragma unroll
                     for (int pr = 0; pr < NPR; ++pr) {
                         if (BITS && pr == 2) continue;   // (see trunk_h_layer)
                         if (W16 && pr == 1) continue;
+                        if (F16 && pr == 2) continue;    // fp16 forward: the activation operand is its high half alone
 #pragma unroll
                         for (int dx = 0; dx < 3; ++dx) {
                             const int i = HALO ? j - dx : j - dx + 1;   // output cell of the tile fed through tap column dx
@@ -896,7 +929,7 @@ struct LayerHArgs {
     unsigned row_cap;
 };
 
-template <int BW, int XT, int NC32, int KIND, bool W16>
+template <int BW, int XT, int NC32, int KIND, int NPROD>
 __device__ __forceinline__ void layer16h_body(const LayerHArgs& a) {
     constexpr int A = BW * BW;
     constexpr int NXT = (BW + XT - 1) / XT;
@@ -912,25 +945,30 @@ __device__ __forceinline__ void layer16h_body(const LayerHArgs& a) {
     const int tile = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
     uint4* dst = a.dst + static_cast<size_t>(grp) * A * NC32 * 2 * 64;
     if (KIND == 2) {
-        trunk_h_layer_tile<BW, XT, NC32, 1, 2, W16>(static_cast<const uint8_t*>(a.src) + static_cast<size_t>(grp) * 16 * kPlaneRow(BW), dst,
+        trunk_h_layer_tile<BW, XT, NC32, 1, 2, NPROD>(static_cast<const uint8_t*>(a.src) + static_cast<size_t>(grp) * 16 * kPlaneRow(BW), dst,
                                                a.layer, false, s_x, tile, lane, xt * XT, yb, ye);
     } else if (KIND == 1) {
-        trunk_h_layer_tile<BW, XT, NC32, 1, 1, W16>(static_cast<const float4*>(a.src) + static_cast<size_t>(grp) * A * 8 * 16, dst, a.layer,
+        trunk_h_layer_tile<BW, XT, NC32, 1, 1, NPROD>(static_cast<const float4*>(a.src) + static_cast<size_t>(grp) * A * 8 * 16, dst, a.layer,
                                                false, s_x, tile, lane, xt * XT, yb, ye);
     } else {
-        trunk_h_layer_tile<BW, XT, NC32, NC32, 0, W16>(static_cast<const uint4*>(a.src) + static_cast<size_t>(grp) * A * NC32 * 2 * 64, dst,
+        trunk_h_layer_tile<BW, XT, NC32, NC32, 0, NPROD>(static_cast<const uint4*>(a.src) + static_cast<size_t>(grp) * A * NC32 * 2 * 64, dst,
                                                       a.layer, a.res != 0, s_x, tile, lane, xt * XT, yb, ye);
     }
 }
 
 template <int BW, int XT, int NC32, int KIND>
 __global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_layer16h(LayerHArgs a) {
-    layer16h_body<BW, XT, NC32, KIND, false>(a);
+    layer16h_body<BW, XT, NC32, KIND, 3>(a);
 }
 // the two-product form (see TrunkHLayerFn, W16): launched from net_w16.hip
 template <int BW, int XT, int NC32, int KIND>
 __global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_layer16h_w16(LayerHArgs a) {
-    layer16h_body<BW, XT, NC32, KIND, true>(a);
+    layer16h_body<BW, XT, NC32, KIND, 2>(a);
+}
+// the one-product form (see trunk_h_layer_tile, NPROD = 1): launched from net_f16_layers.hip
+template <int BW, int XT, int NC32, int KIND>
+__global__ __launch_bounds__(NC32 * 2 * 64, 1) void k_layer16h_f16(LayerHArgs a) {
+    layer16h_body<BW, XT, NC32, KIND, 1>(a);
 }
 
 template <int BW, int NC32, int INK, int FMT, int NPROD = 3>   // NPROD: see TrunkHLayerFn; INK: 1 fp32 plane batch, 2 bit planes (see trunk_h_layer); FMT: see kPairBytes

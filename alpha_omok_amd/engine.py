@@ -126,15 +126,17 @@ class Net:
         self._check(self._L.ao_net_products(self._h, int(request), C.byref(a), C.byref(b)), "ao_net_products")
         return a.value, bool(b.value)
 
-    PRECISIONS = ("fp32", "fp16")       # AO_NET_PRECISION_FP32 / AO_NET_PRECISION_FP16
+    PRECISIONS = ("fp32", "fp16", "fp16-all")       # AO_NET_PRECISION_FP32 / AO_NET_PRECISION_FP16 / AO_NET_PRECISION_FP16_ALL
 
     def precision(self, request=None):
-        """"fp32" (the default: every forward fp32-equivalent) or "fp16" (the opt-in plain-fp16 forward: one MFMA product per
-        multiply-add, activations rounded once to fp16, on the batches planned onto the resident / board-resident trunk) --
-        ao_net_precision. request: None = query, or either string. Belongs to this Net and survives load_state_dict; "fp16" on a
-        network the split-fp16 kernels do not cover raises EngineError."""
+        """"fp32" (the default: every forward fp32-equivalent), "fp16" (the opt-in plain-fp16 forward: one MFMA product per
+        multiply-add, activations rounded once to fp16, on the batches planned onto the resident / board-resident trunk; every
+        other batch keeps its fp32-equivalent kernel) or "fp16-all" (that arithmetic for EVERY forward of this net: the other
+        batches of modes 0 / 5 / 6 run the one-product per-layer kernel k_layer16h_f16; in mode 6 one arithmetic for every batch
+        size) -- ao_net_precision. request: None = query, or one of PRECISIONS. Belongs to this Net and survives load_state_dict;
+        "fp16" / "fp16-all" on a network the split-fp16 kernels do not cover raises EngineError and changes nothing."""
         if request is not None and request not in self.PRECISIONS:
-            raise ValueError("precision must be 'fp32' or 'fp16', not %r" % (request,))
+            raise ValueError("precision must be 'fp32', 'fp16' or 'fp16-all', not %r" % (request,))
         a, b = C.c_int32(0), C.c_int32(0)
         req = -1 if request is None else self.PRECISIONS.index(request)
         self._check(self._L.ao_net_precision(self._h, req, C.byref(a), C.byref(b)), "ao_net_precision")

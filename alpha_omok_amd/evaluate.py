@@ -154,6 +154,16 @@ class _RolloutSide:
         self.eng.close()
 
 
+def check_forward_precision(forward_precision):
+    """evaluate_batched's forward_precision as the pair (player's, enemy's); ValueError for anything that is not None, one of
+    "fp32" / "fp16" / "fp16-all", or a pair of them. Host only."""
+    if forward_precision is None or isinstance(forward_precision, str):
+        forward_precision = (forward_precision, forward_precision)
+    if len(forward_precision) != 2 or any(p not in (None, "fp32", "fp16", "fp16-all") for p in forward_precision):
+        raise ValueError("forward_precision: 'fp32', 'fp16', 'fp16-all' or a pair (player, enemy) of them")
+    return tuple(forward_precision)
+
+
 def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mcts_enemy=None, inplanes=5, n_match=12,
                      player_elo=1500.0, enemy_elo=1500.0, seed=0, device=0, max_plies=None, monitor_model=None,
                      n_mcts_monitor=None, early_stop=False, tactics=None, forward_precision=None):
@@ -166,12 +176,9 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     fewer simulations; the later plies then search on smaller inherited trees, so a match need not be the one full searches play.
     tactics: Engine.search(tactics=) for the ZeroAgent sides -- True or a dict for both, or a pair (player's, enemy's) with None for
     a side that searches plainly, so that the switch's strength can be measured against the same network without it.
-    forward_precision: "fp32" / "fp16" (Net.precision of the exported networks of the ZeroAgent sides) for both, or a pair (player's,
+    forward_precision: "fp32" / "fp16" / "fp16-all" (Net.precision of the exported networks of the ZeroAgent sides) for both, or a pair (player's,
     enemy's); None leaves the default. A side given as an engine.Net keeps the precision it was set to."""
-    if forward_precision is None or isinstance(forward_precision, str):
-        forward_precision = (forward_precision, forward_precision)
-    if len(forward_precision) != 2 or any(p not in (None, "fp32", "fp16") for p in forward_precision):
-        raise ValueError("forward_precision: 'fp32', 'fp16' or a pair (player, enemy) of them")
+    forward_precision = check_forward_precision(forward_precision)
     n_mcts_enemy = n_mcts_player if n_mcts_enemy is None else n_mcts_enemy
     G = n_match
     win_mark = 3 if board_size == 3 else 5

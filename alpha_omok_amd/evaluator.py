@@ -23,7 +23,7 @@ class Evaluator:
         self._warned_width = False
         self._frozen = False   # freeze(): searches keep the weights exported last, whatever happens to the module (main.train_async)
         self.strict_native = False   # True: a PVNet the native forward cannot take raises instead of running on its torch module
-        self.net_precision = "fp32"   # Net.precision of the exported network ("fp16": the opt-in one-product forward; main.configure(forward_precision=))
+        self.net_precision = "fp32"   # Net.precision of the exported network ("fp16": the opt-in one-product forward, "fp16-all": at every batch size; main.configure(forward_precision=))
         self.net_mode = 0      # ao_net_set_mode of the exported network (6: one kernel family for every batch size)
 
     def native_net(self, model, board_size, inplanes):

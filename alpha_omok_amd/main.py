@@ -161,6 +161,9 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     training is untouched (the module trains in torch fp32). A position's evaluation then depends on which kernel its batch is
     planned onto (about 5e-3 in a logit), so it cannot be combined with reproducible=True. Needs a network the split-fp16 kernels
     cover (128 planes, at least one block); "fp32" (the default) is everything as before.
+    forward_precision="fp16-all": that arithmetic for EVERY batch (Net.precision("fp16-all"): the batches planned elsewhere run the
+    one-product per-layer kernel). reproducible=True puts the network on mode 6, where this is one arithmetic for every batch size,
+    so the two DO go together. It can be slower than "fp32" on the small batches it takes from the per-board path.
     rolling=True: a self_play call is ONE rolling search (Engine.roll_begin ... roll_end) instead of search + play per ply: the launch
     loop never stops for a move boundary, every turn_every launches (None: engine.SETTLE_EVERY) the games that have their simulations
     end their move, play and begin the next one, finished slots are refilled and join the running loop. Every game's search is the
@@ -180,8 +183,8 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
         if cfg is None or not _pv.native_supported(cfg[2]) or cfg[3] != (board_size or BOARD_SIZE) or cfg[1] != (in_planes or IN_PLANES):
             raise ValueError("rolling=True needs a model with a native form (a PVNet the MFMA forward covers, or an engine.Net): the "
                              "rolling search runs on the native network only")
-    if forward_precision not in ("fp32", "fp16"):
-        raise ValueError("forward_precision must be 'fp32' or 'fp16', not %r" % (forward_precision,))
+    if forward_precision not in ("fp32", "fp16", "fp16-all"):
+        raise ValueError("forward_precision must be 'fp32', 'fp16' or 'fp16-all', not %r" % (forward_precision,))
     if forward_precision == "fp16" and reproducible:
         raise ValueError("forward_precision='fp16' and reproducible=True do not go together: under the fp16 forward a position's "
                          "evaluation depends on which kernel its batch is planned onto")
@@ -1389,7 +1392,9 @@ if __name__ == '__main__':
     ap.add_argument('--oversubscribe', type=float, default=None, help='game slots per row of the evaluation batch (1.25 with a trained network)')
     ap.add_argument('--overlap-train', action='store_true', help='train beside the next iteration\'s games (train_async)')
     ap.add_argument('--fp16-grid-weights', action='store_true', help='keep the 3x3 conv weights on the fp16 grid: two-product split-fp16 kernels (configure)')
-    ap.add_argument('--fp16-forward', action='store_true', help='searches run the opt-in plain-fp16 forward: one MFMA product per multiply-add (configure(forward_precision="fp16"))')
+    fwd = ap.add_mutually_exclusive_group()
+    fwd.add_argument('--fp16-forward-all', action='store_true', help='the fp16 forward for every batch size, per-layer kernels included (configure(forward_precision="fp16-all")); not with --fp16-forward')
+    fwd.add_argument('--fp16-forward', action='store_true', help='searches run the opt-in plain-fp16 forward: one MFMA product per multiply-add (configure(forward_precision="fp16"))')
     ap.add_argument('--rolling', action='store_true', help='self-play as one rolling search per call: every game moves on its own clock (configure(rolling=True))')
     ap.add_argument('--turn-every', type=int, default=None, metavar='N', help='with --rolling: launches between two turns (default: engine.SETTLE_EVERY)')
     a = ap.parse_args()
@@ -1397,5 +1402,5 @@ if __name__ == '__main__':
     GAMES_PER_ITER, TRAIN_STEPS = a.games_per_iter, a.train_steps
     configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, device_replay=a.device_replay, oversubscribe=a.oversubscribe,
               overlap_train=a.overlap_train, fp16_grid_weights=a.fp16_grid_weights,
-              forward_precision="fp16" if a.fp16_forward else "fp32", rolling=a.rolling, turn_every=a.turn_every)
+              forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32", rolling=a.rolling, turn_every=a.turn_every)
     run(a.iters, a.model, a.dataset, a.selfplay)

@@ -489,18 +489,32 @@ int  ao_net_products(ao_net *n, int32_t request, int32_t *in_force, int32_t *wei
  * activation. BatchNorm, the residual add, ReLU, the clamp and the heads stay fp32; the next conv, the block's residual add and the
  * heads all read the rounded activation. Float input planes that are not fp16 numbers are rounded to nearest by the resident
  * trunk and taken with all their bits by conv1 in front of the board-resident trunk (the engine's 0/1 planes are exact either way).
- * request: -1 = query only, AO_NET_PRECISION_FP32, AO_NET_PRECISION_FP16. in_force: the setting; supported: 1 for networks the
- * split-fp16 kernels cover (128 planes, at least one ResBlock) -- AO_NET_PRECISION_FP16 on any other network is an error. The
- * setting belongs to the ao_net, survives ao_net_finalize and is independent of ao_net_products, which keeps answering for the
- * fp32-equivalent kernels.
- * What runs: exactly the batches that modes 0 / 5 plan onto the resident trunk (boards up to 9x9, >= 192 groups of 16) or the
- * board-resident trunk (wider boards, >= 64 boards) run that kernel's one-product form (k_trunk16h_f16 / k_trunk16hb_f16 /
- * k_boardh_f16; ao_net_dominant_kernel names it). Every other batch size and mode runs the fp32-equivalent kernel it runs
- * anyway -- more accurate, never less. CONSEQUENCE: under AO_NET_PRECISION_FP16 a position's evaluation depends on which kernel
- * its batch is planned onto, to about 5e-3 in a logit; mode 6 (one arithmetic for every batch size) therefore plans no
- * one-product kernel and must not be combined with it. The fp16-range event is reported as ever (AO_NET_FP16_RANGE), and
- * ao_search's recovery on the fp32-MFMA trunk (mode 2) is unchanged. */
-enum { AO_NET_PRECISION_FP32 = 0, AO_NET_PRECISION_FP16 = 1 };
+ * request: -1 = query only, AO_NET_PRECISION_FP32, AO_NET_PRECISION_FP16, AO_NET_PRECISION_FP16_ALL. in_force: the setting;
+ * supported: 1 for networks the split-fp16 kernels cover (128 planes, at least one ResBlock) -- either fp16 setting on any other
+ * network is an error and leaves the setting as it was. The setting belongs to the ao_net, survives ao_net_finalize and is
+ * independent of ao_net_products, which keeps answering for the fp32-equivalent kernels.
+ * What runs under each setting:
+ *   AO_NET_PRECISION_FP32      the fp32-equivalent kernels, at every batch size and in every mode.
+ *   AO_NET_PRECISION_FP16      exactly the batches that modes 0 / 5 plan onto the resident trunk (boards up to 9x9, >= 192 groups
+ *                              of 16) or the board-resident trunk (wider boards, >= 64 boards) run that kernel's one-product form
+ *                              (k_trunk16h_f16 / k_trunk16hb_f16 / k_boardh_f16; ao_net_dominant_kernel names it). Every other
+ *                              batch size and mode runs the fp32-equivalent kernel it runs anyway -- more accurate, never less.
+ *                              CONSEQUENCE: a position's evaluation depends on which kernel its batch is planned onto, to about
+ *                              5e-3 in a logit; mode 6 (one arithmetic for every batch size) plans no one-product kernel under
+ *                              this setting and must not be combined with it.
+ *   AO_NET_PRECISION_FP16_ALL  EVERY forward of the net is the fp16 arithmetic above. The batches of modes 0 / 5 on the resident
+ *                              or board-resident trunk run what AO_NET_PRECISION_FP16 runs there; every other batch of modes
+ *                              0 / 5 / 6 runs the one-product per-layer kernel k_layer16h_f16 for every layer, conv1 included
+ *                              (float planes that are not fp16 numbers are rounded to nearest), and heads that read the rounded
+ *                              activation alone. k_layer16hk, k_row16hk and the per-board path have no one-product form and are
+ *                              not planned: in mode 0 their batches take the per-layer kernel (16-board groups, bit planes for
+ *                              up to 8 input planes). Under mode 6 this is ONE arithmetic for every batch size -- a position's
+ *                              evaluation no longer depends on how many others share its batch --, so it may be combined with
+ *                              reproducible play. Where it displaces the per-board path or k_row16hk it can be SLOWER than the
+ *                              fp32-equivalent kernel.
+ * The fp16-range event is reported as ever (AO_NET_FP16_RANGE), and ao_search's recovery on the fp32-MFMA trunk (mode 2) is
+ * unchanged under every setting. */
+enum { AO_NET_PRECISION_FP32 = 0, AO_NET_PRECISION_FP16 = 1, AO_NET_PRECISION_FP16_ALL = 2 };
 int  ao_net_precision(ao_net *n, int32_t request, int32_t *in_force, int32_t *supported);
 /* name and algorithmic FLOPs per launch (2*MAC, zero padding counted) of the kernel the timing
  * refers to, for a batch of `boards` positions. */

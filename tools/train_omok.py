@@ -75,7 +75,11 @@ def main():
                     help="keep the 3x3 conv weights on the fp16 grid (main.configure(fp16_grid_weights=True): fp32 master copies in Adam, the module holds "
                          "their fp16 rounding) -- such a network runs on the two-product split-fp16 kernels (ao_net_products); the checkpoint stays a "
                          "plain fp32 state_dict the reference loads")
-    ap.add_argument("--fp16-forward", action="store_true",
+    fwd = ap.add_mutually_exclusive_group()
+    fwd.add_argument("--fp16-forward-all", action="store_true",
+                     help="the fp16 forward for EVERY batch size (main.configure(forward_precision='fp16-all'), Net.precision): the batches planned "
+                          "elsewhere run the one-product per-layer kernel; can be slower than fp32 on small batches")
+    fwd.add_argument("--fp16-forward", action="store_true",
                     help="self-play and evaluation searches run the opt-in plain-fp16 forward (main.configure(forward_precision='fp16'), "
                          "Net.precision): one MFMA product per multiply-add on the batches planned onto the resident trunk; training stays "
                          "torch fp32")
@@ -129,8 +133,8 @@ def main():
     m.configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, out_planes=a.planes, seed=a.seed,
                 device_replay=True, carry_over=not a.no_carry_over, oversubscribe=a.oversubscribe, rows=a.rows,
                 fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob,
-                tactics=True if a.tactics else None, forward_precision="fp16" if a.fp16_forward else "fp32", rolling=a.rolling,
-                turn_every=a.turn_every)
+                tactics=True if a.tactics else None, forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32",
+                rolling=a.rolling, turn_every=a.turn_every)
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
