@@ -7,6 +7,10 @@
 //      k_expand_backup, then k_end_move (and k_play for self-play),
 //   3. copies the [G][A] result vectors back.
 // Everything else lives in HBM and in the kernels of tree_kernels.hip.
+//
+// Two drivers queue those launches, MoveSearch under ao_search* and the rolling search under ao_roll_*, on one footing: what a
+// move is (ao::roll_next_move), its Dirichlet draw (draw_noise), the launch plan and the ring of row counters (LaunchLoop), what a
+// failure leaves behind (clear_game_errors). DESIGN.md section 4 says what each driver adds.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +20,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/omok_hip.h"
@@ -51,6 +56,28 @@ struct DevSwitches {
     static bool catchup_window_off() { return getenv("AO_CATCHUP_WINDOW_OFF") != nullptr; }
 };
 
+// What both search drivers run on: the launch plan (the network's input, the driver's copy of the tree parameters) and the ring
+// of row counters d_live[kLive]. With rows handed out per simulation (engine_types.hpp, TreeParams::live) selection launch i
+// counts the rows its leaves ask for in word i % kLive, the network launch behind it reads that word, and the host sums the
+// words up into ao_row_stats where the ring wraps and when a driver asks (search_schedule.hpp). The methods follow ao_engine.
+struct ao_engine;
+struct LaunchLoop {
+    ao_engine* e = nullptr;
+    bool per_sim = false;          // rows are handed out and counted per simulation (otherwise: packed per move by the host, no ring)
+    int cap_rows = 0, in_kind = 1; // rows of one network launch; the input the network wants (net_plan): 2 = bit planes, otherwise the interleaved fp32 batch
+    const float* net_in = nullptr;
+    ao::TreeParams p{};            // the driver's copy of e->tp; `live` changes per launch
+    int64_t launch = 0, harvested = 0;   // selection launches so far; ... of which the row counters are summed up already
+    int64_t* traffic = nullptr;    // where the bytes of a harvest are charged (the rolling search's ao_roll_stats), or null
+    int plan(ao_engine* e, ao_net* net, int rows);   // a fresh loop with the plan for launches of `rows` rows
+    int zero_ring();                     // where a driver sets per_sim, and at every wrap
+    unsigned* slot(int64_t i) const;     // the counter word of launch i (null without per_sim)
+    bool wraps(int64_t i) const { return per_sim && i > 0 && slot(i) == slot(0); }   // launch i counts in the ring's first word again
+    unsigned counted(int64_t i) const;   // what launch i counted, once harvested (until the ring wraps again)
+    int advance();                       // behind a network launch: the next selection launch and its counter word
+    int harvest(int64_t upto);           // sums up the launches [harvested, upto); synchronises if there are any
+};
+
 // The rolling search (ao_roll_*, at the end of this file): what lives from ao_roll_begin to ao_roll_end. The rules are
 // roll_schedule.hpp's, the kernels roll.hip's.
 struct RollState {
@@ -64,11 +91,7 @@ struct RollState {
     std::vector<int32_t> tau_plies;       // [G], empty: tau 1 always
     std::vector<int32_t> sims; int sims_stride = 0;      // [G][stride] budgets by ply, empty: ao_config.sims
     std::vector<uint8_t> noise; int noise_stride = 0;    // [G][stride] noise switches by ply, empty: the engine's
-    // the launch plan: always rows per simulation (MoveSearch::plan's `dynamic`), no sit-out window, no launch order
-    int cap_rows = 0, in_kind = 1;
-    const float* net_in = nullptr;
-    ao::TreeParams p{};
-    int64_t launch = 0, harvested = 0;    // selection launches of the roll; row counters already summed up
+    LaunchLoop loop;                      // always rows per simulation; no sit-out window, no launch order, no fused step
     // compact buffers of a turn, allocated by the first roll of the engine: [G] games, [G][kRollItem], [G][kRollRec], [3][G][A], [G][Ap]
     int32_t* d_games = nullptr; int32_t* d_items = nullptr; int32_t* d_rec = nullptr; double* d_out = nullptr; double* d_noise = nullptr;
     int32_t* h_i32 = nullptr;             // pinned: [4][G] done, target, leaf status, error words; [G] games; [G][kRollItem]; [G][kRollRec]
@@ -91,8 +114,8 @@ struct ao_engine : ao::HandleBase {
     uint8_t* d_planes_u8 = nullptr;                       // bit planes [Gp][u8_row] (input of the split-fp16 kernels)
     int32_t* d_row = nullptr;                             // [2G] batch row of each game in ao_search (active games packed, or handed out per simulation by the tree kernel), then the game of each row
     std::vector<int32_t> h_row;
-    // rows handed out per simulation (engine_types.hpp TreeParams::live): one counter word per launch of a move, zeroed at the start
-    // of the move (and when the ring wraps); row_cap = rows one simulation may take (0: as many as there are active games)
+    // rows handed out per simulation: LaunchLoop's ring of counter words, one per launch; row_cap = rows one simulation may take
+    // (0: as many as there are active games)
     static constexpr int kLive = 2048;
     unsigned* d_live = nullptr;
     int32_t* d_order = nullptr;      // [G] launch order of k_expand_select's slots for over-subscribed searches (k_order, per move); AO_TREE_ORDER=0: off
@@ -166,6 +189,91 @@ static int roll_refuses(ao_engine* e, const char* who) {
 static int roll_refuses_game(ao_engine* e, const char* who, int g) {
     if (!e->roll.open || !e->roll.in_move[g]) return 0;
     return e->fail(std::string(who) + ": game " + std::to_string(g) + " is in a move of the open roll");
+}
+
+int LaunchLoop::plan(ao_engine* e_, ao_net* net, int rows) {
+    *this = LaunchLoop{e_};
+    cap_rows = rows;
+    // the network announces the interleaved input layout it wants for a batch of cap_rows boards
+    ao::net_plan(net, cap_rows, &e->tp.il_group, &e->tp.nchq, &in_kind);
+    // The padding channels of the fp32 input batch (planes 5..31 of a 32-channel slab) are zero and stay zero: the
+    // encoder only writes the quads that hold planes (16 B per lane at a 2 KB stride are partial-line writes --
+    // rocprof showed 152 MB of HBM writes per launch for a 42 MB batch). A change of layout re-zeroes the buffer.
+    // The split-fp16 kernels take the planes as BITS instead (in_kind 2): one byte per cell, 81 contiguous bytes per
+    // leaf, and the fp32 batch is not written at all.
+    if (in_kind != 2 && (e->il_group_zeroed != e->tp.il_group || e->il_nchq_zeroed != e->tp.nchq)) {
+        AO_HIP(e, hipMemsetAsync(e->tp.batch_il, 0, e->il_bytes, e->stream));
+        e->il_group_zeroed = e->tp.il_group;
+        e->il_nchq_zeroed = e->tp.nchq;
+    }
+    // select | net | expand+select | net | ... | expand(+idle select): one launch fewer per simulation
+    // than the step-wise protocol, same device code (tree_device.hpp).
+    p = e->tp;
+    p.batch_nchw = nullptr; p.policy = e->d_policy; p.value = e->d_value; p.row_of_game = e->d_row;
+    p.nchq_live = (e->cfg.inplanes + 3) / 4;
+    net_in = p.batch_il;
+    if (in_kind == 2) {
+        net_in = reinterpret_cast<const float*>(e->d_planes_u8);
+        p.batch_u8 = e->d_planes_u8;
+        p.batch_il = nullptr;
+    }
+    return 0;
+}
+
+int LaunchLoop::zero_ring() { AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream)); return 0; }
+unsigned* LaunchLoop::slot(int64_t i) const { return per_sim ? e->d_live + (i % ao_engine::kLive) : nullptr; }
+unsigned LaunchLoop::counted(int64_t i) const { return e->h_live[slot(i) - e->d_live]; }
+
+int LaunchLoop::advance() {
+    ++launch;
+    if (wraps(launch) && (harvest(launch) || zero_ring())) return 1;   // more than kLive launches since the ring was zeroed: sum it up, zero it
+    p.live = slot(launch);
+    return 0;
+}
+
+int LaunchLoop::harvest(int64_t upto) {   // (each of the launches [harvested, upto) was followed by a network launch)
+    if (!per_sim || upto <= harvested) return 0;
+    const ao::RingSpans s = ao::ring_spans(harvested, upto, ao_engine::kLive);
+    AO_HIP(e, hipMemcpyAsync(e->h_live + s.first, e->d_live + s.first, sizeof(unsigned) * s.head, hipMemcpyDeviceToHost, e->stream));
+    if (s.tail > 0) AO_HIP(e, hipMemcpyAsync(e->h_live, e->d_live, sizeof(unsigned) * s.tail, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    if (traffic) *traffic += sizeof(unsigned) * (s.head + s.tail);
+    for (int64_t i = harvested; i < upto; ++i) e->rs.add(counted(i), cap_rows);
+    harvested = upto;
+    return 0;
+}
+
+// leaves the engine usable after a failure: the games' error words cleared, nothing queued any more
+static void clear_game_errors(ao_engine* e) {
+    (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
+    (void)hipStreamSynchronize(e->stream);
+}
+
+// The Dirichlet draws of the games that begin a move with noise, as (game, staging row of its stream in h_mt / h_pos and of its
+// noise in h_noise). Every game has its own stream, so the draws do not depend on how the list is cut up: a short one inline, a
+// long one on the process's persistent host pool (host_rng.hpp: hardware threads / LOCAL_WORLD_SIZE, at most 32) in chunks of
+// 16, so that the ranks of a node do not oversubscribe the host at the start of every move.
+static void draw_noise(ao_engine* e, const std::vector<std::pair<int32_t, size_t>>& draws) {
+    auto work = [&](int k0, int k1) {
+        for (int k = k0; k < k1; ++k) {
+            const auto [g, row] = draws[k];
+            ao::HostMT r{e->h_mt + row * 624, e->h_pos + row, &e->has_gauss[g], &e->gauss[g]};
+            r.dirichlet(e->cfg.alpha, e->A - static_cast<int>(e->moves[g].size()), e->h_noise + row * e->Ap);
+        }
+    };
+    const int n = static_cast<int>(draws.size());
+    if (n < 64) work(0, n);
+    else ao::HostPool::get().run(n, 16, work);
+}
+
+// A move that ao::roll_next_move refuses fails the call with a message that names the game (and, in a by-ply table, the ply).
+static int move_refused(ao_engine* e, const char* who, int g, const ao::RollMove& m, const std::string& at_ply = "") {
+    if (m.refuse == 1)
+        return e->fail(std::string(who) + ": game " + std::to_string(g) + ": sims " + std::to_string(m.budget) + at_ply + " is outside 1.." +
+                       std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
+    if (m.refuse == 2)
+        return e->fail(std::string(who) + ": game " + std::to_string(g) + ": noise asked for on an engine created without noise");
+    return 0;
 }
 
 extern "C" {
@@ -658,19 +766,18 @@ int ao_get_moves(ao_engine* e, int g, int32_t* out, int32_t* n) {
 static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* sims, const uint8_t* noise) {
     if (roll_refuses(e, "ao_begin_move")) return 1;
     AO_HIP(e, hipSetDevice(e->cfg.device));
-    const int G = e->G, A = e->A, Ap = e->Ap;
+    const int G = e->G, Ap = e->Ap;
     ao::TreeParams& p = e->tp;
     // nothing is touched before every value is known to be in range: a refused call leaves the engine as it was (so the games of
     // this move are worked out beside the engine and become e->active once nothing can refuse the call any more)
     std::vector<uint8_t> act(G);
+    std::vector<ao::RollMove> mv(G);   // what each game's move is (roll_schedule.hpp): the caller's one budget and one switch per game are table rows of stride 1
     for (int g = 0; g < G; ++g) act[g] = (active ? active[g] : 1) && !e->over[g];
     for (int g = 0; g < G; ++g) {
         if (!act[g]) continue;
-        if (sims && (sims[g] < 1 || sims[g] > e->S))
-            return e->fail("ao_begin_move_opts: game " + std::to_string(g) + ": sims " + std::to_string(sims[g]) + " is outside 1.." +
-                           std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
-        if (noise && noise[g] && !p.noise)
-            return e->fail("ao_begin_move_opts: game " + std::to_string(g) + ": noise asked for on an engine created without noise");
+        mv[g] = ao::roll_next_move(static_cast<int>(e->moves[g].size()), -1, sims ? sims + g : nullptr, 1, noise ? noise + g : nullptr, 1,
+                                   p.noise != 0, e->S, e->status[g]);
+        if (move_refused(e, "ao_begin_move_opts", g, mv[g])) return 1;
     }
     // the bar of this move: bitboards that ao_root_tactics left on the device, or the caller's masks (ao_set_root_bar) built here
     const bool bar_dev = e->bar_on_device;
@@ -694,15 +801,12 @@ static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* s
     int maxt = 0;
     e->target_sum = 0;
     e->move_saved = 0;
-    for (int g = 0; g < G; ++g) {
-        target[g] = 0;
-        flags[g] = 0;
-        e->bonus[g] = 0;
-        if (!e->active[g]) continue;
-        e->bonus[g] = (e->status[g] == AO_ROOT_FRESH) ? 1 : 0;
-        target[g] = (sims ? sims[g] : e->S) + e->bonus[g];  // agents.py:107-111
-        const bool quiet = p.noise && noise && !noise[g];   // this game, this move: as on an engine created without noise
-        flags[g] = quiet ? 2 : ((p.noise && e->status[g] == AO_ROOT_EXPANDED) ? 1 : 0);
+    std::vector<std::pair<int32_t, size_t>> draws;   // (no draw for a game without noise: its stream is not touched)
+    for (int g = 0; g < G; ++g) {                    // (a game that is not in this move: all zero)
+        e->bonus[g] = mv[g].target - mv[g].budget;   // a fresh root's own expansion (agents.py:107-111)
+        target[g] = mv[g].target;
+        flags[g] = mv[g].gflags;
+        if (mv[g].draw) draws.emplace_back(g, g);
         maxt = std::max(maxt, target[g]);
         e->target_sum += target[g];
     }
@@ -712,19 +816,7 @@ static int begin_move_impl(ao_engine* e, const uint8_t* active, const int32_t* s
         AO_HIP(e, hipMemcpyAsync(e->h_mt, p.mt, sizeof(uint32_t) * 624 * G, hipMemcpyDeviceToHost, e->stream));
         AO_HIP(e, hipMemcpyAsync(e->h_pos, p.mtpos, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
         AO_HIP(e, hipStreamSynchronize(e->stream));
-        const double alpha = e->cfg.alpha;
-        auto work = [&](int g0, int g1) {
-            for (int g = g0; g < g1; ++g) {
-                if (!e->active[g] || (flags[g] & 2)) continue;   // (no draw for a game without noise: its stream is not touched)
-                ao::HostMT r{e->h_mt + static_cast<size_t>(g) * 624, e->h_pos + g, &e->has_gauss[g], &e->gauss[g]};
-                const int k = A - static_cast<int>(e->moves[g].size());
-                r.dirichlet(alpha, k, e->h_noise + static_cast<size_t>(g) * Ap);
-            }
-        };
-        // the process's persistent host pool (host_rng.hpp: hardware threads / LOCAL_WORLD_SIZE, at most 32); games in
-        // chunks of 16 so that the ranks of a node do not oversubscribe the host at the start of every move
-        if (G < 64) work(0, G);
-        else ao::HostPool::get().run(G, 16, work);
+        draw_noise(e, draws);   // (staging row = game: the streams of all games travel)
         AO_HIP(e, hipMemcpyAsync(p.mt, e->h_mt, sizeof(uint32_t) * 624 * G, hipMemcpyHostToDevice, e->stream));
         AO_HIP(e, hipMemcpyAsync(p.mtpos, e->h_pos, sizeof(int32_t) * G, hipMemcpyHostToDevice, e->stream));
         AO_HIP(e, hipMemcpyAsync(p.noise_buf, e->h_noise, sizeof(double) * G * Ap, hipMemcpyHostToDevice, e->stream));
@@ -860,8 +952,7 @@ static int report_game_errors(ao_engine* e, const int32_t* herr) {
                  (e->row_cap > 0 ? std::to_string(e->row_cap) : std::string("one per game")) + ")";
         }
         // leave the engine usable: the error words are cleared and no move is in flight (the caller resets the game)
-        (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
-        (void)hipStreamSynchronize(e->stream);
+        clear_game_errors(e);
         e->in_move = false;
         e->ended = false;
         return e->fail(m);
@@ -946,37 +1037,35 @@ struct SearchOpts {
 
 // One move of ao_search between begin_move_impl and ao_end_move: what its phases share. search_impl runs them top to bottom:
 // plan (rows and layout), run_sims (the simulations, with settling), run_planned_extra and run_catch_up (over-subscription),
-// finish (row statistics). The arithmetic of the schedule is search_schedule.hpp's.
+// finish (row statistics). The arithmetic of the schedule is search_schedule.hpp's; the launch plan and the ring of row counters
+// are LaunchLoop's, as under the rolling search.
 struct MoveSearch {
     ao_engine* const e;
     ao_net* const net;
     const SearchOpts& opts;
     const DevSwitches& dev = DevSwitches::process();
     // ---- the plan, fixed once plan() has run
-    int rows = 0, cap_rows = 0;    // active games; rows of one network launch: ao_set_row_cap's, or one per active game
-    int in_kind = 1;               // the input the network wants (net_plan): 2 = bit planes, otherwise the interleaved fp32 batch
-    const float* net_in = nullptr;
-    ao::TreeParams p{};            // the move's copy of e->tp; live, ctl, ctl_cur, live_prev and row_target change per launch
+    int rows = 0;                  // active games
+    LaunchLoop loop;               // cap_rows: ao_set_row_cap's, or one per active game; of p also ctl, ctl_cur, live_prev and row_target change per launch
     ao::StepNet step{};            // the fused per-game step (k_step_board)
     bool fused = false;            // a few games on the per-board path: heads, tree step and the next leaf's conv1 are one launch per game
-    bool dynamic = false, oversub = false;   // the tree kernel hands out the rows per simulation; ... and there are fewer of them than active games
+    bool oversub = false;          // rows per simulation (loop.per_sim), and fewer of them than active games
     bool catch_up = false;         // games may be short of their simulations after the nominal number of launches
     bool settle_on = false;        // k_settle runs every opts.settle_every simulations and in every catch-up round
     ao::SitWindow win{};           // over-subscription: the sit-out window the move starts with (the device takes it from there, sit_window)
     int64_t rows_live_before = 0;  // e->rs.rows_live when the move began (ask_frac)
     // ---- progress
-    int launch = 0, harvested = 0; // selection launches of this move so far (launch i counts its rows in slot i % kLive); slots already summed up
     bool first_sim = true;
+    int traced = 0;                // launches whose row counters AO_ROW_TRACE has printed
     bool sit_off = false, all_done = false;   // the catch-up rounds have switched the window off: nobody sits out any more; settling found no unfinished game
     int nominal_sims = 0;          // e->sims_left when the loop began
     std::chrono::steady_clock::time_point t0;   // ... and the time (AO_LAUNCH_TIMING)
 
-    unsigned* slot(int i) const { return dynamic ? e->d_live + (i % ao_engine::kLive) : nullptr; }
-    void set_sit(int i) {
-        p.ctl = (oversub && !sit_off) ? e->d_ctl : nullptr;
-        p.ctl_cur = i & 1;
-        p.live_prev = (oversub && i > 0 && i % ao_engine::kLive != 0) ? slot(i - 1) : nullptr;   // (the ring was zeroed at a wrap: no demand reading for that launch)
-        p.row_target = win.row_target;
+    void set_sit(int64_t i) {
+        loop.p.ctl = (oversub && !sit_off) ? e->d_ctl : nullptr;
+        loop.p.ctl_cur = i & 1;
+        loop.p.live_prev = (oversub && i > 0 && !loop.wraps(i)) ? loop.slot(i - 1) : nullptr;   // (the ring was zeroed at a wrap: no demand reading for that launch)
+        loop.p.row_target = win.row_target;
     }
 
     int plan() {
@@ -997,48 +1086,24 @@ struct MoveSearch {
                 e->h_row[g] = rows++;
             }
         if (rows == 0) return 0;
-        cap_rows = (!dev.static_rows && e->row_cap > 0 && e->row_cap < rows) ? e->row_cap : rows;
-        // the network announces the interleaved input layout it wants for a batch of cap_rows boards
-        ao::net_plan(net, cap_rows, &e->tp.il_group, &e->tp.nchq, &in_kind);
-        // The padding channels of the fp32 input batch (planes 5..31 of a 32-channel slab) are zero and stay zero: the
-        // encoder only writes the quads that hold planes (16 B per lane at a 2 KB stride are partial-line writes --
-        // rocprof showed 152 MB of HBM writes per launch for a 42 MB batch). A change of layout re-zeroes the buffer.
-        // The split-fp16 kernels take the planes as BITS instead (in_kind 2): one byte per cell, 81 contiguous bytes per
-        // leaf, and the fp32 batch is not written at all.
-        if (in_kind != 2 && (e->il_group_zeroed != e->tp.il_group || e->il_nchq_zeroed != e->tp.nchq)) {
-            AO_HIP(e, hipMemsetAsync(e->tp.batch_il, 0, e->il_bytes, e->stream));
-            e->il_group_zeroed = e->tp.il_group;
-            e->il_nchq_zeroed = e->tp.nchq;
-        }
-        // select | net | expand+select | net | ... | expand(+idle select): one launch fewer per simulation
-        // than the step-wise protocol, same device code (tree_device.hpp).
-        p = e->tp;
-        p.batch_nchw = nullptr;
-        p.policy = e->d_policy;
-        p.value = e->d_value;
-        p.row_of_game = e->d_row;
-        p.nchq_live = (e->cfg.inplanes + 3) / 4;
-        net_in = p.batch_il;
-        if (in_kind == 2) {
-            net_in = reinterpret_cast<const float*>(e->d_planes_u8);
-            p.batch_u8 = e->d_planes_u8;
-            p.batch_il = nullptr;
-        }
+        const int cap_rows = (!dev.static_rows && e->row_cap > 0 && e->row_cap < rows) ? e->row_cap : rows;
+        if (loop.plan(e, net, cap_rows)) return 1;
+        ao::TreeParams& p = loop.p;
         // A few games (the per-board network path): heads, tree step and the next leaf's conv1 are ONE launch per game
         // (k_step_board), the network is asked for the residual blocks alone -- 9 launches per simulation instead of 11.
         fused = cap_rows == rows && ao::net_step_params(net, rows, e->d_policy, e->d_value, &step) != 0;
         // (AO_DYNAMIC_ROWS is opt-in: the hand-out costs one atomic per workgroup on one word, ~11 ns each -- 10 us on top of a 20 us tree
         // kernel when 4096 descents of equal depth arrive together, profiles/r5a_row_alloc_atomics.txt; it pays when leaves are terminal)
-        dynamic = !fused && !dev.static_rows && (e->row_cap > 0 || dev.dynamic_rows);
-        if (dynamic) {
-            AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
+        loop.per_sim = !fused && !dev.static_rows && (e->row_cap > 0 || dev.dynamic_rows);
+        if (loop.per_sim) {
+            if (loop.zero_ring()) return 1;
             p.row_cap = static_cast<unsigned>(cap_rows);
         } else {
             AO_HIP(e, hipMemcpyAsync(e->d_row, e->h_row.data(), sizeof(int32_t) * 2 * e->G, hipMemcpyHostToDevice, e->stream));
         }
-        oversub = dynamic && cap_rows < rows;   // more active games than rows per simulation: search_schedule.hpp, SitWindow
+        oversub = loop.per_sim && cap_rows < rows;   // more active games than rows per simulation: search_schedule.hpp, SitWindow
         p.order = (oversub && e->order_on && e->row_cap > 0 && e->row_cap < e->G) ? e->d_order : nullptr;
-        p.max_levels = dynamic ? dev.descent_budget : 0;
+        p.max_levels = loop.per_sim ? dev.descent_budget : 0;
         catch_up = oversub || p.max_levels > 0;
         rows_live_before = e->rs.rows_live;
         // Settling (k_settle): every settle_every simulations, and in every catch-up round, the games of the early_stop mask whose move
@@ -1059,19 +1124,14 @@ struct MoveSearch {
         return 0;
     }
 
-    // sums up the row counters of the selection launches [harvested, upto) -- each of them was followed by a network launch
-    int harvest_rows(int upto) {
-        if (!dynamic || upto <= harvested) return 0;
-        AO_HIP(e, hipMemcpyAsync(e->h_live, e->d_live, sizeof(unsigned) * ao_engine::kLive, hipMemcpyDeviceToHost, e->stream));
-        AO_HIP(e, hipStreamSynchronize(e->stream));
-        if (dev.row_trace) {
-            fprintf(stderr, "AO_ROW_TRACE %d active games, %d rows, launches %d..%d, rows asked for:", rows, cap_rows, harvested, upto - 1);
-            for (int i = harvested; i < upto; ++i) fprintf(stderr, " %u", e->h_live[i % ao_engine::kLive]);
-            fprintf(stderr, "\n");
-        }
-        for (int i = harvested; i < upto; ++i) e->rs.add(e->h_live[i % ao_engine::kLive], cap_rows);
-        harvested = upto;
-        return 0;
+    // AO_ROW_TRACE, behind whatever may have harvested: the launches that the loop has summed up since the last call
+    void trace_rows() {
+        const int from = traced;
+        traced = static_cast<int>(loop.harvested);
+        if (!dev.row_trace || traced <= from) return;
+        fprintf(stderr, "AO_ROW_TRACE %d active games, %d rows, launches %d..%d, rows asked for:", rows, loop.cap_rows, from, traced - 1);
+        for (int i = from; i < traced; ++i) fprintf(stderr, " %u", loop.counted(i));
+        fprintf(stderr, "\n");
     }
 
     // what: 1 = policy + value, 2 = simulation count + leaf status (the fused step computes the heads AND moves on to the next leaf
@@ -1086,25 +1146,21 @@ struct MoveSearch {
 
     // the one place that queues a network launch followed by a tree launch
     int one_sim() {
-        if (ao::net_forward_il(net, net_in, cap_rows, e->d_policy, e->d_value, e->stream, in_kind, fused ? (first_sim ? 3 : 2) : 7,
-                               slot(launch), static_cast<unsigned>(cap_rows)))
+        if (ao::net_forward_il(net, loop.net_in, loop.cap_rows, e->d_policy, e->d_value, e->stream, loop.in_kind, fused ? (first_sim ? 3 : 2) : 7,
+                               loop.slot(loop.launch), static_cast<unsigned>(loop.cap_rows)))
             return e->fail(std::string("network forward failed: ") + ao_net_last_error(net));
         first_sim = false;
         log_evals(fused ? 2 : 3);   // (before the tree kernel moves on / hands out the next simulation's rows)
         const bool timed = e->timer.tick();   // (see ao_tree_timing)
         if (timed) e->timer.begin(e->stream);
-        ++launch;
-        if (dynamic && launch % ao_engine::kLive == 0) {   // the counter ring wraps (more than kLive launches in one move): sum it up, zero it
-            if (harvest_rows(launch)) return 1;
-            AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
-        }
+        if (loop.advance()) return 1;
+        trace_rows();
         if (fused) {
-            ao::launch_step_board(p, step, rows, e->d_row + e->G, e->stream);
+            ao::launch_step_board(loop.p, step, rows, e->d_row + e->G, e->stream);
             log_evals(1);              // (the heads of this simulation ran inside the step kernel)
         } else {
-            p.live = slot(launch);
-            set_sit(launch);
-            ao::launch_expand_select(p, e->stream);
+            set_sit(loop.launch);
+            ao::launch_expand_select(loop.p, e->stream);
         }
         if (timed) e->timer.end(e->stream);
         AO_HIP(e, hipGetLastError());
@@ -1116,9 +1172,9 @@ struct MoveSearch {
     // eager launches here: 71.7 vs 65.7 us per simulation for one game)
     int run_sims() {
         if (e->sims_left > 0) {
-            p.live = slot(0);
+            loop.p.live = loop.slot(0);
             set_sit(0);
-            ao::launch_select(p, e->stream);
+            ao::launch_select(loop.p, e->stream);
             AO_HIP(e, hipGetLastError());
         }
         t0 = std::chrono::steady_clock::now();
@@ -1164,7 +1220,7 @@ struct MoveSearch {
         int32_t* h_done = e->h_i32;
         int32_t* h_target = e->h_i32 + G;
         int32_t* h_err = e->h_i32 + 2 * G;
-        ao::CatchUp rule(cap_rows, e->S, DevSwitches::catchup_rounds(), DevSwitches::catchup_window_off());
+        ao::CatchUp rule(loop.cap_rows, e->S, DevSwitches::catchup_rounds(), DevSwitches::catchup_window_off());
         sit_off = rule.window_off;
         while (rule.open()) {
             if (settle_on && settle_queue(e, e->d_early, 0)) return 1;
@@ -1182,7 +1238,7 @@ struct MoveSearch {
                 const int d = h_target[g] - h_done[g];
                 if (d > 0) { sum += d; mx = std::max(mx, d); }
             }
-            const int extra = rule.next(sum, mx, bad, p.max_levels != 0);
+            const int extra = rule.next(sum, mx, bad, loop.p.max_levels != 0);
             if (extra == 0) break;
             sit_off = rule.window_off;
             for (int k = 0; k < extra; ++k)
@@ -1193,7 +1249,8 @@ struct MoveSearch {
 
     // the row statistics of the move, and the share of its simulations that asked for a row: the next move's window
     int finish() {
-        if (harvest_rows(launch)) return 1;
+        if (loop.harvest(loop.launch)) return 1;
+        trace_rows();
         const int64_t sims_wanted = e->target_sum - e->move_saved;   // (the budgets actually set, less what settling took away)
         if (oversub && sims_wanted > 0)
             e->ask_frac = static_cast<double>(e->rs.rows_live - rows_live_before) / static_cast<double>(sims_wanted);
@@ -1224,8 +1281,7 @@ static int search_impl(ao_engine* e, ao_net* net, const uint8_t* active, const i
 // every move twice -- until new weights are loaded or ao_net_set_mode is called.
 static int recover_fp16_range(ao_engine* e, ao_net* net, const uint8_t* active, const int8_t* tau, double* pi, double* visit,
                               double* policy, bool may_recover, const SearchOpts& opts) {
-    (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
-    (void)hipStreamSynchronize(e->stream);
+    clear_game_errors(e);
     e->in_move = false;
     e->ended = false;
     if (!may_recover)
@@ -1887,37 +1943,9 @@ static void roll_close(ao_engine* e) {
 
 // what a failure inside the loop leaves behind: error words cleared, the roll closed (check_game_errors does the same for its own)
 static int roll_fail(ao_engine* e, const std::string& m) {
-    (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
-    (void)hipStreamSynchronize(e->stream);
+    clear_game_errors(e);
     roll_close(e);
     return e->fail(m);
-}
-
-static unsigned* roll_slot(ao_engine* e, int64_t i) { return e->d_live + (i % ao_engine::kLive); }
-
-// sums up the row counters of the selection launches [harvested, upto): each of them was followed by a network launch. Copies
-// those words only; synchronises.
-static int roll_harvest_rows(ao_engine* e, int64_t upto) {
-    RollState& r = e->roll;
-    if (upto <= r.harvested) return 0;
-    const int64_t first = r.harvested % ao_engine::kLive, count = upto - r.harvested;   // (count <= kLive: the ring is harvested where it wraps)
-    const int64_t head = std::min<int64_t>(count, ao_engine::kLive - first);
-    AO_HIP(e, hipMemcpyAsync(e->h_live + first, e->d_live + first, sizeof(unsigned) * head, hipMemcpyDeviceToHost, e->stream));
-    if (count > head) AO_HIP(e, hipMemcpyAsync(e->h_live, e->d_live, sizeof(unsigned) * (count - head), hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    roll_count(e, sizeof(unsigned) * count);
-    for (int64_t i = r.harvested; i < upto; ++i) e->rs.add(e->h_live[i % ao_engine::kLive], r.cap_rows);
-    r.harvested = upto;
-    return 0;
-}
-
-// the move a game would begin now (roll_schedule.hpp), from the roll's tables and the host mirrors
-static ao::RollMove roll_move_of(const ao_engine* e, int g, int ply) {
-    const RollState& r = e->roll;
-    return ao::roll_next_move(ply, r.tau_plies.empty() ? -1 : r.tau_plies[g],
-                              r.sims.empty() ? nullptr : r.sims.data() + static_cast<size_t>(g) * r.sims_stride, r.sims_stride,
-                              r.noise.empty() ? nullptr : r.noise.data() + static_cast<size_t>(g) * r.noise_stride, r.noise_stride,
-                              e->tp.noise != 0, e->S, e->status[g]);
 }
 
 // Takes the per-game fields of `o` for the games of `act` into the roll's tables -- after every column of theirs has been found in
@@ -1936,11 +1964,7 @@ static int roll_take_tables(ao_engine* e, const ao_roll_opts* o, const std::vect
             const ao::RollMove m = ao::roll_next_move(c, -1, o->sims ? o->sims + static_cast<size_t>(g) * o->sims_stride : nullptr, o->sims_stride,
                                                       o->noise ? o->noise + static_cast<size_t>(g) * o->noise_stride : nullptr, o->noise_stride,
                                                       e->tp.noise != 0, e->S, AO_ROOT_EXPANDED);
-            if (m.refuse == 1)
-                return e->fail(std::string(who) + ": game " + std::to_string(g) + ": sims " + std::to_string(m.budget) + " at ply " + std::to_string(c) +
-                               " is outside 1.." + std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
-            if (m.refuse == 2)
-                return e->fail(std::string(who) + ": game " + std::to_string(g) + ": noise asked for on an engine created without noise");
+            if (move_refused(e, who, g, m, " at ply " + std::to_string(c))) return 1;
         }
     }
     if (fresh) {
@@ -1964,14 +1988,18 @@ static int roll_take_tables(ao_engine* e, const ao_roll_opts* o, const std::vect
 // draw of the games that search with noise is the host's (host_rng.hpp), on the pool; everything travels in compact rows.
 static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, const int32_t* rows) {
     RollState& r = e->roll;
-    const int n = static_cast<int>(games.size()), G = e->G, A = e->A, Ap = e->Ap;
+    const int n = static_cast<int>(games.size()), G = e->G, Ap = e->Ap;
     if (n == 0) return 0;
     int32_t* h_games = r.h_i32 + 4 * static_cast<size_t>(G);
     int32_t* h_items = h_games + G;
     std::vector<ao::RollMove> mv(n);
     bool any_draw = false;
-    for (int k = 0; k < n; ++k) {
-        mv[k] = roll_move_of(e, games[k], static_cast<int>(e->moves[games[k]].size()));
+    for (int k = 0; k < n; ++k) {   // the move each game begins now (roll_schedule.hpp), from the roll's tables and the host mirrors
+        const int g = games[k];
+        mv[k] = ao::roll_next_move(static_cast<int>(e->moves[g].size()), r.tau_plies.empty() ? -1 : r.tau_plies[g],
+                                   r.sims.empty() ? nullptr : r.sims.data() + static_cast<size_t>(g) * r.sims_stride, r.sims_stride,
+                                   r.noise.empty() ? nullptr : r.noise.data() + static_cast<size_t>(g) * r.noise_stride, r.noise_stride,
+                                   e->tp.noise != 0, e->S, e->status[g]);
         any_draw = any_draw || mv[k].draw;
     }
     if (!rows) {
@@ -1988,6 +2016,7 @@ static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, con
         }
     }
     int nrows = 0;   // staging rows in use: [0, nrows)
+    std::vector<std::pair<int32_t, size_t>> draws;   // (no draw for a game without noise: its stream is not touched)
     for (int k = 0; k < n; ++k) {
         const int g = games[k];
         const int row = rows ? rows[k] : k;
@@ -1995,21 +2024,13 @@ static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, con
         it[0] = g; it[1] = mv[k].target; it[2] = mv[k].gflags; it[3] = mv[k].tau;
         it[4] = (r.early && mv[k].tau == 0) ? 1 : 0;
         it[5] = mv[k].draw ? row : -1;
-        if (mv[k].draw) nrows = std::max(nrows, row + 1);
+        if (mv[k].draw) {
+            nrows = std::max(nrows, row + 1);
+            draws.emplace_back(g, row);
+        }
     }
     if (any_draw) {
-        const double alpha = e->cfg.alpha;
-        auto work = [&](int k0, int k1) {
-            for (int k = k0; k < k1; ++k) {
-                if (!mv[k].draw) continue;   // (no draw for a game without noise: its stream is not touched)
-                const int g = games[k];
-                const size_t row = static_cast<size_t>(rows ? rows[k] : k);
-                ao::HostMT rng{e->h_mt + row * 624, e->h_pos + row, &e->has_gauss[g], &e->gauss[g]};
-                rng.dirichlet(alpha, A - static_cast<int>(e->moves[g].size()), e->h_noise + row * Ap);
-            }
-        };
-        if (n < 64) work(0, n);
-        else ao::HostPool::get().run(n, 16, work);
+        draw_noise(e, draws);
         AO_HIP(e, hipMemcpyAsync(e->d_mt_backup, e->h_mt, sizeof(uint32_t) * 624 * nrows, hipMemcpyHostToDevice, e->stream));
         AO_HIP(e, hipMemcpyAsync(e->d_pos_backup, e->h_pos, sizeof(int32_t) * nrows, hipMemcpyHostToDevice, e->stream));
         AO_HIP(e, hipMemcpyAsync(r.d_noise, e->h_noise, sizeof(double) * Ap * nrows, hipMemcpyHostToDevice, e->stream));
@@ -2017,12 +2038,12 @@ static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, con
     }
     AO_HIP(e, hipMemcpyAsync(r.d_items, h_items, sizeof(int32_t) * ao::kRollItem * n, hipMemcpyHostToDevice, e->stream));
     roll_count(e, sizeof(int32_t) * ao::kRollItem * n);
-    ao::launch_roll_begin(r.p, r.d_items, n, e->d_mt_backup, e->d_pos_backup, r.d_noise, e->d_tau, e->d_active, e->d_settled, e->d_early, e->stream);
+    ao::launch_roll_begin(r.loop.p, r.d_items, n, e->d_mt_backup, e->d_pos_backup, r.d_noise, e->d_tau, e->d_active, e->d_settled, e->d_early, e->stream);
     AO_HIP(e, hipGetLastError());
     e->settled_dirty = true;
     for (int k = 0; k < n; ++k) {
         const int g = games[k];
-        e->bonus[g] = (e->status[g] == AO_ROOT_FRESH) ? 1 : 0;
+        e->bonus[g] = mv[k].target - mv[k].budget;
         e->active[g] = 1;
         r.in_move[g] = 1;
         ++r.n_in_move;
@@ -2080,29 +2101,12 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
     r.look_pending = false;
     r.n_in_move = 0;
     r.draining = false;
-    r.launch = r.harvested = 0;
-    // the plan: MoveSearch::plan's rows-per-simulation path for every G, the batch bounded by ao_set_row_cap
-    r.cap_rows = (e->row_cap > 0 && e->row_cap < G) ? e->row_cap : G;
-    ao::net_plan(net, r.cap_rows, &e->tp.il_group, &e->tp.nchq, &r.in_kind);
-    if (r.in_kind != 2 && (e->il_group_zeroed != e->tp.il_group || e->il_nchq_zeroed != e->tp.nchq)) {
-        AO_HIP(e, hipMemsetAsync(e->tp.batch_il, 0, e->il_bytes, e->stream));
-        e->il_group_zeroed = e->tp.il_group;
-        e->il_nchq_zeroed = e->tp.nchq;
-    }
-    ao::TreeParams& p = r.p;
-    p = e->tp;
-    p.batch_nchw = nullptr;
-    p.policy = e->d_policy;
-    p.value = e->d_value;
-    p.row_of_game = e->d_row;
-    p.nchq_live = (e->cfg.inplanes + 3) / 4;
-    r.net_in = p.batch_il;
-    if (r.in_kind == 2) {
-        r.net_in = reinterpret_cast<const float*>(e->d_planes_u8);
-        p.batch_u8 = e->d_planes_u8;
-        p.batch_il = nullptr;
-    }
-    p.row_cap = static_cast<unsigned>(r.cap_rows);
+    // the plan: rows per simulation for every G, the batch bounded by ao_set_row_cap
+    if (r.loop.plan(e, net, (e->row_cap > 0 && e->row_cap < G) ? e->row_cap : G)) return 1;
+    r.loop.per_sim = true;
+    r.loop.traffic = &r.bytes;   // (the row counters a harvest reads count as the roll's traffic, one word per launch)
+    ao::TreeParams& p = r.loop.p;
+    p.row_cap = static_cast<unsigned>(r.loop.cap_rows);
     p.row_target = p.row_cap;
     p.ctl = nullptr; p.live_prev = nullptr; p.order = nullptr; p.max_levels = 0;
     // (a root may still hold kBarQ children of an earlier barred move: an all-zero bar turns them back where a move begins)
@@ -2111,7 +2115,7 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
         AO_HIP(e, hipMemsetAsync(e->d_bar, 0, sizeof(uint64_t) * e->h_bar.size(), e->stream));
         p.bar = e->d_bar;
     }
-    AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
+    if (r.loop.zero_ring()) return 1;
     AO_HIP(e, hipMemsetAsync(e->d_active, 0, G, e->stream));
     AO_HIP(e, hipMemsetAsync(e->d_early, 0, G, e->stream));
     AO_HIP(e, hipMemsetAsync(e->d_settled, 0, G, e->stream));
@@ -2122,7 +2126,7 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
     for (int g = 0; g < G; ++g)
         if (act[g]) games.push_back(g);
     if (roll_begin_games(e, games, nullptr)) { roll_close(e); return 1; }
-    p.live = roll_slot(e, 0);
+    p.live = r.loop.slot(0);
     ao::launch_select(p, e->stream);
     AO_HIP(e, hipGetLastError());
     AO_HIP(e, hipStreamSynchronize(e->stream));
@@ -2153,19 +2157,14 @@ int ao_roll_drain(ao_engine* e) {
 
 // one launch of the loop: the network on the rows the last selection handed out, then expansion + backup and the next selection
 static int roll_launch(ao_engine* e) {
-    RollState& r = e->roll;
-    if (ao::net_forward_il(r.net, r.net_in, r.cap_rows, e->d_policy, e->d_value, e->stream, r.in_kind, 7, roll_slot(e, r.launch),
-                           static_cast<unsigned>(r.cap_rows)))
-        return roll_fail(e, std::string("ao_roll_run: network forward failed: ") + ao_net_last_error(r.net));
+    LaunchLoop& loop = e->roll.loop;
+    if (ao::net_forward_il(e->roll.net, loop.net_in, loop.cap_rows, e->d_policy, e->d_value, e->stream, loop.in_kind, 7, loop.slot(loop.launch),
+                           static_cast<unsigned>(loop.cap_rows)))
+        return roll_fail(e, std::string("ao_roll_run: network forward failed: ") + ao_net_last_error(e->roll.net));
     const bool timed = e->timer.tick();   // (see ao_tree_timing)
     if (timed) e->timer.begin(e->stream);
-    ++r.launch;
-    if (r.launch % ao_engine::kLive == 0) {   // the counter ring wraps: sum it up, zero it
-        if (roll_harvest_rows(e, r.launch)) return 1;
-        AO_HIP(e, hipMemsetAsync(e->d_live, 0, sizeof(unsigned) * ao_engine::kLive, e->stream));
-    }
-    r.p.live = roll_slot(e, r.launch);
-    ao::launch_expand_select(r.p, e->stream);
+    if (loop.advance()) return 1;
+    ao::launch_expand_select(loop.p, e->stream);
     if (timed) e->timer.end(e->stream);
     AO_HIP(e, hipGetLastError());
     return 0;
@@ -2174,9 +2173,9 @@ static int roll_launch(ao_engine* e) {
 // the look: k_settle over the early-stop games (tau == 0 moves) that have run a simulation of their move; a leaf is under way
 static int roll_look(ao_engine* e) {
     RollState& r = e->roll;
-    ao::launch_roll_mask(r.p, e->d_early, e->d_mask, e->stream);
+    ao::launch_roll_mask(r.loop.p, e->d_early, e->d_mask, e->stream);
     AO_HIP(e, hipMemsetAsync(e->d_settle, 0, sizeof(int32_t) * 4, e->stream));
-    ao::launch_settle(r.p, e->d_mask, 0, 1, e->d_settled, e->d_settle, e->stream);
+    ao::launch_settle(r.loop.p, e->d_mask, 0, 1, e->d_settled, e->d_settle, e->stream);
     AO_HIP(e, hipGetLastError());
     AO_HIP(e, hipMemcpyAsync(e->h_settle, e->d_settle, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, e->stream));
     roll_count(e, sizeof(int32_t) * 4);
@@ -2205,7 +2204,7 @@ static int roll_turn(ao_engine* e, ao_roll_records* out) {
     AO_HIP(e, hipMemcpyAsync(h_leaf, e->tp.leaf_status, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
     AO_HIP(e, hipMemcpyAsync(h_err, e->tp.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
     roll_count(e, sizeof(int32_t) * 4 * G);
-    if (roll_harvest_rows(e, r.launch)) return 1;
+    if (r.loop.harvest(r.loop.launch)) return 1;
     AO_HIP(e, hipStreamSynchronize(e->stream));
     if (r.look_pending) {
         int unfinished = 0, owed = 0;
@@ -2225,8 +2224,8 @@ static int roll_turn(ao_engine* e, ao_roll_records* out) {
     double* d_visit = r.want_visit ? r.d_out + nA : nullptr;
     double* d_policy = r.want_policy ? r.d_out + 2 * nA : nullptr;
     AO_HIP(e, hipMemcpyAsync(r.d_games, h_games, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
-    ao::launch_roll_turn(r.p, r.d_games, n, e->d_active, e->d_settled, r.d_rec, d_pi, d_visit, d_policy, e->stream);
-    (void)ao::launch_reroot(r.p, n, r.d_games, e->stream);   // (cannot refuse: ao_roll_begin checked reroot_fits)
+    ao::launch_roll_turn(r.loop.p, r.d_games, n, e->d_active, e->d_settled, r.d_rec, d_pi, d_visit, d_policy, e->stream);
+    (void)ao::launch_reroot(r.loop.p, n, r.d_games, e->stream);   // (cannot refuse: ao_roll_begin checked reroot_fits)
     AO_HIP(e, hipGetLastError());
     AO_HIP(e, hipMemcpyAsync(h_rec, r.d_rec, sizeof(int32_t) * ao::kRollRec * n, hipMemcpyDeviceToHost, e->stream));
     AO_HIP(e, hipMemcpyAsync(e->h_out, d_pi, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
@@ -2235,7 +2234,7 @@ static int roll_turn(ao_engine* e, ao_roll_records* out) {
     roll_count(e, sizeof(int32_t) * (1 + ao::kRollRec) * n + sizeof(double) * nA * (1 + (d_visit ? 1 : 0) + (d_policy ? 1 : 0)));
     const bool gather = e->tp.noise != 0 && !r.draining;   // the streams of the played games, for the draws of their next moves
     if (gather) {
-        ao::launch_roll_gather(r.p, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
+        ao::launch_roll_gather(r.loop.p, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
         AO_HIP(e, hipGetLastError());
         AO_HIP(e, hipMemcpyAsync(e->h_mt, e->d_mt_backup, sizeof(uint32_t) * 624 * n, hipMemcpyDeviceToHost, e->stream));
         AO_HIP(e, hipMemcpyAsync(e->h_pos, e->d_pos_backup, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
@@ -2314,7 +2313,7 @@ int ao_roll_end(ao_engine* e) {
     if (r.n_in_move > 0)
         return e->fail("ao_roll_end: " + std::to_string(r.n_in_move) + " game(s) are still in a move (ao_roll_drain, then ao_roll_run until nothing is)");
     AO_HIP(e, hipSetDevice(e->cfg.device));
-    if (roll_harvest_rows(e, r.launch)) return 1;
+    if (r.loop.harvest(r.loop.launch)) return 1;
     AO_HIP(e, hipStreamSynchronize(e->stream));
     roll_close(e);
     return 0;

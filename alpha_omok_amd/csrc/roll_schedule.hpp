@@ -1,7 +1,9 @@
-// roll_schedule.hpp -- the host rules of the rolling search (engine.hip, the ao_roll_* driver): which games are turned (their move
-// ended, played, the next one begun) while the others go on searching, what a turned game's next move is, when a run call
-// returns, what draining means, and in which order looks, launches and turns follow each other. No HIP, no engine: plain C++17,
-// tested on the host (tests/host/roll_schedule_main.cpp).
+// roll_schedule.hpp -- the host rules of the moves a game makes one after the other: roll_next_move, what the move a game
+// begins is (budget, target, noise, refusals), is the rule of BOTH drivers: ao_begin_move* / ao_search* ask it once per game and
+// call, the rolling search (ao_roll_*) per game and turn. The rest is the rolling search's own: which games are turned (their
+// move ended, played, the next one begun) while the others go on searching, when a run call returns, what draining means, and
+// in which order looks, launches and turns follow each other. No HIP, no engine: plain C++17, tested on the host
+// (tests/host/roll_schedule_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -24,7 +26,8 @@ struct RollMove { int tau, budget, target, gflags, draw, refuse; };
 // noise_row: the game's rows of the by-ply tables (null: the engine's S / the engine's noise); root_status: AO_ROOT_* of the
 // position (0 fresh, 1 known, 2 expanded). target counts a fresh root's own expansion; gflags are TreeParams::gflags (bit 0:
 // re-noise the inherited root when the move begins, bit 1: no noise at this move's root); draw: the game's stream pays for a
-// Dirichlet draw before the move.
+// Dirichlet draw before the move. (ao_begin_move_opts passes its one budget and its one switch per game as rows of stride 1
+// and tau_plies = -1: its tau arrives with ao_end_move.)
 inline RollMove roll_next_move(int ply, int tau_plies, const int32_t* sims_row, int sims_stride, const uint8_t* noise_row,
                                int noise_stride, bool engine_noise, int S, int root_status) {
     RollMove m{};

@@ -1,6 +1,7 @@
-// search_schedule.hpp -- the host arithmetic of ao_search's launch schedule (engine.hip, MoveSearch): how wide the sit-out
-// window of an over-subscribed move is, how many launches it plans beyond its simulations, when the catch-up rounds go on and
-// when they give up, and how harvested row counters add up to ao_row_stats. No HIP, no engine: plain C++17, tested on the host
+// search_schedule.hpp -- the host arithmetic of the launch schedule (engine.hip). For ao_search's MoveSearch: how wide the
+// sit-out window of an over-subscribed move is, how many launches it plans beyond its simulations, when the catch-up rounds go
+// on and when they give up. For the LaunchLoop under both MoveSearch and the rolling search: which words of the row-counter ring
+// a harvest reads and how the harvested counters add up to ao_row_stats. No HIP, no engine: plain C++17, tested on the host
 // (tests/host/search_schedule_main.cpp).
 #pragma once
 #include <algorithm>
@@ -82,5 +83,16 @@ struct RowLedger {
         ++launches;
     }
 };
+
+// The row counters live in a ring of `ring` device words: launch i counts in word i % ring. What has to be read to sum up the
+// launches [harvested, upto): the words [first, first + head) and, where the range runs past the ring's end, [0, tail) -- at
+// most `ring` words (the launch loop harvests wherever the ring wraps, so a range never holds more launches than that).
+struct RingSpans { int first, head, tail; };
+inline RingSpans ring_spans(int64_t harvested, int64_t upto, int ring) {
+    if (upto <= harvested) return {0, 0, 0};
+    const int count = static_cast<int>(std::min<int64_t>(upto - harvested, ring)), first = static_cast<int>(harvested % ring);
+    const int head = std::min(count, ring - first);
+    return {first, head, count - head};
+}
 
 }  // namespace ao

@@ -6,6 +6,7 @@
 //                                                  -> C then per round "<launches>:<window_off>", "stop" (the rule ended the
 //                                                     loop) or "closed" (the round bound did), then rounds=<rounds looked at>
 //   L cap_rows n  want (n times)                   -> L launches rows_live rows_launched waits
+//   R harvested upto ring                          -> R first head tail
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -66,6 +67,12 @@ int main() {
             }
             std::printf("L %lld %lld %lld %lld\n", static_cast<long long>(led.launches), static_cast<long long>(led.rows_live),
                         static_cast<long long>(led.rows_launched), static_cast<long long>(led.waits));
+        } else if (kind == "R") {
+            long long harvested, upto;
+            int ring;
+            in >> harvested >> upto >> ring;
+            const ao::RingSpans s = ao::ring_spans(harvested, upto, ring);
+            std::printf("R %d %d %d\n", s.first, s.head, s.tail);
         } else {
             std::fprintf(stderr, "unknown case: %s\n", line.c_str());
             return 2;

@@ -318,6 +318,40 @@ def test_over_subscribed_handful_of_games_on_the_per_board_path_vs_oracle(oracle
     net.close()
 
 
+def test_one_move_of_more_launches_than_the_row_counter_ring_has_slots():
+    """The rows of a launch are counted in a ring of 2048 device words, summed up and zeroed where it wraps. One move of 2200
+    simulations for 3 games on 2 rows (over-subscribed: rows per simulation, no fused step) runs past the wrap: pi, visits and
+    priors equal the same search without a row cap (the fused per-game step; mode 3 is the per-board path for every batch,
+    one arithmetic for both), and the ledger still counts every launch and every evaluated leaf exactly once."""
+    from alpha_omok_amd.engine import Engine, Net
+    G, S_, CAP, RING = 3, 2200, 2, 2048
+    net = Net(2, 5, 128, B, 0)
+    net.load_state_dict(_trained_state_dict())
+    net.set_mode(3)
+    out = {}
+    try:
+        for name, cap in (("capped", CAP), ("plain", 0)):
+            eng = Engine(B, S_, 5, games=G, noise=True)
+            try:
+                eng.seed_all(np.arange(63000, 63000 + G, dtype=np.uint32))
+                if cap:
+                    eng.set_row_cap(cap)
+                res = eng.search(net, tau=np.ones(G, np.int8))
+                out[name] = (res, eng.row_stats(), eng.search_stats())
+            finally:
+                eng.close()
+    finally:
+        net.close()
+    for i, what in enumerate(("pi", "visits", "priors")):
+        np.testing.assert_array_equal(out["capped"][0][i], out["plain"][0][i], err_msg=what)
+    rows, st = out["capped"][1], out["capped"][2]
+    print("row stats %s, search stats %s" % (rows, st))
+    assert rows["launches"] > RING, rows
+    assert rows["rows_live"] == st["evaluated"], (rows, st)
+    assert rows["rows_launched"] == CAP * rows["launches"], rows
+    assert out["plain"][1]["launches"] == 0
+
+
 def test_self_play_with_the_trained_network_replayed_by_the_oracle(oracle):
     """main.self_play(n) -- the whole drop-in loop: Evaluator export of the trained PVNet, ao_search with the planner following
     the shrinking number of active games (k_row16hk -> per-board path), get_action, env step, re-rooting -- with three

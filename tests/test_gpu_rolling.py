@@ -36,9 +36,9 @@ def net():
         n.close()
 
 
-def _engine(row_cap=0, games=G, seeds=SEEDS, openings=OPENINGS):
+def _engine(row_cap=0, games=G, seeds=SEEDS, openings=OPENINGS, sims=S):
     from alpha_omok_amd.engine import Engine
-    eng = Engine(B, S, 5, games=games, noise=True)
+    eng = Engine(B, sims, 5, games=games, noise=True)
     eng.seed_all(seeds)
     if openings is not None:
         assert (eng.set_roots(openings) == 0).all()
@@ -78,10 +78,12 @@ def _roll(eng, net, plies, tau_rel, **kw):
     return recs, played
 
 
-def _oracle(net, recs, played, tau_rel, row_cap=0):
+def _oracle(net, recs, played, tau_rel, row_cap=0, **engine_kw):
     """The synchronous run: per relative ply k the games that the roll played at k, with the budgets its records report.
-    Returns {(game, rel ply): (pi, visit, policy, action, win)} and the engine (open: the caller reads streams and closes)."""
-    eng = _engine(row_cap)
+    Returns {(game, rel ply): (pi, visit, policy, action, win)} and the engine (open: the caller reads streams and closes).
+    engine_kw: what _engine was given for the roll beyond the row cap (games, seeds, openings, sims)."""
+    eng = _engine(row_cap, **engine_kw)
+    G = eng.G
     sims = {(int(r["game"]), r["rel"]): int(r["sims"]) for r in recs}
     out = {}
     for k in range(int(played.max())):
@@ -172,6 +174,36 @@ def test_early_stop(net, turn_every, row_cap):
         ref.close()
     np.testing.assert_array_equal(mt, rmt, err_msg="streams after the last ply")
     np.testing.assert_array_equal(pos, rpos, err_msg="stream positions after the last ply")
+
+
+@pytest.mark.parametrize("row_cap", (0, 1))
+def test_more_launches_than_the_row_counter_ring_has_slots(net, row_cap):
+    """The rows of a launch are counted in a ring of 2048 device words, summed up at every turn and zeroed where it wraps. Two
+    games on 300 simulations a move, a turn every 4 launches, 8 plies: about 2400 launches (twice that on one row), so the roll
+    runs past the wrap. Every record and the final streams equal the synchronous run's, and the ledger counts every launch."""
+    kw = dict(games=2, seeds=SEEDS[:2], openings=OPENINGS[:2], sims=300)
+    eng = _engine(row_cap, **kw)
+    try:
+        recs, played = _roll(eng, net, 8, 2, turn_every=4)
+        mt, pos = _streams(eng)
+        rows = eng.row_stats()
+    finally:
+        eng.close()
+    print("row_cap %d: plies played %s, row stats %s" % (row_cap, played.tolist(), rows))
+    for r in recs:
+        assert int(r["sims"]) == 300 and not r["settled"]
+    oracle, ref = _oracle(net, recs, played, 2, row_cap, **kw)
+    try:
+        _compare(recs, oracle, "past the ring wrap, row_cap %d" % row_cap)
+        rmt, rpos = _streams(ref)
+    finally:
+        ref.close()
+    np.testing.assert_array_equal(mt, rmt, err_msg="streams after the last ply")
+    np.testing.assert_array_equal(pos, rpos, err_msg="stream positions after the last ply")
+    assert rows["launches"] > 2048, rows
+    assert rows["rows_live"] <= rows["rows_launched"]
+    if row_cap:
+        assert rows["rows_launched"] == row_cap * rows["launches"]
 
 
 def test_protocol(net):

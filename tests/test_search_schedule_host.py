@@ -2,7 +2,7 @@
 (tests/host/search_schedule_main.cpp) with the host C++ compiler and fed cases on stdin. What it prints is compared with the same
 formulas written out below in Python -- restated from search_impl as it stood before the header existed (the sit-out window, the
 planned extra launches, the catch-up loop's stall rule, the row statistics), not from the header -- and with values worked out
-by hand."""
+by hand. The spans of the row-counter ring that a harvest reads are restated as the list of words they must cover."""
 import math
 import os
 import shutil
@@ -204,3 +204,38 @@ def test_row_ledger(program):
     got = program(["L %d %d %s" % (cap, len(w), " ".join(map(str, w))) for cap, w in cases])
     for (cap, w), line in zip(cases, got):
         assert tuple(int(x) for x in line.split()[1:]) == ledger(cap, w)
+
+
+# ---- the spans of the row-counter ring -------------------------------------------------------------------------------------------
+def ring_words(harvested, upto, ring):
+    """The ring words that hold the counters of the launches [harvested, upto), in launch order: launch i counts in word i % ring."""
+    return [i % ring for i in range(harvested, upto)]
+
+
+def test_ring_spans(program):
+    RING = 2048
+    by_hand = {
+        (0, 0): "R 0 0 0", (700, 700): "R 0 0 0", (700, 650): "R 0 0 0",      # an empty range copies nothing
+        (100, 164): "R 100 64 0",                                             # inside the ring: one span
+        (2000, 2048): "R 2000 48 0",                                          # ends exactly at the wrap: still one span, no empty tail
+        (4000, 4096): "R 1952 96 0",                                          # ... at the second wrap
+        (2040, 2060): "R 2040 8 12",                                          # crosses the wrap: the end of the ring, then its start
+        (0, 2048): "R 0 2048 0", (2048, 4096): "R 0 2048 0",                  # a full ring from its first word
+        (5, 2053): "R 5 2043 5",                                              # a full ring from the middle
+    }
+    cases = [(h, u, RING) for h, u in by_hand]
+    rng = np.random.default_rng(24)
+    for _ in range(300):
+        ring = int(rng.choice([1, 2, 7, 64, RING]))
+        h = int(rng.integers(0, 5 * ring + 1))
+        cases.append((h, h + int(rng.integers(0, ring + 1)), ring))
+    cases.append((2 ** 33 + 2040, 2 ** 33 + 2060, RING))                      # (launch counts of a long roll are 64-bit)
+    got = program(["R %d %d %d" % c for c in cases])
+    for (h, u, ring), line in zip(cases, got):
+        first, head, tail = (int(x) for x in line.split()[1:])
+        assert 0 <= first < ring and head >= 0 and tail >= 0 and first + head <= ring and head + tail <= ring, (h, u, ring, line)
+        assert tail == 0 or first + head == ring                              # a second span only behind the ring's end
+        assert list(range(first, first + head)) + list(range(tail)) == ring_words(h, u, ring), (h, u, ring, line)
+        if (h, u) in by_hand and ring == RING:
+            assert line == by_hand[(h, u)], (h, u, line)
+    assert got[-1] == "R 2040 8 12"
