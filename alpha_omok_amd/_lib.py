@@ -84,6 +84,8 @@ SYMBOLS = {
     "ao_seed": (C.c_int, [_vp, C.c_int, C.c_uint32]),
     "ao_seed_all": (C.c_int, [_vp, _u32p]),
     "ao_seed_games": (C.c_int, [_vp, _i32p, _u32p, C.c_int32]),
+    "ao_set_leaf_symmetry": (C.c_int, [_vp, C.c_int, C.c_uint32]),
+    "ao_set_leaf_symmetry_keys": (C.c_int, [_vp, _i32p, _u32p, C.c_int32]),
     "ao_get_rng_state": (C.c_int, [_vp, C.c_int, _u32p, _i32p, _i32p, _f64p]),
     "ao_set_rng_state": (C.c_int, [_vp, C.c_int, _u32p, C.c_int32, C.c_int32, C.c_double]),
     "ao_reset": (C.c_int, [_vp, _u8p]),
@@ -178,6 +180,8 @@ SYMBOLS = {
     "ao_positions_check_win": (C.c_int, [_vp, _i8p, C.c_int32, _i32p]),
     "ao_positions_from_moves": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _i32p, _i32p, _i32p, _i8p, _u8p, _vp, _i32p]),
     "ao_positions_evaluate": (C.c_int, [_vp, _vp, _i32p, C.c_int32, _i32p, C.c_int32, _P(C.c_float), _P(C.c_float), _i32p, _i32p]),
+    "ao_positions_evaluate_sym": (C.c_int, [_vp, _vp, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, _P(C.c_float), _P(C.c_float), _i32p,
+                                            _i32p]),
     "ao_positions_win_cells": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _u8p, _u8p, _i32p, _i32p, _i32p]),
     "ao_positions_audit": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, _u8p, _i32p, _i32p]),
     "ao_positions_forced_wins": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _u8p,

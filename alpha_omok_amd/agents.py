@@ -89,8 +89,11 @@ class _TreeView(object):
 
 
 class ZeroAgent(Agent):
-    def __init__(self, board_size, num_mcts, inplanes, noise=True, device=0, node_cap=0):
+    def __init__(self, board_size, num_mcts, inplanes, noise=True, device=0, node_cap=0, leaf_symmetry=None):
+        """leaf_symmetry: None, or an int key -- every leaf of the search is then evaluated under a symmetry of the board
+        drawn from (key, stones on the leaf, simulation index) (Engine.set_leaf_symmetry)."""
         super(ZeroAgent, self).__init__(board_size)
+        self.leaf_symmetry = leaf_symmetry
         self.board_size = board_size
         self.num_mcts = num_mcts
         self.inplanes = inplanes
@@ -114,6 +117,8 @@ class ZeroAgent(Agent):
             self._engine = Engine(self.board_size, self.num_mcts, self.inplanes, games=1, noise=self.noise,
                                   device=self._device, node_cap=self._node_cap, c_puct=float(self.c_puct),
                                   alpha=float(self.alpha), win_mark=self.win_mark)
+            if self.leaf_symmetry is not None:
+                self._engine.set_leaf_symmetry(self.leaf_symmetry)
         return self._engine
 
     # -- reference API ----------------------------------------------------------------------
@@ -197,7 +202,15 @@ class ZeroAgent(Agent):
         """The number del_parents prints as `tree depth` in the reference (agents.py:241-250), from the device tree."""
         return 0 if self._engine is None else int(self._engine.tree_stats()["depth"][0])
 
-    def get_pv(self, root_id):
+    def get_pv(self, root_id, symmetries=1):
+        """symmetries=8: the mean over the eight symmetries of the board (PositionBatch.evaluate); needs a model the native
+        forward takes."""
+        if symmetries != 1:
+            net = self.model if hasattr(self.model, "forward_ptr") else self._evaluator.native_net(self.model, self.board_size, self.inplanes)
+            if net is None:
+                raise ValueError("get_pv(symmetries=%r) needs a model in the PVNet wire format or an engine.Net" % (symmetries,))
+            p, v, _, _ = self._position_batch().evaluate(net, [tuple(root_id)], symmetries=symmetries)
+            return p[0], v[0]
         import torch
         from . import utils
         state = utils.get_state_pt(root_id, self.board_size, self.inplanes)

@@ -31,6 +31,7 @@
 #include "roll_schedule.hpp"
 #include "search_schedule.hpp"
 #include "snapshot_check.hpp"
+#include "symmetry.hpp"
 #include "tactics_limits.hpp"
 #include "tree_snapshot.hpp"
 
@@ -177,7 +178,25 @@ struct ao_engine : ao::HandleBase {
     // HIP-event timing of the per-simulation tree kernel (k_expand_select) on the launch stream (ao_tree_timing)
     ao::EventTimer timer{256};
     RollState roll;
+    // leaf symmetries (ao_set_leaf_symmetry): the seed most recently given to each game (never seeded: g), the keys made of
+    // them -- or set one by one, ao_set_leaf_symmetry_keys -- and their device copy, which tp.sym_key names while the switch is on
+    std::vector<uint32_t> sym_seed, sym_keys;
+    uint32_t* d_sym_key = nullptr;
+    bool sym_on = false;
+    uint32_t sym_base = 0;
 };
+
+// The keys of the games as the device must see them. A seed call ends here as well: an episode's symmetries follow its seed.
+static int sym_upload(ao_engine* e) {
+    if (!e->sym_on) return 0;
+    AO_HIP(e, hipMemcpyAsync(e->d_sym_key, e->sym_keys.data(), sizeof(uint32_t) * e->G, hipMemcpyHostToDevice, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+static void sym_reseed(ao_engine* e, int g, uint32_t seed) {
+    e->sym_seed[g] = seed;
+    e->sym_keys[g] = ao::leaf_key(e->sym_base, seed);
+}
 
 // Inside an open roll the engine's games move on their own clocks: everything that begins, ends or steps a move of the whole
 // engine, moves roots or reads trees in bulk is refused until ao_roll_end.
@@ -432,7 +451,11 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
     if (e->pool.alloc(e, &e->d_live, ao_engine::kLive) || e->pool.alloc(e, &e->d_log_games, G) || e->pool.alloc(e, &e->d_ctl, 8) || e->pool.alloc(e, &e->d_order, G)) return 1;
     if (e->pool.alloc(e, &e->d_settled, G) || e->pool.alloc(e, &e->d_early, G) || e->pool.alloc(e, &e->d_settle, 4)) return 1;
     AO_HIP(e, hipMemsetAsync(e->d_settled, 0, G, e->stream));
-    if (e->pool.alloc(e, &e->d_bar, static_cast<size_t>(G) * ao::kBBWords)) return 1;
+    if (e->pool.alloc(e, &e->d_bar, static_cast<size_t>(G) * ao::kBBWords) || e->pool.alloc(e, &e->d_sym_key, G)) return 1;
+    p.sym_key = nullptr;
+    e->sym_seed.resize(G);
+    e->sym_keys.resize(G);
+    for (int g = 0; g < G; ++g) sym_reseed(e, g, static_cast<uint32_t>(g));
     e->h_bar.assign(static_cast<size_t>(G) * ao::kBBWords, 0);
     e->bar_has.assign(G, 0);
     p.bar = nullptr;
@@ -527,7 +550,9 @@ int ao_get_rng_state(ao_engine* e, int g, uint32_t* mt, int32_t* pos, int32_t* h
 int ao_seed(ao_engine* e, int g, uint32_t seed) {
     std::vector<uint32_t> mt(624);
     ao::HostMT::seed(mt.data(), seed);
-    return ao_set_rng_state(e, g, mt.data(), 624, 0, 0.0);
+    if (ao_set_rng_state(e, g, mt.data(), 624, 0, 0.0)) return 1;
+    sym_reseed(e, g, seed);
+    return sym_upload(e);
 }
 
 int ao_seed_games(ao_engine* e, const int32_t* games, const uint32_t* seeds, int32_t n) {
@@ -548,9 +573,10 @@ int ao_seed_games(ao_engine* e, const int32_t* games, const uint32_t* seeds, int
         AO_HIP(e, hipMemcpyAsync(e->tp.mt + static_cast<size_t>(g) * 624, e->h_mt + static_cast<size_t>(g) * 624, sizeof(uint32_t) * 624,
                                  hipMemcpyHostToDevice, e->stream));
         AO_HIP(e, hipMemcpyAsync(e->tp.mtpos + g, e->h_pos + g, sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+        sym_reseed(e, g, seeds[k]);
     }
     AO_HIP(e, hipStreamSynchronize(e->stream));
-    return 0;
+    return sym_upload(e);
 }
 
 int ao_seed_all(ao_engine* e, const uint32_t* seeds) {
@@ -564,11 +590,46 @@ int ao_seed_all(ao_engine* e, const uint32_t* seeds) {
         e->h_pos[g] = 624;
         e->has_gauss[g] = 0;
         e->gauss[g] = 0.0;
+        sym_reseed(e, g, seeds[g]);
     }
     AO_HIP(e, hipMemcpyAsync(e->tp.mt, e->h_mt, sizeof(uint32_t) * 624 * e->G, hipMemcpyHostToDevice, e->stream));
     AO_HIP(e, hipMemcpyAsync(e->tp.mtpos, e->h_pos, sizeof(int32_t) * e->G, hipMemcpyHostToDevice, e->stream));
     AO_HIP(e, hipStreamSynchronize(e->stream));
+    return sym_upload(e);
+}
+
+// ---- leaf symmetries -------------------------------------------------------------------------
+// The switch changes what the kernels of the NEXT launch see: e->tp, and the copy an open roll launches with.
+static void sym_publish(ao_engine* e) {
+    e->tp.sym_key = e->sym_on ? e->d_sym_key : nullptr;
+    if (e->roll.open) e->roll.loop.p.sym_key = e->tp.sym_key;
+}
+
+int ao_set_leaf_symmetry(ao_engine* e, int enable, uint32_t base_key) {
+    if (e->in_move) return e->fail("ao_set_leaf_symmetry inside a move (its leaves so far were evaluated under the old keys)");
+    for (int g = 0; g < e->G; ++g)
+        if (roll_refuses_game(e, "ao_set_leaf_symmetry", g)) return 1;
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    e->sym_on = enable != 0;
+    e->sym_base = enable ? base_key : 0u;
+    for (int g = 0; g < e->G; ++g) e->sym_keys[g] = ao::leaf_key(e->sym_base, e->sym_seed[g]);
+    if (sym_upload(e)) return 1;
+    sym_publish(e);
     return 0;
+}
+
+int ao_set_leaf_symmetry_keys(ao_engine* e, const int32_t* games, const uint32_t* keys, int32_t n) {
+    if (n <= 0) return 0;
+    if (e->in_move) return e->fail("ao_set_leaf_symmetry_keys inside a move (its leaves so far were evaluated under the old keys)");
+    if (!e->sym_on) return e->fail("ao_set_leaf_symmetry_keys: leaf symmetries are off (ao_set_leaf_symmetry switches them on)");
+    if (!games || !keys) return e->fail("ao_set_leaf_symmetry_keys: null buffer");
+    for (int k = 0; k < n; ++k)
+        if (games[k] < 0 || games[k] >= e->G) return e->fail("ao_set_leaf_symmetry_keys: game index out of range");
+    for (int k = 0; k < n; ++k)
+        if (roll_refuses_game(e, "ao_set_leaf_symmetry_keys", games[k])) return 1;
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    for (int k = 0; k < n; ++k) e->sym_keys[games[k]] = keys[k];
+    return sym_upload(e);
 }
 
 // ---- the root bar ----------------------------------------------------------------------------

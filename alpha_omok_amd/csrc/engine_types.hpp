@@ -131,6 +131,11 @@ struct TreeParams {
     // LS_EXPAND_ROOT) and where a move begins on an expanded root (k_begin_move). The selection never looks at it: a barred
     // child carries Q = kBarQ in the root's record.
     const uint64_t* bar;
+    // Leaf symmetries: [G] keys, or null = every leaf is evaluated as it stands. With keys, the leaf of simulation `sim` (the
+    // game's sims_done) is written into the evaluation batch under s = leaf_symmetry(sym_key[g], leaf ply, sim) (symmetry.hpp)
+    // and its policy row is read back through the same map. Read in two places only: where planes are encoded (select_game) and
+    // at the policy gather of expand_backup_game; no network kernel knows of it.
+    const uint32_t* sym_key;
 };
 
 // Device buffers of ao_root_tactics (engine.hip -> launch_root_tactics, root_tactics.hip): the forced-win solver's verdict on the

@@ -125,7 +125,8 @@ struct PositionsParams {
     int32_t* status; int32_t* end_ply; int32_t* turn; int32_t* err;
     int8_t* board;          // [n][A]
     uint8_t* legal;         // [n][A]
-    float* planes;          // [n][C][A]
+    float* planes;          // [n][nsym][C][A]
+    int nsym;               // 1, or 8: row 8 i + s of `planes` holds sym_planes(planes of position i, s) (symmetry.hpp)
 };
 
 template <int NCH>
@@ -156,15 +157,44 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_positions_from_moves(Positio
     store_cell_mask<NCH>(q.legal ? q.legal + static_cast<size_t>(i) * A : nullptr, A, empty, p.ok);
     if (q.planes) {
         if (p.ok || q.bad_as_empty) {
-            TreeParams tp{};   // the encoder's view of the batch: row i of a plain NCHW plane batch
+            TreeParams tp{};   // the encoder's view of the batch: row i of a plain NCHW plane batch (no keys: the identity ...)
             tp.C = q.C;
             tp.A = A;
+            tp.B = q.ids.B;
             tp.batch_nchw = q.planes;
-            encode_planes<NCH>(tp, i, s, i);
+            if (q.nsym == 1) encode_planes<NCH>(tp, i, s, i);
+            else   // ... or all eight symmetries of the position, in rows of their own
+                for (int sym = 0; sym < q.nsym; ++sym) encode_planes<NCH>(tp, q.nsym * i + sym, s, 0, nullptr, sym);
         } else {
-            float* out = q.planes + static_cast<size_t>(i) * q.C * A;
-            for (int idx = lane; idx < q.C * A; idx += 64) out[idx] = 0.f;
+            float* out = q.planes + static_cast<size_t>(i) * q.nsym * q.C * A;
+            for (int idx = lane; idx < q.nsym * q.C * A; idx += 64) out[idx] = 0.f;
         }
+    }
+}
+
+// The 8-fold mean of ao_positions_evaluate_sym: rows 8 i + s of policy_in / value_in are the network's answers on the eight
+// symmetries of position i; each policy row is brought back into the board's own frame (cell c of symmetry s is read where c
+// went, sym_cell_inv) and the eight are added in fp32 in the order ((p_0 + p_1) + p_2) + ... + p_7, then scaled by 1/8.
+template <int NCH>
+__global__ __launch_bounds__(64 * kPosPerWG) void k_sym_mean(const float* __restrict__ policy_in, const float* __restrict__ value_in, int n,
+                                                             int B, float* __restrict__ policy, float* __restrict__ value) {
+    const int i = wave_item();
+    if (i >= n) return;
+    const int lane = lane_id();
+    const int A = B * B;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int cell = lane + 64 * c;
+        if (cell >= A) continue;
+        float acc = policy_in[static_cast<size_t>(8 * i) * A + cell];
+        for (int sym = 1; sym < 8; ++sym)
+            acc = __fadd_rn(acc, policy_in[static_cast<size_t>(8 * i + sym) * A + sym_cell_inv(sym, cell, B)]);
+        policy[static_cast<size_t>(i) * A + cell] = __fmul_rn(0.125f, acc);
+    }
+    if (lane == 0) {
+        float acc = value_in[8 * i];
+        for (int sym = 1; sym < 8; ++sym) acc = __fadd_rn(acc, value_in[8 * i + sym]);
+        value[i] = __fmul_rn(0.125f, acc);
     }
 }
 
@@ -429,6 +459,7 @@ struct ao_positions : ao::HandleBase {
     ao::DevBuf<float> d_planes{&pool};     // [cap][C][A]   -- the three below: allocated by the first ao_positions_evaluate
     ao::DevBuf<float> d_policy{&pool};     // [cap][A]
     ao::DevBuf<float> d_value{&pool};      // [cap]
+    ao::DevBuf<float> d_mean{&pool};       // [cap / 8][A] policy, then [cap / 8] value -- allocated by the first ao_positions_evaluate_sym with nsym 8
     ao::DevBuf<int32_t> d_counts{&pool};   // [cap][8]      -- allocated by the first ao_positions_audit
     ao::DevBuf<int32_t> d_forced{&pool};   // [5][cap]: ForcedSlot -- these two: by the first ao_positions_forced_wins
     ao::DevBuf<int16_t> d_line{&pool};     // [cap][2 * 16 - 1]
@@ -475,7 +506,8 @@ int stage_moves(ao_positions* p, const char* who, const int32_t* host_moves, int
 }
 
 // what every id-batch entry point is called with
-struct IdArgs { const char* who; const int32_t* moves; int32_t stride; const int32_t* n_moves; int32_t n; };
+struct IdArgs { const char* who; const int32_t* moves; int32_t stride; const int32_t* n_moves; int32_t n;
+                int32_t per_chunk = 0; };   // ids of one chunk; 0: the handle's capacity
 // its first check; what is particular to an entry point (limits, the network) is checked by the entry point after this one
 bool negative_ids(ao_positions* p, const IdArgs& c, const char* noun = "position") {
     return (c.n < 0 || c.stride < 0) && p->fail(std::string(c.who) + ": negative " + noun + " count or stride");
@@ -500,8 +532,9 @@ int for_id_chunks(ao_positions* p, const IdArgs& c, Prepare&& prepare, Chunk&& c
     AO_HIP(p, hipSetDevice(p->device));
     if (prepare()) return 1;
     std::vector<Fetch> out;
-    for (int64_t first = 0; first < c.n; first += p->cap) {
-        const int m = static_cast<int>(std::min<int64_t>(p->cap, c.n - first));
+    const int per_chunk = c.per_chunk > 0 ? c.per_chunk : p->cap;
+    for (int64_t first = 0; first < c.n; first += per_chunk) {
+        const int m = static_cast<int>(std::min<int64_t>(per_chunk, c.n - first));
         if (stage_moves(p, c.who, c.moves, c.stride, c.n_moves, first, m)) return 1;
         out.clear();
         if (chunk(first, m, out)) return 1;
@@ -525,8 +558,9 @@ const auto kNothing = [] { return 0; };
 
 // k_positions_from_moves on the m staged ids: the outputs asked for land in d_i32, d_board, d_cells1 (legal) and `planes`
 int launch_from_moves(ao_positions* p, int m, bool status, bool end_ply, bool turn, bool board, bool legal, float* planes, bool err,
-                      bool bad_as_empty) {
+                      bool bad_as_empty, int nsym = 1) {
     ao::PositionsParams q{};
+    q.nsym = nsym;
     q.ids = staged_ids(p, m);
     q.C = p->C;
     q.bad_as_empty = bad_as_empty ? 1 : 0;
@@ -708,31 +742,49 @@ int ao_positions_forced_defences(ao_positions* p, const int32_t* host_moves, int
         });
 }
 
-int ao_positions_evaluate(ao_positions* p, ao_net* net, const int32_t* host_moves, int32_t stride, const int32_t* host_n,
-                          int32_t n, float* host_policy, float* host_value, int32_t* host_status, int32_t* host_err) {
+}  // extern "C"
+
+// nsym 1: the network's answer on each position as it stands. nsym 8: the mean over the eight symmetries -- eight rows per
+// position through ONE forward (so a chunk holds capacity / 8 positions), brought back and added up by k_sym_mean.
+static int evaluate_impl(ao_positions* p, const char* who, ao_net* net, const int32_t* host_moves, int32_t stride, const int32_t* host_n,
+                         int32_t n, int nsym, float* host_policy, float* host_value, int32_t* host_status, int32_t* host_err) {
     const size_t A = static_cast<size_t>(p->A), cap = static_cast<size_t>(p->cap);
-    const IdArgs call{"ao_positions_evaluate", host_moves, stride, host_n, n};
+    const std::string w(who);
+    if (nsym != 1 && nsym != 8) return p->fail(w + ": nsym must be 1 or 8");
+    if (nsym == 8 && p->cap < 8) return p->fail(w + ": eight rows per position need a capacity of at least 8");
+    const IdArgs call{who, host_moves, stride, host_n, n, nsym == 8 ? p->cap / 8 : 0};
     if (negative_ids(p, call)) return 1;
-    if (!net) return p->fail("ao_positions_evaluate: null network");
+    if (!net) return p->fail(w + ": null network");
     std::string why;
-    if (ao::net_check(net, p->B, p->C, p->device, &why)) return p->fail("ao_positions_evaluate: " + why);
+    if (ao::net_check(net, p->B, p->C, p->device, &why)) return p->fail(w + ": " + why);
     if (n == 0) return 0;
-    if (!host_n || (!host_moves && stride > 0) || !host_policy || !host_value) return p->fail("ao_positions_evaluate: null buffer");
+    if (!host_n || (!host_moves && stride > 0) || !host_policy || !host_value) return p->fail(w + ": null buffer");
     std::vector<int32_t> own_err(host_err ? 0 : static_cast<size_t>(n));
     int32_t* err = host_err ? host_err : own_err.data();
+    const size_t cap8 = cap / 8;
     return for_id_chunks(
         p, call,
         [&]() -> int {
             AO_HIP(p, hipDeviceSynchronize());   // the network's workspace may still serve a forward queued on another stream
-            return p->d_planes.reserve(p, cap * p->C * A) || p->d_policy.reserve(p, cap * A) || p->d_value.reserve(p, cap);
+            return p->d_planes.reserve(p, cap * p->C * A) || p->d_policy.reserve(p, cap * A) || p->d_value.reserve(p, cap) ||
+                   (nsym == 8 && p->d_mean.reserve(p, cap8 * (A + 1)));
         },
         [&](int64_t, int m, std::vector<Fetch>& out) {
             // a position with an error is fed as the empty board: its row must not disturb the rest of the chunk
-            if (launch_from_moves(p, m, true, false, false, false, false, p->d_planes.p, true, true)) return 1;
-            if (ao_net_forward(net, p->d_planes.p, m, p->d_policy.p, p->d_value.p, p->stream))
-                return p->fail(std::string("ao_positions_evaluate: ") + ao_net_last_error(net));
-            out = {fetch(host_policy, p->d_policy.p, A), fetch(host_value, p->d_value.p), fetch(host_status, d_status(p)),
-                   fetch(err, d_err(p))};
+            if (launch_from_moves(p, m, true, false, false, false, false, p->d_planes.p, true, true, nsym)) return 1;
+            if (ao_net_forward(net, p->d_planes.p, m * nsym, p->d_policy.p, p->d_value.p, p->stream))
+                return p->fail(w + ": " + ao_net_last_error(net));
+            const float* policy = p->d_policy.p;
+            const float* value = p->d_value.p;
+            if (nsym == 8) {
+                float* mp = p->d_mean.p;
+                float* mv = p->d_mean.p + cap8 * A;
+                AO_DISPATCH_NCH(ao::nch_of_cells(p->A), hipLaunchKernelGGL(ao::k_sym_mean<NCH>, wave_grid(m), kBlock, 0, p->stream, policy, value,
+                                                                           m, p->B, mp, mv));
+                policy = mp;
+                value = mv;
+            }
+            out = {fetch(host_policy, policy, A), fetch(host_value, value), fetch(host_status, d_status(p)), fetch(err, d_err(p))};
             return 0;
         },
         [&](int64_t first, int m) {
@@ -742,6 +794,19 @@ int ao_positions_evaluate(ao_positions* p, ao_net* net, const int32_t* host_move
                 host_value[k] = 0.f;
             }
         });
+}
+
+extern "C" {
+
+int ao_positions_evaluate(ao_positions* p, ao_net* net, const int32_t* host_moves, int32_t stride, const int32_t* host_n,
+                          int32_t n, float* host_policy, float* host_value, int32_t* host_status, int32_t* host_err) {
+    return evaluate_impl(p, "ao_positions_evaluate", net, host_moves, stride, host_n, n, 1, host_policy, host_value, host_status, host_err);
+}
+
+int ao_positions_evaluate_sym(ao_positions* p, ao_net* net, const int32_t* host_moves, int32_t stride, const int32_t* host_n,
+                              int32_t n, int32_t nsym, float* host_policy, float* host_value, int32_t* host_status, int32_t* host_err) {
+    return evaluate_impl(p, "ao_positions_evaluate_sym", net, host_moves, stride, host_n, n, nsym, host_policy, host_value, host_status,
+                         host_err);
 }
 
 }  // extern "C"

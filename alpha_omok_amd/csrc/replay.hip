@@ -23,22 +23,9 @@
 #include <vector>
 
 #include "replay_ring.hpp"
+#include "symmetry.hpp"   // sym_source: source cell of output cell (i, j) under symmetry sym = 2*r + f
 
 namespace ao {
-
-// source cell of output cell (i, j) under symmetry sym = 2*r + f (rot90 by r, then flip if f)
-__device__ __forceinline__ int sym_source(int sym, int i, int j, int B) {
-    const int r = sym >> 1;
-    const int jj = (sym & 1) ? B - 1 - j : j;
-    int si, sj;
-    switch (r) {
-        case 0: si = i; sj = jj; break;
-        case 1: si = jj; sj = B - 1 - i; break;
-        case 2: si = B - 1 - i; sj = B - 1 - jj; break;
-        default: si = B - 1 - jj; sj = i; break;
-    }
-    return si * B + sj;
-}
 
 // staged samples [n][C][A] f32 / [n][A] f64 / [n] f32  ->  ring slots (start + k) % cap,
 // k = 8 * sample + sym (nsym = 8) or k = sample (nsym = 1)

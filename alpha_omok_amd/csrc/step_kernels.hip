@@ -36,7 +36,7 @@ __device__ unsigned long long ao_prof_step[8];   // game 0, thread 0: start / he
 #define AO_ST(k) do { } while (0)
 #endif
 
-template <int NCH>
+template <int NCH, bool SYM>   // SYM: leaf symmetries, as in tree_kernels.hip
 __global__ __launch_bounds__(1024) void k_step_board(TreeParams p, StepNet f, const int32_t* __restrict__ game_of_row) {
     extern __shared__ __attribute__((aligned(16))) float s_hb[];   // heads_lds_floats(A, planes)
     __shared__ uint32_t s_mt[624];
@@ -81,9 +81,9 @@ __global__ __launch_bounds__(1024) void k_step_board(TreeParams p, StepNet f, co
     };
     if (w == 0) {
         GameHdr hdr;
-        expand_backup_game<NCH>(p, g, s_ord, s_prior, s_tab, &hdr);
+        expand_backup_game<NCH, SYM>(p, g, s_ord, s_prior, s_tab, &hdr);
         wsync();
-        select_game<NCH>(p, g, s_mt, s_lin, &hdr);
+        select_game<NCH, SYM>(p, g, s_mt, s_lin, &hdr);
     } else {
         load_a(w % nt);
     }
@@ -144,7 +144,8 @@ __global__ __launch_bounds__(1024) void k_step_board(TreeParams p, StepNet f, co
 
 void launch_step_board(const TreeParams& p, const StepNet& f, int rows, const int32_t* game_of_row, hipStream_t s) {
     const size_t lds = heads_lds_floats(p.A, f.planes) * sizeof(float);
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_step_board<NCH>, dim3(rows), dim3(1024), lds, s, p, f, game_of_row));
+    if (p.sym_key) { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_step_board<NCH, true>), dim3(rows), dim3(1024), lds, s, p, f, game_of_row)); }
+    else { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_step_board<NCH, false>), dim3(rows), dim3(1024), lds, s, p, f, game_of_row)); }
 #ifdef AO_PROF
     if (getenv("AO_PROF_TREE")) {
         static int count = 0;

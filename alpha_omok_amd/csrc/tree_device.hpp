@@ -6,6 +6,7 @@
 // reference map and the arithmetic contract.
 #pragma once
 #include "engine_types.hpp"
+#include "symmetry.hpp"
 
 #ifdef AO_PROF
 static __device__ unsigned long long ao_prof_tree[16];   // game 0 of k_expand_select: phase ends (shader-clock ticks)
@@ -366,12 +367,24 @@ struct MtDev {
     }
 };
 
+// The symmetry under which the leaf of game g's simulation `sim` (sims_done[g]: the same value when the leaf is selected,
+// when a waiting leaf is encoded later, and when it is expanded) goes through the network; wave-uniform.
+// SYM is a template parameter of the per-simulation kernels, chosen by their launchers from TreeParams::sym_key (null: false),
+// not a branch inside them: without keys the kernels are instruction for instruction what they are without this feature -- a
+// wave-uniform test of the pointer in the middle of the expansion's load sequence measured 1 us on k_expand_select's 23 us.
+template <bool SYM>
+__device__ __forceinline__ int leaf_sym(const TreeParams& p, int g, int ply, int sim) {
+    if constexpr (SYM) return leaf_symmetry(p.sym_key[g], static_cast<uint32_t>(ply), static_cast<uint32_t>(sim));
+    else return 0;
+}
+
 // ----------------------------------------------------------------------------------------------
 // get_state_pt (utils.py:139-168): planes [X_{k-C+2} .. X_k, colour], X_j = stones of the player
 // who made move j as they stood after move j. Written into the evaluation batch.
 // ----------------------------------------------------------------------------------------------
 template <int NCH>
-__device__ __forceinline__ void encode_planes(const TreeParams& p, int g, const PosR& s, int row = -1, uint8_t* lds_bits = nullptr) {
+__device__ __forceinline__ void encode_planes(const TreeParams& p, int g, const PosR& s, int row = -1, uint8_t* lds_bits = nullptr,
+                                              const int sym = 0) {
     const int lane = lane_id();
     // batch row of the native network (active games packed); select_game requests it with the game header -- read here it was a
     // dependent memory round trip at the very end of the kernel (AO_PROF: 1.7 k of the 5 k cycles after the descent)
@@ -407,10 +420,20 @@ __device__ __forceinline__ void encode_planes(const TreeParams& p, int g, const 
         }
         bits[c] = bc;
     }
+    // Under a symmetry (sym != 0, wave-uniform; a literal 0 in the kernels without keys) the lane still owns SOURCE cell lane + 64 c and writes it where the symmetry
+    // sends it: sym_planes(X, s)[dst] = X[src] with sym_cell(s, dst) = src. The map is a dozen integer operations per lane
+    // (a uniform division aside), cheaper than filling and reading back a table in LDS behind a barrier for 64 lanes.
+    int dst[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) dst[c] = lane + 64 * c;
+    if (sym != 0) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) dst[c] = sym_cell_inv(sym, dst[c] < p.A ? dst[c] : 0, p.B);
+    }
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        const int cell = lane + 64 * c;
-        if (cell >= p.A) continue;
+        if (lane + 64 * c >= p.A) continue;
+        const int cell = dst[c];
         const unsigned bq = bits[c] | ((stm == 0) ? (1u << (C - 1)) : 0u);   // + the colour plane
         if (lds_bits) {   // the fused per-game step (k_step_board): the planes stay in the workgroup, as bits
             lds_bits[cell] = static_cast<uint8_t>(bq & ((1u << C) - 1u));
@@ -513,7 +536,7 @@ struct TakeRowNone {   // rows are not handed out by the kernel (TreeParams::liv
 };
 
 // `exists` false: a wave of the workgroup beyond the last game -- it only keeps the row hand-out's barrier company.
-template <int NCH, class TakeRow = TakeRowNone>
+template <int NCH, bool SYM = false, class TakeRow = TakeRowNone>
 __device__ __forceinline__ void select_game(const TreeParams& p, const int g, uint32_t* s_mt /*[624]*/, uint8_t* lds_bits = nullptr,
                                             const GameHdr* hdr = nullptr, const TakeRow& take = TakeRow(), const bool exists = true,
                                             const unsigned sit_n = 0u, const unsigned sit_off = 0u) {
@@ -554,7 +577,7 @@ __device__ __forceinline__ void select_game(const TreeParams& p, const int g, ui
         const int r = TakeRowWave{p.live, p.row_cap}(true);
         if (r >= 0) {
             const PosR wl = pos_load(p.leaf_pos + g);
-            encode_planes<NCH>(p, g, wl, r, lds_bits);
+            encode_planes<NCH>(p, g, wl, r, lds_bits, leaf_sym<SYM>(p, g, wl.ply, done));   // (`done` has not moved since the descent)
             if (lane == 0) {
                 p.row_of_game[g] = r;
                 p.leaf_status[g] = prev == LS_WAIT ? LS_EXPAND : LS_EXPAND_ROOT;
@@ -756,7 +779,7 @@ __device__ __forceinline__ void select_game(const TreeParams& p, const int g, ui
         lp.nchild = 0;
         if (lane == 0) pos_store(p.leaf_pos + g, lp);
         AO_TT(9);
-        if (!wait) encode_planes<NCH>(p, g, lp, batch_row, lds_bits);
+        if (!wait) encode_planes<NCH>(p, g, lp, batch_row, lds_bits, leaf_sym<SYM>(p, g, lp.ply, done));
     }
     AO_TT(10);
     if (lane == 0) {
@@ -877,7 +900,7 @@ __device__ __forceinline__ double pairwise_sum_dev(const double* a, int n) {
 // ----------------------------------------------------------------------------------------------
 // k_expand_backup
 // ----------------------------------------------------------------------------------------------
-template <int NCH>
+template <int NCH, bool SYM = false>
 __device__ __forceinline__ void expand_backup_game(const TreeParams& p, const int g, uint8_t* s_ord /*[256]*/,
                                                    double* s_prior /*[256]*/, int16_t* s_tab /*[256]*/, GameHdr* hdr = nullptr) {
     const int lane = lane_id();
@@ -910,10 +933,22 @@ __device__ __forceinline__ void expand_backup_game(const TreeParams& p, const in
     }
     float v_eval = p.value[row];
     float pol[NCH];
+    if constexpr (SYM) {
+        // leaf symmetries: the row is the network's answer on sym_planes(leaf, s); the lane that owns cell d reads it where d
+        // went. The index needs the leaf and `done`, so this gather is a round trip of its own -- on the opt-in path only.
+        const int sym = leaf_sym<SYM>(p, g, lp.ply, done);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int cell = lane + 64 * c;
-        pol[c] = p.policy[static_cast<size_t>(row) * p.A + (cell < p.A ? cell : p.A - 1)];
+        for (int c = 0; c < NCH; ++c) {
+            const int cell = lane + 64 * c;
+            const int d = cell < p.A ? cell : p.A - 1;
+            pol[c] = p.policy[static_cast<size_t>(row) * p.A + (sym ? sym_cell_inv(sym, d, p.B) : d)];
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int cell = lane + 64 * c;
+            pol[c] = p.policy[static_cast<size_t>(row) * p.A + (cell < p.A ? cell : p.A - 1)];
+        }
     }
     // the path entries' edge statistics (the backup's read-modify-write below) are requested here, before the expansion's
     // arithmetic, not after it: the rows of the new node and the parent's CH entry are the only things the expansion writes

@@ -30,20 +30,21 @@
 
 namespace ao {
 
-template <int NCH>
+// SYM: leaf symmetries (TreeParams::sym_key is set; tree_device.hpp, leaf_sym) -- kernels of their own, picked by the launchers
+template <int NCH, bool SYM>
 __global__ __launch_bounds__(64) void k_select(TreeParams p) {
     __shared__ uint32_t s_mt[624];
     unsigned sit_n, sit_off;
     sit_window(p, sit_n, sit_off);
-    select_game<NCH>(p, blockIdx.x, s_mt, nullptr, nullptr, TakeRowWave{p.live, p.row_cap}, true, sit_n, sit_off);
+    select_game<NCH, SYM>(p, blockIdx.x, s_mt, nullptr, nullptr, TakeRowWave{p.live, p.row_cap}, true, sit_n, sit_off);
 }
 
-template <int NCH>
+template <int NCH, bool SYM>
 __global__ __launch_bounds__(64) void k_expand_backup(TreeParams p) {
     __shared__ uint8_t s_ord[256];
     __shared__ double s_prior[256];
     __shared__ int16_t s_tab[256];
-    expand_backup_game<NCH>(p, blockIdx.x, s_ord, s_prior, s_tab);
+    expand_backup_game<NCH, SYM>(p, blockIdx.x, s_ord, s_prior, s_tab);
 }
 
 // expansion + backup of simulation i, then selection + input planes of simulation i+1, in one
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(64) void k_expand_backup(TreeParams p) {
 // kGamesPerWG games per workgroup (one wave each, nothing shared between them): a quarter of the workgroups to
 // dispatch at 4096 games.
 constexpr int kGamesPerWG = 4;
-template <int NCH>
+template <int NCH, bool SYM>
 __global__ __launch_bounds__(64 * kGamesPerWG) void k_expand_select(TreeParams p) {
     __shared__ uint32_t s_mt[kGamesPerWG][624];
     __shared__ uint8_t s_ord[kGamesPerWG][256];
@@ -71,11 +72,11 @@ __global__ __launch_bounds__(64 * kGamesPerWG) void k_expand_select(TreeParams p
     sit_window(p, sit_n, sit_off);
     AO_TT(0);
     GameHdr hdr;
-    if (exists) expand_backup_game<NCH>(p, g, s_ord[w], s_prior[w], s_tab[w], &hdr);
+    if (exists) expand_backup_game<NCH, SYM>(p, g, s_ord[w], s_prior[w], s_tab[w], &hdr);
     wsync();
     AO_TT(1);
     // (rows handed out per simulation: the waves of the workgroup meet once inside select_game, see TakeRowWG)
-    select_game<NCH>(p, g, s_mt[w], nullptr, &hdr, TakeRowWG<kGamesPerWG>{p.live, p.row_cap, s_need}, exists, sit_n, sit_off);
+    select_game<NCH, SYM>(p, g, s_mt[w], nullptr, &hdr, TakeRowWG<kGamesPerWG>{p.live, p.row_cap, s_need}, exists, sit_n, sit_off);
     AO_TT(2);
 }
 
@@ -344,13 +345,17 @@ __global__ void k_reset(TreeParams p, const uint8_t* mask) {
 // launchers (called from engine.hip)
 // ----------------------------------------------------------------------------------------------
 void launch_select(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_select<NCH>, dim3(p.G), dim3(64), 0, s, p));
+    if (p.sym_key) { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_select<NCH, true>), dim3(p.G), dim3(64), 0, s, p)); }
+    else { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_select<NCH, false>), dim3(p.G), dim3(64), 0, s, p)); }
 }
 void launch_expand_backup(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_expand_backup<NCH>, dim3(p.G), dim3(64), 0, s, p));
+    if (p.sym_key) { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_expand_backup<NCH, true>), dim3(p.G), dim3(64), 0, s, p)); }
+    else { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_expand_backup<NCH, false>), dim3(p.G), dim3(64), 0, s, p)); }
 }
 void launch_expand_select(const TreeParams& p, hipStream_t s) {
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_expand_select<NCH>, dim3((p.G + kGamesPerWG - 1) / kGamesPerWG), dim3(64 * kGamesPerWG), 0, s, p));
+    const dim3 grid((p.G + kGamesPerWG - 1) / kGamesPerWG), block(64 * kGamesPerWG);
+    if (p.sym_key) { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_expand_select<NCH, true>), grid, block, 0, s, p)); }
+    else { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_expand_select<NCH, false>), grid, block, 0, s, p)); }
 #ifdef AO_PROF
     if (getenv("AO_PROF_TREE")) {
         static int count = 0;

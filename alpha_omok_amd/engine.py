@@ -212,6 +212,26 @@ class Engine:
         if g.size:
             self._check(self._L.ao_seed_games(self._h, _ptr(g, C.c_int32), _ptr(s, C.c_uint32), int(g.size)), "ao_seed_games")
 
+    def set_leaf_symmetry(self, base_key=None, keys=None, games=None):
+        """Leaf symmetries (ao_set_leaf_symmetry): with a base key (an int) every leaf is evaluated under the symmetry
+        utils.leaf_symmetry(key_g, stones on the leaf, simulation index) -- planes in, policy back --, where key_g =
+        utils.leaf_key(base_key, seed of game g) follows the seed calls (a game never seeded: g). None switches it off: every
+        result is then what it is on an engine that never had it. keys (with games, default all) sets the keys of single games
+        directly afterwards (ao_set_leaf_symmetry_keys; needs a base key in this or an earlier call). Refused inside a move.
+        Tree snapshots do not carry the keys, and set_eval_log records rows in the network's frame."""
+        if base_key is not None or keys is None:
+            on = base_key is not None
+            self._check(self._L.ao_set_leaf_symmetry(self._h, 1 if on else 0, (int(base_key) & 0xFFFFFFFF) if on else 0),
+                        "ao_set_leaf_symmetry")
+        if keys is not None:
+            k = np.ascontiguousarray(np.asarray(keys, np.uint64) & 0xFFFFFFFF, np.uint32).reshape(-1)
+            g = np.arange(self.G, dtype=np.int32) if games is None else np.ascontiguousarray(games, np.int32).reshape(-1)
+            if g.size != k.size:
+                raise ValueError("set_leaf_symmetry: %d keys for %d games" % (k.size, g.size))
+            if g.size:
+                self._check(self._L.ao_set_leaf_symmetry_keys(self._h, _ptr(g, C.c_int32), _ptr(k, C.c_uint32), int(g.size)),
+                            "ao_set_leaf_symmetry_keys")
+
     def get_rng_state(self, game):
         mt = np.zeros(624, np.uint32)
         pos, hg, gs = C.c_int32(0), C.c_int32(0), C.c_double(0)

@@ -98,10 +98,14 @@ last_search_totals = {}      # evaluate_batched: searches, simulations asked for
 class _ZeroSide:
     """One network's side of evaluate_batched: a G-game engine + evaluator; searches the masked matches at their ids."""
 
-    def __init__(self, model, sims, board_size, inplanes, G, device, early_stop=False, tactics=None, forward_precision=None):
+    def __init__(self, model, sims, board_size, inplanes, G, device, early_stop=False, tactics=None, forward_precision=None,
+                 leaf_symmetry=None, seeds=None):
         from .engine import Engine
         from .evaluator import Evaluator
         self.eng = Engine(board_size, sims, inplanes, games=G, noise=False, device=device)
+        if leaf_symmetry is not None:
+            # the matches' streams are handed from side to side as states, not seeds: the keys are set from the matches' seeds directly
+            self.eng.set_leaf_symmetry(leaf_symmetry, keys=[utils.leaf_key(leaf_symmetry, s) for s in seeds])
         self.ev, self.model = Evaluator(device), model
         if forward_precision is not None:
             self.ev.net_precision = forward_precision    # Net.precision of this side's exported network ("fp16": the opt-in one-product forward)
@@ -166,7 +170,7 @@ def check_forward_precision(forward_precision):
 
 def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mcts_enemy=None, inplanes=5, n_match=12,
                      player_elo=1500.0, enemy_elo=1500.0, seed=0, device=0, max_plies=None, monitor_model=None,
-                     n_mcts_monitor=None, early_stop=False, tactics=None, forward_precision=None):
+                     n_mcts_monitor=None, early_stop=False, tactics=None, forward_precision=None, leaf_symmetry=None):
     """All n_match games at once (colours swapped every game, eval_main.py:213-333). `*_model`: whatever
     ZeroAgent.model accepts (a PVNet-shaped module runs on the native forward), or 'puct' / 'uct' for the rollout
     agents (eval_main.py:68-73,106-111). With a rollout PLAYER and a `monitor_model`, the monitor ZeroAgent searches
@@ -177,7 +181,10 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     tactics: Engine.search(tactics=) for the ZeroAgent sides -- True or a dict for both, or a pair (player's, enemy's) with None for
     a side that searches plainly, so that the switch's strength can be measured against the same network without it.
     forward_precision: "fp32" / "fp16" / "fp16-all" (Net.precision of the exported networks of the ZeroAgent sides) for both, or a pair (player's,
-    enemy's); None leaves the default. A side given as an engine.Net keeps the precision it was set to."""
+    enemy's); None leaves the default. A side given as an engine.Net keeps the precision it was set to.
+    leaf_symmetry: an int key -- the ZeroAgent sides evaluate every leaf under a symmetry of the board drawn per leaf
+    (Engine.set_leaf_symmetry; match i's key is utils.leaf_key(key, seed + i)) -- for both, or a pair (player's, enemy's) with None
+    for a side that searches plainly, as for tactics."""
     forward_precision = check_forward_precision(forward_precision)
     n_mcts_enemy = n_mcts_player if n_mcts_enemy is None else n_mcts_enemy
     G = n_match
@@ -187,13 +194,18 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     if len(side_tactics) != 2:
         raise ValueError("tactics: one value for both sides or a pair (player, enemy)")
 
-    def make(model, sims, tac, prec):
+    side_sym = tuple(leaf_symmetry) if isinstance(leaf_symmetry, (tuple, list)) else (leaf_symmetry, leaf_symmetry)
+    if len(side_sym) != 2:
+        raise ValueError("leaf_symmetry: one value for both sides or a pair (player, enemy)")
+    match_seeds = [(seed + i) & 0xFFFFFFFF for i in range(G)]
+
+    def make(model, sims, tac, prec, sym):
         if isinstance(model, str):
             return _RolloutSide(model, sims, board_size, G, device)
-        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac, prec)
+        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac, prec, sym, match_seeds)
 
-    sides = [make(player_model, n_mcts_player, side_tactics[0], forward_precision[0]),
-             make(enemy_model, n_mcts_enemy, side_tactics[1], forward_precision[1])]
+    sides = [make(player_model, n_mcts_player, side_tactics[0], forward_precision[0], side_sym[0]),
+             make(enemy_model, n_mcts_enemy, side_tactics[1], forward_precision[1], side_sym[1])]
     monitor = None
     if monitor_model is not None and isinstance(player_model, str):
         monitor = _ZeroSide(monitor_model, n_mcts_monitor or n_mcts_enemy, board_size, inplanes, G, device)

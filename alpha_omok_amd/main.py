@@ -109,6 +109,7 @@ playout_totals = {'full': 0, 'fast': 0}   # move decisions of either kind since 
 ROLLING = False              # configure(rolling=True): self-play runs ONE rolling search per call (Engine.roll_*): every game ends its move, plays and
 TURN_EVERY = None            # begins the next on its own clock, looked at every TURN_EVERY launches (None: engine.SETTLE_EVERY), instead of search + play per ply
 roll_sims_log = None         # a list: the rolling loop appends (global episode number, ply, simulations run, settled) per move decision (tests, tools)
+LEAF_SYMMETRY = None         # configure(leaf_symmetry=KEY): every self-play leaf is evaluated under a symmetry drawn from (KEY, the episode's seed, ply, simulation)
 FP16_GRID = False            # configure(fp16_grid_weights=True): the 3x3 conv weights of Agent.model are kept on the fp16 grid (see _grid_sync)
 _grid_masters = []           # ... [(parameter, fp32 master copy)]: Adam moves the master, the module holds its projection
 
@@ -117,7 +118,7 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
               model=None, gpu=None, noise=True, device_replay=False, node_cap=None, strict=None, reproducible=False,
               carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None,
               early_stop=False, fast_sims=None, full_prob=0.25, tactics=None, forward_precision="fp32", rolling=False,
-              turn_every=None):
+              turn_every=None, leaf_symmetry=None):
     """Build `Agent`, `Agent.model` and `optimizer` (main.py:58-85). Call instead of editing constants.
     node_cap: expanded-node capacity of a game's tree arena (0 = 16*(n_mcts+1) where 40 % of the HBM
     holds that for all games, at least 4*(n_mcts+1); -1 = grow into the free HBM);
@@ -169,7 +170,14 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     end their move, play and begin the next one, finished slots are refilled and join the running loop. Every game's search is the
     same strictly sequential one, so with reproducible=True an episode is bit for bit the episode of rolling=False. Combines with
     early_stop, fast_sims / full_prob, oversubscribe, carry_over, overlap_train, fp16_grid_weights, forward_precision and
-    reproducible; not with tactics= (the rolling search has no root bar), and it needs a model with a native form."""
+    reproducible; not with tactics= (the rolling search has no root bar), and it needs a model with a native form.
+    leaf_symmetry=KEY (an int; None: off): every leaf of every self-play search -- and of Agent's own get_pi -- goes through the
+    network under one of the eight symmetries of the board, drawn as utils.leaf_symmetry(utils.leaf_key(KEY, the episode's seed),
+    stones on the leaf, simulation index) (Engine.set_leaf_symmetry): the planes are transformed on their way into the batch and the
+    policy on its way back, so no forward is added. An episode's symmetries follow its seed, in any slot: it composes with rolling,
+    early_stop, fast_sims, oversubscribe, carry_over, tactics, every forward_precision and reproducible. The samples are recorded in
+    the board's own frame, as before."""
+    global LEAF_SYMMETRY
     global BOARD_SIZE, N_MCTS, N_BLOCKS, IN_PLANES, OUT_PLANES, SEED, Agent, optimizer, device
     global _engine, _evaluator, _episodes_played, rep_memory, STRICT, NODE_CAP, CARRY_OVER, _pool, OVERSUBSCRIBE, ROWS, _terminal_share
     global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS, ROLLING, TURN_EVERY
@@ -194,6 +202,7 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     if not 0.0 <= float(full_prob) <= 1.0:
         raise ValueError("full_prob must be in [0, 1]")
     EARLY_STOP = bool(early_stop)
+    LEAF_SYMMETRY = None if leaf_symmetry is None else int(leaf_symmetry) & 0xFFFFFFFF
     ROLLING = bool(rolling)
     TURN_EVERY = None if turn_every is None else int(turn_every)
     TACTICS = tactics if tactics else None
@@ -244,7 +253,7 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     np.random.seed(SEED)
     torch.manual_seed(SEED)
     agents.PRINT_MCTS = PRINT_SELFPLAY
-    Agent = agents.ZeroAgent(BOARD_SIZE, N_MCTS, IN_PLANES, noise=noise, device=gpu)
+    Agent = agents.ZeroAgent(BOARD_SIZE, N_MCTS, IN_PLANES, noise=noise, device=gpu, leaf_symmetry=LEAF_SYMMETRY)
     Agent.model = model if model is not None else PVNet(N_BLOCKS, IN_PLANES, OUT_PLANES, BOARD_SIZE).to(device)
     if hasattr(Agent.model, "parameters"):
         parallel.broadcast_parameters(Agent.model)
@@ -312,6 +321,8 @@ def _get_engine(games):
         frac = 0.5 if (NODE_CAP == 0 and games > MAX_CONCURRENT) else 0.0
         _engine = Engine(BOARD_SIZE, N_MCTS, IN_PLANES, games=games, noise=Agent.noise, device=Agent._device, node_cap=NODE_CAP,
                          arena_fraction=frac)
+        if LEAF_SYMMETRY is not None:
+            _engine.set_leaf_symmetry(LEAF_SYMMETRY)   # (the keys follow the seed calls: ao_set_leaf_symmetry)
     return _engine
 
 
@@ -1397,10 +1408,12 @@ if __name__ == '__main__':
     fwd.add_argument('--fp16-forward', action='store_true', help='searches run the opt-in plain-fp16 forward: one MFMA product per multiply-add (configure(forward_precision="fp16"))')
     ap.add_argument('--rolling', action='store_true', help='self-play as one rolling search per call: every game moves on its own clock (configure(rolling=True))')
     ap.add_argument('--turn-every', type=int, default=None, metavar='N', help='with --rolling: launches between two turns (default: engine.SETTLE_EVERY)')
+    ap.add_argument('--leaf-symmetry', type=int, nargs='?', const=0, default=None, metavar='KEY', help='evaluate every leaf under a symmetry of the board drawn per leaf (configure(leaf_symmetry=KEY)); KEY defaults to 0')
     a = ap.parse_args()
     parallel.init_from_env()
     GAMES_PER_ITER, TRAIN_STEPS = a.games_per_iter, a.train_steps
     configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, device_replay=a.device_replay, oversubscribe=a.oversubscribe,
               overlap_train=a.overlap_train, fp16_grid_weights=a.fp16_grid_weights,
-              forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32", rolling=a.rolling, turn_every=a.turn_every)
+              forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32", rolling=a.rolling, turn_every=a.turn_every,
+              leaf_symmetry=a.leaf_symmetry)
     run(a.iters, a.model, a.dataset, a.selfplay)

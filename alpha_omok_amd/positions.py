@@ -214,11 +214,15 @@ class PositionBatch:
                              "(or an engine.Net)" % (self.board_size, self.board_size, self.inplanes))
         return net
 
-    def evaluate(self, model, root_ids, leading_zero=True):
+    def evaluate(self, model, root_ids, leading_zero=True, symmetries=1):
         """ZeroAgent.get_pv for every id in one call: (policy float32 [n, A] -- the softmax over all cells, nothing masked --,
         value float32 [n], status int32 [n], err int32 [n]). Terminal positions are evaluated too (status says which they
         are); ids with err != 0 get zeros. `model`: a module in the PVNet wire format (exported to the native forward as
-        ZeroAgent does, re-exported when its parameters change) or an engine.Net."""
+        ZeroAgent does, re-exported when its parameters change) or an engine.Net. symmetries=8: the mean over the eight
+        symmetries of the board, each policy brought back into the board's own frame (ao_positions_evaluate_sym: one forward
+        over eight rows per position, fp32 sum in the order s = 0..7, times 1/8; capacity >= 8); 1: the position as it stands."""
+        if symmetries not in (1, 8):
+            raise ValueError("symmetries must be 1 or 8")
         moves, n = pack_ids(root_ids, leading_zero)
         net = self._native(model)
         cnt = n.shape[0]
@@ -226,10 +230,16 @@ class PositionBatch:
         val = np.zeros(cnt, np.float32)
         status = np.zeros(cnt, np.int32)
         err = np.zeros(cnt, np.int32)
-        self._check(self._L.ao_positions_evaluate(
-            self._handle(), net._h, _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt,
-            _ptr(pol, C.c_float), _ptr(val, C.c_float), _ptr(status, C.c_int32), _ptr(err, C.c_int32)),
-            "ao_positions_evaluate")
+        if symmetries == 1:
+            self._check(self._L.ao_positions_evaluate(
+                self._handle(), net._h, _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt,
+                _ptr(pol, C.c_float), _ptr(val, C.c_float), _ptr(status, C.c_int32), _ptr(err, C.c_int32)),
+                "ao_positions_evaluate")
+        else:
+            self._check(self._L.ao_positions_evaluate_sym(
+                self._handle(), net._h, _ptr(moves, C.c_int32), moves.shape[1], _ptr(n, C.c_int32), cnt, int(symmetries),
+                _ptr(pol, C.c_float), _ptr(val, C.c_float), _ptr(status, C.c_int32), _ptr(err, C.c_int32)),
+                "ao_positions_evaluate_sym")
         return pol, val, status, err
 
     # -- tactics: defined through utils.check_win alone (utils.win_cells / utils.audit_moves are the host definition)

@@ -718,3 +718,75 @@ def augment_dataset(memory, board_size):
             out.append((s_r.copy(), p_r.reshape(-1).copy(), z))
             out.append((s_r[:, :, ::-1].copy(), p_r[:, ::-1].reshape(-1).copy(), z))
     return out
+
+
+# ---- the eight symmetries of the board as index maps (csrc/symmetry.hpp holds the same functions; the two agree bit for bit) ----
+def sym_cell(s, c, board_size):
+    """Source cell of output cell c under symmetry s = 2*r + f (rot90 by r, then a flip of the last axis if f; the order of
+    augment_dataset): sym_planes(X, s)[..., c] = X[..., sym_cell(s, c)]. c may be an array."""
+    B = board_size
+    c = np.asarray(c)
+    i, j = c // B, c % B
+    jj = B - 1 - j if s & 1 else j
+    r = s >> 1
+    if r == 0:
+        si, sj = i, jj
+    elif r == 1:
+        si, sj = jj, B - 1 - i
+    elif r == 2:
+        si, sj = B - 1 - i, B - 1 - jj
+    else:
+        si, sj = B - 1 - jj, i
+    out = si * B + sj
+    return int(out) if out.ndim == 0 else out
+
+
+def sym_inverse(s):
+    """The symmetry that undoes s: the opposite rotation; a rotation followed by a flip is a reflection and undoes itself."""
+    return s if s & 1 else (8 - s) & 7
+
+
+def sym_cell_inv(s, d, board_size):
+    """Where source cell d goes under s: the c with sym_cell(s, c) == d."""
+    return sym_cell(sym_inverse(s), d, board_size)
+
+
+def sym_planes(x, s, board_size=None):
+    """x under symmetry s, same shape: the s-th state augment_dataset makes of x. x is [..., B, B], or flat [..., A] when
+    board_size is given and the last two axes are not (B, B)."""
+    x = np.asarray(x)
+    B = x.shape[-1] if board_size is None else board_size
+    A = B * B
+    grid = x.ndim >= 2 and x.shape[-2:] == (B, B)
+    flat = x.reshape(x.shape[:-2] + (A,)) if grid else x
+    return flat[..., sym_cell(s, np.arange(A), B)].reshape(x.shape)
+
+
+def sym_policy_back(p, s, board_size=None):
+    """The policy in the board's own frame, given the network's answer p [..., A] on sym_planes(X, s):
+    out[sym_cell(s, c)] = p[c]."""
+    p = np.asarray(p)
+    A = p.shape[-1]
+    if board_size is None:
+        board_size = int(round(np.sqrt(A)))
+    out = np.empty_like(p)
+    out[..., sym_cell(s, np.arange(A), board_size)] = p
+    return out
+
+
+def leaf_symmetry(key, ply, sim):
+    """The symmetry (0..7) under which the leaf with `ply` stones is evaluated in simulation `sim` (0-based inside the move) of
+    the game with key `key`; arithmetic mod 2^32. Stateless: host, oracle and device compute it independently."""
+    M = 0xFFFFFFFF
+    x = (int(key) ^ (int(ply) * 0x9E3779B1) ^ (int(sim) * 0x85EBCA77)) & M
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & M
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & M
+    x ^= x >> 16
+    return x >> 29
+
+
+def leaf_key(base, seed):
+    """The key of a game from the caller's base key and the game's seed (Engine.set_leaf_symmetry)."""
+    return (int(base) ^ (int(seed) * 0xC2B2AE35)) & 0xFFFFFFFF

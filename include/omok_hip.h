@@ -78,6 +78,31 @@ int ao_get_rng_state(ao_engine *e, int game, uint32_t *host_mt /*[624]*/, int32_
 int ao_set_rng_state(ao_engine *e, int game, const uint32_t *host_mt, int32_t pos,
                      int32_t has_gauss, double gauss);
 
+/* ---- leaf symmetries ---- (opt-in; off, every result is bit for bit what it is without these calls)
+ * With the switch on, every leaf goes through the network under one of the eight symmetries of the square, drawn per leaf
+ * as AlphaGo Zero does: the planes are written into the evaluation batch as sym_planes(planes, s) and the policy row comes
+ * back through the same map (sym_policy_back), the value as it is. Symmetry s = 2*r + f is rot90 by r, then a flip if f --
+ * the numbering of utils.augment_dataset and of the replay ring; s = 0 is the identity. s is a stateless function
+ *   s = leaf_symmetry(key_g, ply, sim)       (csrc/symmetry.hpp; alpha_omok_amd/utils.py has the same function)
+ * of the game's key, the number of stones on the leaf's board and the game's 0-based simulation index inside the current
+ * move. Nothing else changes: not the games' MT19937 streams, not the noise, not the selection; a terminal leaf uses up a
+ * simulation index and is not evaluated, as before. It holds for every forward mode, precision and batch plan, for the
+ * step-wise protocol (ao_collect_leaves hands out the planes already transformed; ao_apply_evals takes the network's rows
+ * as they are) and for the rolling search.
+ *   key_g = leaf_key(base_key, seed_g) = base_key ^ (seed_g * 0xC2B2AE35), seed_g the seed most recently given to game g by
+ * ao_seed / ao_seed_all / ao_seed_games (never seeded: g). The engine remembers the seeds: an episode's symmetries are a
+ * function of its seed and the base key alone, in any slot, under carry-over and under rolling refills. enable == 0
+ * switches off (base_key is ignored). ao_set_leaf_symmetry_keys sets the keys of the n listed games directly, for callers
+ * that hand streams around with ao_set_rng_state; it needs the switch on, and a later seed call or ao_set_leaf_symmetry
+ * replaces what it set.
+ * Both fail inside a move (between ao_begin_move and ao_end_move) and, while a roll is open, for a game that is in a move
+ * of the roll -- where ao_seed_games fails (ao_set_leaf_symmetry touches every game).
+ * What does NOT carry the keys: tree snapshots (ao_tree_export) -- to resume bit for bit the importer sets the same base
+ * key and seeds; ao_get_rng_state. ao_set_eval_log records the evaluation batch's rows as they are, in the NETWORK's frame:
+ * a replay brings the policy back with the leaf's symmetry. */
+int ao_set_leaf_symmetry(ao_engine *e, int enable, uint32_t base_key);
+int ao_set_leaf_symmetry_keys(ao_engine *e, const int32_t *host_games, const uint32_t *host_keys, int32_t n);
+
 /* ---- game / tree state ---- */
 /* ZeroAgent.reset() (agents.py:55-58) for the games with mask[g] != 0 (NULL = all): clears the
  * tree and the move list (root id becomes (0,)). */
@@ -703,6 +728,15 @@ int  ao_positions_from_moves(ao_positions *p, const int32_t *host_moves, int32_t
 int  ao_positions_evaluate(ao_positions *p, ao_net *net, const int32_t *host_moves, int32_t stride, const int32_t *host_n,
                            int32_t n, float *host_policy /*[n][A]*/, float *host_value /*[n]*/,
                            int32_t *host_status, int32_t *host_err);
+/* ao_positions_evaluate with the 8-fold symmetry ensemble. nsym is 1 or 8; nsym 1 returns the bits of
+ * ao_positions_evaluate. nsym 8: row 8 i + s of the forward's batch is sym_planes(planes of position i, s) (numbering as
+ * for ao_set_leaf_symmetry), ONE forward runs over the eight rows of every position of a chunk -- a chunk holds
+ * capacity / 8 positions, so capacity must be at least 8 -- and a kernel brings each policy row back into the board's own
+ * frame and takes the mean in fp32, in this order: policy[i][c] = 0.125f * (((p_0 + p_1) + p_2) + ... + p_7), p_s the
+ * value of row 8 i + s at the cell c went to under s; host_value likewise. Everything else as ao_positions_evaluate. */
+int  ao_positions_evaluate_sym(ao_positions *p, ao_net *net, const int32_t *host_moves, int32_t stride, const int32_t *host_n,
+                               int32_t n, int32_t nsym, float *host_policy /*[n][A]*/, float *host_value /*[n]*/,
+                               int32_t *host_status, int32_t *host_err);
 /* The cells that win at once. No reference counterpart: the definition is utils.check_win (utils.py:30-59) and nothing
  * else. P is the position of id i (moves as for ao_positions_from_moves), k its side to move (black on even plies). A
  * cell c is a WINNING CELL of colour j in P if check_win(P) == 0, c is empty, and check_win of P's board with a stone of
