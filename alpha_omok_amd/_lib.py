@@ -188,6 +188,9 @@ SYMBOLS = {
                                            _P(C.c_int16), _i32p, _i32p, _i32p, _i32p, _i32p]),
     "ao_positions_forced_defences": (C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _u8p, _u8p,
                                                _u8p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "ao_guard_check": (C.c_int, [_i32p, _i32p, C.c_char_p, C.c_int]),
+    "ao_guard_block": (C.c_int, [C.c_int32, _P(_vp), _i64p, _i64p]),
+    "ao_guard_mode": (C.c_int, [_i64p, _i32p]),
 }
 
 _lib = None

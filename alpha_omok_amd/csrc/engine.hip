@@ -299,6 +299,13 @@ extern "C" {
 
 const char* ao_version(void) { return "alpha_omok_amd 0.1 (gfx950)"; }
 int ao_abi_version(void) { return AO_ABI_VERSION; }
+int ao_guard_check(int32_t* blocks, int32_t* damaged, char* msg, int cap) { return ao::guard_check(blocks, damaged, msg, cap); }
+int ao_guard_block(int32_t index, void** ptr, int64_t* bytes, int64_t* guard) { return ao::guard_block(index, ptr, bytes, guard); }
+int ao_guard_mode(int64_t* guard, int32_t* fill) {
+    if (guard) *guard = static_cast<int64_t>(ao::guard::guard_bytes(getenv("AO_POOL_GUARD")));
+    if (fill) *fill = ao::guard::fill_byte(getenv("AO_POOL_FILL"));
+    return 0;
+}
 
 const char* ao_last_error(const ao_engine* e) { return e ? e->err.c_str() : ao::create_error<ao_engine>().c_str(); }
 void* ao_stream(ao_engine* e) { return e ? e->stream : nullptr; }
@@ -413,9 +420,8 @@ static int create_impl(ao_engine* e, const ao_config* cfg) {
     for (;;) {
         const size_t slots = static_cast<size_t>(2) * G * p.cap;
         void* arena = nullptr;
-        const hipError_t st = hipMalloc(&arena, std::max<size_t>(slots * p.rec, 16));
+        const hipError_t st = e->pool.alloc_bytes(&arena, slots * p.rec);
         if (st == hipSuccess) {
-            e->pool.adopt(arena);
             p.arena = static_cast<unsigned char*>(arena);
             break;
         }

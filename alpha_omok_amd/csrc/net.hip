@@ -114,9 +114,8 @@ static int param_alloc(ao_net* n, T** out, size_t count) {
         return 0;
     }
     void* p = nullptr;
-    hipError_t st = hipMalloc(&p, bytes);
+    hipError_t st = n->pool.alloc_bytes(&p, count * sizeof(T));
     if (st != hipSuccess) return n->fail(std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(st));
-    n->pool.adopt(p);
     if (n->pcursor < n->pallocs.size()) {
         n->pool.release(n->pallocs[n->pcursor].first);
         n->pallocs[n->pcursor] = {p, bytes};

@@ -42,6 +42,38 @@ def plan_kernel(n_block, inplanes, planes, board_size, boards, in_kind=2, trunk_
     return buf.value.decode(), f.value
 
 
+def guard_check():
+    """(guarded device blocks alive, damaged blocks, message) -- ao_guard_check. Blocks are guarded when their handle was created
+    under AO_POOL_GUARD=<bytes> (with AO_POOL_FILL=<0..255> written to the guards and the body); a damaged block has a guard byte
+    that is no longer the fill: something wrote outside the block. Waits for the devices that have guarded blocks. Blocks whose
+    damage was found when they were freed are counted too; every damaged block is reported once. The message has one line
+    per block (the first few), as include/omok_hip.h words it."""
+    L = _lib.load()
+    blocks, damaged = C.c_int32(0), C.c_int32(0)
+    buf = C.create_string_buffer(4096)
+    if L.ao_guard_check(C.byref(blocks), C.byref(damaged), buf, 4096):
+        raise EngineError("ao_guard_check: " + buf.value.decode())
+    return blocks.value, damaged.value, buf.value.decode()
+
+
+def guard_block(index):
+    """(device pointer of the body, bytes, guard bytes) of the index-th live guarded block in allocation order, or None past
+    the end (ao_guard_block)."""
+    L = _lib.load()
+    p, n, g = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+    if L.ao_guard_block(int(index), C.byref(p), C.byref(n), C.byref(g)):
+        return None
+    return p.value or 0, n.value, g.value
+
+
+def guard_mode():
+    """(guard bytes an allocation made now would get: AO_POOL_GUARD rounded up to 4096, 0 = off; the fill byte) -- ao_guard_mode."""
+    L = _lib.load()
+    g, f = C.c_int64(0), C.c_int32(0)
+    L.ao_guard_mode(C.byref(g), C.byref(f))
+    return g.value, f.value
+
+
 class Net:
     """model.PVNet(n_block, inplanes, planes, board_size) in eval() mode, on the MI355X."""
 

@@ -829,6 +829,30 @@ int  ao_positions_forced_defences(ao_positions *p, const int32_t *host_moves, in
                                   uint8_t *host_threat_moves, uint8_t *host_reply, uint8_t *host_depth, int32_t *host_counts,
                                   int32_t *host_nodes, int32_t *host_status, int32_t *host_turn, int32_t *host_err);
 
+/* ---- guarded device allocations (a test mode of the host code; off by default) -------------------------------------------
+ * Two environment variables, read at every device allocation of every handle (ao_engine, ao_net, ao_replay, ao_rollout,
+ * ao_ttt, ao_positions):
+ *   AO_POOL_GUARD=<bytes>  unset or 0: plain hipMalloc, as ever. Otherwise the value is rounded up to a multiple of 4096 and
+ *                          every block gets that many guard bytes in front and behind.
+ *   AO_POOL_FILL=<0..255>  default 255: the byte written to both guards and to the whole body of a guarded block, before the
+ *                          owner sees it (hipMemset, hipDeviceSynchronize).
+ * The mode costs allocation-time and free-time work only; no kernel and no launch differs. A guard byte that differs from the
+ * fill is a stray write; outputs that differ between two fills, or from the plain mode, are stale or stray reads.
+ *
+ * ao_guard_check waits for every device that has guarded blocks (the current device is the same afterwards), reads all guards
+ * back and reports in *blocks how many guarded blocks are alive and in *damaged how many are damaged -- including those whose
+ * damage was found when they were freed, which are kept until this call reports them. msg (cap bytes, always terminated)
+ * describes the first few, one per line:
+ *   block #<allocation ordinal> (<bytes> B, device <d>): <n> damaged byte(s), first at start-<k>|end+<k>, found 0x.. (fill 0x..)
+ * start-k is k bytes before the block's first byte, end+k is k bytes after the first byte behind it (end+0). Reported guards are
+ * filled again: the next call reports only new damage. Returns non-zero on a HIP error (its text in msg).
+ * ao_guard_block names the index-th live guarded block in allocation order (pointer to the body, its bytes, its guard
+ * bytes); non-zero past the end. ao_guard_mode reports what an allocation made now would use: the guard bytes after rounding
+ * (0: mode off) and the fill byte. Any output may be NULL. */
+int  ao_guard_check(int32_t *blocks, int32_t *damaged, char *msg, int cap);
+int  ao_guard_block(int32_t index, void **ptr, int64_t *bytes, int64_t *guard);
+int  ao_guard_mode(int64_t *guard, int32_t *fill);
+
 #ifdef __cplusplus
 }
 #endif
