@@ -103,6 +103,9 @@ SYMBOLS = {
     "ao_roll_drain": (C.c_int, [_vp]),
     "ao_roll_end": (C.c_int, [_vp]),
     "ao_roll_stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "ao_roll_set_tactics": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ao_roll_tactics_records": (C.c_int, [_vp, _i32p, _i32p, _i32p, _i32p, _u8p]),
+    "ao_roll_tactics_stats": (C.c_int, [_vp, _i64p]),
     "ao_set_root_bar": (C.c_int, [_vp, _u8p]),
     "ao_root_tactics": (C.c_int, [_vp, _u8p, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _u8p, _i32p, _i32p]),
     "ao_collect_leaves": (C.c_int, [_vp, _vp]),

@@ -81,13 +81,44 @@ struct LaunchLoop {
 
 // The rolling search (ao_roll_*, at the end of this file): what lives from ao_roll_begin to ao_roll_end. The rules are
 // roll_schedule.hpp's, the kernels roll.hip's.
+// The forced-win solver beside the loop (ao_roll_set_tactics). A BATCH is the solver's run on the roots of the games that were
+// to begin a move at one turn (or begin / join): queued on `stream`, which touches nothing but the batch's own buffer, between two
+// events. Its games wait (ROLL_WAITING) until a later turn finds the second event reached; then they begin their move on the
+// engine's stream with the batch's bar rows and verdicts (k_roll_verdict in front of k_roll_begin).
+struct RollBatch {
+    bool busy = false;
+    int n = 0, age = 0;                   // games; turns since it was started
+    hipEvent_t ready = nullptr, done = nullptr;   // engine stream: the position rows are written; solver stream: the verdicts are
+    std::vector<int32_t> games;           // [n]
+    std::vector<uint8_t> bonus;           // [n] the root was fresh when the game was listed
+    std::vector<uint32_t> mt; std::vector<int32_t> pos;   // [n][624], [n] the games' streams as gathered when they were listed
+    ao::DevBuf<unsigned char> buf{nullptr};   // position rows, won / stage / pair words, verdict words, bar rows, allowed rows: O(n A)
+    ao::RollBatchView view{};
+};
+struct RollTactics {
+    int max_depth = 0, max_nodes = 0, solved_sims = 0;   // ao_roll_set_tactics; max_depth == 0: disarmed
+    bool want_allowed = false;
+    bool on = false;                      // the open roll runs with the solver
+    int hold = 0;                         // AO_ROLL_TACTICS_HOLD, read at ao_roll_begin
+    hipStream_t stream = nullptr;
+    RollBatch slot[ao::kRollBatchSlots];
+    std::vector<int> pending;             // busy slots, oldest first
+    int n_waiting = 0;
+    int32_t* d_words = nullptr; uint8_t* d_allowed = nullptr;      // [G][4], [G][A]: what the solver said at the root of each game's current move
+    int32_t* d_out_words = nullptr; uint8_t* d_out_allowed = nullptr;   // compact rows of a turn's records
+    int32_t* h_words = nullptr; uint8_t* h_allowed = nullptr;      // pinned, [G][4], [G][A]
+    std::vector<int32_t> rec_words; std::vector<uint8_t> rec_allowed; int rec_count = 0;   // of the last ao_roll_run
+    int64_t stats[6] = {0, 0, 0, 0, 0, 0};   // ao_roll_tactics_stats
+};
+
 struct RollState {
     bool open = false, draining = false;
+    RollTactics tac;
     ao_net* net = nullptr;
     bool early = false, want_visit = false, want_policy = false;
     ao::RollCadence cad;
     bool look_pending = false;            // a look's counters have not been read yet
-    std::vector<uint8_t> in_move;         // [G]
+    std::vector<uint8_t> in_move;         // [G] ao::RollGame: out of a move, searching, or waiting for the solver's verdict
     int n_in_move = 0;
     std::vector<int32_t> tau_plies;       // [G], empty: tau 1 always
     std::vector<int32_t> sims; int sims_stride = 0;      // [G][stride] budgets by ply, empty: ao_config.sims
@@ -326,6 +357,17 @@ void ao_destroy(ao_engine* e) {
     if (!e) return;
     hipSetDevice(e->cfg.device);
     if (e->stream) hipStreamSynchronize(e->stream);
+    RollTactics& t = e->roll.tac;
+    if (t.stream) {   // (before any buffer goes: a batch may still be running)
+        hipStreamSynchronize(t.stream);
+        for (RollBatch& b : t.slot) {
+            if (b.ready) hipEventDestroy(b.ready);
+            if (b.done) hipEventDestroy(b.done);
+        }
+        hipStreamDestroy(t.stream);
+    }
+    if (t.h_words) hipHostFree(t.h_words);
+    if (t.h_allowed) hipHostFree(t.h_allowed);
     e->pool.free_all();
     if (e->h_mt) hipHostFree(e->h_mt);
     if (e->h_pos) hipHostFree(e->h_pos);
@@ -2000,6 +2042,14 @@ static void roll_count(ao_engine* e, size_t bytes) { e->roll.bytes += static_cas
 // every way out of a roll, the failures included: no game is in a move and the engine is between moves
 static void roll_close(ao_engine* e) {
     RollState& r = e->roll;
+    if (r.tac.on) {   // the solver's stream first: no batch runs on when the buffers are reused; roots may hold the sentinels of a bar
+        (void)hipStreamSynchronize(r.tac.stream);
+        for (RollBatch& b : r.tac.slot) b.busy = false;
+        r.tac.pending.clear();
+        r.tac.n_waiting = 0;
+        r.tac.on = false;
+        e->bar_dirty = true;
+    }
     r.open = false;
     r.draining = false;
     std::fill(r.in_move.begin(), r.in_move.end(), 0);
@@ -2053,7 +2103,9 @@ static int roll_take_tables(ao_engine* e, const ao_roll_opts* o, const std::vect
 // Begins the next move of the listed games (not in a move, not over). rows: where game games[k]'s stream lies in the compact
 // staging rows (h_mt / h_pos, gathered by the turn that just played it), or null: the streams are gathered here. The Dirichlet
 // draw of the games that search with noise is the host's (host_rng.hpp), on the pool; everything travels in compact rows.
-static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, const int32_t* rows) {
+// batches (with the solver beside the loop): the games are those of the listed finished batches, in order, and were waiting;
+// k_roll_verdict takes each batch's bar rows and verdicts to its games in front of k_roll_begin.
+static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, const int32_t* rows, const std::vector<int>* batches = nullptr) {
     RollState& r = e->roll;
     const int n = static_cast<int>(games.size()), G = e->G, Ap = e->Ap;
     if (n == 0) return 0;
@@ -2090,6 +2142,7 @@ static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, con
         int32_t* it = h_items + static_cast<size_t>(k) * ao::kRollItem;
         it[0] = g; it[1] = mv[k].target; it[2] = mv[k].gflags; it[3] = mv[k].tau;
         it[4] = (r.early && mv[k].tau == 0) ? 1 : 0;
+        if (batches && mv[k].target != mv[k].budget) it[4] |= 2;   // (k_roll_verdict caps the budget, not the root's own expansion)
         it[5] = mv[k].draw ? row : -1;
         if (mv[k].draw) {
             nrows = std::max(nrows, row + 1);
@@ -2105,6 +2158,16 @@ static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, con
     }
     AO_HIP(e, hipMemcpyAsync(r.d_items, h_items, sizeof(int32_t) * ao::kRollItem * n, hipMemcpyHostToDevice, e->stream));
     roll_count(e, sizeof(int32_t) * ao::kRollItem * n);
+    if (batches) {
+        RollTactics& t = r.tac;
+        size_t at = 0;
+        for (int i : *batches) {
+            RollBatch& b = t.slot[i];
+            AO_HIP(e, hipStreamWaitEvent(e->stream, b.done, 0));   // (reached already: the host saw it, or waited for it)
+            ao::launch_roll_verdict(r.d_items + at * ao::kRollItem, b.view, e->A, t.solved_sims, e->d_bar, t.d_words, t.d_allowed, e->stream);
+            at += static_cast<size_t>(b.n);
+        }
+    }
     ao::launch_roll_begin(r.loop.p, r.d_items, n, e->d_mt_backup, e->d_pos_backup, r.d_noise, e->d_tau, e->d_active, e->d_settled, e->d_early, e->stream);
     AO_HIP(e, hipGetLastError());
     e->settled_dirty = true;
@@ -2112,8 +2175,171 @@ static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, con
         const int g = games[k];
         e->bonus[g] = mv[k].target - mv[k].budget;
         e->active[g] = 1;
-        r.in_move[g] = 1;
-        ++r.n_in_move;
+        if (r.in_move[g] == ao::ROLL_OUT) ++r.n_in_move;   // (a game that waited for its verdict has been in a move since it was listed)
+        r.in_move[g] = ao::ROLL_SEARCHING;
+    }
+    return 0;
+}
+
+// ---- the solver beside the loop ----
+// the batch's buffer for n games, carved up: the solver's RootTacticsBufs, the position rows, the games; *view: what k_roll_verdict reads
+static int roll_batch_layout(ao_engine* e, RollBatch& b, int n, ao::RootTacticsBufs* bufs, ao::Pos** rows) {
+    RollTactics& t = e->roll.tac;
+    const size_t N = static_cast<size_t>(n), A = static_cast<size_t>(e->A);
+    auto up = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
+    const size_t at_pos = 0, at_won = up(at_pos + N * sizeof(ao::Pos)), at_bar = up(at_won + N * ao::kBBWords * 8), at_stage = up(at_bar + N * ao::kBBWords * 8),
+                 at_pair = up(at_stage + N * 8), at_words = up(at_pair + N * A * 4), at_allowed = up(at_words + N * 16),
+                 bytes = at_allowed + (t.want_allowed ? N * A : 0);
+    if (!b.buf.p || bytes > b.buf.n) {   // (grows: the slot's last batch was read by kernels queued on the engine's stream)
+        AO_HIP(e, hipStreamSynchronize(e->stream));
+        b.buf.pool = &e->pool;
+        if (b.buf.reserve(e, bytes)) return 1;
+    }
+    unsigned char* p = b.buf.p;
+    *rows = reinterpret_cast<ao::Pos*>(p + at_pos);
+    *bufs = ao::RootTacticsBufs{};
+    bufs->won = reinterpret_cast<uint64_t*>(p + at_won);
+    bufs->bar = reinterpret_cast<uint64_t*>(p + at_bar);
+    bufs->stage = reinterpret_cast<uint32_t*>(p + at_stage);
+    bufs->pair = reinterpret_cast<uint32_t*>(p + at_pair);
+    bufs->verdict = reinterpret_cast<int32_t*>(p + at_words);
+    bufs->depth = bufs->verdict + N; bufs->nodes = bufs->depth + N; bufs->unknown = bufs->nodes + N;
+    bufs->allowed = t.want_allowed ? p + at_allowed : nullptr;
+    b.view = ao::RollBatchView{bufs->bar, bufs->verdict, bufs->allowed, n};
+    return 0;
+}
+
+// Starts a batch for the listed games in a free slot: their root positions into the batch's rows on the engine's stream, the
+// three solver launches behind an event on the solver's. streams: the games' MT19937 states and positions ([n][624], [n]) as the
+// host holds them now -- the Dirichlet draw of the move comes from them when the batch's games begin.
+static int roll_batch_start(ao_engine* e, const std::vector<int32_t>& games, std::vector<uint32_t>&& mt, std::vector<int32_t>&& pos) {
+    RollState& r = e->roll;
+    RollTactics& t = r.tac;
+    const int n = static_cast<int>(games.size());
+    int i = 0;
+    while (i < ao::kRollBatchSlots && t.slot[i].busy) ++i;
+    if (i == ao::kRollBatchSlots) return e->fail("ao_roll: no free solver batch slot");   // (roll_must_block keeps one free)
+    RollBatch& b = t.slot[i];
+    ao::RootTacticsBufs bufs;
+    ao::Pos* rows = nullptr;
+    if (roll_batch_layout(e, b, n, &bufs, &rows)) return 1;
+    if (!b.ready) {
+        AO_HIP(e, hipEventCreateWithFlags(&b.ready, hipEventDisableTiming));
+        AO_HIP(e, hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
+    }
+    b.games = games;
+    b.mt = std::move(mt);
+    b.pos = std::move(pos);
+    b.n = n;
+    b.age = 0;
+    // (d_games is free: whatever listed these games -- a turn, a begin, a join -- has synchronised behind its last use)
+    AO_HIP(e, hipMemcpyAsync(r.d_games, b.games.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
+    ao::launch_roll_rootpos(e->tp, r.d_games, n, rows, e->stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipEventRecord(b.ready, e->stream));
+    AO_HIP(e, hipStreamWaitEvent(t.stream, b.ready, 0));
+    AO_HIP(e, hipMemsetAsync(bufs.bar, 0, sizeof(uint64_t) * ao::kBBWords * n, t.stream));   // (no caller's bar under rolling)
+    ao::launch_root_tactics_rows(rows, n, e->tp.B, e->A, e->tp.win_mark, t.max_depth, t.max_nodes, bufs, t.stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipEventRecord(b.done, t.stream));
+    b.busy = true;
+    t.pending.push_back(i);
+    for (int g : games) {
+        if (r.in_move[g] == ao::ROLL_OUT) ++r.n_in_move;
+        r.in_move[g] = ao::ROLL_WAITING;
+    }
+    t.n_waiting += n;
+    t.stats[0] += 1;
+    t.stats[5] += static_cast<int64_t>(sizeof(int32_t)) * n;
+    roll_count(e, sizeof(int32_t) * n);
+    return 0;
+}
+
+// The games of the taken batches begin their move, in one k_roll_begin: their streams go back into the staging rows first.
+static int roll_batches_begin(ao_engine* e, const std::vector<int>& taken) {
+    RollTactics& t = e->roll.tac;
+    if (taken.empty()) return 0;
+    std::vector<int32_t> games, rows;
+    for (int i : taken) {
+        RollBatch& b = t.slot[i];
+        for (int k = 0; k < b.n; ++k) {
+            const size_t row = games.size();
+            if (!b.mt.empty()) {
+                std::memcpy(e->h_mt + row * 624, b.mt.data() + static_cast<size_t>(k) * 624, sizeof(uint32_t) * 624);
+                e->h_pos[row] = b.pos[k];
+            }
+            games.push_back(b.games[k]);
+            rows.push_back(static_cast<int32_t>(row));
+        }
+    }
+    const int rc = roll_begin_games(e, games, rows.data(), &taken);
+    for (int i : taken) {
+        t.slot[i].busy = false;
+        t.n_waiting -= t.slot[i].n;
+        t.stats[1] += t.slot[i].n;
+    }
+    return rc;
+}
+
+// What a turn (at_turn), a begin or a join does about the solver once it knows which games are to begin a move (`next`; rows:
+// where their streams lie in the staging rows, or null: they are gathered here). The order matters: the streams of `next` leave
+// the staging rows first; the batches whose verdicts are in begin their games (which uses the staging rows, and reads the
+// batches' buffers on the engine's stream); only then does the new batch take a slot. The engine's stream has been synchronised
+// by the caller. The host waits for nothing but the oldest batch's recorded event, and only where roll_must_block says so.
+static int roll_tactics_step(ao_engine* e, const std::vector<int32_t>& next, const int32_t* rows, bool at_turn) {
+    RollState& r = e->roll;
+    RollTactics& t = r.tac;
+    const int n = static_cast<int>(next.size());
+    std::vector<uint32_t> mt;
+    std::vector<int32_t> pos;
+    if (!at_turn) AO_HIP(e, hipStreamSynchronize(e->stream));   // (the pinned staging rows are free)
+    if (n > 0 && e->tp.noise != 0) {
+        if (!rows) {
+            int32_t* h_games = r.h_i32 + 4 * static_cast<size_t>(e->G);
+            std::copy(next.begin(), next.end(), h_games);
+            AO_HIP(e, hipMemcpyAsync(r.d_games, h_games, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
+            ao::launch_roll_gather(e->tp, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
+            AO_HIP(e, hipGetLastError());
+            AO_HIP(e, hipMemcpyAsync(e->h_mt, e->d_mt_backup, sizeof(uint32_t) * 624 * n, hipMemcpyDeviceToHost, e->stream));
+            AO_HIP(e, hipMemcpyAsync(e->h_pos, e->d_pos_backup, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+            AO_HIP(e, hipStreamSynchronize(e->stream));
+            roll_count(e, static_cast<size_t>(n) * (4 + 624 * 4 + 4));
+        }
+        mt.resize(static_cast<size_t>(n) * 624);
+        pos.resize(n);
+        for (int k = 0; k < n; ++k) {
+            const size_t row = rows ? rows[k] : k;
+            std::memcpy(mt.data() + static_cast<size_t>(k) * 624, e->h_mt + row * 624, sizeof(uint32_t) * 624);
+            pos[k] = e->h_pos[row];
+        }
+    }
+    std::vector<int> taken;
+    auto take_oldest = [&]() { taken.push_back(t.pending.front()); t.pending.erase(t.pending.begin()); };
+    if (at_turn)
+        for (int i : t.pending) { ++t.slot[i].age; t.stats[2] += t.slot[i].n; }
+    const int searching = r.n_in_move - t.n_waiting;
+    if (!t.pending.empty() && ao::roll_must_block(static_cast<int>(t.pending.size()), ao::kRollBatchSlots, n > 0, searching, static_cast<int>(t.pending.size()))) {
+        AO_HIP(e, hipEventSynchronize(t.slot[t.pending.front()].done));
+        ++t.stats[3];
+        take_oldest();
+    }
+    while (at_turn && !t.pending.empty()) {
+        const RollBatch& b = t.slot[t.pending.front()];
+        const hipError_t q = hipEventQuery(b.done);
+        if (q != hipSuccess && q != hipErrorNotReady) return e->fail(std::string("ao_roll: hipEventQuery: ") + hipGetErrorString(q));
+        if (!ao::roll_batch_begins(q == hipSuccess, b.age, t.hold, false)) break;
+        take_oldest();
+    }
+    if (roll_batches_begin(e, taken)) return 1;
+    if (n == 0) return 0;
+    if (roll_batch_start(e, next, std::move(mt), std::move(pos))) return 1;
+    if (ao::roll_must_block(static_cast<int>(t.pending.size()), ao::kRollBatchSlots, false, r.n_in_move - t.n_waiting, static_cast<int>(t.pending.size()))) {
+        // (nothing was pending before, or its games would be searching now: the staging rows are not in use)
+        AO_HIP(e, hipEventSynchronize(t.slot[t.pending.front()].done));
+        ++t.stats[3];
+        taken.clear();
+        take_oldest();
+        if (roll_batches_begin(e, taken)) return 1;
     }
     return 0;
 }
@@ -2140,6 +2366,10 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
     if (e->bar_pending || e->bar_on_device) return e->fail("ao_roll_begin: a root bar is pending (ao_set_root_bar / ao_root_tactics with apply): the rolling search has no root bar");
     if (e->log_n > 0) return e->fail("ao_roll_begin: an eval log is set (ao_set_eval_log): the rolling search does not feed it");
     if (o->turn_every < 1) return e->fail("ao_roll_begin: turn_every must be >= 1");
+    RollTactics& t = r.tac;
+    const bool armed = t.max_depth > 0;
+    if (armed && (e->tp.win_mark < 3 || e->tp.win_mark > 5 || e->tp.win_mark > e->cfg.board))
+        return e->fail("ao_roll_begin: the solver (ao_roll_set_tactics) needs win_mark in 3..5 and at most the board size");
     std::string why;
     if (ao::net_check(net, e->cfg.board, e->cfg.inplanes, e->cfg.device, &why)) return e->fail("ao_roll_begin: " + why);
     // (every turn re-roots: the bound is fixed per engine, so it is checked here, where the call can still be refused)
@@ -2155,6 +2385,15 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
             return 1;
         AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&r.h_i32), sizeof(int32_t) * G * (5 + ao::kRollItem + ao::kRollRec), hipHostMallocDefault));
     }
+    if (armed && !t.stream) {   // the solver's stream and the per-game verdict rows, by the first roll that runs with it
+        if (e->pool.alloc(e, &t.d_words, static_cast<size_t>(G) * 4) || e->pool.alloc(e, &t.d_out_words, static_cast<size_t>(G) * 4)) return 1;
+        AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&t.h_words), sizeof(int32_t) * 4 * G, hipHostMallocDefault));
+        AO_HIP(e, hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
+    }
+    if (armed && t.want_allowed && !t.d_allowed) {
+        if (e->pool.alloc(e, &t.d_allowed, static_cast<size_t>(G) * A) || e->pool.alloc(e, &t.d_out_allowed, static_cast<size_t>(G) * A)) return 1;
+        AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&t.h_allowed), static_cast<size_t>(G) * A, hipHostMallocDefault));
+    }
     if (roll_take_tables(e, o, act, true, "ao_roll_begin")) return 1;
     // nothing can refuse the call any more
     r.in_move.assign(G, 0);
@@ -2168,6 +2407,12 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
     r.look_pending = false;
     r.n_in_move = 0;
     r.draining = false;
+    t.on = armed;
+    t.hold = (armed && getenv("AO_ROLL_TACTICS_HOLD")) ? std::max(0, atoi(getenv("AO_ROLL_TACTICS_HOLD"))) : 0;
+    t.pending.clear();
+    t.n_waiting = 0;
+    t.rec_count = 0;
+    std::fill(t.stats, t.stats + 6, 0);
     // the plan: rows per simulation for every G, the batch bounded by ao_set_row_cap
     if (r.loop.plan(e, net, (e->row_cap > 0 && e->row_cap < G) ? e->row_cap : G)) return 1;
     r.loop.per_sim = true;
@@ -2177,8 +2422,9 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
     p.row_target = p.row_cap;
     p.ctl = nullptr; p.live_prev = nullptr; p.order = nullptr; p.max_levels = 0;
     // (a root may still hold kBarQ children of an earlier barred move: an all-zero bar turns them back where a move begins)
+    // (with the solver every game's row is the bar of its current move: k_roll_verdict writes it before the move begins)
     p.bar = nullptr;
-    if (e->bar_dirty) {
+    if (e->bar_dirty || t.on) {
         AO_HIP(e, hipMemsetAsync(e->d_bar, 0, sizeof(uint64_t) * e->h_bar.size(), e->stream));
         p.bar = e->d_bar;
     }
@@ -2192,7 +2438,7 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
     std::vector<int32_t> games;
     for (int g = 0; g < G; ++g)
         if (act[g]) games.push_back(g);
-    if (roll_begin_games(e, games, nullptr)) { roll_close(e); return 1; }
+    if (t.on ? roll_tactics_step(e, games, nullptr, false) : roll_begin_games(e, games, nullptr)) { roll_close(e); return 1; }
     p.live = r.loop.slot(0);
     ao::launch_select(p, e->stream);
     AO_HIP(e, hipGetLastError());
@@ -2212,7 +2458,7 @@ int ao_roll_join(ao_engine* e, const ao_roll_opts* o) {
     for (int g = 0; g < e->G; ++g)
         if (act[g]) games.push_back(g);
     // (a joined game has LS_IDLE: the next launch's expansion half does nothing for it, its selection half starts simulation 0)
-    if (roll_begin_games(e, games, nullptr)) return roll_fail(e, e->err);
+    if (e->roll.tac.on ? roll_tactics_step(e, games, nullptr, false) : roll_begin_games(e, games, nullptr)) return roll_fail(e, e->err);
     return 0;
 }
 
@@ -2281,11 +2527,16 @@ static int roll_turn(ao_engine* e, ao_roll_records* out) {
     if (report_game_errors(e, h_err)) { roll_close(e); return 1; }
     int n = 0;
     for (int g = 0; g < G; ++g)
-        if (ao::roll_turns(r.in_move[g] != 0, h_done[g], h_target[g], h_leaf[g] == ao::LS_IDLE)) h_games[n++] = g;
+        if (ao::roll_game_turns(r.in_move[g], h_done[g], h_target[g], h_leaf[g] == ao::LS_IDLE)) h_games[n++] = g;
     ++r.turns;
     r.last_games = n;
     out->count = 0;
-    if (n == 0) { r.last_bytes = r.bytes - bytes0; return 0; }
+    RollTactics& t = r.tac;
+    if (n == 0) {
+        if (t.on && roll_tactics_step(e, std::vector<int32_t>(), nullptr, true)) return roll_fail(e, e->err);   // (verdicts may be in)
+        r.last_bytes = r.bytes - bytes0;
+        return 0;
+    }
     const size_t nA = static_cast<size_t>(n) * A;
     double* d_pi = r.d_out;
     double* d_visit = r.want_visit ? r.d_out + nA : nullptr;
@@ -2299,6 +2550,15 @@ static int roll_turn(ao_engine* e, ao_roll_records* out) {
     if (d_visit) AO_HIP(e, hipMemcpyAsync(e->h_out + nA, d_visit, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
     if (d_policy) AO_HIP(e, hipMemcpyAsync(e->h_out + 2 * nA, d_policy, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
     roll_count(e, sizeof(int32_t) * (1 + ao::kRollRec) * n + sizeof(double) * nA * (1 + (d_visit ? 1 : 0) + (d_policy ? 1 : 0)));
+    if (t.on) {   // what the solver said at the root of the move each turned game just played: 16 B (+ A) per game
+        ao::launch_roll_words(r.d_games, n, A, t.d_words, t.d_allowed, t.d_out_words, t.want_allowed ? t.d_out_allowed : nullptr, e->stream);
+        AO_HIP(e, hipGetLastError());
+        AO_HIP(e, hipMemcpyAsync(t.h_words, t.d_out_words, sizeof(int32_t) * 4 * n, hipMemcpyDeviceToHost, e->stream));
+        if (t.want_allowed) AO_HIP(e, hipMemcpyAsync(t.h_allowed, t.d_out_allowed, nA, hipMemcpyDeviceToHost, e->stream));
+        const size_t bytes = static_cast<size_t>(n) * 16 + (t.want_allowed ? nA : 0);
+        t.stats[5] += static_cast<int64_t>(bytes);
+        roll_count(e, bytes);
+    }
     const bool gather = e->tp.noise != 0 && !r.draining;   // the streams of the played games, for the draws of their next moves
     if (gather) {
         ao::launch_roll_gather(r.loop.p, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
@@ -2332,7 +2592,7 @@ static int roll_turn(ao_engine* e, ao_roll_records* out) {
         e->status[g] = rec[6];
         e->over[g] = rec[2];
         e->active[g] = 0;
-        r.in_move[g] = 0;
+        r.in_move[g] = ao::ROLL_OUT;
         --r.n_in_move;
         if (ao::roll_begins_next(rec[2], r.draining)) { next.push_back(g); next_rows.push_back(b); }
     }
@@ -2341,6 +2601,16 @@ static int roll_turn(ao_engine* e, ao_roll_records* out) {
     if (out->policy && d_policy) std::memcpy(out->policy, e->h_out + 2 * nA, sizeof(double) * nA);
     out->count = n;
     r.games_turned += n;
+    if (t.on) {
+        t.rec_count = n;
+        t.rec_words.assign(t.h_words, t.h_words + 4 * static_cast<size_t>(n));
+        if (t.want_allowed) t.rec_allowed.assign(t.h_allowed, t.h_allowed + nA);
+        for (int b = 0; b < n; ++b) t.stats[4] += t.rec_words[4 * static_cast<size_t>(b) + 2];
+        // (with noise the streams of `next` lie in the staging rows; without, nothing of them is needed)
+        if (roll_tactics_step(e, next, gather ? next_rows.data() : nullptr, true)) return roll_fail(e, e->err);
+        r.last_bytes = r.bytes - bytes0;
+        return 0;
+    }
     if (roll_begin_games(e, next, gather ? next_rows.data() : nullptr)) return roll_fail(e, e->err);
     r.last_bytes = r.bytes - bytes0;
     return 0;
@@ -2354,6 +2624,7 @@ int ao_roll_run(ao_engine* e, int64_t max_launches, ao_roll_records* out) {
     if (max_launches < 0) return e->fail("ao_roll_run: max_launches must be >= 0");
     AO_HIP(e, hipSetDevice(e->cfg.device));
     out->count = 0;
+    r.tac.rec_count = 0;
     int64_t launches = 0;
     if (ao::roll_run_returns(0, r.n_in_move, launches, max_launches)) return 0;
     for (;;) {
@@ -2383,6 +2654,41 @@ int ao_roll_end(ao_engine* e) {
     if (r.loop.harvest(r.loop.launch)) return 1;
     AO_HIP(e, hipStreamSynchronize(e->stream));
     roll_close(e);
+    return 0;
+}
+
+int ao_roll_set_tactics(ao_engine* e, int32_t max_depth, int32_t max_nodes, int32_t solved_sims, int32_t want_allowed) {
+    if (roll_refuses(e, "ao_roll_set_tactics")) return 1;
+    RollTactics& t = e->roll.tac;
+    if (max_depth == 0) {
+        t.max_depth = t.max_nodes = t.solved_sims = 0;
+        t.want_allowed = false;
+        return 0;
+    }
+    const std::string bad_limits = ao::fw_limits_error("ao_roll_set_tactics", max_depth, max_nodes);
+    if (!bad_limits.empty()) return e->fail(bad_limits);
+    if (solved_sims < 0 || solved_sims > e->S)
+        return e->fail("ao_roll_set_tactics: solved_sims must be in 0.." + std::to_string(e->S) + " (0: no cap)");
+    t.max_depth = max_depth; t.max_nodes = max_nodes; t.solved_sims = solved_sims;
+    t.want_allowed = want_allowed != 0;
+    return 0;
+}
+
+int ao_roll_tactics_records(ao_engine* e, int32_t* verdict, int32_t* depth, int32_t* nodes, int32_t* unknown, uint8_t* allowed) {
+    const RollTactics& t = e->roll.tac;
+    if (allowed && t.rec_count > 0 && t.rec_allowed.size() < static_cast<size_t>(t.rec_count) * e->A)
+        return e->fail("ao_roll_tactics_records: allowed rows need ao_roll_set_tactics(..., want_allowed = 1)");
+    int32_t* out[4] = {verdict, depth, nodes, unknown};
+    for (int b = 0; b < t.rec_count; ++b)
+        for (int w = 0; w < 4; ++w)
+            if (out[w]) out[w][b] = t.rec_words[4 * static_cast<size_t>(b) + w];
+    if (allowed && t.rec_count > 0) std::memcpy(allowed, t.rec_allowed.data(), static_cast<size_t>(t.rec_count) * e->A);
+    return 0;
+}
+
+int ao_roll_tactics_stats(ao_engine* e, int64_t* out) {
+    if (!out) return e->fail("ao_roll_tactics_stats: null argument");
+    std::copy(e->roll.tac.stats, e->roll.tac.stats + 6, out);
     return 0;
 }
 

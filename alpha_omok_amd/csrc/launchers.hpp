@@ -38,6 +38,20 @@ void launch_roll_gather(const TreeParams& p, const int32_t* games, int n, uint32
 void launch_roll_begin(const TreeParams& p, const int32_t* items, int n, const uint32_t* in_mt, const int32_t* in_pos, const double* in_noise,
                        int8_t* tau, uint8_t* active, uint8_t* settled, uint8_t* early, hipStream_t s);
 void launch_roll_mask(const TreeParams& p, const uint8_t* early, uint8_t* out, hipStream_t s);
+// ... with the solver beside the loop (ao_roll_set_tactics): the root positions of the listed games into a batch's compact rows;
+// a finished batch's bar rows, verdict words and allowed rows into its games' own rows, and the targets of its begin items
+// worked out from the verdicts; the verdict words of the turned games for their records
+struct RollBatchView {
+    const uint64_t* bar;      // [n][kBBWords]
+    const int32_t* verdict;   // [4][n]: verdict, depth, nodes, unknown
+    const uint8_t* allowed;   // [n][A] or null
+    int n;
+};
+void launch_roll_rootpos(const TreeParams& p, const int32_t* games, int n, Pos* rows, hipStream_t s);
+void launch_roll_verdict(int32_t* items, const RollBatchView& b, int A, int solved_sims, uint64_t* bar, int32_t* game_words, uint8_t* game_allowed,
+                         hipStream_t s);
+void launch_roll_words(const int32_t* games, int n, int A, const int32_t* game_words, const uint8_t* game_allowed, int32_t* out_words,
+                       uint8_t* out_allowed, hipStream_t s);
 // tree_readout.hip
 void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
                         int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
@@ -45,6 +59,9 @@ void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32
 int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s);
 // root_tactics.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
 void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s);
+// the list form: the same three kernels on n compact position rows, every buffer of b indexed by the row (a batch of the rolling search)
+void launch_root_tactics_rows(const Pos* rows, int n, int B, int A, int win_mark, int max_depth, int max_nodes, const RootTacticsBufs& b,
+                              hipStream_t s);
 // step_kernels.hip
 void launch_step_board(const TreeParams& p, const StepNet& f, int rows, const int32_t* game_of_row, hipStream_t s);
 // net.hip

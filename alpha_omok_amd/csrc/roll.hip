@@ -11,9 +11,16 @@
 //   k_roll_begin    the states and the noise rows back, then the begin of the next move: targets, flags, tau, the settle
 //                   mask, and begin_move_game (the body of k_begin_move: re-noise of an inherited root)
 //   k_roll_mask     the games a look may settle: early-stop games that have run a simulation of their move
+// With the forced-win solver beside the loop (ao_roll_set_tactics; root_tactics.hip runs on a stream of its own, on a batch's rows):
+//   k_roll_rootpos  the listed games' root positions into the batch's compact rows: the solver reads nothing of the engine
+//   k_roll_verdict  in front of k_roll_begin, for the games of a finished batch: the bar row of the move into TreeParams::bar, the
+//                   verdict words (and the allowed row) into the game's own row, and the target of the begin item from the verdict
+//                   (roll_solved_budget, roll_schedule.hpp)
+//   k_roll_words    the verdict words (and allowed rows) of the turned games into compact rows, for their records
 #include "host_handle.hpp"
 #include "launchers.hpp"
 #include "move_device.hpp"
+#include "roll_schedule.hpp"
 
 namespace ao {
 
@@ -97,6 +104,54 @@ __global__ void k_roll_mask(TreeParams p, const uint8_t* early, uint8_t* out) {
     if (g < p.G) out[g] = (early[g] && p.sims_done[g] >= 1) ? 1 : 0;
 }
 
+__global__ __launch_bounds__(64) void k_roll_rootpos(TreeParams p, const int32_t* games, Pos* rows) {
+    static_assert(sizeof(Pos) % 4 == 0, "a position row is copied in words");
+    const int g = __builtin_amdgcn_readfirstlane(games[blockIdx.x]);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(p.rootpos + g);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(rows + blockIdx.x);
+    for (int i = lane_id(); i < static_cast<int>(sizeof(Pos) / 4); i += 64) dst[i] = src[i];
+}
+
+// Item k of `items` is the begin item of the game in row k of the batch. Word 4 carries the settle mask in bit 0 and, in bit 1,
+// whether the target counts a fresh root's own expansion on top of the budget: the cap of a proven win applies to the budget.
+__global__ __launch_bounds__(64) void k_roll_verdict(int32_t* items, RollBatchView b, int A, int solved_sims, uint64_t* bar, int32_t* game_words,
+                                                     uint8_t* game_allowed) {
+    const int k = blockIdx.x;
+    int32_t* it = items + static_cast<size_t>(k) * kRollItem;
+    const int g = __builtin_amdgcn_readfirstlane(it[0]);
+    const int lane = lane_id();
+    if (lane < kBBWords) bar[static_cast<size_t>(g) * kBBWords + lane] = b.bar[static_cast<size_t>(k) * kBBWords + lane];
+    if (lane < 4) game_words[static_cast<size_t>(g) * 4 + lane] = b.verdict[static_cast<size_t>(lane) * b.n + k];
+    if (game_allowed)                                                   // (uniform over the wave)
+        for (int i = lane; i < A; i += 64) game_allowed[static_cast<size_t>(g) * A + i] = b.allowed[static_cast<size_t>(k) * A + i];
+    if (lane == 0) {
+        const int bonus = (it[4] >> 1) & 1;
+        it[1] = roll_solved_budget(it[1] - bonus, b.verdict[k], solved_sims) + bonus;
+        it[4] &= 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_roll_words(const int32_t* games, int A, const int32_t* game_words, const uint8_t* game_allowed,
+                                                   int32_t* out_words, uint8_t* out_allowed) {
+    const int b = blockIdx.x;
+    const int g = __builtin_amdgcn_readfirstlane(games[b]);
+    const int lane = lane_id();
+    if (lane < 4) out_words[static_cast<size_t>(b) * 4 + lane] = game_words[static_cast<size_t>(g) * 4 + lane];
+    if (out_allowed)                                                    // (uniform over the wave)
+        for (int i = lane; i < A; i += 64) out_allowed[static_cast<size_t>(b) * A + i] = game_allowed[static_cast<size_t>(g) * A + i];
+}
+
+void launch_roll_rootpos(const TreeParams& p, const int32_t* games, int n, Pos* rows, hipStream_t s) {
+    hipLaunchKernelGGL(k_roll_rootpos, dim3(n), dim3(64), 0, s, p, games, rows);
+}
+void launch_roll_verdict(int32_t* items, const RollBatchView& b, int A, int solved_sims, uint64_t* bar, int32_t* game_words, uint8_t* game_allowed,
+                         hipStream_t s) {
+    hipLaunchKernelGGL(k_roll_verdict, dim3(b.n), dim3(64), 0, s, items, b, A, solved_sims, bar, game_words, game_allowed);
+}
+void launch_roll_words(const int32_t* games, int n, int A, const int32_t* game_words, const uint8_t* game_allowed, int32_t* out_words,
+                       uint8_t* out_allowed, hipStream_t s) {
+    hipLaunchKernelGGL(k_roll_words, dim3(n), dim3(64), 0, s, games, A, game_words, game_allowed, out_words, out_allowed);
+}
 void launch_roll_turn(const TreeParams& p, const int32_t* games, int n, uint8_t* active, const uint8_t* settled, int32_t* rec, double* rec_pi,
                       double* rec_visit, double* rec_policy, hipStream_t s) {
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_roll_turn<NCH>, dim3(n), dim3(64), 0, s, p, games, active, settled, rec, rec_pi,

@@ -43,6 +43,42 @@ inline RollMove roll_next_move(int ply, int tau_plies, const int32_t* sims_row, 
     return m;
 }
 
+// ---- tactics beside the loop (ao_roll_set_tactics) ------------------------------------------------------------------------------
+// With the forced-win solver armed a game that is to begin a move first WAITS for the solver's verdict on its root: the solver
+// runs in batches on a stream of its own while the other games go on searching. A game of an open roll is in one of three states;
+// "in a move" for ao_reset / ao_seed* / ao_roll_end is everything but ROLL_OUT.
+enum RollGame : uint8_t { ROLL_OUT = 0, ROLL_SEARCHING = 1, ROLL_WAITING = 2 };
+
+// A waiting game is never turned, whatever its counters say: done == target is left over from the move it just played.
+inline bool roll_game_turns(int state, int done, int target, bool leaf_idle) {
+    return roll_turns(state == ROLL_SEARCHING, done, target, leaf_idle);
+}
+
+// The budget of a move whose root the solver has looked at: a proven win (verdict 1, RT_WIN) is capped at solved_sims
+// simulations; solved_sims == 0 is no cap; every other verdict leaves the budget alone. One rule for the host (ao_search's
+// callers, the tests) and the device (k_roll_begin works out the target of a game from the verdict words of its batch).
+#if defined(__HIPCC__)
+#define AO_ROLL_HD __host__ __device__
+#else
+#define AO_ROLL_HD
+#endif
+AO_ROLL_HD inline int roll_solved_budget(int budget, int verdict, int solved_sims) {
+    return (verdict == 1 && solved_sims > 0 && solved_sims < budget) ? solved_sims : budget;
+}
+
+// The ring of solver batches. A batch is started at a turn (or at begin / join) and asked about at every LATER turn, oldest
+// first: `age` counts the turns since it was started. Its games begin their move once its event has been reached and it has been
+// held for `hold` further turns (AO_ROLL_TACTICS_HOLD, a test knob; 0: none) -- or at once when the host had to block on it.
+inline bool roll_batch_begins(bool event_done, int age, int hold, bool blocked) {
+    return blocked || (event_done && age >= 1 + hold);
+}
+// The host blocks on the OLDEST batch's event when a batch is to be started and every slot is busy, or when nothing is searching
+// and a batch is pending (the loop would launch empty batches until the verdict arrives).
+inline bool roll_must_block(int busy_slots, int slots, bool starts_batch, int searching, int pending) {
+    return (starts_batch && busy_slots >= slots) || (searching == 0 && pending > 0);
+}
+constexpr int kRollBatchSlots = 4;
+
 // ---- drain ----------------------------------------------------------------------------------------------------------------------
 // a turned game begins another move unless its game is over or the roll is draining
 inline bool roll_begins_next(int win, bool draining) { return win == 0 && !draining; }

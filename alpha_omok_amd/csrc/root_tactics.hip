@@ -141,18 +141,34 @@ __global__ __launch_bounds__(64 * kPosPerWG) void k_root_tactics_rows(RootTactic
     }
 }
 
+// The kernels index everything by the position's number in q.rootpos, 0 .. q.G - 1. ao_root_tactics hands them the engine's [G]
+// roots; the rolling search hands them n compact rows copied out of the roots (k_roll_rootpos) and a batch's own buffers: the
+// LIST form is the same code with G = n, grids ceil(2n / kPosPerWG), n x ceil(A / kPosPerWG) and ceil(n / kPosPerWG).
+static void launch_root_tactics_q(const RootTacticsParams& q, hipStream_t s) {
+    const dim3 block(64 * kPosPerWG);
+    const dim3 grid_a(static_cast<unsigned>((2 * q.G + kPosPerWG - 1) / kPosPerWG));
+    const dim3 grid_b(static_cast<unsigned>(q.G), static_cast<unsigned>((q.A + kPosPerWG - 1) / kPosPerWG));
+    const dim3 grid_r(static_cast<unsigned>((q.G + kPosPerWG - 1) / kPosPerWG));
+    AO_DISPATCH_NCH(nch_of_cells(q.A), hipLaunchKernelGGL(k_root_tactics_a<NCH>, grid_a, block, 0, s, q);
+                    hipLaunchKernelGGL(k_root_tactics_b<NCH>, grid_b, block, 0, s, q);
+                    hipLaunchKernelGGL(k_root_tactics_rows<NCH>, grid_r, block, 0, s, q));
+}
+
 void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s) {
     RootTacticsParams q{};
     q.rootpos = p.rootpos; q.active = active;
     q.G = p.G; q.B = p.B; q.A = p.A; q.win_mark = p.win_mark; q.max_depth = max_depth; q.max_nodes = max_nodes;
     q.b = b;
-    const dim3 block(64 * kPosPerWG);
-    const dim3 grid_a(static_cast<unsigned>((2 * p.G + kPosPerWG - 1) / kPosPerWG));
-    const dim3 grid_b(static_cast<unsigned>(p.G), static_cast<unsigned>((p.A + kPosPerWG - 1) / kPosPerWG));
-    const dim3 grid_r(static_cast<unsigned>((p.G + kPosPerWG - 1) / kPosPerWG));
-    AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_root_tactics_a<NCH>, grid_a, block, 0, s, q);
-                    hipLaunchKernelGGL(k_root_tactics_b<NCH>, grid_b, block, 0, s, q);
-                    hipLaunchKernelGGL(k_root_tactics_rows<NCH>, grid_r, block, 0, s, q));
+    launch_root_tactics_q(q, s);
+}
+
+void launch_root_tactics_rows(const Pos* rows, int n, int B, int A, int win_mark, int max_depth, int max_nodes, const RootTacticsBufs& b,
+                              hipStream_t s) {
+    RootTacticsParams q{};
+    q.rootpos = rows; q.active = nullptr;
+    q.G = n; q.B = B; q.A = A; q.win_mark = win_mark; q.max_depth = max_depth; q.max_nodes = max_nodes;
+    q.b = b;
+    launch_root_tactics_q(q, s);
 }
 
 }  // namespace ao

@@ -496,16 +496,45 @@ class Engine:
                             want_visit=1 if visit else 0, want_policy=1 if policy else 0)
         return o, keep                                   # (the struct holds pointers into `keep`: the caller keeps it until the call returns)
 
+    def _roll_tactics(self, tactics):
+        """roll_begin(tactics=): validated like search(tactics=) (+ allowed=True: the records carry the allowed rows); arms or
+        disarms the solver for the roll that is about to open (ao_roll_set_tactics). Returns (armed, allowed rows asked for)."""
+        from .positions import _check_limits
+        if tactics is None or tactics is False:
+            if getattr(self, "_roll_armed", False):
+                self._check(self._L.ao_roll_set_tactics(self._h, 0, 0, 0, 0), "ao_roll_set_tactics")
+                self._roll_armed = False
+            return False, False
+        opt = {} if tactics is True else dict(tactics)
+        unknown = set(opt) - {"max_depth", "max_nodes", "solved_sims", "allowed"}
+        if unknown:
+            raise ValueError("tactics: unknown key(s) %s" % sorted(unknown))
+        k = opt.get("solved_sims")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= self.num_mcts):
+            raise ValueError("tactics: solved_sims must be an integer in 1..%d, got %r" % (self.num_mcts, k))
+        depth, nodes = opt.get("max_depth", 6), opt.get("max_nodes", 512)
+        _check_limits(depth, nodes)
+        want = bool(opt.get("allowed", False))
+        self._check(self._L.ao_roll_set_tactics(self._h, int(depth), int(nodes), 0 if k is None else int(k), 1 if want else 0),
+                    "ao_roll_set_tactics")
+        self._roll_armed = True
+        return True, want
+
     def roll_begin(self, net, active=None, tau_plies=None, sims=None, noise=None, early_stop=False, turn_every=None,
-                   visit=False, policy=False):
+                   visit=False, policy=False, tactics=None):
         """Opens a rolling search on `net` (ao_roll_begin): the listed games (None: all that are not over) begin a move and
         from then on every game ends its move, plays and begins the next one on its own clock, turn_every launches apart
         (None: SETTLE_EVERY), while the others go on searching. tau_plies: int or [G], tau is 1 while fewer moves than that
         are on the board (None: always); sims / noise: budgets and noise switches by ply, a scalar, [G] or [G, P] (a ply
         beyond P reads the last column); early_stop: tau == 0 moves stop once decided; visit / policy: roll_run returns
-        them. Until roll_end, begin_move / search / end_move / play / set_root(s) / export_trees ... raise EngineError."""
+        them. tactics: True or dict(max_depth, max_nodes, solved_sims, allowed) -- every move of the roll is begun as
+        search(tactics=dict(max_depth, max_nodes, solved_sims)) begins it, the solver running beside the loop
+        (ao_roll_set_tactics); roll_run's records then carry verdict, depth, nodes, unknown (and, with allowed=True, allowed).
+        Until roll_end, begin_move / search / end_move / play / set_root(s) / export_trees ... raise EngineError."""
+        tac = self._roll_tactics(tactics)
         o, keep = self._roll_opts(active, tau_plies, sims, noise, early_stop, turn_every, visit, policy)
         self._check(self._L.ao_roll_begin(self._h, net._h, C.byref(o)), "ao_roll_begin")
+        self._roll_tac = tac
         self._roll_buf = self._roll_buffers(visit, policy)
 
     def _roll_buffers(self, visit=False, policy=False):
@@ -517,8 +546,10 @@ class Engine:
         """Runs the loop until a turn has produced a record, nothing is in a move, or max_launches launches are spent (0: no
         bound) -- ao_roll_run. Returns a dict of arrays cut to the record count, one entry per game that ended a move: game,
         ply (moves on the board before it), action, win, tau, sims (simulations run, budget units), settled (bool), pi
-        [n, A], and visit / policy [n, A] where roll_begin asked for them. A game with win != 0 is over; every other one is
-        already searching its next move (unless draining)."""
+        [n, A], and visit / policy [n, A] where roll_begin asked for them. With roll_begin(tactics=...) also what the solver said
+        at the root of the move each record played: verdict, depth, nodes, unknown int32 [n] (and allowed bool [n, A] with
+        tactics=dict(..., allowed=True)) -- ao_roll_tactics_records; without tactics the keys are the ones above. A game with
+        win != 0 is over; every other one is already searching its next move, or waits for its verdict (unless draining)."""
         b = getattr(self, "_roll_buf", None) or self._roll_buffers()
         rec = _lib.AoRollRecords(count=0, pi=_ptr(b["pi"], C.c_double), visit=_ptr(b["visit"], C.c_double),
                                  policy=_ptr(b["policy"], C.c_double),
@@ -530,6 +561,16 @@ class Engine:
         for k in ("visit", "policy"):
             if b[k] is not None:
                 out[k] = b[k][:n].copy()
+        armed, want = getattr(self, "_roll_tac", (False, False))
+        if armed:
+            w = [np.zeros(max(n, 1), np.int32) for _ in range(4)]
+            al = np.zeros((max(n, 1), self.A), np.uint8) if want else None
+            self._check(self._L.ao_roll_tactics_records(self._h, *[_ptr(x, C.c_int32) for x in w], _ptr(al, C.c_uint8)),
+                        "ao_roll_tactics_records")
+            for k, x in zip(("verdict", "depth", "nodes", "unknown"), w):
+                out[k] = x[:n]
+            if want:
+                out["allowed"] = al[:n].astype(bool)
         return out
 
     def roll_join(self, active=None, tau_plies=None, sims=None, noise=None):
@@ -551,6 +592,14 @@ class Engine:
         v = [C.c_int64(0) for _ in range(5)]
         self._check(self._L.ao_roll_stats(self._h, *[C.byref(x) for x in v]), "ao_roll_stats")
         return dict(zip(("turns", "games_turned", "bytes", "last_games", "last_bytes"), (x.value for x in v)))
+
+    def roll_tactics_stats(self):
+        """dict(batches, games_solved, waited_turns, host_blocks, nodes, bytes) of the solver beside the open (or the last) roll
+        (ao_roll_tactics_stats): waited_turns sums, over the games, the turns they spent waiting for a verdict; host_blocks
+        counts the times the host had to wait for a batch; bytes are also part of roll_stats()["bytes"]."""
+        v = (C.c_int64 * 6)()
+        self._check(self._L.ao_roll_tactics_stats(self._h, v), "ao_roll_tactics_stats")
+        return dict(zip(("batches", "games_solved", "waited_turns", "host_blocks", "nodes", "bytes"), (int(x) for x in v)))
 
     def fp16_range_events(self):
         """(moves ao_search repeated on the fp32-MFMA trunk, games searched again) since the engine was created."""

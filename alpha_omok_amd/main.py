@@ -108,6 +108,7 @@ FULL_PROB = 0.25             # configured, sample recorded; probability FULL_PRO
 playout_totals = {'full': 0, 'fast': 0}   # move decisions of either kind since configure() (all of them 'full' without fast_sims)
 ROLLING = False              # configure(rolling=True): self-play runs ONE rolling search per call (Engine.roll_*): every game ends its move, plays and
 TURN_EVERY = None            # begins the next on its own clock, looked at every TURN_EVERY launches (None: engine.SETTLE_EVERY), instead of search + play per ply
+ROLL_TACTICS = None          # configure(rolling=True, roll_tactics=True or dict): the forced-win solver runs beside the rolling loop (Engine.roll_begin(tactics=...))
 roll_sims_log = None         # a list: the rolling loop appends (global episode number, ply, simulations run, settled) per move decision (tests, tools)
 LEAF_SYMMETRY = None         # configure(leaf_symmetry=KEY): every self-play leaf is evaluated under a symmetry drawn from (KEY, the episode's seed, ply, simulation)
 FP16_GRID = False            # configure(fp16_grid_weights=True): the 3x3 conv weights of Agent.model are kept on the fp16 grid (see _grid_sync)
@@ -118,7 +119,7 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
               model=None, gpu=None, noise=True, device_replay=False, node_cap=None, strict=None, reproducible=False,
               carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None,
               early_stop=False, fast_sims=None, full_prob=0.25, tactics=None, forward_precision="fp32", rolling=False,
-              turn_every=None, leaf_symmetry=None):
+              turn_every=None, leaf_symmetry=None, roll_tactics=None):
     """Build `Agent`, `Agent.model` and `optimizer` (main.py:58-85). Call instead of editing constants.
     node_cap: expanded-node capacity of a game's tree arena (0 = 16*(n_mcts+1) where 40 % of the HBM
     holds that for all games, at least 4*(n_mcts+1); -1 = grow into the free HBM);
@@ -170,7 +171,13 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     end their move, play and begin the next one, finished slots are refilled and join the running loop. Every game's search is the
     same strictly sequential one, so with reproducible=True an episode is bit for bit the episode of rolling=False. Combines with
     early_stop, fast_sims / full_prob, oversubscribe, carry_over, overlap_train, fp16_grid_weights, forward_precision and
-    reproducible; not with tactics= (the rolling search has no root bar), and it needs a model with a native form.
+    reproducible, and it needs a model with a native form. It does not take tactics= (that switch belongs to the synchronous search);
+    roll_tactics= is the rolling search's own:
+    roll_tactics=True or dict(max_depth, max_nodes, solved_sims) (with rolling=True only): every move of the rolling search is begun
+    as a tactics= search begins it -- the solver's bar at the root, a proven win capped at solved_sims simulations -- with the solver
+    running beside the launch loop on a stream of its own (Engine.roll_begin(tactics=...)): the games turned wait for their verdict
+    while the others go on searching. With reproducible=True an episode is bit for bit the episode of rolling=False, tactics=the same.
+    Not with strict=True, as tactics=.
     leaf_symmetry=KEY (an int; None: off): every leaf of every self-play search -- and of Agent's own get_pi -- goes through the
     network under one of the eight symmetries of the board, drawn as utils.leaf_symmetry(utils.leaf_key(KEY, the episode's seed),
     stones on the leaf, simulation index) (Engine.set_leaf_symmetry): the planes are transformed on their way into the batch and the
@@ -180,9 +187,15 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     global LEAF_SYMMETRY
     global BOARD_SIZE, N_MCTS, N_BLOCKS, IN_PLANES, OUT_PLANES, SEED, Agent, optimizer, device
     global _engine, _evaluator, _episodes_played, rep_memory, STRICT, NODE_CAP, CARRY_OVER, _pool, OVERSUBSCRIBE, ROWS, _terminal_share
-    global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS, ROLLING, TURN_EVERY
+    global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS, ROLLING, TURN_EVERY, ROLL_TACTICS
     if rolling and tactics:
-        raise ValueError("rolling=True and tactics= do not go together: the rolling search has no root bar")
+        raise ValueError("rolling=True and tactics= do not go together: tactics= is the synchronous search's switch; the rolling "
+                         "search takes roll_tactics= (the solver runs beside its loop)")
+    if roll_tactics and not rolling:
+        raise ValueError("roll_tactics= needs rolling=True (the synchronous search takes tactics=)")
+    if roll_tactics and (STRICT if strict is None else strict):
+        raise ValueError("roll_tactics and strict=True do not go together: a barred root child forgets its inherited visits, which "
+                         "the strict visit-count check would report")
     if turn_every is not None and int(turn_every) < 1:
         raise ValueError("turn_every must be >= 1")
     if rolling and model is not None and not hasattr(model, "forward_ptr"):
@@ -206,6 +219,7 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     ROLLING = bool(rolling)
     TURN_EVERY = None if turn_every is None else int(turn_every)
     TACTICS = tactics if tactics else None
+    ROLL_TACTICS = roll_tactics if roll_tactics else None
     if TACTICS is not None and (STRICT if strict is None else strict):
         raise ValueError("tactics and strict=True do not go together: a barred root child forgets its inherited visits, which "
                          "the strict visit-count check would report")
@@ -476,7 +490,7 @@ def _roll_play(eng, gid, ply, active, inherit, sample, moved, finish, start, sto
     sims, noise = _roll_tables(gid)
     budget = (lambda g, p: N_MCTS) if sims is None else (lambda g, p: sims[g, np.minimum(p, sims.shape[1] - 1)])
     eng.roll_begin(net, active=active, tau_plies=TAU_THRES, sims=sims, noise=noise, early_stop=EARLY_STOP, turn_every=TURN_EVERY,
-                   visit=STRICT)
+                   visit=STRICT, tactics=ROLL_TACTICS)
     draining = False
     try:
         while True:
@@ -1408,6 +1422,7 @@ if __name__ == '__main__':
     fwd.add_argument('--fp16-forward', action='store_true', help='searches run the opt-in plain-fp16 forward: one MFMA product per multiply-add (configure(forward_precision="fp16"))')
     ap.add_argument('--rolling', action='store_true', help='self-play as one rolling search per call: every game moves on its own clock (configure(rolling=True))')
     ap.add_argument('--turn-every', type=int, default=None, metavar='N', help='with --rolling: launches between two turns (default: engine.SETTLE_EVERY)')
+    ap.add_argument('--roll-tactics', action='store_true', help='with --rolling: the forced-win solver restricts the roots, running beside the launch loop (configure(roll_tactics=True))')
     ap.add_argument('--leaf-symmetry', type=int, nargs='?', const=0, default=None, metavar='KEY', help='evaluate every leaf under a symmetry of the board drawn per leaf (configure(leaf_symmetry=KEY)); KEY defaults to 0')
     a = ap.parse_args()
     parallel.init_from_env()
@@ -1415,5 +1430,5 @@ if __name__ == '__main__':
     configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, device_replay=a.device_replay, oversubscribe=a.oversubscribe,
               overlap_train=a.overlap_train, fp16_grid_weights=a.fp16_grid_weights,
               forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32", rolling=a.rolling, turn_every=a.turn_every,
-              leaf_symmetry=a.leaf_symmetry)
+              leaf_symmetry=a.leaf_symmetry, roll_tactics=a.roll_tactics or None)
     run(a.iters, a.model, a.dataset, a.selfplay)

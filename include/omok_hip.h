@@ -209,8 +209,10 @@ int ao_search_sims(ao_engine *e, int32_t *host_sims_run, uint8_t *host_settled, 
  * Protocol: ao_roll_begin -> repeat ao_roll_run (records come back as games turn; refill finished slots with ao_reset(mask),
  * ao_seed_games, ao_roll_join) -> ao_roll_drain -> ao_roll_run until nothing is in a move -> ao_roll_end.
  * Inside an open roll ao_begin_move*, ao_search*, ao_end_move, ao_play, ao_settle, ao_collect_leaves, ao_apply_evals,
- * ao_set_root(s), ao_set_root_bar, ao_set_row_cap, ao_set_eval_log, ao_tree_export, ao_tree_import and ao_root_tactics fail
- * with a message that says a roll is open; ao_reset, ao_seed*, ao_set_rng_state fail, naming the game, for a game that is in
+ * ao_set_root(s), ao_set_root_bar, ao_set_row_cap, ao_set_eval_log, ao_tree_export, ao_tree_import, ao_root_tactics and
+ * ao_roll_set_tactics fail with a message that says a roll is open (the forced-win solver combines with a roll through
+ * ao_roll_set_tactics, called BEFORE ao_roll_begin: see below; the caller's own masks, the fp16-range repeat and a torch-module
+ * evaluator do not); ao_reset, ao_seed*, ao_set_rng_state fail, naming the game, for a game that is in
  * a move, and work for the others. The tree read-outs (ao_tree_lookup, ao_tree_pv, ao_tree_stats, ao_get_root_children)
  * stay legal between ao_roll_run calls; ao_destroy is legal at any time. ao_search_sims' totals, ao_row_stats,
  * ao_trim_stats and ao_search_stats keep counting. */
@@ -265,6 +267,35 @@ int ao_roll_end(ao_engine *e);
  * few KB per game it turns; the turned games' error words come back in their records -- never a second [G]-wide read, and
  * never a [G]-wide copy of pi, visit, policy or the streams. */
 int ao_roll_stats(ao_engine *e, int64_t *turns, int64_t *games_turned, int64_t *bytes, int64_t *last_games, int64_t *last_bytes);
+/* ---- the forced-win solver beside the rolling loop ----
+ * Arms the solver for the rolls opened AFTERWARDS: every move a game begins inside such a roll (at ao_roll_begin, at
+ * ao_roll_join, after a turn) is begun as ao_root_tactics(apply = 1) + ao_search_opts begin it -- utils.root_tactics of the
+ * game's root gives the bar of that one move, and a proven RT_WIN lowers the move's budget to min(budget, solved_sims)
+ * (solved_sims == 0: no cap). The sentence above still holds: per game and ply a record is, to the bit, what
+ * ao_root_tactics(apply = 1) + ao_search_opts + ao_play return from the same stream, budget and noise switch.
+ * The solver does not run inside a turn (one call lasts as long as its slowest wavefront, tens of milliseconds at the
+ * default limits): it runs in BATCHES on a second stream that touches nothing but the batch's own buffers. The games listed
+ * at a turn WAIT for their batch -- they count as in a move for ao_reset / ao_seed* / ao_roll_join / ao_roll_end -- while all
+ * others go on searching; every later turn asks, oldest batch first, whether its event has been reached and then begins its
+ * games. A ring of four batches; the host waits (for the oldest batch's recorded event, once) only when a batch is to be
+ * started and all four are busy, or when nothing is searching and a batch is pending. Nothing of a record depends on when
+ * a verdict arrived. Draining starts no batch; ao_roll_run returns "nothing is in a move" only when no batch is pending.
+ * AO_ROLL_TACTICS_HOLD=<k> (read at ao_roll_begin; a test knob) holds every finished batch for at least k further turns.
+ * max_depth == 0 disarms: the roll's launches, arguments and host traffic are then exactly those without this call.
+ * Refused: inside an open roll; limits outside 1..16 / 1..65536; solved_sims outside 0..ao_config.sims. With the solver armed
+ * ao_roll_begin also refuses a win_mark outside 3..5 or above the board size (as ao_root_tactics does). A pending root bar
+ * still refuses ao_roll_begin, and ao_root_tactics / ao_set_root_bar still fail inside a roll: the caller's own masks do not
+ * combine with a roll. ao_roll_end (and every failure that closes a roll) leaves the engine so that the next synchronous
+ * move clears the sentinels of barred root children, as a move after a barred move does. */
+int ao_roll_set_tactics(ao_engine *e, int32_t max_depth, int32_t max_nodes, int32_t solved_sims, int32_t want_allowed);
+/* Index-aligned with the records of the LAST ao_roll_run: entry b is what the solver said at the root of the move that
+ * record b played (verdict AO RT_*: 0 none, 1 win, 2 defend, 3 lost; depth; nodes; unknown bits, as ao_root_tactics;
+ * allowed [count][A], which needs want_allowed). Any pointer may be NULL. */
+int ao_roll_tactics_records(ao_engine *e, int32_t *verdict, int32_t *depth, int32_t *nodes, int32_t *unknown, uint8_t *allowed);
+/* out[6], since the roll was opened: batches started, games solved, turns that games spent waiting for a verdict (summed
+ * over the games), times the host had to wait for a batch, solver nodes summed over the records, and bytes moved between host
+ * and device for tactics (also counted in ao_roll_stats' bytes). */
+int ao_roll_tactics_stats(ao_engine *e, int64_t *out);
 
 /* ---- root move restriction ("the bar", no reference counterpart) ----
  * host_allowed uint8 [G][A]: 1 = the cell may be searched at game g's root in the NEXT ao_begin_move* / ao_search*; NULL

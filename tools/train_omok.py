@@ -98,6 +98,8 @@ def main():
                     help="self-play as one rolling search per call (main.configure(rolling=True)): every game ends its move, plays and begins "
                          "the next one on its own clock inside one launch loop; not with --tactics")
     ap.add_argument("--turn-every", type=int, default=None, metavar="N", help="with --rolling: launches between two turns (default: engine.SETTLE_EVERY)")
+    ap.add_argument("--roll-tactics", action="store_true",
+                    help="with --rolling: the forced-win solver restricts the roots, running beside the launch loop (main.configure(roll_tactics=True))")
     ap.add_argument("--leaf-symmetry", type=int, nargs="?", const=0, default=None, metavar="KEY",
                     help="every self-play leaf is evaluated under a symmetry of the board drawn from (KEY, the episode's seed, ply, "
                          "simulation) (main.configure(leaf_symmetry=KEY)); KEY defaults to 0")
@@ -137,7 +139,7 @@ def main():
                 device_replay=True, carry_over=not a.no_carry_over, oversubscribe=a.oversubscribe, rows=a.rows,
                 fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob,
                 tactics=True if a.tactics else None, forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32",
-                rolling=a.rolling, turn_every=a.turn_every, leaf_symmetry=a.leaf_symmetry)
+                rolling=a.rolling, turn_every=a.turn_every, leaf_symmetry=a.leaf_symmetry, roll_tactics=a.roll_tactics or None)
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
