@@ -86,6 +86,8 @@ SYMBOLS = {
     "ao_seed_games": (C.c_int, [_vp, _i32p, _u32p, C.c_int32]),
     "ao_set_leaf_symmetry": (C.c_int, [_vp, C.c_int, C.c_uint32]),
     "ao_set_leaf_symmetry_keys": (C.c_int, [_vp, _i32p, _u32p, C.c_int32]),
+    "ao_set_leaf_tactics": (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    "ao_leaf_tactics_stats": (C.c_int, [_vp, _i64p, _i32p, C.c_int]),
     "ao_get_rng_state": (C.c_int, [_vp, C.c_int, _u32p, _i32p, _i32p, _f64p]),
     "ao_set_rng_state": (C.c_int, [_vp, C.c_int, _u32p, C.c_int32, C.c_int32, C.c_double]),
     "ao_reset": (C.c_int, [_vp, _u8p]),

@@ -89,11 +89,16 @@ class _TreeView(object):
 
 
 class ZeroAgent(Agent):
-    def __init__(self, board_size, num_mcts, inplanes, noise=True, device=0, node_cap=0, leaf_symmetry=None):
+    def __init__(self, board_size, num_mcts, inplanes, noise=True, device=0, node_cap=0, leaf_symmetry=None, leaf_tactics=None):
         """leaf_symmetry: None, or an int key -- every leaf of the search is then evaluated under a symmetry of the board
-        drawn from (key, stones on the leaf, simulation index) (Engine.set_leaf_symmetry)."""
+        drawn from (key, stones on the leaf, simulation index) (Engine.set_leaf_symmetry).
+        leaf_tactics: None / False, True (max_depth 2, max_nodes 16) or dict(max_depth, max_nodes) -- a leaf whose mover has a
+        proven forced win by continuous fours is valued +1 (Engine.set_leaf_tactics). A one-game engine then runs without the
+        fused per-game step."""
         super(ZeroAgent, self).__init__(board_size)
         self.leaf_symmetry = leaf_symmetry
+        from . import utils
+        self.leaf_tactics = utils.leaf_tactics_limits(leaf_tactics)
         self.board_size = board_size
         self.num_mcts = num_mcts
         self.inplanes = inplanes
@@ -119,6 +124,8 @@ class ZeroAgent(Agent):
                                   alpha=float(self.alpha), win_mark=self.win_mark)
             if self.leaf_symmetry is not None:
                 self._engine.set_leaf_symmetry(self.leaf_symmetry)
+            if self.leaf_tactics is not None:
+                self._engine.set_leaf_tactics(*self.leaf_tactics)
         return self._engine
 
     # -- reference API ----------------------------------------------------------------------

@@ -77,6 +77,13 @@ struct LaunchLoop {
     unsigned counted(int64_t i) const;   // what launch i counted, once harvested (until the ring wraps again)
     int advance();                       // behind a network launch: the next selection launch and its counter word
     int harvest(int64_t upto);           // sums up the launches [harvested, upto); synchronises if there are any
+    // Leaf tactics (ao_set_leaf_tactics), called on either side of every network launch that a tree launch follows; nothing at
+    // all with the switch off. before_net: the solver on the leaves of the last selection, on the engine's second stream behind
+    // an event recorded here -- it runs beside the network. Otherwise (behind the network launch and the eval log): the engine's
+    // stream waits for the solver's event and writes +1 into the rows of the proven leaves. lt_serial (AO_LEAF_TACTICS_SERIAL,
+    // read by plan()): both kernels on the engine's own stream behind the network launch instead; the same bits.
+    bool lt_serial = false;
+    int leaf_tactics(bool before_net);
 };
 
 // The rolling search (ao_roll_*, at the end of this file): what lives from ao_roll_begin to ao_roll_end. The rules are
@@ -215,6 +222,13 @@ struct ao_engine : ao::HandleBase {
     uint32_t* d_sym_key = nullptr;
     bool sym_on = false;
     uint32_t sym_base = 0;
+    // leaf tactics (ao_set_leaf_tactics): the solver's limits (lt_depth == 0: off), its stream and the two events of a launch
+    // pair, the byte and the counters of every game; all made by the first call that switches it on
+    int lt_depth = 0, lt_nodes = 0;
+    hipStream_t lt_stream = nullptr;
+    hipEvent_t lt_ready = nullptr, lt_done = nullptr;   // engine stream: the leaves are written; solver stream: the bytes are
+    uint8_t* d_lt_proven = nullptr;                     // [G]
+    int32_t* d_lt_counts = nullptr;                     // [G][4] searched, proven, out of nodes, nodes
 };
 
 // The keys of the games as the device must see them. A seed call ends here as well: an episode's symmetries follow its seed.
@@ -258,6 +272,7 @@ int LaunchLoop::plan(ao_engine* e_, ao_net* net, int rows) {
     }
     // select | net | expand+select | net | ... | expand(+idle select): one launch fewer per simulation
     // than the step-wise protocol, same device code (tree_device.hpp).
+    lt_serial = getenv("AO_LEAF_TACTICS_SERIAL") != nullptr;   // (read per search, as AO_CATCHUP_ROUNDS is)
     p = e->tp;
     p.batch_nchw = nullptr; p.policy = e->d_policy; p.value = e->d_value; p.row_of_game = e->d_row;
     p.nchq_live = (e->cfg.inplanes + 3) / 4;
@@ -290,6 +305,33 @@ int LaunchLoop::harvest(int64_t upto) {   // (each of the launches [harvested, u
     if (traffic) *traffic += sizeof(unsigned) * (s.head + s.tail);
     for (int64_t i = harvested; i < upto; ++i) e->rs.add(counted(i), cap_rows);
     harvested = upto;
+    return 0;
+}
+
+// the solver on the leaves that stand in p.leaf_pos, queued on `s` (leaf_tactics.hip)
+static void leaf_tactics_search(ao_engine* e, const ao::TreeParams& p, hipStream_t s) {
+    ao::LeafTacticsParams q{};
+    q.leaf_pos = p.leaf_pos; q.leaf_status = p.leaf_status; q.active = p.active;
+    q.G = p.G; q.B = p.B; q.A = p.A; q.win_mark = p.win_mark; q.max_depth = e->lt_depth; q.max_nodes = e->lt_nodes;
+    q.proven = e->d_lt_proven; q.counts = e->d_lt_counts;
+    ao::launch_leaf_tactics(q, s);
+}
+
+int LaunchLoop::leaf_tactics(bool before_net) {
+    if (e->lt_depth == 0) return 0;
+    if (before_net) {
+        if (lt_serial) return 0;
+        AO_HIP(e, hipEventRecord(e->lt_ready, e->stream));
+        AO_HIP(e, hipStreamWaitEvent(e->lt_stream, e->lt_ready, 0));
+        leaf_tactics_search(e, p, e->lt_stream);
+        AO_HIP(e, hipGetLastError());
+        AO_HIP(e, hipEventRecord(e->lt_done, e->lt_stream));
+        return 0;
+    }
+    if (lt_serial) leaf_tactics_search(e, p, e->stream);
+    else AO_HIP(e, hipStreamWaitEvent(e->stream, e->lt_done, 0));
+    ao::launch_leaf_values(e->d_lt_proven, p.row_of_game, e->d_value, p.G, e->stream);
+    AO_HIP(e, hipGetLastError());
     return 0;
 }
 
@@ -368,6 +410,12 @@ void ao_destroy(ao_engine* e) {
     }
     if (t.h_words) hipHostFree(t.h_words);
     if (t.h_allowed) hipHostFree(t.h_allowed);
+    if (e->lt_stream) {   // (a call that failed between the solver's launch and its join may have left it running)
+        hipStreamSynchronize(e->lt_stream);
+        if (e->lt_ready) hipEventDestroy(e->lt_ready);
+        if (e->lt_done) hipEventDestroy(e->lt_done);
+        hipStreamDestroy(e->lt_stream);
+    }
     e->pool.free_all();
     if (e->h_mt) hipHostFree(e->h_mt);
     if (e->h_pos) hipHostFree(e->h_pos);
@@ -678,6 +726,49 @@ int ao_set_leaf_symmetry_keys(ao_engine* e, const int32_t* games, const uint32_t
     AO_HIP(e, hipSetDevice(e->cfg.device));
     for (int k = 0; k < n; ++k) e->sym_keys[games[k]] = keys[k];
     return sym_upload(e);
+}
+
+// ---- leaf tactics ------------------------------------------------------------------------------
+// The limits live in the engine, where both launch loops read them at every launch (LaunchLoop::leaf_tactics): an open roll
+// needs no copy. Refused like ao_set_leaf_symmetry: a move's leaves so far were valued under the old switch.
+int ao_set_leaf_tactics(ao_engine* e, int32_t max_depth, int32_t max_nodes) {
+    if (max_depth != 0) {   // (before anything touches the device)
+        const std::string bad = ao::fw_limits_error("ao_set_leaf_tactics", max_depth, max_nodes, ao::kLeafMaxNodes);
+        if (!bad.empty()) return e->fail(bad);
+        if (e->tp.win_mark < 3 || e->tp.win_mark > 5 || e->tp.win_mark > e->cfg.board)
+            return e->fail("ao_set_leaf_tactics: the solver needs win_mark in 3..5 and at most the board size");
+    }
+    if (e->in_move) return e->fail("ao_set_leaf_tactics inside a move (its leaves so far were valued under the old switch)");
+    for (int g = 0; g < e->G; ++g)
+        if (roll_refuses_game(e, "ao_set_leaf_tactics", g)) return 1;
+    if (max_depth != 0 && !e->lt_stream) {
+        AO_HIP(e, hipSetDevice(e->cfg.device));
+        if (!e->d_lt_proven && (e->pool.alloc(e, &e->d_lt_proven, e->G) || e->pool.alloc(e, &e->d_lt_counts, static_cast<size_t>(e->G) * 4))) return 1;
+        AO_HIP(e, hipMemsetAsync(e->d_lt_proven, 0, e->G, e->stream));
+        AO_HIP(e, hipMemsetAsync(e->d_lt_counts, 0, sizeof(int32_t) * 4 * e->G, e->stream));
+        AO_HIP(e, hipStreamSynchronize(e->stream));
+        if (!e->lt_ready) AO_HIP(e, hipEventCreateWithFlags(&e->lt_ready, hipEventDisableTiming));
+        if (!e->lt_done) AO_HIP(e, hipEventCreateWithFlags(&e->lt_done, hipEventDisableTiming));
+        AO_HIP(e, hipStreamCreateWithFlags(&e->lt_stream, hipStreamNonBlocking));
+    }
+    e->lt_depth = max_depth;
+    e->lt_nodes = max_depth != 0 ? max_nodes : 0;
+    return 0;
+}
+
+int ao_leaf_tactics_stats(ao_engine* e, int64_t out[4], int32_t* per_game, int reset) {
+    for (int k = 0; out && k < 4; ++k) out[k] = 0;
+    if (per_game) std::fill(per_game, per_game + static_cast<size_t>(e->G) * 4, 0);
+    if (!e->d_lt_counts) return 0;   // never switched on
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->lt_stream));
+    std::vector<int32_t> h(static_cast<size_t>(e->G) * 4);
+    AO_HIP(e, hipMemcpy(h.data(), e->d_lt_counts, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; out && i < h.size(); ++i) out[i & 3] += h[i];
+    if (per_game) std::copy(h.begin(), h.end(), per_game);
+    if (reset) AO_HIP(e, hipMemset(e->d_lt_counts, 0, sizeof(int32_t) * h.size()));
+    return 0;
 }
 
 // ---- the root bar ----------------------------------------------------------------------------
@@ -1033,6 +1124,13 @@ int ao_apply_evals(ao_engine* e, const float* dev_policy, const float* dev_value
     ao::TreeParams p = e->tp;
     p.policy = dev_policy;
     p.value = dev_value;
+    if (e->lt_depth != 0) {
+        // leaf tactics: the caller's values stay untouched -- the tree launch reads a copy in which the proven leaves hold +1
+        AO_HIP(e, hipMemcpyAsync(e->d_value, dev_value, sizeof(float) * e->G, hipMemcpyDeviceToDevice, e->stream));
+        leaf_tactics_search(e, p, e->stream);
+        ao::launch_leaf_values(e->d_lt_proven, p.row_of_game, e->d_value, e->G, e->stream);
+        p.value = e->d_value;
+    }
     ao::launch_expand_backup(p, e->stream);
     AO_HIP(e, hipGetLastError());
     if (e->sims_left > 0) --e->sims_left;
@@ -1200,7 +1298,9 @@ struct MoveSearch {
         ao::TreeParams& p = loop.p;
         // A few games (the per-board network path): heads, tree step and the next leaf's conv1 are ONE launch per game
         // (k_step_board), the network is asked for the residual blocks alone -- 9 launches per simulation instead of 11.
-        fused = cap_rows == rows && ao::net_step_params(net, rows, e->d_policy, e->d_value, &step) != 0;
+        // (not with leaf tactics: the step computes its own heads, no launch stands between the value and its reader. A one-game
+        // ZeroAgent then pays the 11 launches per simulation of the unfused path plus the solver's two: DESIGN.md section 4)
+        fused = cap_rows == rows && e->lt_depth == 0 && ao::net_step_params(net, rows, e->d_policy, e->d_value, &step) != 0;
         // (AO_DYNAMIC_ROWS is opt-in: the hand-out costs one atomic per workgroup on one word, ~11 ns each -- 10 us on top of a 20 us tree
         // kernel when 4096 descents of equal depth arrive together, profiles/r5a_row_alloc_atomics.txt; it pays when leaves are terminal)
         loop.per_sim = !fused && !dev.static_rows && (e->row_cap > 0 || dev.dynamic_rows);
@@ -1255,11 +1355,13 @@ struct MoveSearch {
 
     // the one place that queues a network launch followed by a tree launch
     int one_sim() {
+        if (loop.leaf_tactics(true)) return 1;
         if (ao::net_forward_il(net, loop.net_in, loop.cap_rows, e->d_policy, e->d_value, e->stream, loop.in_kind, fused ? (first_sim ? 3 : 2) : 7,
                                loop.slot(loop.launch), static_cast<unsigned>(loop.cap_rows)))
             return e->fail(std::string("network forward failed: ") + ao_net_last_error(net));
         first_sim = false;
         log_evals(fused ? 2 : 3);   // (before the tree kernel moves on / hands out the next simulation's rows)
+        if (loop.leaf_tactics(false)) return 1;   // (behind the log: it records what the network said)
         const bool timed = e->timer.tick();   // (see ao_tree_timing)
         if (timed) e->timer.begin(e->stream);
         if (loop.advance()) return 1;
@@ -2471,9 +2573,11 @@ int ao_roll_drain(ao_engine* e) {
 // one launch of the loop: the network on the rows the last selection handed out, then expansion + backup and the next selection
 static int roll_launch(ao_engine* e) {
     LaunchLoop& loop = e->roll.loop;
+    if (loop.leaf_tactics(true)) return 1;
     if (ao::net_forward_il(e->roll.net, loop.net_in, loop.cap_rows, e->d_policy, e->d_value, e->stream, loop.in_kind, 7, loop.slot(loop.launch),
                            static_cast<unsigned>(loop.cap_rows)))
         return roll_fail(e, std::string("ao_roll_run: network forward failed: ") + ao_net_last_error(e->roll.net));
+    if (loop.leaf_tactics(false)) return 1;
     const bool timed = e->timer.tick();   // (see ao_tree_timing)
     if (timed) e->timer.begin(e->stream);
     if (loop.advance()) return 1;

@@ -151,6 +151,18 @@ struct RootTacticsBufs {
     uint64_t* bar;        // [G][kBBWords] the caller's bar in, the bar of the move out (TreeParams::bar); or null
 };
 
+// What k_leaf_tactics (leaf_tactics.hip; ao_set_leaf_tactics, engine.hip) takes: the forced-win solver on the leaves of the
+// simulation under way. proven: 1 where the leaf's mover has a proven forced win (0 for every game the launch did not search).
+// counts: per game, cumulative -- leaves searched, proven, searches that ran out of max_nodes, solver nodes.
+struct LeafTacticsParams {
+    const Pos* leaf_pos;          // [G] TreeParams::leaf_pos
+    const int32_t* leaf_status;   // [G] TreeParams::leaf_status
+    const uint8_t* active;        // [G] or null
+    int G, B, A, win_mark, max_depth, max_nodes;
+    uint8_t* proven;              // [G]
+    int32_t* counts;              // [G][4]
+};
+
 __host__ __device__ inline size_t node_slot(const TreeParams& p, int arena, int g, int node) {
     return (static_cast<size_t>(arena) * p.G + g) * p.cap + node;
 }

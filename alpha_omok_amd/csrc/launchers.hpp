@@ -62,6 +62,10 @@ void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_dep
 // the list form: the same three kernels on n compact position rows, every buffer of b indexed by the row (a batch of the rolling search)
 void launch_root_tactics_rows(const Pos* rows, int n, int B, int A, int win_mark, int max_depth, int max_nodes, const RootTacticsBufs& b,
                               hipStream_t s);
+// leaf_tactics.hip: the forced-win solver on the leaves of the simulation under way (k_leaf_tactics), and +1 into the value row
+// of every proven leaf (k_leaf_values; row_of_game null: row g)
+void launch_leaf_tactics(const LeafTacticsParams& q, hipStream_t s);
+void launch_leaf_values(const uint8_t* proven, const int32_t* row_of_game, float* value, int G, hipStream_t s);
 // step_kernels.hip
 void launch_step_board(const TreeParams& p, const StepNet& f, int rows, const int32_t* game_of_row, hipStream_t s);
 // net.hip

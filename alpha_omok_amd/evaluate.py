@@ -99,13 +99,16 @@ class _ZeroSide:
     """One network's side of evaluate_batched: a G-game engine + evaluator; searches the masked matches at their ids."""
 
     def __init__(self, model, sims, board_size, inplanes, G, device, early_stop=False, tactics=None, forward_precision=None,
-                 leaf_symmetry=None, seeds=None):
+                 leaf_symmetry=None, seeds=None, leaf_tactics=None):
         from .engine import Engine
         from .evaluator import Evaluator
         self.eng = Engine(board_size, sims, inplanes, games=G, noise=False, device=device)
         if leaf_symmetry is not None:
             # the matches' streams are handed from side to side as states, not seeds: the keys are set from the matches' seeds directly
             self.eng.set_leaf_symmetry(leaf_symmetry, keys=[utils.leaf_key(leaf_symmetry, s) for s in seeds])
+        limits = utils.leaf_tactics_limits(leaf_tactics)
+        if limits is not None:
+            self.eng.set_leaf_tactics(*limits)
         self.ev, self.model = Evaluator(device), model
         if forward_precision is not None:
             self.ev.net_precision = forward_precision    # Net.precision of this side's exported network ("fp16": the opt-in one-product forward)
@@ -170,7 +173,8 @@ def check_forward_precision(forward_precision):
 
 def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mcts_enemy=None, inplanes=5, n_match=12,
                      player_elo=1500.0, enemy_elo=1500.0, seed=0, device=0, max_plies=None, monitor_model=None,
-                     n_mcts_monitor=None, early_stop=False, tactics=None, forward_precision=None, leaf_symmetry=None):
+                     n_mcts_monitor=None, early_stop=False, tactics=None, forward_precision=None, leaf_symmetry=None,
+                     leaf_tactics=None):
     """All n_match games at once (colours swapped every game, eval_main.py:213-333). `*_model`: whatever
     ZeroAgent.model accepts (a PVNet-shaped module runs on the native forward), or 'puct' / 'uct' for the rollout
     agents (eval_main.py:68-73,106-111). With a rollout PLAYER and a `monitor_model`, the monitor ZeroAgent searches
@@ -184,7 +188,10 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     enemy's); None leaves the default. A side given as an engine.Net keeps the precision it was set to.
     leaf_symmetry: an int key -- the ZeroAgent sides evaluate every leaf under a symmetry of the board drawn per leaf
     (Engine.set_leaf_symmetry; match i's key is utils.leaf_key(key, seed + i)) -- for both, or a pair (player's, enemy's) with None
-    for a side that searches plainly, as for tactics."""
+    for a side that searches plainly, as for tactics.
+    leaf_tactics: True or dict(max_depth, max_nodes) -- the ZeroAgent sides value a leaf whose mover has a proven forced win +1
+    (Engine.set_leaf_tactics) -- for both, or a pair (player's, enemy's) with None for a side that searches plainly. Each side
+    has its own engine."""
     forward_precision = check_forward_precision(forward_precision)
     n_mcts_enemy = n_mcts_player if n_mcts_enemy is None else n_mcts_enemy
     G = n_match
@@ -197,15 +204,20 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     side_sym = tuple(leaf_symmetry) if isinstance(leaf_symmetry, (tuple, list)) else (leaf_symmetry, leaf_symmetry)
     if len(side_sym) != 2:
         raise ValueError("leaf_symmetry: one value for both sides or a pair (player, enemy)")
+    side_leaf = tuple(leaf_tactics) if isinstance(leaf_tactics, (tuple, list)) else (leaf_tactics, leaf_tactics)
+    if len(side_leaf) != 2:
+        raise ValueError("leaf_tactics: one value for both sides or a pair (player, enemy)")
+    for lt in side_leaf:
+        utils.leaf_tactics_limits(lt)            # (a bad value is an argument error before any engine exists)
     match_seeds = [(seed + i) & 0xFFFFFFFF for i in range(G)]
 
-    def make(model, sims, tac, prec, sym):
+    def make(model, sims, tac, prec, sym, leaf):
         if isinstance(model, str):
             return _RolloutSide(model, sims, board_size, G, device)
-        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac, prec, sym, match_seeds)
+        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac, prec, sym, match_seeds, leaf)
 
-    sides = [make(player_model, n_mcts_player, side_tactics[0], forward_precision[0], side_sym[0]),
-             make(enemy_model, n_mcts_enemy, side_tactics[1], forward_precision[1], side_sym[1])]
+    sides = [make(player_model, n_mcts_player, side_tactics[0], forward_precision[0], side_sym[0], side_leaf[0]),
+             make(enemy_model, n_mcts_enemy, side_tactics[1], forward_precision[1], side_sym[1], side_leaf[1])]
     monitor = None
     if monitor_model is not None and isinstance(player_model, str):
         monitor = _ZeroSide(monitor_model, n_mcts_monitor or n_mcts_enemy, board_size, inplanes, G, device)

@@ -455,6 +455,59 @@ def root_tactics(moves, board_size, win_mark, max_depth=6, max_nodes=512):
     return out
 
 
+LEAF_MAX_NODES = 1024        # Engine.set_leaf_tactics: max_nodes 1..1024 (the solver runs once per simulation)
+
+
+def leaf_tactics_value(moves, board_size, win_mark, value, max_depth, max_nodes):
+    """The value of the leaf reached by `moves` under leaf tactics (Engine.set_leaf_tactics), by forced_win alone: exactly
+    np.float32(1.0) where the side to move has a proven forced win by continuous fours -- the value is the leaf mover's own
+    (the search backs up -value into the leaf's record) -- and `value` as it is otherwise: no forced win within max_depth, a
+    search that ran out of max_nodes (FW_UNKNOWN), a terminal position. No reference counterpart."""
+    if forced_win(moves, board_size, win_mark, max_depth, max_nodes)["result"] == FW_WIN:
+        return np.float32(1.0)
+    return value
+
+
+def leaf_tactics_evaluator(evaluator, board_size, win_mark, max_depth, max_nodes):
+    """The evaluator of a search with leaf tactics, around evaluator(moves, planes, sim) -> (policy, value): the policy as it
+    is, the value through leaf_tactics_value. A search with the switch on is the reference search under this evaluator."""
+    def f(moves, planes, sim):
+        p, v = evaluator(moves, planes, sim)
+        return p, leaf_tactics_value(moves, board_size, win_mark, v, max_depth, max_nodes)
+    return f
+
+
+def leaf_tactics_limits(leaf_tactics):
+    """The leaf_tactics= argument of ZeroAgent / evaluate_batched / main.configure as (max_depth, max_nodes), or None for off
+    (None / False): True is the default 2 / 16 -- see Engine.set_leaf_tactics --, a dict names max_depth and / or
+    max_nodes. ValueError for anything else or limits outside 1..16 / 1..LEAF_MAX_NODES."""
+    if leaf_tactics is None or leaf_tactics is False:
+        return None
+    if leaf_tactics is True:
+        d, n = 2, 16
+    elif isinstance(leaf_tactics, dict):
+        extra = set(leaf_tactics) - {"max_depth", "max_nodes"}
+        if extra:
+            raise ValueError("leaf_tactics: unknown keys %r" % sorted(extra))
+        d, n = leaf_tactics.get("max_depth", 2), leaf_tactics.get("max_nodes", 16)
+    else:
+        raise ValueError("leaf_tactics must be None, False, True or a dict(max_depth, max_nodes), got %r" % (leaf_tactics,))
+    for name, v, hi in (("max_depth", d, FW_MAX_DEPTH), ("max_nodes", n, LEAF_MAX_NODES)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError("leaf_tactics: %s must be an integer in 1..%d, got %r" % (name, hi, v))
+    return int(d), int(n)
+
+
+def parse_leaf_tactics(text):
+    """The command line's --leaf-tactics value "DEPTH,NODES" as the dict configure(leaf_tactics=) takes; None stays None."""
+    if text is None:
+        return None
+    parts = str(text).split(",")
+    if len(parts) != 2:
+        raise ValueError("--leaf-tactics takes DEPTH,NODES, got %r" % (text,))
+    return dict(max_depth=int(parts[0]), max_nodes=int(parts[1]))
+
+
 def check_allowed(allowed, games, cells):
     """The `allowed` argument of Engine.begin_move / search as uint8 [games, cells] (None stays None). ValueError for
     another shape or for values that are not 0 / 1 / bool."""

@@ -103,6 +103,32 @@ int ao_set_rng_state(ao_engine *e, int game, const uint32_t *host_mt, int32_t po
 int ao_set_leaf_symmetry(ao_engine *e, int enable, uint32_t base_key);
 int ao_set_leaf_symmetry_keys(ao_engine *e, const int32_t *host_games, const uint32_t *host_keys, int32_t n);
 
+/* ---- leaf tactics ---- (opt-in; no reference counterpart; off, every result is bit for bit what it is without these calls)
+ * With the switch on, the forced-win solver of ao_positions_forced_wins (continuous fours, utils.forced_win) runs on every
+ * leaf the search expands -- a fresh root included -- for the side to move there, and its PROOF overrides the value:
+ *   leaf_tactics_value(moves, value) = 1.0f   if forced_win(moves, board, win_mark, max_depth, max_nodes).result == FW_WIN
+ *                                      value  otherwise: FW_NONE, FW_UNKNOWN (the node budget ran out), a terminal position
+ * (alpha_omok_amd/utils.py: leaf_tactics_value, leaf_tactics_evaluator). The value is the leaf mover's own (agents.py:223-239
+ * backs up -value into the leaf's record), so a forced win for the side to move is +1. Nothing else changes: not the policy
+ * row, the noise, the selection, the MT19937 streams or the terminal leaves -- a search with leaf tactics is the reference
+ * search under the evaluator f(moves, planes, sim) = (p, leaf_tactics_value(moves, v)) with (p, v) the plain evaluation, and
+ * that is all it is. The opponent's threats (a leaf that is proven LOST) are not looked for, and the network still evaluates
+ * a proven leaf: its priors are needed.
+ * max_depth 1..16, max_nodes 1..1024 (checked before the device is touched); max_depth == 0 switches off (max_nodes is
+ * ignored). win_mark must be 3..5 and at most the board size. Fails inside a move and, while a roll is open, if any game is in
+ * a move of the roll (the rules of ao_set_leaf_symmetry). It holds for ao_search*, the rolling search and the step-wise protocol
+ * (ao_apply_evals reads the caller's values, which stay untouched, and expands from a copy), combines with leaf symmetries,
+ * budgets, early stop, the root bar, over-subscription and every forward mode and precision; the fp16-range repeat searches its
+ * move again under the same switch (the counters then count both runs). With the switch on the fused per-game step is not
+ * planned (a handful of games pay the unfused launch sequence). Tree snapshots do not carry the switch. In ao_search* and the
+ * roll the solver runs on a stream of the engine's own beside the network launch; the environment variable
+ * AO_LEAF_TACTICS_SERIAL (read by every search) queues it on the engine's stream behind the network instead: the same bits.
+ * ao_leaf_tactics_stats: out[4] = leaves searched, proven, searches that ran out of max_nodes, solver nodes, summed over the
+ * games since the last reset (or since the switch first went on); per_game [G][4] the same per game, or NULL; reset != 0 zeroes
+ * the counters afterwards. The per-game counters are int32. Synchronises. */
+int ao_set_leaf_tactics(ao_engine *e, int32_t max_depth, int32_t max_nodes);
+int ao_leaf_tactics_stats(ao_engine *e, int64_t out[4], int32_t *host_per_game, int reset);
+
 /* ---- game / tree state ---- */
 /* ZeroAgent.reset() (agents.py:55-58) for the games with mask[g] != 0 (NULL = all): clears the
  * tree and the move list (root id becomes (0,)). */
@@ -483,7 +509,8 @@ int ao_row_stats(ao_engine *e, int64_t *launches, int64_t *rows_live, int64_t *r
  * status (1 / 2: the leaf waits for exactly this evaluation; 3: terminal leaf, no evaluation -- the reference evaluates and
  * discards; 0 / 4 / 5: nothing of this game was evaluated in this launch). Launches beyond capacity_floats are not recorded;
  * n == 0 switches the log off; dev_log must stay valid until then (or until ao_destroy). ao_eval_log_count: the launches
- * recorded so far. */
+ * recorded so far. With leaf tactics on (ao_set_leaf_tactics) the log records what the NETWORK said: the override of a
+ * proven leaf's value is written behind it. */
 int ao_set_eval_log(ao_engine *e, const int32_t *host_games, int32_t n, float *dev_log, int64_t capacity_floats);
 int ao_eval_log_count(ao_engine *e);
 

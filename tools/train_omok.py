@@ -103,6 +103,9 @@ def main():
     ap.add_argument("--leaf-symmetry", type=int, nargs="?", const=0, default=None, metavar="KEY",
                     help="every self-play leaf is evaluated under a symmetry of the board drawn from (KEY, the episode's seed, ply, "
                          "simulation) (main.configure(leaf_symmetry=KEY)); KEY defaults to 0")
+    ap.add_argument("--leaf-tactics", nargs="?", const="2,16", default=None, metavar="DEPTH,NODES",
+                    help="a self-play leaf whose mover has a proven forced win by continuous fours is valued +1 "
+                         "(main.configure(leaf_tactics=dict(max_depth=DEPTH, max_nodes=NODES))); defaults to 2,16")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--resume", default=None, help="state_dict to start from")
     ap.add_argument("--save-replay", default=None, metavar="PATH",
@@ -113,7 +116,7 @@ def main():
 
     import torch
     import alpha_omok_amd.main as m
-    from alpha_omok_amd import evaluate
+    from alpha_omok_amd import evaluate, utils
     from alpha_omok_amd.pvnet import PVNet
 
     os.makedirs(a.out, exist_ok=True)
@@ -139,7 +142,8 @@ def main():
                 device_replay=True, carry_over=not a.no_carry_over, oversubscribe=a.oversubscribe, rows=a.rows,
                 fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob,
                 tactics=True if a.tactics else None, forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32",
-                rolling=a.rolling, turn_every=a.turn_every, leaf_symmetry=a.leaf_symmetry, roll_tactics=a.roll_tactics or None)
+                rolling=a.rolling, turn_every=a.turn_every, leaf_symmetry=a.leaf_symmetry, roll_tactics=a.roll_tactics or None,
+                leaf_tactics=utils.parse_leaf_tactics(a.leaf_tactics))
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
