@@ -309,6 +309,10 @@ __device__ __forceinline__ void conv_cells_tile_h(const float4* __restrict__ in,
                 v.z = fmaf(acc[2], e_sc.z, e_sh.z); v.w = fmaf(acc[3], e_sc.w, e_sh.w);
                 if (relu_res) { v.x += e_res.x; v.y += e_res.y; v.z += e_res.z; v.w += e_res.w; }
                 v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                // this path keeps its activations in fp32 and clamps them where the next conv splits them: the LAST layer is
+                // read by the heads alone, unclamped. It is reported here all the same, so that what ao_net_status says of a
+                // network and a position does not depend on which kernel the batch size planned (live boards, real cells only)
+                peak = fmaxf(peak, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
                 out[o_idx] = v;
             }
         }

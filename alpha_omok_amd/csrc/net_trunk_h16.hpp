@@ -454,7 +454,10 @@ static __device__ __forceinline__ void run(const void* src, uint4* dst, const Tr
     // (conv1 on its resident board, RES1, reads neither buffer as such: the board spans both, and the one barrier in front of
     // its hand-off epilogues is what frees them.) A last layer that hands its two rows to the heads does so exactly as to a next
     // layer; trunk_heads finds row BW-1 in the buffer `par` would name next and row BW-2 in the other one.
-    const int po = (BW & 1) ? 0 : par;
+    // (A layer that was handed nothing -- conv1, the 3-byte format, the knock-out builds -- stages its row 0 into buffer 0
+    // itself, whatever par says: the resident kernel toggles par per layer for every format, and with an even BW the 3-byte
+    // format read its rows from the buffer the other parity names -- every board of AO_TRUNK_FMT=1 wrong at widths 4, 6, 8.)
+    const int po = ((BW & 1) || !HANDED) ? 0 : par;
     uint4* const hand2 = s_x + static_cast<size_t>(FIRST ? 1 : (BW + po) & 1) * NFRO * 64;       // output row BW-2
     uint4* const hand1 = s_x + static_cast<size_t>(FIRST ? 0 : (BW - 1 + po) & 1) * NFRO * 64;   // output row BW-1
     constexpr std::integral_constant<bool, true> kHand{};

@@ -282,7 +282,8 @@ class Engine:
     def leaf_tactics_stats(self, per_game=False, reset=False):
         """dict(searched, proven, unknown, nodes): the leaves the solver searched, those it proved won, the searches that ran out
         of max_nodes and the solver's nodes, since the last reset (ao_leaf_tactics_stats); per_game=True adds `per_game`,
-        int32 [G, 4] in that order."""
+        int32 [G, 4] in that order. A move that search() repeated on the fp32-MFMA trunk (fp16_range_events) counts with BOTH
+        attempts: the leaves of the discarded first one were searched, and nothing but reset=True clears the counters."""
         out = np.zeros(4, np.int64)
         pg = np.zeros((self.G, 4), np.int32) if per_game else None
         self._check(self._L.ao_leaf_tactics_stats(self._h, _ptr(out, C.c_int64), _ptr(pg, C.c_int32), 1 if reset else 0),
@@ -778,6 +779,9 @@ class Engine:
                                             int(capacity_floats)), "ao_set_eval_log")
 
     def eval_log_count(self):
+        """Simulations recorded since set_eval_log (ao_eval_log_count). A move that search() repeated on the fp32-MFMA trunk
+        (fp16_range_events) is in the log with BOTH attempts: the rows of the discarded first one -- clamped evaluations --
+        come first, the repeat's follow them, as long as the buffer has room."""
         return int(self._L.ao_eval_log_count(self._h))
 
     def close(self):

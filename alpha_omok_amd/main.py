@@ -462,7 +462,8 @@ def _check_visits(eng, vis, act, on, inherit, fp16_seen, sims=None):
     got = vis[on].sum(axis=1)
     # (sims: the simulations each game ran when the move had budgets of its own or could stop early -- never more than asked for)
     ran = N_MCTS if sims is None else np.asarray(sims)[on]
-    want = (inherit[on] if ev == fp16_seen else 0) + ran
+    # (a repeated move of a plain search leaves two scalars here: broadcast, or array_equal compares a shape with none)
+    want = np.broadcast_to((inherit[on] if ev == fp16_seen else 0) + ran, got.shape)
     if not np.array_equal(got, want):
         bad = np.flatnonzero(got != want)
         g = int(on[bad[0]])
