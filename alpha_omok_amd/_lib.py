@@ -122,6 +122,9 @@ SYMBOLS = {
                                  _P(C.c_float), _f64p]),
     "ao_tree_pv": (C.c_int, [_vp, _u8p, C.c_int32, _i32p, _i32p, _P(C.c_float), _i32p]),
     "ao_tree_stats": (C.c_int, [_vp, _u8p, _i32p]),
+    "ao_tree_proofs": (C.c_int, [_vp, _u8p, C.c_int32, _i32p, _i8p, _P(C.c_int16), _i32p, _i32p]),
+    "ao_set_proof_moves": (C.c_int, [_vp, C.c_int]),
+    "ao_proof_move_records": (C.c_int, [_vp, _i32p, _i64p, C.c_int]),
     "ao_tree_export": (C.c_int, [_vp, _u8p, _P(AoTreeSnapshot)]),
     "ao_tree_import": (C.c_int, [_vp, _i32p, C.c_int32, _P(AoTreeSnapshot)]),
     "ao_tree_snapshot_check": (C.c_int, [_P(AoTreeSnapshot)]),

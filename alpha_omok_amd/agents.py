@@ -89,13 +89,18 @@ class _TreeView(object):
 
 
 class ZeroAgent(Agent):
-    def __init__(self, board_size, num_mcts, inplanes, noise=True, device=0, node_cap=0, leaf_symmetry=None, leaf_tactics=None):
+    def __init__(self, board_size, num_mcts, inplanes, noise=True, device=0, node_cap=0, leaf_symmetry=None, leaf_tactics=None,
+                 proof_moves=False):
         """leaf_symmetry: None, or an int key -- every leaf of the search is then evaluated under a symmetry of the board
         drawn from (key, stones on the leaf, simulation index) (Engine.set_leaf_symmetry).
         leaf_tactics: None / False, True (max_depth 2, max_nodes 16) or dict(max_depth, max_nodes) -- a leaf whose mover has a
         proven forced win by continuous fours is valued +1 (Engine.set_leaf_tactics). A one-game engine then runs without the
-        fused per-game step."""
+        fused per-game step.
+        proof_moves: True -- get_pi's pi follows what the root's tree proves (Engine.set_proof_moves, utils.proof_pi): one-hot on
+        the fastest proven win, or without the moves that are proven lost; last_proof_verdict tells which (PM_*)."""
         super(ZeroAgent, self).__init__(board_size)
+        self.proof_moves = bool(proof_moves)
+        self.last_proof_verdict = 0
         self.leaf_symmetry = leaf_symmetry
         from . import utils
         self.leaf_tactics = utils.leaf_tactics_limits(leaf_tactics)
@@ -126,6 +131,8 @@ class ZeroAgent(Agent):
                 self._engine.set_leaf_symmetry(self.leaf_symmetry)
             if self.leaf_tactics is not None:
                 self._engine.set_leaf_tactics(*self.leaf_tactics)
+            if self.proof_moves:
+                self._engine.set_proof_moves(True)
         return self._engine
 
     # -- reference API ----------------------------------------------------------------------
@@ -164,6 +171,8 @@ class ZeroAgent(Agent):
         pi, visit, policy = self._evaluator.search(eng, self.model, tau, on_sim=progress, sims=sims,
                                                    early_stop=True if early_stop else None, allowed=allowed, tactics=tactics)
         self.last_tactics = eng.last_tactics()
+        if self.proof_moves:
+            self.last_proof_verdict = int(eng.proof_move_stats(per_game=True)["verdict"][0])
         mt, pos, has_gauss, gauss = eng.get_rng_state(0)
         np.random.set_state(('MT19937', mt, pos, has_gauss, gauss))
         self.message = 'simulation: {}\r'.format(num)
@@ -188,6 +197,21 @@ class ZeroAgent(Agent):
         r = self._engine.principal_variations(max_len)
         k = int(r["len"][0])
         return r["action"][0, :k].copy(), r["n"][0, :k].copy(), r["q"][0, :k].copy()
+
+    def get_proof(self, root_id=None, max_len=None):
+        """What the tree below the current root proves (Engine.tree_proofs; no reference counterpart): dict(status -- PROOF_*
+        for the side to move at the root --, plies to the end of the game, cells int8 [B, B]: the PROOF_* of the move on each
+        cell for the mover, -1 on a cell without a move, cell_plies int16 [B, B], line: the actions of the proof line). root_id:
+        None or the id of the last get_pi / load_tree -- the engine keeps that root's subtree only. Before any search: unknown."""
+        B = self.board_size
+        if root_id is not None and self.root_id is not None and tuple(root_id) != tuple(self.root_id):
+            raise ValueError("get_proof: %r is not the current root %r" % (tuple(root_id), tuple(self.root_id)))
+        if self._engine is None:
+            return dict(status=0, plies=0, cells=np.full((B, B), -1, np.int8), cell_plies=np.zeros((B, B), np.int16),
+                        line=np.zeros(0, np.int32))
+        r = self._engine.tree_proofs(max_len=max_len)
+        return dict(status=int(r["status"][0]), plies=int(r["plies"][0]), cells=r["child_status"][0].reshape(B, B).copy(),
+                    cell_plies=r["child_plies"][0].reshape(B, B).copy(), line=r["line"][0, :int(r["len"][0])].copy())
 
     def save_tree(self, path):
         """Puts the searched position aside: the tree below the current root, its id and the numpy stream position the last

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libomok_hip.so")
 SOURCES = ["tree_kernels.hip", "step_kernels.hip", "engine.hip", "net.hip", "net_w16.hip", "net_f16.hip", "net_f16_layers.hip", "replay.hip", "rollout.hip",
-           "positions.hip", "root_tactics.hip", "leaf_tactics.hip", "tree_readout.hip", "tree_snapshot.hip", "replay_snapshot.hip", "roll.hip"]
+           "positions.hip", "root_tactics.hip", "leaf_tactics.hip", "tree_readout.hip", "tree_proofs.hip", "tree_snapshot.hip", "replay_snapshot.hip", "roll.hip"]
 # every header under csrc/ (listed from the directory, so a new kernel header can never be missing from the staleness
 # check or from source_hash() -- round 4 shipped net_layer_ksplit.hpp outside this list) + the C ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join(INC, "omok_hip.h")]

@@ -229,6 +229,16 @@ struct ao_engine : ao::HandleBase {
     hipEvent_t lt_ready = nullptr, lt_done = nullptr;   // engine stream: the leaves are written; solver stream: the bytes are
     uint8_t* d_lt_proven = nullptr;                     // [G]
     int32_t* d_lt_counts = nullptr;                     // [G][4] searched, proven, out of nodes, nodes
+    // proven outcomes (ao_tree_proofs, ao_set_proof_moves): the proof words' workspace and the root's edge values, made by the
+    // first call that needs them (proofs_alloc); the switch, the verdicts of the last ao_end_move under it and the totals
+    int32_t* d_pf_ws = nullptr;                         // [G][cap] a node's proof word, by arena node
+    int32_t* d_pf_root = nullptr;                       // [G][4]
+    int8_t* d_pf_status = nullptr;                      // [G][A]
+    int16_t* d_pf_plies = nullptr;                      // [G][A]
+    int32_t* d_pf_verdict = nullptr;                    // [G]
+    bool proof_moves = false;
+    std::vector<int32_t> pm_verdict;                    // [G]
+    int64_t pm_totals[4] = {0, 0, 0, 0};
 };
 
 // The keys of the games as the device must see them. A seed call ends here as well: an episode's symmetries follow its seed.
@@ -1187,6 +1197,15 @@ int ao_end_move(ao_engine* e, const int8_t* tau, double* pi, double* visit, doub
         p.tau = nullptr;
     }
     ao::launch_end_move(p, e->stream);
+    int32_t* hv = e->h_i32;   // (the action row of ao_play: free until then)
+    if (e->proof_moves) {
+        // the proofs of the active games behind k_end_move (which wrote the error word of a short game), then pi in place
+        if (ao::launch_tree_proofs(p, p.active, e->d_pf_ws, 1, e->d_pf_root, e->d_pf_status, e->d_pf_plies, nullptr, nullptr, e->stream))
+            return queue_refused(e, "ao_end_move (proof moves)");
+        ao::launch_proof_pi(p, e->d_pf_status, e->d_pf_plies, e->d_pf_verdict, e->stream);
+        AO_HIP(e, hipGetLastError());
+        AO_HIP(e, hipMemcpyAsync(hv, e->d_pf_verdict, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+    }
     const size_t n = static_cast<size_t>(G) * A;
     if (pi) AO_HIP(e, hipMemcpyAsync(e->h_out, p.out_pi, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
     if (visit) AO_HIP(e, hipMemcpyAsync(e->h_out + n, p.out_visit, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
@@ -1195,6 +1214,12 @@ int ao_end_move(ao_engine* e, const int8_t* tau, double* pi, double* visit, doub
     if (pi) std::memcpy(pi, e->h_out, sizeof(double) * n);
     if (visit) std::memcpy(visit, e->h_out + n, sizeof(double) * n);
     if (policy) std::memcpy(policy, e->h_out + 2 * n, sizeof(double) * n);
+    if (e->proof_moves)
+        for (int g = 0; g < G; ++g)
+            if (e->active[g]) {
+                e->pm_verdict[g] = hv[g];
+                e->pm_totals[hv[g] & 3] += 1;
+            }
     // after a search every searched root is expanded (it was expanded by sim 0 at the latest)
     for (int g = 0; g < G; ++g)
         if (e->active[g]) e->status[g] = AO_ROOT_EXPANDED;
@@ -1822,6 +1847,73 @@ int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
         if (h_mask[g] && h[4 * g] < 0) return e->fail("ao_tree_stats: game " + std::to_string(g) + ": the tree reaches more nodes than the arena holds (inconsistent tree)");
     for (size_t g = 0; g < G; ++g)
         if (h_mask[g]) std::memcpy(out + 4 * g, h + 4 * g, 16);
+    return 0;
+}
+
+// ---- proven outcomes (tree_proofs.hip) ----------------------------------------------------------
+static int proofs_alloc(ao_engine* e) {
+    if (e->d_pf_ws) return 0;
+    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A);
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    if (e->pool.alloc(e, &e->d_pf_root, 4 * G) || e->pool.alloc(e, &e->d_pf_status, G * A) || e->pool.alloc(e, &e->d_pf_plies, G * A) ||
+        e->pool.alloc(e, &e->d_pf_verdict, G) || e->pool.alloc(e, &e->d_pf_ws, G * static_cast<size_t>(e->tp.cap)))
+        return 1;
+    AO_HIP(e, hipMemsetAsync(e->d_pf_verdict, 0, sizeof(int32_t) * G, e->stream));
+    return 0;
+}
+
+// utils.tree_proofs of every masked game
+int ao_tree_proofs(ao_engine* e, const uint8_t* mask, int32_t max_len, int32_t* root, int8_t* child_status, int16_t* child_plies,
+                   int32_t* line, int32_t* line_len) {
+    if (roll_refuses(e, "ao_tree_proofs")) return 1;
+    if (e->in_move) return e->fail("ao_tree_proofs inside a move (between ao_begin_move and ao_end_move)");
+    if (max_len < 1 || max_len > e->A) return e->fail("ao_tree_proofs: max_len must be in 1..A");
+    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A), GL = G * static_cast<size_t>(max_len);
+    // workspace layout: line [G][max_len] and line_len [G] (int32), root [G][4] (int32), plies [G][A] (int16), status [G][A], mask [G]
+    const size_t o_len = 4 * GL, o_root = o_len + 4 * G, o_plies = o_root + 16 * G, o_status = o_plies + 2 * G * A, o_mask = o_status + G * A;
+    if (readout_begin(e, "ao_tree_proofs", o_mask + G) || proofs_alloc(e)) return 1;
+    uint8_t* h_mask = e->h_ro.data() + o_mask;
+    readout_mask(e, mask, h_mask);
+    unsigned char* d = e->d_ro.p;
+    AO_HIP(e, hipMemcpyAsync(d + o_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
+    if (ao::launch_tree_proofs(e->tp, d + o_mask, e->d_pf_ws, max_len, reinterpret_cast<int32_t*>(d + o_root), reinterpret_cast<int8_t*>(d + o_status),
+                               reinterpret_cast<int16_t*>(d + o_plies), reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + o_len), e->stream))
+        return queue_refused(e, "ao_tree_proofs");
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), d, o_mask, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    const unsigned char* h = e->h_ro.data();
+    const int32_t* h_root = reinterpret_cast<const int32_t*>(h + o_root);
+    for (size_t g = 0; g < G; ++g)
+        if (h_mask[g] && h_root[4 * g + 3] < 0) return e->fail("ao_tree_proofs: game " + std::to_string(g) + ": the tree reaches more nodes than the arena holds (inconsistent tree)");
+    for (size_t g = 0; g < G; ++g) {
+        if (!h_mask[g]) continue;
+        if (root) std::memcpy(root + 4 * g, h_root + 4 * g, 16);
+        if (child_status) std::memcpy(child_status + g * A, h + o_status + g * A, A);
+        if (child_plies) std::memcpy(child_plies + g * A, h + o_plies + 2 * g * A, 2 * A);
+        if (line) std::memcpy(line + g * max_len, h + 4 * g * max_len, 4 * static_cast<size_t>(max_len));
+        if (line_len) line_len[g] = reinterpret_cast<const int32_t*>(h + o_len)[g];
+    }
+    return 0;
+}
+
+int ao_set_proof_moves(ao_engine* e, int enable) {
+    if (roll_refuses(e, "ao_set_proof_moves")) return 1;
+    if (e->in_move) return e->fail("ao_set_proof_moves inside a move (between ao_begin_move and ao_end_move)");
+    if (enable) {
+        if (!ao::reroot_fits(e->tp)) return queue_refused(e, "ao_set_proof_moves");
+        if (proofs_alloc(e)) return 1;
+        if (e->pm_verdict.empty()) e->pm_verdict.assign(e->G, 0);
+    }
+    e->proof_moves = enable != 0;
+    return 0;
+}
+
+int ao_proof_move_records(ao_engine* e, int32_t* verdict, int64_t totals[4], int reset) {
+    if (verdict)
+        for (int g = 0; g < e->G; ++g) verdict[g] = e->pm_verdict.empty() ? 0 : e->pm_verdict[g];
+    if (totals) std::memcpy(totals, e->pm_totals, sizeof(e->pm_totals));
+    if (reset) std::fill(e->pm_totals, e->pm_totals + 4, 0);
     return 0;
 }
 
@@ -2467,6 +2559,7 @@ int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
     if (!net || !o) return e->fail("ao_roll_begin: null argument");
     if (e->bar_pending || e->bar_on_device) return e->fail("ao_roll_begin: a root bar is pending (ao_set_root_bar / ao_root_tactics with apply): the rolling search has no root bar");
     if (e->log_n > 0) return e->fail("ao_roll_begin: an eval log is set (ao_set_eval_log): the rolling search does not feed it");
+    if (e->proof_moves) return e->fail("ao_roll_begin: proof moves are on (ao_set_proof_moves): the roll's turn on the device does not apply them");
     if (o->turn_every < 1) return e->fail("ao_roll_begin: turn_every must be >= 1");
     RollTactics& t = r.tac;
     const bool armed = t.max_depth > 0;

@@ -57,6 +57,11 @@ void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int 
                         int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
 void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s);
 int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s);
+// tree_proofs.hip: exact minimax over what the roots reach (ws: int32 [G][cap] workspace; non-zero = refused, as launch_tree_stats),
+// and utils.proof_pi on TreeParams::out_pi in place
+int launch_tree_proofs(const TreeParams& p, const uint8_t* mask, int32_t* ws, int max_len, int32_t* root_out, int8_t* child_status,
+                       int16_t* child_plies, int32_t* line, int32_t* line_len, hipStream_t s);
+void launch_proof_pi(const TreeParams& p, const int8_t* child_status, const int16_t* child_plies, int32_t* verdict, hipStream_t s);
 // root_tactics.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
 void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s);
 // the list form: the same three kernels on n compact position rows, every buffer of b indexed by the row (a batch of the rolling search)

@@ -23,6 +23,8 @@ SETTLE_EVERY = 16
 # include/omok_hip.h, the float32 nearest to -1e30. Such a child has n == 0 and w == 0; Engine.root_children shows it.
 BAR_Q = float(np.float32(-1.0e30))
 RT_NONE, RT_WIN, RT_DEFEND, RT_LOST = 0, 1, 2, 3      # `verdict` of Engine.root_tactics / utils.root_tactics
+# Engine.tree_proofs' status of a node for its side to move, and the verdicts of Engine.set_proof_moves (utils.proof_pi)
+from .utils import PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW, PM_NONE, PM_WIN, PM_PRUNED, PM_MOVED  # noqa: E402,F401
 
 
 def _ptr(a, ctype):
@@ -709,6 +711,44 @@ class Engine:
         out = np.full((self.G, 4), -1, np.int32)
         self._check(self._L.ao_tree_stats(self._h, _ptr(mk, C.c_uint8), _ptr(out, C.c_int32)), "ao_tree_stats")
         return dict(expanded=out[:, 0].copy(), entries=out[:, 1].copy(), depth=out[:, 2].copy(), nodes_used=out[:, 3].copy())
+
+    # -- proven outcomes
+    def tree_proofs(self, mask=None, max_len=None):
+        """What every masked game's tree PROVES, by exact minimax over it on the device (ao_tree_proofs; the definition is
+        utils.tree_proofs). Read-only, as the other read-outs; fails inside a move and while a roll is open. Returns a dict:
+        status, plies, proven, walked int32 [G] (the root's PROOF_* for its side to move, plies to the end, proven nodes, nodes
+        walked; -1 for unmasked games), child_status int8 [G, A] (the root's edge by action, -1: no edge), child_plies int16
+        [G, A], line int32 [G, max_len] (the proof line's actions, -1 beyond it; max_len None: A) and len int32 [G]."""
+        L = self.A if max_len is None else int(max_len)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        root = np.full((self.G, 4), -1, np.int32)
+        cs, cp = np.full((self.G, self.A), -1, np.int8), np.zeros((self.G, self.A), np.int16)
+        line, ln = np.full((self.G, L), -1, np.int32), np.zeros(self.G, np.int32)
+        self._check(self._L.ao_tree_proofs(self._h, _ptr(mk, C.c_uint8), L, _ptr(root, C.c_int32), _ptr(cs, C.c_int8),
+                                           _ptr(cp, C.c_int16), _ptr(line, C.c_int32), _ptr(ln, C.c_int32)), "ao_tree_proofs")
+        return dict(status=root[:, 0].copy(), plies=root[:, 1].copy(), proven=root[:, 2].copy(), walked=root[:, 3].copy(),
+                    child_status=cs, child_plies=cp, line=line, len=ln)
+
+    def set_proof_moves(self, on=True):
+        """Proof moves (ao_set_proof_moves): with the switch on, end_move / search rewrite pi by what the root's tree proves
+        before it is returned and played -- utils.proof_pi: one-hot on the fastest proven win, or renormalised over the moves
+        that are not proven lost. visit, policy and the games' streams are what they are without it; the recorded pi is then no
+        longer pure visit counts. Off (the default) nothing runs. Refused inside a move and for an open roll; roll_begin raises
+        while it is on."""
+        self._check(self._L.ao_set_proof_moves(self._h, 1 if on else 0), "ao_set_proof_moves")
+
+    def proof_move_stats(self, per_game=False, reset=False):
+        """dict(none, win, pruned, moved): the moves that got each verdict (PM_*) under set_proof_moves since the last reset,
+        over the active games of every end_move (ao_proof_move_records); per_game=True adds `verdict`, int32 [G]: each game's
+        most recent one. A move that search() repeated on the fp32-MFMA trunk is ended once and counts once."""
+        out = np.zeros(4, np.int64)
+        v = np.zeros(self.G, np.int32) if per_game else None
+        self._check(self._L.ao_proof_move_records(self._h, _ptr(v, C.c_int32), _ptr(out, C.c_int64), 1 if reset else 0),
+                    "ao_proof_move_records")
+        d = dict(none=int(out[0]), win=int(out[1]), pruned=int(out[2]), moved=int(out[3]))
+        if per_game:
+            d["verdict"] = v
+        return d
 
     # -- tree snapshots
     def export_trees(self, mask=None):

@@ -92,6 +92,7 @@ def evaluate(player, enemy, board_size, n_match=12, player_elo=1500.0, enemy_elo
     return result, (player_elo, enemy_elo)
 
 
+last_proof_moves = {}        # evaluate_batched(proof_moves=): side index -> Engine.proof_move_stats() of that side's engine over the matches
 last_search_totals = {}      # evaluate_batched: searches, simulations asked for, searches settled and simulations saved by early stop
 
 
@@ -99,7 +100,7 @@ class _ZeroSide:
     """One network's side of evaluate_batched: a G-game engine + evaluator; searches the masked matches at their ids."""
 
     def __init__(self, model, sims, board_size, inplanes, G, device, early_stop=False, tactics=None, forward_precision=None,
-                 leaf_symmetry=None, seeds=None, leaf_tactics=None):
+                 leaf_symmetry=None, seeds=None, leaf_tactics=None, proof_moves=False):
         from .engine import Engine
         from .evaluator import Evaluator
         self.eng = Engine(board_size, sims, inplanes, games=G, noise=False, device=device)
@@ -109,6 +110,9 @@ class _ZeroSide:
         limits = utils.leaf_tactics_limits(leaf_tactics)
         if limits is not None:
             self.eng.set_leaf_tactics(*limits)
+        self.proof_moves = bool(proof_moves)
+        if self.proof_moves:
+            self.eng.set_proof_moves(True)                # the move follows what the root's tree proves (utils.proof_pi)
         self.ev, self.model = Evaluator(device), model
         if forward_precision is not None:
             self.ev.net_precision = forward_precision    # Net.precision of this side's exported network ("fp16": the opt-in one-product forward)
@@ -174,7 +178,7 @@ def check_forward_precision(forward_precision):
 def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mcts_enemy=None, inplanes=5, n_match=12,
                      player_elo=1500.0, enemy_elo=1500.0, seed=0, device=0, max_plies=None, monitor_model=None,
                      n_mcts_monitor=None, early_stop=False, tactics=None, forward_precision=None, leaf_symmetry=None,
-                     leaf_tactics=None):
+                     leaf_tactics=None, proof_moves=False):
     """All n_match games at once (colours swapped every game, eval_main.py:213-333). `*_model`: whatever
     ZeroAgent.model accepts (a PVNet-shaped module runs on the native forward), or 'puct' / 'uct' for the rollout
     agents (eval_main.py:68-73,106-111). With a rollout PLAYER and a `monitor_model`, the monitor ZeroAgent searches
@@ -191,7 +195,10 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
     for a side that searches plainly, as for tactics.
     leaf_tactics: True or dict(max_depth, max_nodes) -- the ZeroAgent sides value a leaf whose mover has a proven forced win +1
     (Engine.set_leaf_tactics) -- for both, or a pair (player's, enemy's) with None for a side that searches plainly. Each side
-    has its own engine."""
+    has its own engine.
+    proof_moves: True -- the ZeroAgent sides play what their root's tree proves (Engine.set_proof_moves: the fastest proven win,
+    never a move that is proven lost while another is not) -- for both, or a pair (player's, enemy's) of bools; the verdicts are
+    counted per side in evaluate.last_proof_moves."""
     forward_precision = check_forward_precision(forward_precision)
     n_mcts_enemy = n_mcts_player if n_mcts_enemy is None else n_mcts_enemy
     G = n_match
@@ -209,15 +216,18 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
         raise ValueError("leaf_tactics: one value for both sides or a pair (player, enemy)")
     for lt in side_leaf:
         utils.leaf_tactics_limits(lt)            # (a bad value is an argument error before any engine exists)
+    side_proof = tuple(proof_moves) if isinstance(proof_moves, (tuple, list)) else (proof_moves, proof_moves)
+    if len(side_proof) != 2 or any(not isinstance(pm, (bool, np.bool_, type(None))) for pm in side_proof):
+        raise ValueError("proof_moves: one bool for both sides or a pair (player, enemy)")
     match_seeds = [(seed + i) & 0xFFFFFFFF for i in range(G)]
 
-    def make(model, sims, tac, prec, sym, leaf):
+    def make(model, sims, tac, prec, sym, leaf, proof):
         if isinstance(model, str):
             return _RolloutSide(model, sims, board_size, G, device)
-        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac, prec, sym, match_seeds, leaf)
+        return _ZeroSide(model, sims, board_size, inplanes, G, device, early_stop, tac, prec, sym, match_seeds, leaf, proof)
 
-    sides = [make(player_model, n_mcts_player, side_tactics[0], forward_precision[0], side_sym[0], side_leaf[0]),
-             make(enemy_model, n_mcts_enemy, side_tactics[1], forward_precision[1], side_sym[1], side_leaf[1])]
+    sides = [make(player_model, n_mcts_player, side_tactics[0], forward_precision[0], side_sym[0], side_leaf[0], side_proof[0]),
+             make(enemy_model, n_mcts_enemy, side_tactics[1], forward_precision[1], side_sym[1], side_leaf[1], side_proof[1])]
     monitor = None
     if monitor_model is not None and isinstance(player_model, str):
         monitor = _ZeroSide(monitor_model, n_mcts_monitor or n_mcts_enemy, board_size, inplanes, G, device)
@@ -259,6 +269,10 @@ def evaluate_batched(player_model, enemy_model, board_size, n_mcts_player, n_mct
                     running[i] = False
         ply += 1
     last_search_totals.clear()
+    last_proof_moves.clear()
+    for k, sd in enumerate(sides):
+        if isinstance(sd, _ZeroSide) and sd.proof_moves:
+            last_proof_moves[k] = sd.eng.proof_move_stats()
     for sd in sides:
         if isinstance(sd, _ZeroSide):                                # what early stop saved, over both sides (tools/time_early_stop.py)
             ran = sd.eng.sims_run()

@@ -110,6 +110,7 @@ ROLLING = False              # configure(rolling=True): self-play runs ONE rolli
 TURN_EVERY = None            # begins the next on its own clock, looked at every TURN_EVERY launches (None: engine.SETTLE_EVERY), instead of search + play per ply
 ROLL_TACTICS = None          # configure(rolling=True, roll_tactics=True or dict): the forced-win solver runs beside the rolling loop (Engine.roll_begin(tactics=...))
 roll_sims_log = None         # a list: the rolling loop appends (global episode number, ply, simulations run, settled) per move decision (tests, tools)
+PROOF_MOVES = False          # configure(proof_moves=True): every self-play move follows what its root's tree proves (Engine.set_proof_moves)
 LEAF_TACTICS = None          # configure(leaf_tactics=True or dict): (max_depth, max_nodes) of the forced-win solver on every self-play leaf (Engine.set_leaf_tactics)
 LEAF_SYMMETRY = None         # configure(leaf_symmetry=KEY): every self-play leaf is evaluated under a symmetry drawn from (KEY, the episode's seed, ply, simulation)
 FP16_GRID = False            # configure(fp16_grid_weights=True): the 3x3 conv weights of Agent.model are kept on the fp16 grid (see _grid_sync)
@@ -120,7 +121,7 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
               model=None, gpu=None, noise=True, device_replay=False, node_cap=None, strict=None, reproducible=False,
               carry_over=None, oversubscribe=None, rows=None, overlap_train=None, fp16_grid_weights=None,
               early_stop=False, fast_sims=None, full_prob=0.25, tactics=None, forward_precision="fp32", rolling=False,
-              turn_every=None, leaf_symmetry=None, roll_tactics=None, leaf_tactics=None):
+              turn_every=None, leaf_symmetry=None, roll_tactics=None, leaf_tactics=None, proof_moves=False):
     """Build `Agent`, `Agent.model` and `optimizer` (main.py:58-85). Call instead of editing constants.
     node_cap: expanded-node capacity of a game's tree arena (0 = 16*(n_mcts+1) where 40 % of the HBM
     holds that for all games, at least 4*(n_mcts+1); -1 = grow into the free HBM);
@@ -189,14 +190,21 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     runs on every leaf of every self-play search -- and of Agent's own get_pi -- and a leaf whose mover has a proven forced win by
     continuous fours is valued +1 instead of what the value head said (Engine.set_leaf_tactics, utils.leaf_tactics_value); nothing
     else of the search changes. It composes with leaf_symmetry, early_stop, fast_sims, oversubscribe, carry_over, tactics, rolling
-    and roll_tactics, every forward_precision and reproducible."""
-    global LEAF_SYMMETRY, LEAF_TACTICS
+    and roll_tactics, every forward_precision and reproducible.
+    proof_moves=True: every self-play search -- and Agent's own get_pi -- is followed by an exact minimax over the root's tree, and pi
+    follows what it proves (Engine.set_proof_moves, utils.proof_pi): one-hot on the fastest proven win, or without the moves that are
+    proven lost. The played move is drawn from that pi and the RECORDED pi is that pi: no longer pure visit counts. Visits, trees
+    and streams are what they are without it. Not with rolling=True (the roll's turn on the device does not apply it)."""
+    global LEAF_SYMMETRY, LEAF_TACTICS, PROOF_MOVES
     global BOARD_SIZE, N_MCTS, N_BLOCKS, IN_PLANES, OUT_PLANES, SEED, Agent, optimizer, device
     global _engine, _evaluator, _episodes_played, rep_memory, STRICT, NODE_CAP, CARRY_OVER, _pool, OVERSUBSCRIBE, ROWS, _terminal_share
     global OVERLAP_TRAIN, FP16_GRID, EARLY_STOP, FAST_SIMS, FULL_PROB, TACTICS, ROLLING, TURN_EVERY, ROLL_TACTICS
     if rolling and tactics:
         raise ValueError("rolling=True and tactics= do not go together: tactics= is the synchronous search's switch; the rolling "
                          "search takes roll_tactics= (the solver runs beside its loop)")
+    if rolling and proof_moves:
+        raise ValueError("rolling=True and proof_moves=True do not go together: the rolling search ends its moves on the device, "
+                         "where proof moves are not applied")
     if roll_tactics and not rolling:
         raise ValueError("roll_tactics= needs rolling=True (the synchronous search takes tactics=)")
     if roll_tactics and (STRICT if strict is None else strict):
@@ -223,6 +231,7 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     EARLY_STOP = bool(early_stop)
     LEAF_SYMMETRY = None if leaf_symmetry is None else int(leaf_symmetry) & 0xFFFFFFFF
     LEAF_TACTICS = utils.leaf_tactics_limits(leaf_tactics)
+    PROOF_MOVES = bool(proof_moves)
     ROLLING = bool(rolling)
     TURN_EVERY = None if turn_every is None else int(turn_every)
     TACTICS = tactics if tactics else None
@@ -275,7 +284,8 @@ def configure(board_size=None, n_mcts=None, n_blocks=None, in_planes=None, out_p
     torch.manual_seed(SEED)
     agents.PRINT_MCTS = PRINT_SELFPLAY
     Agent = agents.ZeroAgent(BOARD_SIZE, N_MCTS, IN_PLANES, noise=noise, device=gpu, leaf_symmetry=LEAF_SYMMETRY,
-                             leaf_tactics=None if LEAF_TACTICS is None else dict(max_depth=LEAF_TACTICS[0], max_nodes=LEAF_TACTICS[1]))
+                             leaf_tactics=None if LEAF_TACTICS is None else dict(max_depth=LEAF_TACTICS[0], max_nodes=LEAF_TACTICS[1]),
+                             proof_moves=PROOF_MOVES)
     Agent.model = model if model is not None else PVNet(N_BLOCKS, IN_PLANES, OUT_PLANES, BOARD_SIZE).to(device)
     if hasattr(Agent.model, "parameters"):
         parallel.broadcast_parameters(Agent.model)
@@ -347,6 +357,8 @@ def _get_engine(games):
             _engine.set_leaf_symmetry(LEAF_SYMMETRY)   # (the keys follow the seed calls: ao_set_leaf_symmetry)
         if LEAF_TACTICS is not None:
             _engine.set_leaf_tactics(*LEAF_TACTICS)
+        if PROOF_MOVES:
+            _engine.set_proof_moves(True)
     return _engine
 
 
@@ -1436,11 +1448,13 @@ if __name__ == '__main__':
     ap.add_argument('--roll-tactics', action='store_true', help='with --rolling: the forced-win solver restricts the roots, running beside the launch loop (configure(roll_tactics=True))')
     ap.add_argument('--leaf-symmetry', type=int, nargs='?', const=0, default=None, metavar='KEY', help='evaluate every leaf under a symmetry of the board drawn per leaf (configure(leaf_symmetry=KEY)); KEY defaults to 0')
     ap.add_argument('--leaf-tactics', nargs='?', const='2,16', default=None, metavar='DEPTH,NODES', help='value a leaf whose mover has a proven forced win by continuous fours +1 (configure(leaf_tactics=dict(max_depth=DEPTH, max_nodes=NODES))); defaults to 2,16')
+    ap.add_argument('--proof-moves', action='store_true', help='play what the root\'s tree proves: the fastest proven win, never a move proven lost while another is not (configure(proof_moves=True)); not with --rolling')
     a = ap.parse_args()
     parallel.init_from_env()
     GAMES_PER_ITER, TRAIN_STEPS = a.games_per_iter, a.train_steps
     configure(board_size=a.board, n_mcts=a.sims, n_blocks=a.blocks, device_replay=a.device_replay, oversubscribe=a.oversubscribe,
               overlap_train=a.overlap_train, fp16_grid_weights=a.fp16_grid_weights,
               forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32", rolling=a.rolling, turn_every=a.turn_every,
-              leaf_symmetry=a.leaf_symmetry, roll_tactics=a.roll_tactics or None, leaf_tactics=utils.parse_leaf_tactics(a.leaf_tactics))
+              leaf_symmetry=a.leaf_symmetry, roll_tactics=a.roll_tactics or None, leaf_tactics=utils.parse_leaf_tactics(a.leaf_tactics),
+              proof_moves=a.proof_moves)
     run(a.iters, a.model, a.dataset, a.selfplay)

@@ -508,6 +508,124 @@ def parse_leaf_tactics(text):
     return dict(max_depth=int(parts[0]), max_nodes=int(parts[1]))
 
 
+# proven outcomes (Engine.tree_proofs / utils.tree_proofs): a node's status for its side to move; Engine.set_proof_moves' verdicts
+PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW = 0, 1, 2, 3
+PM_NONE, PM_WIN, PM_PRUNED, PM_MOVED = 0, 1, 2, 3
+_PROOF_FLIP = (PROOF_UNKNOWN, PROOF_LOSS, PROOF_WIN, PROOF_DRAW)
+
+
+def tree_proofs(snapshot, game, max_len=None):
+    """What game `game` of a TreeSnapshot (Engine.export_trees) PROVES, by exact minimax over the tree as it stands -- the
+    definition of Engine.tree_proofs. No reference counterpart: the reference stores a visited terminal child like any other and
+    only its backed-up value tells. Every expanded node gets a status for its side to move and the plies to the end of the game.
+    An edge, seen from the node's mover: a CH_TERMINAL child -- the stone is placed and check_win asked -- is (WIN, 1) if the
+    mover has won, (DRAW, 1) on a full board; an expanded child c is its status with WIN and LOSS swapped and plies[c] + 1; an
+    unvisited child (a barred root child is one) is UNKNOWN. A node: any WIN edge -> (WIN, fewest plies); else any UNKNOWN edge ->
+    UNKNOWN; else any DRAW edge -> (DRAW, fewest plies among the draws); else (LOSS, most plies). The proof line: from the root,
+    while the node is proven, the first edge in stored order that carries the node's own (status, plies).
+    Returns a dict: root int32 [4] = status, plies, proven nodes, nodes walked; child_status int8 [A] (-1: the root has no edge
+    for the action) and child_plies int16 [A] by action; line int32 [max_len] (-1 beyond it; max_len None: A) and len; status
+    int8 / plies int32 [nodes] for every node in the snapshot's breadth-first numbering."""
+    s = snapshot
+    B = s.board
+    A = B * B
+    L = A if max_len is None else int(max_len)
+    n0 = int(s.hdr[:game, 0].sum())
+    e0 = int(s.hdr[:game, 1].sum())
+    N = int(s.hdr[game, 0])
+    nch = s.nchild[n0:n0 + N].astype(np.int64)
+    first = e0 + np.concatenate([[0], np.cumsum(nch)])[:N]
+    moves = [int(a) for a in s.moves[game, :int(s.hdr[game, 2])]]
+    # the moves that lead to every node: breadth first, a parent comes before its children
+    path = [None] * N
+    for j in range(N):
+        if j == 0:
+            path[j] = moves
+        else:
+            par, pe = int(s.parent[n0 + j]), int(s.parent_edge[n0 + j])
+            path[j] = path[par] + [int(s.act[first[par] + pe])]
+    status, plies = np.zeros(N, np.int8), np.zeros(N, np.int32)
+
+    def edges(j):
+        """[(status, plies)] of node j's edges in stored order"""
+        out = []
+        for k in range(int(nch[j])):
+            at = first[j] + k
+            c = int(s.child[at])
+            if c >= 0:
+                cs = int(status[c])
+                out.append((_PROOF_FLIP[cs], int(plies[c]) + 1 if cs != PROOF_UNKNOWN else 0))
+            elif c == -2:                                   # CH_TERMINAL
+                mv = path[j] + [int(s.act[at])]
+                w = check_win(get_board([0] + mv, B), s.win_mark)
+                mover = 1 + (len(path[j]) & 1)              # check_win's index of the side that placed the stone
+                out.append((PROOF_WIN, 1) if w == mover else ((PROOF_DRAW, 1) if w == 3 else (PROOF_UNKNOWN, 0)))
+            else:
+                out.append((PROOF_UNKNOWN, 0))
+        return out
+
+    for j in range(N - 1, -1, -1):
+        ev = edges(j)
+        wins = [p for st, p in ev if st == PROOF_WIN]
+        draws = [p for st, p in ev if st == PROOF_DRAW]
+        if wins:
+            status[j], plies[j] = PROOF_WIN, min(wins)
+        elif not ev or any(st == PROOF_UNKNOWN for st, _ in ev):
+            status[j], plies[j] = PROOF_UNKNOWN, 0
+        elif draws:
+            status[j], plies[j] = PROOF_DRAW, min(draws)
+        else:
+            status[j], plies[j] = PROOF_LOSS, max(p for _, p in ev)
+    child_status, child_plies = np.full(A, -1, np.int8), np.zeros(A, np.int16)
+    line, n = np.full(L, -1, np.int32), 0
+    root = np.zeros(4, np.int32)
+    if N:
+        for k, (st, p) in enumerate(edges(0)):
+            a = int(s.act[first[0] + k])
+            child_status[a], child_plies[a] = st, p
+        root[:] = (status[0], plies[0], int(np.count_nonzero(status)), N)
+        j = 0
+        while status[j] != PROOF_UNKNOWN and n < L:
+            k = edges(j).index((int(status[j]), int(plies[j])))
+            line[n] = s.act[first[j] + k]
+            n += 1
+            j = int(s.child[first[j] + k])
+            if j < 0:
+                break
+    return dict(root=root, child_status=child_status, child_plies=child_plies, line=line, len=n, status=status, plies=plies)
+
+
+def proof_pi(pi, visit, child_status, child_plies):
+    """What Engine.set_proof_moves makes of one game's pi [A] (Engine.end_move) given the root's edge values by action
+    (tree_proofs): (pi', verdict).
+    PM_WIN: some edge is WIN -- pi' is one-hot on the WIN edge with the fewest plies, ties to the larger visit, then to the lowest
+    action. PM_PRUNED: no WIN edge, some edge is LOSS, some is not, and some LOSS edge has pi > 0 -- with s the sum of pi over the
+    edges that are not LOSS (sequential in ascending action order, fp64), pi' = pi / s on them and 0 elsewhere; if s == 0 (a
+    tau == 0 one-hot on a lost move) the verdict is PM_MOVED and pi' is one-hot on the non-lost edge with the most visits, lowest
+    action on ties. PM_NONE: everything else, a root proven LOSS included -- pi' is `pi` itself."""
+    pi = np.asarray(pi, np.float64)
+    st = np.asarray(child_status)
+    win = np.flatnonzero(st == PROOF_WIN)
+    if win.size:
+        a = min(win, key=lambda a: (int(child_plies[a]), -float(visit[a]), int(a)))
+        out = np.zeros_like(pi)
+        out[a] = 1.0
+        return out, PM_WIN
+    lost = st == PROOF_LOSS
+    keep = (st == PROOF_UNKNOWN) | (st == PROOF_DRAW)
+    if not (lost.any() and keep.any() and (pi[lost] > 0).any()):
+        return pi, PM_NONE
+    s = 0.0
+    for a in np.flatnonzero(keep):
+        s = s + float(pi[a])
+    out = np.zeros_like(pi)
+    if s > 0:
+        out[keep] = pi[keep] / s
+        return out, PM_PRUNED
+    out[min(np.flatnonzero(keep), key=lambda a: (-float(visit[a]), int(a)))] = 1.0
+    return out, PM_MOVED
+
+
 def check_allowed(allowed, games, cells):
     """The `allowed` argument of Engine.begin_move / search as uint8 [games, cells] (None stays None). ValueError for
     another shape or for values that are not 0 / 1 / bool."""

@@ -399,6 +399,51 @@ int ao_tree_pv(ao_engine *e, const uint8_t *host_mask, int32_t max_len, int32_t 
  * holds: what exceeds the first number is dead until the next compaction) }. Rows of unmasked games are left as they are. */
 int ao_tree_stats(ao_engine *e, const uint8_t *host_mask, int32_t *out);
 
+/* ---- proven outcomes ---- (no reference counterpart; beside get_pi, agents.py:64-80) A visited child whose position ends the
+ * game is stored as such, so a tree can hold a complete proof that its root is won, lost or drawn; backup only folds those facts
+ * into w / q. ao_tree_proofs runs an exact minimax over what each masked game's root reaches (the walk of ao_tree_stats, then a
+ * sweep over its ply levels from the deepest to the root) and is read-only like the other read-outs. The definition is
+ * alpha_omok_amd/utils.py: tree_proofs. Every expanded node gets a status for its side to move and the plies to the end:
+ *   edge of a node, seen from the node's mover:  a terminal child that wins for the mover (WIN, 1), that fills the board
+ *   (DRAW, 1); an expanded child c: its status with WIN and LOSS swapped, plies[c] + 1; an unvisited child -- a barred root
+ *   child is one -- UNKNOWN
+ *   node:  any WIN edge -> (WIN, fewest plies); else any UNKNOWN edge -> UNKNOWN; else any DRAW edge -> (DRAW, fewest plies
+ *   among the draws); else (LOSS, most plies). An expanded node owns an edge for every legal move.
+ *   line:  from the root, while the node is proven, the first edge in stored order that carries the node's own status and plies;
+ *   its length is the root's plies (cut at max_len) and it ends on a terminal edge.
+ * Host outputs, any may be NULL; rows of unmasked games are left as they are; a masked game without an expanded root gets
+ * zeros, -1 in child_status and an empty line:
+ *   root         int32 [G][4]        status, plies, proven nodes, nodes walked
+ *   child_status int8  [G][A]        AO_PROOF_* of the root's edge that plays the action, -1 where the root has no such edge
+ *   child_plies  int16 [G][A]        its plies, 0 where unknown or no edge
+ *   line         int32 [G][max_len]  the actions of the proof line, -1 beyond it;  line_len int32 [G]
+ * max_len in 1..A. Fails, with nothing touched, between ao_begin_move and ao_end_move and while a roll is open. One upload, one
+ * launch, one download, one synchronisation. The proofs feed nothing back into selection or backup. */
+enum { AO_PROOF_UNKNOWN = 0, AO_PROOF_WIN = 1, AO_PROOF_LOSS = 2, AO_PROOF_DRAW = 3 };
+int ao_tree_proofs(ao_engine *e, const uint8_t *host_mask, int32_t max_len, int32_t *root, int8_t *child_status,
+                   int16_t *child_plies, int32_t *line, int32_t *line_len);
+/* Proof moves (opt-in; off, no kernel of this section is launched and every result is what it is without these calls). With
+ * the switch on, ao_end_move -- and so ao_search*, and the repeat of a move after an fp16-range event -- runs the proofs of
+ * the active games behind k_end_move and rewrites pi on the device before it is copied out (utils.proof_pi):
+ *   AO_PM_WIN     some root edge is WIN: pi is one-hot on the WIN edge with the fewest plies, ties to the larger visit count,
+ *                 then to the lowest action
+ *   AO_PM_PRUNED  no WIN edge, some edge is LOSS, some is not, and some LOSS edge has pi > 0: with s the sum of pi over the
+ *                 edges that are not LOSS (sequential, ascending action, fp64), pi = pi / s there and 0 elsewhere; if s == 0 (a
+ *   AO_PM_MOVED   tau == 0 one-hot on a lost move) pi is one-hot on the non-lost edge with the most visits, lowest action on ties
+ *   AO_PM_NONE    everything else, a root proven LOSS included: pi is untouched, bit for bit
+ * ao_play then draws from that pi, so the recorded pi is no longer pure visit counts. visit and policy are untouched, and the
+ * games' MT19937 streams advance exactly as without the switch (the tau == 0 tie draw has happened before, ao_play draws its
+ * one double either way). Inactive games keep their rows; a game short of its simulations gets AO_PM_NONE. ao_set_proof_moves
+ * fails inside a move and while a roll is open; ao_roll_begin fails while the switch is on (the roll's turn does not know it).
+ * Tree snapshots do not carry the switch.
+ * ao_proof_move_records: verdict int32 [G] of each game's most recent ao_end_move under the switch (0 before any), totals
+ * int64 [4] = moves that got NONE, WIN, PRUNED, MOVED since the last reset, over the active games of every ao_end_move under
+ * the switch (a move that the fp16-range recovery repeats is ended once and counts once); either may be NULL; reset != 0 zeroes
+ * the totals. */
+enum { AO_PM_NONE = 0, AO_PM_WIN = 1, AO_PM_PRUNED = 2, AO_PM_MOVED = 3 };
+int ao_set_proof_moves(ao_engine *e, int enable);
+int ao_proof_move_records(ao_engine *e, int32_t *verdict, int64_t totals[4], int reset);
+
 /* ---- tree snapshots ---- the reference's `self.tree` lives as long as its process and can be pickled like any dict
  * (agents.py:52); these move the engine's trees and streams out of an engine and back in. A snapshot is host data without
  * device pointers: what the root of each game reaches, breadth first with the root as node 0 (the numbering of a re-rooting),

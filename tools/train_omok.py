@@ -106,6 +106,10 @@ def main():
     ap.add_argument("--leaf-tactics", nargs="?", const="2,16", default=None, metavar="DEPTH,NODES",
                     help="a self-play leaf whose mover has a proven forced win by continuous fours is valued +1 "
                          "(main.configure(leaf_tactics=dict(max_depth=DEPTH, max_nodes=NODES))); defaults to 2,16")
+    ap.add_argument("--proof-moves", action="store_true",
+                    help="every self-play move follows what its root's tree proves: the fastest proven win, never a move proven lost "
+                         "while another is not (main.configure(proof_moves=True)); the recorded pi is then not pure visit counts; not "
+                         "with --rolling")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--resume", default=None, help="state_dict to start from")
     ap.add_argument("--save-replay", default=None, metavar="PATH",
@@ -143,7 +147,7 @@ def main():
                 fp16_grid_weights=a.fp16_grid_weights, early_stop=a.early_stop, fast_sims=a.fast_sims, full_prob=a.full_prob,
                 tactics=True if a.tactics else None, forward_precision="fp16-all" if a.fp16_forward_all else "fp16" if a.fp16_forward else "fp32",
                 rolling=a.rolling, turn_every=a.turn_every, leaf_symmetry=a.leaf_symmetry, roll_tactics=a.roll_tactics or None,
-                leaf_tactics=utils.parse_leaf_tactics(a.leaf_tactics))
+                leaf_tactics=utils.parse_leaf_tactics(a.leaf_tactics), proof_moves=a.proof_moves)
     if a.resume:
         m.Agent.model.load_state_dict(torch.load(a.resume, map_location=m.device))
         m._grid_sync()                                   # (fp16-grid mode: masters = the loaded weights, module = their rounding)
