@@ -8,9 +8,13 @@
 //   3. copies the [G][A] result vectors back.
 // Everything else lives in HBM and in the kernels of tree_kernels.hip.
 //
-// Two drivers queue those launches, MoveSearch under ao_search* and the rolling search under ao_roll_*, on one footing: what a
-// move is (ao::roll_next_move), its Dirichlet draw (draw_noise), the launch plan and the ring of row counters (LaunchLoop), what a
-// failure leaves behind (clear_game_errors). DESIGN.md section 4 says what each driver adds.
+// Two drivers queue those launches, MoveSearch under ao_search* (here) and the rolling search under ao_roll_* (roll.hip), on one
+// footing: what a move is (ao::roll_next_move), its Dirichlet draw (draw_noise), the launch plan and the ring of row counters
+// (LaunchLoop), what a failure leaves behind (clear_game_errors). DESIGN.md section 4 says what each driver adds.
+//
+// This file: the engine's lifecycle, seeding, the symmetry and leaf-tactics switches, the root bar, roots and reset, the step-wise
+// protocol, MoveSearch with the fp16-range recovery, and the small getters. ao_engine itself is engine.hpp's; the host drivers of
+// the rolling search, the tree read-out, the proven outcomes, the root tactics and the tree snapshots stand beside their kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,223 +27,11 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/omok_hip.h"
-#include "engine_types.hpp"
-#include "host_handle.hpp"
+#include "engine.hpp"
 #include "host_rng.hpp"
 #include "launchers.hpp"
-#include "roll_schedule.hpp"
-#include "search_schedule.hpp"
-#include "snapshot_check.hpp"
 #include "symmetry.hpp"
 #include "tactics_limits.hpp"
-#include "tree_snapshot.hpp"
-
-// The developer switches of the search driver (MoveSearch below; INTEGRATION.md has the table). They have two lifetimes:
-//  * read ONCE per process, by its first search: they pick a code path for an experiment or a profile and hold for the run;
-//  * read ANEW by every search that enters the catch-up rounds: tests/test_gpu_production_loop.py sets and unsets them between
-//    the searches of one process.
-struct DevSwitches {
-    bool static_rows;     // AO_STATIC_ROWS: the per-move packing of rounds 3 - 4 everywhere
-    bool dynamic_rows;    // AO_DYNAMIC_ROWS: hand out rows per simulation without ao_set_row_cap
-    int descent_budget;   // AO_DESCENT_BUDGET (experiment): levels of a descent per launch, 0 = no bound
-    bool row_trace;       // AO_ROW_TRACE: rows asked for, launch by launch, on stderr
-    bool launch_timing;   // AO_LAUNCH_TIMING: is the simulation loop host-bound?
-    static const DevSwitches& process() {
-        static const DevSwitches s{getenv("AO_STATIC_ROWS") != nullptr, getenv("AO_DYNAMIC_ROWS") != nullptr,
-                                   getenv("AO_DESCENT_BUDGET") ? atoi(getenv("AO_DESCENT_BUDGET")) : 0,
-                                   getenv("AO_ROW_TRACE") != nullptr, getenv("AO_LAUNCH_TIMING") != nullptr};
-        return s;
-    }
-    // per search: cut the catch-up loop short (-1 = not set; tests: 0 = a short search must be an error) / run its rounds
-    // without a sit-out window from the start
-    static int catchup_rounds() { const char* v = getenv("AO_CATCHUP_ROUNDS"); return v ? atoi(v) : -1; }
-    static bool catchup_window_off() { return getenv("AO_CATCHUP_WINDOW_OFF") != nullptr; }
-};
-
-// What both search drivers run on: the launch plan (the network's input, the driver's copy of the tree parameters) and the ring
-// of row counters d_live[kLive]. With rows handed out per simulation (engine_types.hpp, TreeParams::live) selection launch i
-// counts the rows its leaves ask for in word i % kLive, the network launch behind it reads that word, and the host sums the
-// words up into ao_row_stats where the ring wraps and when a driver asks (search_schedule.hpp). The methods follow ao_engine.
-struct ao_engine;
-struct LaunchLoop {
-    ao_engine* e = nullptr;
-    bool per_sim = false;          // rows are handed out and counted per simulation (otherwise: packed per move by the host, no ring)
-    int cap_rows = 0, in_kind = 1; // rows of one network launch; the input the network wants (net_plan): 2 = bit planes, otherwise the interleaved fp32 batch
-    const float* net_in = nullptr;
-    ao::TreeParams p{};            // the driver's copy of e->tp; `live` changes per launch
-    int64_t launch = 0, harvested = 0;   // selection launches so far; ... of which the row counters are summed up already
-    int64_t* traffic = nullptr;    // where the bytes of a harvest are charged (the rolling search's ao_roll_stats), or null
-    int plan(ao_engine* e, ao_net* net, int rows);   // a fresh loop with the plan for launches of `rows` rows
-    int zero_ring();                     // where a driver sets per_sim, and at every wrap
-    unsigned* slot(int64_t i) const;     // the counter word of launch i (null without per_sim)
-    bool wraps(int64_t i) const { return per_sim && i > 0 && slot(i) == slot(0); }   // launch i counts in the ring's first word again
-    unsigned counted(int64_t i) const;   // what launch i counted, once harvested (until the ring wraps again)
-    int advance();                       // behind a network launch: the next selection launch and its counter word
-    int harvest(int64_t upto);           // sums up the launches [harvested, upto); synchronises if there are any
-    // Leaf tactics (ao_set_leaf_tactics), called on either side of every network launch that a tree launch follows; nothing at
-    // all with the switch off. before_net: the solver on the leaves of the last selection, on the engine's second stream behind
-    // an event recorded here -- it runs beside the network. Otherwise (behind the network launch and the eval log): the engine's
-    // stream waits for the solver's event and writes +1 into the rows of the proven leaves. lt_serial (AO_LEAF_TACTICS_SERIAL,
-    // read by plan()): both kernels on the engine's own stream behind the network launch instead; the same bits.
-    bool lt_serial = false;
-    int leaf_tactics(bool before_net);
-};
-
-// The rolling search (ao_roll_*, at the end of this file): what lives from ao_roll_begin to ao_roll_end. The rules are
-// roll_schedule.hpp's, the kernels roll.hip's.
-// The forced-win solver beside the loop (ao_roll_set_tactics). A BATCH is the solver's run on the roots of the games that were
-// to begin a move at one turn (or begin / join): queued on `stream`, which touches nothing but the batch's own buffer, between two
-// events. Its games wait (ROLL_WAITING) until a later turn finds the second event reached; then they begin their move on the
-// engine's stream with the batch's bar rows and verdicts (k_roll_verdict in front of k_roll_begin).
-struct RollBatch {
-    bool busy = false;
-    int n = 0, age = 0;                   // games; turns since it was started
-    hipEvent_t ready = nullptr, done = nullptr;   // engine stream: the position rows are written; solver stream: the verdicts are
-    std::vector<int32_t> games;           // [n]
-    std::vector<uint8_t> bonus;           // [n] the root was fresh when the game was listed
-    std::vector<uint32_t> mt; std::vector<int32_t> pos;   // [n][624], [n] the games' streams as gathered when they were listed
-    ao::DevBuf<unsigned char> buf{nullptr};   // position rows, won / stage / pair words, verdict words, bar rows, allowed rows: O(n A)
-    ao::RollBatchView view{};
-};
-struct RollTactics {
-    int max_depth = 0, max_nodes = 0, solved_sims = 0;   // ao_roll_set_tactics; max_depth == 0: disarmed
-    bool want_allowed = false;
-    bool on = false;                      // the open roll runs with the solver
-    int hold = 0;                         // AO_ROLL_TACTICS_HOLD, read at ao_roll_begin
-    hipStream_t stream = nullptr;
-    RollBatch slot[ao::kRollBatchSlots];
-    std::vector<int> pending;             // busy slots, oldest first
-    int n_waiting = 0;
-    int32_t* d_words = nullptr; uint8_t* d_allowed = nullptr;      // [G][4], [G][A]: what the solver said at the root of each game's current move
-    int32_t* d_out_words = nullptr; uint8_t* d_out_allowed = nullptr;   // compact rows of a turn's records
-    int32_t* h_words = nullptr; uint8_t* h_allowed = nullptr;      // pinned, [G][4], [G][A]
-    std::vector<int32_t> rec_words; std::vector<uint8_t> rec_allowed; int rec_count = 0;   // of the last ao_roll_run
-    int64_t stats[6] = {0, 0, 0, 0, 0, 0};   // ao_roll_tactics_stats
-};
-
-struct RollState {
-    bool open = false, draining = false;
-    RollTactics tac;
-    ao_net* net = nullptr;
-    bool early = false, want_visit = false, want_policy = false;
-    ao::RollCadence cad;
-    bool look_pending = false;            // a look's counters have not been read yet
-    std::vector<uint8_t> in_move;         // [G] ao::RollGame: out of a move, searching, or waiting for the solver's verdict
-    int n_in_move = 0;
-    std::vector<int32_t> tau_plies;       // [G], empty: tau 1 always
-    std::vector<int32_t> sims; int sims_stride = 0;      // [G][stride] budgets by ply, empty: ao_config.sims
-    std::vector<uint8_t> noise; int noise_stride = 0;    // [G][stride] noise switches by ply, empty: the engine's
-    LaunchLoop loop;                      // always rows per simulation; no sit-out window, no launch order, no fused step
-    // compact buffers of a turn, allocated by the first roll of the engine: [G] games, [G][kRollItem], [G][kRollRec], [3][G][A], [G][Ap]
-    int32_t* d_games = nullptr; int32_t* d_items = nullptr; int32_t* d_rec = nullptr; double* d_out = nullptr; double* d_noise = nullptr;
-    int32_t* h_i32 = nullptr;             // pinned: [4][G] done, target, leaf status, error words; [G] games; [G][kRollItem]; [G][kRollRec]
-    // ao_roll_stats
-    int64_t turns = 0, games_turned = 0, bytes = 0, last_games = 0, last_bytes = 0;
-};
-
-struct ao_engine : ao::HandleBase {
-    ao_config cfg{};
-    ao::TreeParams tp{};
-    hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;
-    int A = 0, Ap = 0, G = 0, Gp = 0, S = 0;
-    ao::DevPool pool;
-    // device scratch
-    uint8_t* d_active = nullptr; int8_t* d_tau = nullptr; int32_t* d_extra = nullptr;
-    uint8_t* d_mask = nullptr;
-    std::vector<int32_t> h_walk;     // staging of ao_set_root(s): [G][A] moves + games, counts, prev_known, status
-    float* d_policy = nullptr; float* d_value = nullptr;  // native-net outputs [Gp][A], [Gp]
-    uint8_t* d_planes_u8 = nullptr;                       // bit planes [Gp][u8_row] (input of the split-fp16 kernels)
-    int32_t* d_row = nullptr;                             // [2G] batch row of each game in ao_search (active games packed, or handed out per simulation by the tree kernel), then the game of each row
-    std::vector<int32_t> h_row;
-    // rows handed out per simulation: LaunchLoop's ring of counter words, one per launch; row_cap = rows one simulation may take
-    // (0: as many as there are active games)
-    static constexpr int kLive = 2048;
-    unsigned* d_live = nullptr;
-    int32_t* d_order = nullptr;      // [G] launch order of k_expand_select's slots for over-subscribed searches (k_order, per move); AO_TREE_ORDER=0: off
-    bool order_on = true;
-    unsigned* h_live = nullptr;                           // pinned [kLive]
-    unsigned* d_ctl = nullptr;                            // [2][4] the sit-out window of the current / the next launch (tree_device.hpp, sit_window)
-    int row_cap = 0;
-    double ask_frac = 1.0;                                // rows asked for per simulation of a game in the last over-subscribed move (1 - terminal share)
-    ao::RowLedger rs;                                     // ao_row_stats
-    // ao_set_eval_log: what the network returned to the listed games, per simulation of the current ao_search
-    int32_t* d_log_games = nullptr; int log_n = 0; float* log_dev = nullptr; int64_t log_cap = 0; int64_t log_sim = 0;
-    size_t il_bytes = 0; int il_group_zeroed = -1, il_nchq_zeroed = -1;  // layout for which batch_il's padding is zero
-    // host mirrors
-    std::vector<std::vector<int32_t>> moves;
-    std::vector<int32_t> status;     // AO_ROOT_*
-    std::vector<int32_t> over;       // win index once the game ended
-    std::vector<uint8_t> active;
-    std::vector<int32_t> has_gauss; std::vector<double> gauss;
-    uint32_t* h_mt = nullptr; int32_t* h_pos = nullptr; double* h_noise = nullptr;  // pinned
-    double* h_out = nullptr;         // pinned [3][G][A]
-    int32_t* h_i32 = nullptr;        // pinned [4][G]
-    int sims_left = 0;
-    bool in_move = false, ended = false;
-    // per-game budgets and settling (ao_begin_move_opts, ao_settle, ao_search_opts, ao_search_sims)
-    std::vector<int32_t> bonus;      // [G] 1 where this move's root was fresh (its expansion is one simulation more than the budget)
-    int64_t target_sum = 0;          // simulations the current move set out to run, over the active games
-    int64_t move_saved = 0;          // ... and how many of them settling took away
-    bool leaf_open = false;          // a selection has been launched whose leaves are not backed up yet (k_settle's `pending`)
-    uint8_t* d_settled = nullptr;    // [G] 1 where k_settle lowered the game's target in this move
-    bool settled_dirty = false;      // d_settled may hold ones
-    uint8_t* d_early = nullptr;      // [G] ao_search_opts' early_stop mask
-    int32_t* d_settle = nullptr;     // [4] k_settle's counters of one launch
-    int32_t* h_settle = nullptr;     // pinned [4]
-    int64_t settled_total = 0, saved_total = 0;
-    // the root bar (ao_set_root_bar, ao_root_tactics with apply): what the NEXT ao_begin_move* / ao_search* is restricted to.
-    // Either the caller's masks on the host (bar_allowed / bar_has), turned into bitboards and uploaded by begin_move_impl, or
-    // bitboards that ao_root_tactics left in d_bar (bar_on_device). begin_move_impl consumes it; `used_*` is what the current
-    // move consumed, for the move the fp16-range recovery repeats.
-    uint64_t* d_bar = nullptr;              // [G][kBBWords] barred actions of the current move
-    std::vector<uint64_t> h_bar;            // staging of d_bar
-    std::vector<uint8_t> bar_allowed;       // [G][A] the caller's masks
-    std::vector<uint8_t> bar_has;           // [G] 1 where the game has a row in bar_allowed
-    bool bar_pending = false;               // some bar_has is set
-    bool bar_on_device = false;             // d_bar holds the next move's bar
-    bool bar_dirty = false;                 // a root may hold kBarQ children: the next move passes the bar array (zeros, if no game
-                                            // is barred) so that k_begin_move turns them back into unvisited children
-    std::vector<uint8_t> used_allowed, used_has;
-    bool used_pending = false, used_on_device = false;
-    bool bar_keep = false;                  // the fp16-range recovery resets its games and sets their roots again: the bar stays
-    // fp16-range recovery of ao_search: the games' MT19937 states as they were before the move (device copy), the host
-    // half of the stream (legacy gauss cache), the number of recovered moves and of games searched again
-    uint32_t* d_mt_backup = nullptr; int32_t* d_pos_backup = nullptr;
-    std::vector<int32_t> has_gauss_backup; std::vector<double> gauss_backup;
-    int64_t fp16_events = 0, fp16_games_redone = 0;
-    int node_cap_auto = 0;           // 1: node_cap was derived from the free HBM (ao_config.node_cap == -1)
-    // tree read-out (ao_tree_lookup / ao_tree_pv / ao_tree_stats): one device workspace, grown on demand, and its host mirror
-    ao::DevBuf<unsigned char> d_ro{&pool};
-    std::vector<unsigned char> h_ro;
-    // HIP-event timing of the per-simulation tree kernel (k_expand_select) on the launch stream (ao_tree_timing)
-    ao::EventTimer timer{256};
-    RollState roll;
-    // leaf symmetries (ao_set_leaf_symmetry): the seed most recently given to each game (never seeded: g), the keys made of
-    // them -- or set one by one, ao_set_leaf_symmetry_keys -- and their device copy, which tp.sym_key names while the switch is on
-    std::vector<uint32_t> sym_seed, sym_keys;
-    uint32_t* d_sym_key = nullptr;
-    bool sym_on = false;
-    uint32_t sym_base = 0;
-    // leaf tactics (ao_set_leaf_tactics): the solver's limits (lt_depth == 0: off), its stream and the two events of a launch
-    // pair, the byte and the counters of every game; all made by the first call that switches it on
-    int lt_depth = 0, lt_nodes = 0;
-    hipStream_t lt_stream = nullptr;
-    hipEvent_t lt_ready = nullptr, lt_done = nullptr;   // engine stream: the leaves are written; solver stream: the bytes are
-    uint8_t* d_lt_proven = nullptr;                     // [G]
-    int32_t* d_lt_counts = nullptr;                     // [G][4] searched, proven, out of nodes, nodes
-    // proven outcomes (ao_tree_proofs, ao_set_proof_moves): the proof words' workspace and the root's edge values, made by the
-    // first call that needs them (proofs_alloc); the switch, the verdicts of the last ao_end_move under it and the totals
-    int32_t* d_pf_ws = nullptr;                         // [G][cap] a node's proof word, by arena node
-    int32_t* d_pf_root = nullptr;                       // [G][4]
-    int8_t* d_pf_status = nullptr;                      // [G][A]
-    int16_t* d_pf_plies = nullptr;                      // [G][A]
-    int32_t* d_pf_verdict = nullptr;                    // [G]
-    bool proof_moves = false;
-    std::vector<int32_t> pm_verdict;                    // [G]
-    int64_t pm_totals[4] = {0, 0, 0, 0};
-};
 
 // The keys of the games as the device must see them. A seed call ends here as well: an episode's symmetries follow its seed.
 static int sym_upload(ao_engine* e) {
@@ -253,17 +45,145 @@ static void sym_reseed(ao_engine* e, int g, uint32_t seed) {
     e->sym_keys[g] = ao::leaf_key(e->sym_base, seed);
 }
 
+// ---- the helpers that the engine's other files call as well (declared in engine.hpp) ----------------
+namespace ao {
+
 // Inside an open roll the engine's games move on their own clocks: everything that begins, ends or steps a move of the whole
 // engine, moves roots or reads trees in bulk is refused until ao_roll_end.
-static int roll_refuses(ao_engine* e, const char* who) {
+int roll_refuses(ao_engine* e, const char* who) {
     if (!e->roll.open) return 0;
     return e->fail(std::string(who) + ": a roll is open (ao_roll_begin ... ao_roll_end); drain it (ao_roll_drain, ao_roll_run) and close it with ao_roll_end first");
 }
 // ... and what touches single games is refused for a game that is in a move of the roll
-static int roll_refuses_game(ao_engine* e, const char* who, int g) {
+int roll_refuses_game(ao_engine* e, const char* who, int g) {
     if (!e->roll.open || !e->roll.in_move[g]) return 0;
     return e->fail(std::string(who) + ": game " + std::to_string(g) + " is in a move of the open roll");
 }
+
+// a launcher refused by walk_lds_bytes (tree_walk.hpp); ao_create's node_cap <= 15000 keeps every engine below that bound
+int queue_refused(ao_engine* e, const char* who) {
+    return e->fail(std::string(who) + ": the breadth-first queue of a node_cap = " + std::to_string(e->tp.cap) + " arena does not fit the LDS of a workgroup");
+}
+
+// leaves the engine usable after a failure: the games' error words cleared, nothing queued any more
+void clear_game_errors(ao_engine* e) {
+    (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
+    (void)hipStreamSynchronize(e->stream);
+}
+
+// herr [G]: the games' error words as just read from the device. The first game with one fails the call with a message that
+// names it; the words are cleared and no move is in flight afterwards.
+int report_game_errors(ao_engine* e, const int32_t* herr) {
+    for (int g = 0; g < e->G; ++g) {
+        if (!herr[g]) continue;
+        std::string m = "game " + std::to_string(g) + ":";
+        if (herr[g] & ao::ERR_NODE_CAP) m += " tree arena full (raise ao_config.node_cap)";
+        if (herr[g] & ao::ERR_PATH) m += " no selectable child (priors are NaN: the policy summed to 0 over the legal moves -- the reference's prior /= prior.sum(), agents.py:189 -- or the tree is inconsistent)";
+        if (herr[g] & ao::ERR_BAD_MOVE) m += " move onto an occupied cell";
+        if (herr[g] & ao::ERR_SHORT) {
+            // the reference always runs num_mcts simulations (agents.py:105-132): a pi from fewer visits is never handed out
+            int32_t dt[2] = {0, 0};
+            (void)hipMemcpy(&dt[0], e->tp.sims_done + g, sizeof(int32_t), hipMemcpyDeviceToHost);
+            (void)hipMemcpy(&dt[1], e->tp.sims_target + g, sizeof(int32_t), hipMemcpyDeviceToHost);
+            int nshort = 0, nact = 0;
+            for (int k = 0; k < e->G; ++k) { nshort += (herr[k] & ao::ERR_SHORT) ? 1 : 0; nact += e->active[k] ? 1 : 0; }
+            m += " search ended after " + std::to_string(dt[0]) + " of " + std::to_string(dt[1]) + " simulations (" + std::to_string(nshort) + " of " +
+                 std::to_string(nact) + " active games are short; rows per simulation: " +
+                 (e->row_cap > 0 ? std::to_string(e->row_cap) : std::string("one per game")) + ")";
+        }
+        // leave the engine usable: the error words are cleared and no move is in flight (the caller resets the game)
+        clear_game_errors(e);
+        e->in_move = false;
+        e->ended = false;
+        return e->fail(m);
+    }
+    return 0;
+}
+
+// The Dirichlet draws of the games that begin a move with noise, as (game, staging row of its stream in h_mt / h_pos and of its
+// noise in h_noise). Every game has its own stream, so the draws do not depend on how the list is cut up: a short one inline, a
+// long one on the process's persistent host pool (host_rng.hpp: hardware threads / LOCAL_WORLD_SIZE, at most 32) in chunks of
+// 16, so that the ranks of a node do not oversubscribe the host at the start of every move.
+void draw_noise(ao_engine* e, const std::vector<std::pair<int32_t, size_t>>& draws) {
+    auto work = [&](int k0, int k1) {
+        for (int k = k0; k < k1; ++k) {
+            const auto [g, row] = draws[k];
+            ao::HostMT r{e->h_mt + row * 624, e->h_pos + row, &e->has_gauss[g], &e->gauss[g]};
+            r.dirichlet(e->cfg.alpha, e->A - static_cast<int>(e->moves[g].size()), e->h_noise + row * e->Ap);
+        }
+    };
+    const int n = static_cast<int>(draws.size());
+    if (n < 64) work(0, n);
+    else ao::HostPool::get().run(n, 16, work);
+}
+
+// A move that ao::roll_next_move refuses fails the call with a message that names the game (and, in a by-ply table, the ply).
+int move_refused(ao_engine* e, const char* who, int g, const ao::RollMove& m, const std::string& at_ply) {
+    if (m.refuse == 1)
+        return e->fail(std::string(who) + ": game " + std::to_string(g) + ": sims " + std::to_string(m.budget) + at_ply + " is outside 1.." +
+                       std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
+    if (m.refuse == 2)
+        return e->fail(std::string(who) + ": game " + std::to_string(g) + ": noise asked for on an engine created without noise");
+    return 0;
+}
+
+// k_settle's counters (settle_queue below), once the stream behind it has been synchronised
+void settle_harvest(ao_engine* e, int* unfinished, int* owed) {
+    *unfinished = e->h_settle[0];
+    *owed = e->h_settle[1];
+    e->settled_total += e->h_settle[2];
+    e->saved_total += e->h_settle[3];
+    e->move_saved += e->h_settle[3];
+}
+
+// The pending bar of the masked games (null: all) is dropped: their position changes (ao_play, ao_reset, ao_set_root(s)).
+int bar_forget(ao_engine* e, const uint8_t* mask) {
+    if (e->bar_keep || (!e->bar_pending && !e->bar_on_device)) return 0;
+    bool left = false;
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    for (int g = 0; g < e->G; ++g) {
+        if (!mask || mask[g]) {
+            e->bar_has[g] = 0;
+            if (e->bar_on_device)
+                AO_HIP(e, hipMemsetAsync(e->d_bar + static_cast<size_t>(g) * ao::kBBWords, 0, sizeof(uint64_t) * ao::kBBWords, e->stream));
+        }
+        left = left || e->bar_has[g];
+    }
+    e->bar_pending = left;
+    if (!mask) e->bar_on_device = false;
+    return 0;
+}
+
+// The pending masks as bitboards of barred actions in h_bar, for the games of `act` [G]: the empty cells of a game that its row
+// does not allow (ones on stones are ignored). A row that allows none of its game's empty cells is an error that names the game;
+// *any: some game is barred from some cell.
+int bar_build(ao_engine* e, const std::vector<uint8_t>& act, bool* any, const char* who) {
+    const int G = e->G, A = e->A;
+    *any = false;
+    std::fill(e->h_bar.begin(), e->h_bar.end(), 0ull);
+    if (!e->bar_pending) return 0;
+    std::vector<uint8_t> stone(A);
+    for (int g = 0; g < G; ++g) {
+        if (!act[g] || !e->bar_has[g]) continue;
+        std::fill(stone.begin(), stone.end(), 0);
+        for (int32_t m : e->moves[g]) stone[m] = 1;
+        const uint8_t* row = e->bar_allowed.data() + static_cast<size_t>(g) * A;
+        uint64_t* bits = e->h_bar.data() + static_cast<size_t>(g) * ao::kBBWords;
+        int open = 0, barred = 0;
+        for (int a = 0; a < A; ++a) {
+            if (stone[a]) continue;
+            if (row[a]) { ++open; continue; }
+            bits[a >> 6] |= 1ull << (a & 63);
+            ++barred;
+        }
+        if (open == 0 && barred > 0)
+            return e->fail(std::string(who) + ": game " + std::to_string(g) + ": the root bar allows no empty cell of the position");
+        *any = *any || barred > 0;
+    }
+    return 0;
+}
+
+}  // namespace ao
 
 int LaunchLoop::plan(ao_engine* e_, ao_net* net, int rows) {
     *this = LaunchLoop{e_};
@@ -345,39 +265,6 @@ int LaunchLoop::leaf_tactics(bool before_net) {
     return 0;
 }
 
-// leaves the engine usable after a failure: the games' error words cleared, nothing queued any more
-static void clear_game_errors(ao_engine* e) {
-    (void)hipMemsetAsync(e->tp.err, 0, sizeof(int32_t) * e->G, e->stream);
-    (void)hipStreamSynchronize(e->stream);
-}
-
-// The Dirichlet draws of the games that begin a move with noise, as (game, staging row of its stream in h_mt / h_pos and of its
-// noise in h_noise). Every game has its own stream, so the draws do not depend on how the list is cut up: a short one inline, a
-// long one on the process's persistent host pool (host_rng.hpp: hardware threads / LOCAL_WORLD_SIZE, at most 32) in chunks of
-// 16, so that the ranks of a node do not oversubscribe the host at the start of every move.
-static void draw_noise(ao_engine* e, const std::vector<std::pair<int32_t, size_t>>& draws) {
-    auto work = [&](int k0, int k1) {
-        for (int k = k0; k < k1; ++k) {
-            const auto [g, row] = draws[k];
-            ao::HostMT r{e->h_mt + row * 624, e->h_pos + row, &e->has_gauss[g], &e->gauss[g]};
-            r.dirichlet(e->cfg.alpha, e->A - static_cast<int>(e->moves[g].size()), e->h_noise + row * e->Ap);
-        }
-    };
-    const int n = static_cast<int>(draws.size());
-    if (n < 64) work(0, n);
-    else ao::HostPool::get().run(n, 16, work);
-}
-
-// A move that ao::roll_next_move refuses fails the call with a message that names the game (and, in a by-ply table, the ply).
-static int move_refused(ao_engine* e, const char* who, int g, const ao::RollMove& m, const std::string& at_ply = "") {
-    if (m.refuse == 1)
-        return e->fail(std::string(who) + ": game " + std::to_string(g) + ": sims " + std::to_string(m.budget) + at_ply + " is outside 1.." +
-                       std::to_string(e->S) + " (the arena and the descent bounds were sized by ao_config.sims)");
-    if (m.refuse == 2)
-        return e->fail(std::string(who) + ": game " + std::to_string(g) + ": noise asked for on an engine created without noise");
-    return 0;
-}
-
 extern "C" {
 
 const char* ao_version(void) { return "alpha_omok_amd 0.1 (gfx950)"; }
@@ -409,17 +296,7 @@ void ao_destroy(ao_engine* e) {
     if (!e) return;
     hipSetDevice(e->cfg.device);
     if (e->stream) hipStreamSynchronize(e->stream);
-    RollTactics& t = e->roll.tac;
-    if (t.stream) {   // (before any buffer goes: a batch may still be running)
-        hipStreamSynchronize(t.stream);
-        for (RollBatch& b : t.slot) {
-            if (b.ready) hipEventDestroy(b.ready);
-            if (b.done) hipEventDestroy(b.done);
-        }
-        hipStreamDestroy(t.stream);
-    }
-    if (t.h_words) hipHostFree(t.h_words);
-    if (t.h_allowed) hipHostFree(t.h_allowed);
+    roll_destroy(e);   // (before any buffer goes: a batch of the roll's solver may still be running)
     if (e->lt_stream) {   // (a call that failed between the solver's launch and its join may have left it running)
         hipStreamSynchronize(e->lt_stream);
         if (e->lt_ready) hipEventDestroy(e->lt_ready);
@@ -434,7 +311,6 @@ void ao_destroy(ao_engine* e) {
     if (e->h_i32) hipHostFree(e->h_i32);
     if (e->h_live) hipHostFree(e->h_live);
     if (e->h_settle) hipHostFree(e->h_settle);
-    if (e->roll.h_i32) hipHostFree(e->roll.h_i32);
     e->timer.destroy();
     if (e->own_stream) hipStreamDestroy(e->own_stream);
     delete e;
@@ -782,53 +658,6 @@ int ao_leaf_tactics_stats(ao_engine* e, int64_t out[4], int32_t* per_game, int r
 }
 
 // ---- the root bar ----------------------------------------------------------------------------
-// The pending bar of the masked games (null: all) is dropped: their position changes (ao_play, ao_reset, ao_set_root(s)).
-static int bar_forget(ao_engine* e, const uint8_t* mask) {
-    if (e->bar_keep || (!e->bar_pending && !e->bar_on_device)) return 0;
-    bool left = false;
-    AO_HIP(e, hipSetDevice(e->cfg.device));
-    for (int g = 0; g < e->G; ++g) {
-        if (!mask || mask[g]) {
-            e->bar_has[g] = 0;
-            if (e->bar_on_device)
-                AO_HIP(e, hipMemsetAsync(e->d_bar + static_cast<size_t>(g) * ao::kBBWords, 0, sizeof(uint64_t) * ao::kBBWords, e->stream));
-        }
-        left = left || e->bar_has[g];
-    }
-    e->bar_pending = left;
-    if (!mask) e->bar_on_device = false;
-    return 0;
-}
-
-// The pending masks as bitboards of barred actions in h_bar, for the games of `act` [G]: the empty cells of a game that its row
-// does not allow (ones on stones are ignored). A row that allows none of its game's empty cells is an error that names the game;
-// *any: some game is barred from some cell.
-static int bar_build(ao_engine* e, const std::vector<uint8_t>& act, bool* any, const char* who) {
-    const int G = e->G, A = e->A;
-    *any = false;
-    std::fill(e->h_bar.begin(), e->h_bar.end(), 0ull);
-    if (!e->bar_pending) return 0;
-    std::vector<uint8_t> stone(A);
-    for (int g = 0; g < G; ++g) {
-        if (!act[g] || !e->bar_has[g]) continue;
-        std::fill(stone.begin(), stone.end(), 0);
-        for (int32_t m : e->moves[g]) stone[m] = 1;
-        const uint8_t* row = e->bar_allowed.data() + static_cast<size_t>(g) * A;
-        uint64_t* bits = e->h_bar.data() + static_cast<size_t>(g) * ao::kBBWords;
-        int open = 0, barred = 0;
-        for (int a = 0; a < A; ++a) {
-            if (stone[a]) continue;
-            if (row[a]) { ++open; continue; }
-            bits[a >> 6] |= 1ull << (a & 63);
-            ++barred;
-        }
-        if (open == 0 && barred > 0)
-            return e->fail(std::string(who) + ": game " + std::to_string(g) + ": the root bar allows no empty cell of the position");
-        *any = *any || barred > 0;
-    }
-    return 0;
-}
-
 int ao_set_root_bar(ao_engine* e, const uint8_t* allowed) {
     if (roll_refuses(e, "ao_set_root_bar")) return 1;
     if (e->in_move) return e->fail("ao_set_root_bar inside a move (between ao_begin_move and ao_end_move)");
@@ -860,11 +689,6 @@ int ao_reset(ao_engine* e, const uint8_t* mask) {
     }
     e->in_move = false;
     return 0;
-}
-
-// a launcher refused by walk_lds_bytes (tree_walk.hpp); ao_create's node_cap <= 15000 keeps every engine below that bound
-static int queue_refused(ao_engine* e, const char* who) {
-    return e->fail(std::string(who) + ": the breadth-first queue of a node_cap = " + std::to_string(e->tp.cap) + " arena does not fit the LDS of a workgroup");
 }
 
 // Walks the listed games along their new ids in ONE launch (k_walk: a workgroup per listed game).
@@ -1068,13 +892,6 @@ static int settle_queue(ao_engine* e, const uint8_t* dmask, int stop_now) {
     e->settled_dirty = true;
     return 0;
 }
-static void settle_harvest(ao_engine* e, int* unfinished, int* owed) {
-    *unfinished = e->h_settle[0];
-    *owed = e->h_settle[1];
-    e->settled_total += e->h_settle[2];
-    e->saved_total += e->h_settle[3];
-    e->move_saved += e->h_settle[3];
-}
 
 int ao_settle(ao_engine* e, const uint8_t* mask, int stop_now, int32_t* unfinished) {
     if (roll_refuses(e, "ao_settle")) return 1;
@@ -1145,35 +962,6 @@ int ao_apply_evals(ao_engine* e, const float* dev_policy, const float* dev_value
     AO_HIP(e, hipGetLastError());
     if (e->sims_left > 0) --e->sims_left;
     e->leaf_open = false;
-    return 0;
-}
-
-// herr [G]: the games' error words as just read from the device. The first game with one fails the call with a message that
-// names it; the words are cleared and no move is in flight afterwards.
-static int report_game_errors(ao_engine* e, const int32_t* herr) {
-    for (int g = 0; g < e->G; ++g) {
-        if (!herr[g]) continue;
-        std::string m = "game " + std::to_string(g) + ":";
-        if (herr[g] & ao::ERR_NODE_CAP) m += " tree arena full (raise ao_config.node_cap)";
-        if (herr[g] & ao::ERR_PATH) m += " no selectable child (priors are NaN: the policy summed to 0 over the legal moves -- the reference's prior /= prior.sum(), agents.py:189 -- or the tree is inconsistent)";
-        if (herr[g] & ao::ERR_BAD_MOVE) m += " move onto an occupied cell";
-        if (herr[g] & ao::ERR_SHORT) {
-            // the reference always runs num_mcts simulations (agents.py:105-132): a pi from fewer visits is never handed out
-            int32_t dt[2] = {0, 0};
-            (void)hipMemcpy(&dt[0], e->tp.sims_done + g, sizeof(int32_t), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(&dt[1], e->tp.sims_target + g, sizeof(int32_t), hipMemcpyDeviceToHost);
-            int nshort = 0, nact = 0;
-            for (int k = 0; k < e->G; ++k) { nshort += (herr[k] & ao::ERR_SHORT) ? 1 : 0; nact += e->active[k] ? 1 : 0; }
-            m += " search ended after " + std::to_string(dt[0]) + " of " + std::to_string(dt[1]) + " simulations (" + std::to_string(nshort) + " of " +
-                 std::to_string(nact) + " active games are short; rows per simulation: " +
-                 (e->row_cap > 0 ? std::to_string(e->row_cap) : std::string("one per game")) + ")";
-        }
-        // leave the engine usable: the error words are cleared and no move is in flight (the caller resets the game)
-        clear_game_errors(e);
-        e->in_move = false;
-        e->ended = false;
-        return e->fail(m);
-    }
     return 0;
 }
 
@@ -1707,492 +1495,6 @@ int ao_tree_nodes(ao_engine* e, int g, int64_t* expanded, int64_t* dict_entries)
     return 0;
 }
 
-// ---- tree read-out on the device (tree_readout.hip) -------------------------------------------
-static int readout_begin(ao_engine* e, const char* who, size_t bytes) {
-    if (e->in_move) return e->fail(std::string(who) + " inside a move (between ao_begin_move and ao_end_move)");
-    AO_HIP(e, hipSetDevice(e->cfg.device));
-    if (bytes > e->d_ro.n) {
-        AO_HIP(e, hipStreamSynchronize(e->stream));   // nothing queued reads the old workspace
-        if (e->d_ro.reserve(e, bytes)) return 1;
-    }
-    if (e->h_ro.size() < bytes) e->h_ro.resize(bytes);
-    return 0;
-}
-
-// per game: 0 = not asked for, 1 = asked for, 2 = asked for and the root is a key of the reference's dict
-static void readout_mask(const ao_engine* e, const uint8_t* mask, uint8_t* out) {
-    for (int g = 0; g < e->G; ++g)
-        out[g] = (mask && !mask[g]) ? 0 : (e->status[g] != AO_ROOT_FRESH ? 2 : 1);
-}
-
-// replaces self.tree[node_id] (agents.py:52,206-210)
-int ao_tree_lookup(ao_engine* e, const int32_t* games, const int32_t* moves, int32_t stride, const int32_t* m, int32_t n,
-                   int32_t* status, double* node_nwqp, int32_t* nchild, int32_t* child_action, int32_t* child_n, float* child_w,
-                   float* child_q, double* child_p) {
-    constexpr int kChunk = 1024;   // queries per launch
-    if (e->in_move) return e->fail("ao_tree_lookup inside a move (between ao_begin_move and ao_end_move)");
-    if (n < 0 || stride < 0) return e->fail("ao_tree_lookup: negative query count or stride");
-    if (n == 0) return 0;
-    if (!games || !m || (!moves && stride > 0)) return e->fail("ao_tree_lookup: null argument");
-    const int A = e->A;
-    for (int i = 0; i < n; ++i) {
-        if (games[i] < 0 || games[i] >= e->G) return e->fail("game index out of range");
-        if (m[i] < 0) return e->fail("ao_tree_lookup: negative id length");
-        if (m[i] > stride && m[i] <= A) return e->fail("ao_tree_lookup: m[i] exceeds the row stride");
-    }
-    const bool kids = child_action || child_n || child_w || child_q || child_p;
-    const size_t qs = 3 + static_cast<size_t>(A);   // a query row: game, suffix length, root_known, suffix
-    const size_t in_bytes = kChunk * qs * 4;
-    const size_t out_bytes = static_cast<size_t>(kChunk) * (32 + 8 + (kids ? 24 * static_cast<size_t>(A) : 0));
-    if (readout_begin(e, "ao_tree_lookup", in_bytes + out_bytes)) return 1;
-    for (int64_t first = 0; first < n; first += kChunk) {
-        const int c = static_cast<int>(std::min<int64_t>(kChunk, n - first));
-        const size_t cA = static_cast<size_t>(c) * A;
-        int32_t* hq = reinterpret_cast<int32_t*>(e->h_ro.data());
-        for (int k = 0; k < c; ++k) {
-            const int64_t i = first + k;
-            const int g = games[i];
-            const std::vector<int32_t>& cur = e->moves[g];
-            const int32_t* id = moves + i * static_cast<int64_t>(stride);
-            int32_t* row = hq + static_cast<size_t>(k) * qs;
-            const bool extends = m[i] <= A && static_cast<size_t>(m[i]) >= cur.size() && std::equal(cur.begin(), cur.end(), id);
-            row[0] = g;
-            row[1] = extends ? m[i] - static_cast<int>(cur.size()) : -1;
-            row[2] = e->status[g] != AO_ROOT_FRESH ? 1 : 0;
-            if (extends) std::copy(id + cur.size(), id + m[i], row + 3);
-        }
-        // device layout of a chunk of c queries: the 8-byte arrays first
-        unsigned char* d = e->d_ro.p + in_bytes;
-        double* d_nwqp = reinterpret_cast<double*>(d);
-        double* d_cp = d_nwqp + 4 * static_cast<size_t>(c);
-        int32_t* d_status = reinterpret_cast<int32_t*>(d_cp + (kids ? cA : 0));
-        int32_t* d_nchild = d_status + c;
-        int32_t* d_ca = d_nchild + c;
-        int32_t* d_cn = d_ca + cA;
-        float* d_cw = reinterpret_cast<float*>(d_cn + cA);
-        float* d_cq = d_cw + cA;
-        const size_t used = static_cast<size_t>(c) * (32 + 8 + (kids ? 24 * static_cast<size_t>(A) : 0));
-        AO_HIP(e, hipMemcpyAsync(e->d_ro.p, hq, static_cast<size_t>(c) * qs * 4, hipMemcpyHostToDevice, e->stream));
-        ao::launch_tree_lookup(e->tp, reinterpret_cast<const int32_t*>(e->d_ro.p), c, static_cast<int>(qs), d_status, d_nchild, d_nwqp,
-                               kids ? d_ca : nullptr, kids ? d_cn : nullptr, kids ? d_cw : nullptr, kids ? d_cq : nullptr,
-                               kids ? d_cp : nullptr, e->stream);
-        AO_HIP(e, hipGetLastError());
-        unsigned char* h = e->h_ro.data() + in_bytes;
-        AO_HIP(e, hipMemcpyAsync(h, d, used, hipMemcpyDeviceToHost, e->stream));
-        AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffers are reused by the next chunk
-        auto at = [&](const void* dev) { return h + (static_cast<const unsigned char*>(dev) - d); };
-        if (node_nwqp) std::memcpy(node_nwqp + 4 * first, at(d_nwqp), sizeof(double) * 4 * c);
-        if (status) std::memcpy(status + first, at(d_status), sizeof(int32_t) * c);
-        if (nchild) std::memcpy(nchild + first, at(d_nchild), sizeof(int32_t) * c);
-        if (child_action) std::memcpy(child_action + first * A, at(d_ca), sizeof(int32_t) * cA);
-        if (child_n) std::memcpy(child_n + first * A, at(d_cn), sizeof(int32_t) * cA);
-        if (child_w) std::memcpy(child_w + first * A, at(d_cw), sizeof(float) * cA);
-        if (child_q) std::memcpy(child_q + first * A, at(d_cq), sizeof(float) * cA);
-        if (child_p) std::memcpy(child_p + first * A, at(d_cp), sizeof(double) * cA);
-    }
-    return 0;
-}
-
-// the line the search expects to be played: arg-max of agents.py:67-69's visit vector, node after node
-int ao_tree_pv(ao_engine* e, const uint8_t* mask, int32_t max_len, int32_t* action, int32_t* n, float* q, int32_t* len) {
-    if (e->in_move) return e->fail("ao_tree_pv inside a move (between ao_begin_move and ao_end_move)");
-    if (max_len < 1 || max_len > e->A) return e->fail("ao_tree_pv: max_len must be in 1..A");
-    const size_t G = static_cast<size_t>(e->G), GL = G * static_cast<size_t>(max_len);
-    const size_t out_bytes = (3 * GL + G) * 4;
-    if (readout_begin(e, "ao_tree_pv", out_bytes + G)) return 1;
-    uint8_t* h_mask = e->h_ro.data() + out_bytes;
-    readout_mask(e, mask, h_mask);
-    uint8_t* d_mask = e->d_ro.p + out_bytes;
-    int32_t* d_act = reinterpret_cast<int32_t*>(e->d_ro.p);
-    int32_t* d_n = d_act + GL;
-    float* d_q = reinterpret_cast<float*>(d_n + GL);
-    int32_t* d_len = reinterpret_cast<int32_t*>(d_q + GL);
-    AO_HIP(e, hipMemcpyAsync(d_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
-    ao::launch_tree_pv(e->tp, d_mask, max_len, d_act, d_n, d_q, d_len, e->stream);
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, out_bytes, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    const int32_t* h_act = reinterpret_cast<const int32_t*>(e->h_ro.data());
-    const int32_t* h_n = h_act + GL;
-    const float* h_q = reinterpret_cast<const float*>(h_n + GL);
-    const int32_t* h_len = reinterpret_cast<const int32_t*>(h_q + GL);
-    for (size_t g = 0; g < G; ++g) {
-        if (!h_mask[g]) continue;
-        const size_t l = static_cast<size_t>(h_len[g]), o = g * max_len;
-        if (action) std::memcpy(action + o, h_act + o, 4 * l);
-        if (n) std::memcpy(n + o, h_n + o, 4 * l);
-        if (q) std::memcpy(q + o, h_q + o, 4 * l);
-        if (len) len[g] = h_len[g];
-    }
-    return 0;
-}
-
-// replaces the prints of del_parents (agents.py:241-250)
-int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
-    if (e->in_move) return e->fail("ao_tree_stats inside a move (between ao_begin_move and ao_end_move)");
-    if (!out) return e->fail("ao_tree_stats: null output");
-    const size_t G = static_cast<size_t>(e->G);
-    if (readout_begin(e, "ao_tree_stats", 16 * G + G)) return 1;
-    uint8_t* h_mask = e->h_ro.data() + 16 * G;
-    readout_mask(e, mask, h_mask);
-    uint8_t* d_mask = e->d_ro.p + 16 * G;
-    AO_HIP(e, hipMemcpyAsync(d_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
-    if (ao::launch_tree_stats(e->tp, d_mask, reinterpret_cast<int32_t*>(e->d_ro.p), e->stream))
-        return queue_refused(e, "ao_tree_stats");
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, 16 * G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    const int32_t* h = reinterpret_cast<const int32_t*>(e->h_ro.data());
-    for (size_t g = 0; g < G; ++g)
-        if (h_mask[g] && h[4 * g] < 0) return e->fail("ao_tree_stats: game " + std::to_string(g) + ": the tree reaches more nodes than the arena holds (inconsistent tree)");
-    for (size_t g = 0; g < G; ++g)
-        if (h_mask[g]) std::memcpy(out + 4 * g, h + 4 * g, 16);
-    return 0;
-}
-
-// ---- proven outcomes (tree_proofs.hip) ----------------------------------------------------------
-static int proofs_alloc(ao_engine* e) {
-    if (e->d_pf_ws) return 0;
-    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A);
-    AO_HIP(e, hipSetDevice(e->cfg.device));
-    if (e->pool.alloc(e, &e->d_pf_root, 4 * G) || e->pool.alloc(e, &e->d_pf_status, G * A) || e->pool.alloc(e, &e->d_pf_plies, G * A) ||
-        e->pool.alloc(e, &e->d_pf_verdict, G) || e->pool.alloc(e, &e->d_pf_ws, G * static_cast<size_t>(e->tp.cap)))
-        return 1;
-    AO_HIP(e, hipMemsetAsync(e->d_pf_verdict, 0, sizeof(int32_t) * G, e->stream));
-    return 0;
-}
-
-// utils.tree_proofs of every masked game
-int ao_tree_proofs(ao_engine* e, const uint8_t* mask, int32_t max_len, int32_t* root, int8_t* child_status, int16_t* child_plies,
-                   int32_t* line, int32_t* line_len) {
-    if (roll_refuses(e, "ao_tree_proofs")) return 1;
-    if (e->in_move) return e->fail("ao_tree_proofs inside a move (between ao_begin_move and ao_end_move)");
-    if (max_len < 1 || max_len > e->A) return e->fail("ao_tree_proofs: max_len must be in 1..A");
-    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A), GL = G * static_cast<size_t>(max_len);
-    // workspace layout: line [G][max_len] and line_len [G] (int32), root [G][4] (int32), plies [G][A] (int16), status [G][A], mask [G]
-    const size_t o_len = 4 * GL, o_root = o_len + 4 * G, o_plies = o_root + 16 * G, o_status = o_plies + 2 * G * A, o_mask = o_status + G * A;
-    if (readout_begin(e, "ao_tree_proofs", o_mask + G) || proofs_alloc(e)) return 1;
-    uint8_t* h_mask = e->h_ro.data() + o_mask;
-    readout_mask(e, mask, h_mask);
-    unsigned char* d = e->d_ro.p;
-    AO_HIP(e, hipMemcpyAsync(d + o_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
-    if (ao::launch_tree_proofs(e->tp, d + o_mask, e->d_pf_ws, max_len, reinterpret_cast<int32_t*>(d + o_root), reinterpret_cast<int8_t*>(d + o_status),
-                               reinterpret_cast<int16_t*>(d + o_plies), reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + o_len), e->stream))
-        return queue_refused(e, "ao_tree_proofs");
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), d, o_mask, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    const unsigned char* h = e->h_ro.data();
-    const int32_t* h_root = reinterpret_cast<const int32_t*>(h + o_root);
-    for (size_t g = 0; g < G; ++g)
-        if (h_mask[g] && h_root[4 * g + 3] < 0) return e->fail("ao_tree_proofs: game " + std::to_string(g) + ": the tree reaches more nodes than the arena holds (inconsistent tree)");
-    for (size_t g = 0; g < G; ++g) {
-        if (!h_mask[g]) continue;
-        if (root) std::memcpy(root + 4 * g, h_root + 4 * g, 16);
-        if (child_status) std::memcpy(child_status + g * A, h + o_status + g * A, A);
-        if (child_plies) std::memcpy(child_plies + g * A, h + o_plies + 2 * g * A, 2 * A);
-        if (line) std::memcpy(line + g * max_len, h + 4 * g * max_len, 4 * static_cast<size_t>(max_len));
-        if (line_len) line_len[g] = reinterpret_cast<const int32_t*>(h + o_len)[g];
-    }
-    return 0;
-}
-
-int ao_set_proof_moves(ao_engine* e, int enable) {
-    if (roll_refuses(e, "ao_set_proof_moves")) return 1;
-    if (e->in_move) return e->fail("ao_set_proof_moves inside a move (between ao_begin_move and ao_end_move)");
-    if (enable) {
-        if (!ao::reroot_fits(e->tp)) return queue_refused(e, "ao_set_proof_moves");
-        if (proofs_alloc(e)) return 1;
-        if (e->pm_verdict.empty()) e->pm_verdict.assign(e->G, 0);
-    }
-    e->proof_moves = enable != 0;
-    return 0;
-}
-
-int ao_proof_move_records(ao_engine* e, int32_t* verdict, int64_t totals[4], int reset) {
-    if (verdict)
-        for (int g = 0; g < e->G; ++g) verdict[g] = e->pm_verdict.empty() ? 0 : e->pm_verdict[g];
-    if (totals) std::memcpy(totals, e->pm_totals, sizeof(e->pm_totals));
-    if (reset) std::fill(e->pm_totals, e->pm_totals + 4, 0);
-    return 0;
-}
-
-// ---- the forced-win solver on the engine's own roots (root_tactics.hip) -------------------------
-// utils.root_tactics of every active game's root position, read where it lives (TreeParams::rootpos): no move list goes to
-// the device. apply: the bar of the next move is left on the device -- the caller's pending masks (ao_set_root_bar)
-// intersected with what the solver allows, game by game; a game whose intersection would be empty keeps the caller's.
-int ao_root_tactics(ao_engine* e, const uint8_t* active, int32_t max_depth, int32_t max_nodes, int32_t apply, int32_t* verdict,
-                    int32_t* depth, uint8_t* allowed, int32_t* nodes, int32_t* unknown) {
-    if (roll_refuses(e, "ao_root_tactics")) return 1;
-    if (e->in_move) return e->fail("ao_root_tactics inside a move (between ao_begin_move and ao_end_move)");
-    const std::string bad_limits = ao::fw_limits_error("ao_root_tactics", max_depth, max_nodes);
-    if (!bad_limits.empty()) return e->fail(bad_limits);
-    if (e->tp.win_mark < 3 || e->tp.win_mark > 5 || e->tp.win_mark > e->cfg.board)
-        return e->fail("ao_root_tactics: the solver needs win_mark in 3..5 and at most the board size");
-    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A);
-    std::vector<uint8_t> act(G);
-    for (size_t g = 0; g < G; ++g) act[g] = (active ? active[g] : 1) && !e->over[g];
-    bool bar_any = false;
-    if (apply && bar_build(e, act, &bar_any, "ao_root_tactics")) return 1;   // (before any device call)
-    const size_t at_stage = G * ao::kBBWords * 8, at_pair = at_stage + G * 8, at_out = at_pair + G * A * 4;
-    const size_t out_bytes = G * 16 + G * A, at_mask = at_out + out_bytes;
-    if (readout_begin(e, "ao_root_tactics", at_mask + G)) return 1;
-    ao::RootTacticsBufs b{};
-    b.won = reinterpret_cast<uint64_t*>(e->d_ro.p);
-    b.stage = reinterpret_cast<uint32_t*>(e->d_ro.p + at_stage);
-    b.pair = reinterpret_cast<uint32_t*>(e->d_ro.p + at_pair);
-    b.verdict = reinterpret_cast<int32_t*>(e->d_ro.p + at_out);
-    b.depth = b.verdict + G; b.nodes = b.depth + G; b.unknown = b.nodes + G;
-    b.allowed = e->d_ro.p + at_out + G * 16;
-    uint8_t* d_act = e->d_ro.p + at_mask;
-    AO_HIP(e, hipMemcpyAsync(d_act, act.data(), G, hipMemcpyHostToDevice, e->stream));
-    if (apply) {
-        AO_HIP(e, hipMemcpyAsync(e->d_bar, e->h_bar.data(), sizeof(uint64_t) * e->h_bar.size(), hipMemcpyHostToDevice, e->stream));
-        b.bar = e->d_bar;
-    }
-    ao::launch_root_tactics(e->tp, d_act, max_depth, max_nodes, b, e->stream);
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p + at_out, out_bytes, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    if (apply) e->bar_on_device = true;
-    const int32_t* h = reinterpret_cast<const int32_t*>(e->h_ro.data());
-    if (verdict) std::memcpy(verdict, h, 4 * G);
-    if (depth) std::memcpy(depth, h + G, 4 * G);
-    if (nodes) std::memcpy(nodes, h + 2 * G, 4 * G);
-    if (unknown) std::memcpy(unknown, h + 3 * G, 4 * G);
-    if (allowed) std::memcpy(allowed, e->h_ro.data() + G * 16, G * A);
-    return 0;
-}
-
-// ---- tree snapshots (tree_snapshot.hip) --------------------------------------------------------
-// games of one chunk: [first, first + count) of the call's list, N nodes and E edges together
-struct SnapChunk { int first, count; size_t N, E; };
-
-// closes a chunk when its packed games reach kSnapChunkBytes (a chunk holds at least one game): the device workspace is
-// bounded by that plus one game, whatever node_cap is
-static std::vector<SnapChunk> snap_chunks(const std::vector<int32_t>& nodes, const std::vector<int32_t>& edges) {
-    constexpr size_t kSnapChunkBytes = static_cast<size_t>(64) << 20;
-    std::vector<SnapChunk> out;
-    SnapChunk c{0, 0, 0, 0};
-    for (int i = 0; i < static_cast<int>(nodes.size()); ++i) {
-        c.count += 1;
-        c.N += static_cast<size_t>(nodes[i]);
-        c.E += static_cast<size_t>(edges[i]);
-        if (ao::snap_packed_bytes(c.N, c.E) >= kSnapChunkBytes) {
-            out.push_back(c);
-            c = SnapChunk{i + 1, 0, 0, 0};
-        }
-    }
-    if (c.count > 0) out.push_back(c);
-    return out;
-}
-
-// workspace of a chunk: the packed arrays (+ `first`), the game table, and for an import the moves and the streams
-static size_t snap_table_at(const SnapChunk& c) { return (ao::snap_dev_bytes(c.N, c.E) + 15) & ~static_cast<size_t>(15); }
-static size_t snap_chunk_bytes(const SnapChunk& c, int A, bool import) {
-    return snap_table_at(c) + static_cast<size_t>(c.count) * 4 * (ao::kSnapRow + (import ? A + 624 : 0));
-}
-
-int ao_tree_export(ao_engine* e, const uint8_t* mask, ao_tree_snapshot* out) {
-    if (roll_refuses(e, "ao_tree_export")) return 1;
-    if (e->in_move) return e->fail("ao_tree_export inside a move (between ao_begin_move and ao_end_move)");
-    if (!out) return e->fail("ao_tree_export: null snapshot");
-    const int G = e->G, A = e->A;
-    std::vector<int32_t> games;
-    for (int g = 0; g < G; ++g)
-        if (!mask || mask[g]) games.push_back(g);
-    const int ng = static_cast<int>(games.size());
-    if (ng > 0 && (!out->hdr || !out->gauss || !out->mt || !out->moves)) return e->fail("ao_tree_export: null hdr / gauss / mt / moves array");
-    // one stats pass: what every masked game's root reaches
-    std::vector<int32_t> st(static_cast<size_t>(G) * 4, 0);
-    if (ao_tree_stats(e, mask, st.data())) return 1;
-    std::vector<int32_t> nodes(ng), edges(ng);
-    int64_t N = 0, E = 0;
-    for (int i = 0; i < ng; ++i) {
-        const int32_t* s4 = st.data() + 4 * static_cast<size_t>(games[i]);
-        nodes[i] = s4[0];
-        edges[i] = s4[0] > 0 ? s4[1] - 1 : 0;
-        N += nodes[i];
-        E += edges[i];
-    }
-    if (N > out->nodes || E > out->edges)
-        return e->fail("ao_tree_export: the masked games hold " + std::to_string(N) + " nodes and " + std::to_string(E) + " edges, the snapshot's arrays " +
-                       std::to_string(out->nodes) + " and " + std::to_string(out->edges));
-    if (N > 0 && (!out->nchild || !out->parent || !out->parent_edge)) return e->fail("ao_tree_export: null node array");
-    if (E > 0 && (!out->act || !out->n || !out->w || !out->q || !out->p || !out->child)) return e->fail("ao_tree_export: null edge array");
-    const std::vector<SnapChunk> chunks = snap_chunks(nodes, edges);
-    size_t ws = 0;
-    for (const SnapChunk& c : chunks) ws = std::max(ws, snap_chunk_bytes(c, A, false));
-    if (readout_begin(e, "ao_tree_export", ws)) return 1;
-    size_t n0 = 0, e0 = 0;   // first node / edge of the chunk in the caller's arrays
-    for (const SnapChunk& c : chunks) {
-        if (c.N == 0) continue;
-        const size_t tab_at = snap_table_at(c);
-        int32_t* h_tab = reinterpret_cast<int32_t*>(e->h_ro.data() + tab_at);
-        size_t no = 0, eo = 0;
-        for (int k = 0; k < c.count; ++k) {
-            int32_t* row = h_tab + static_cast<size_t>(k) * ao::kSnapRow;
-            const int i = c.first + k;
-            row[0] = games[i]; row[1] = static_cast<int32_t>(no); row[2] = static_cast<int32_t>(eo); row[3] = nodes[i]; row[4] = edges[i];
-            row[5] = row[6] = row[7] = 0;
-            no += nodes[i];
-            eo += edges[i];
-        }
-        const ao::SnapDev d = ao::snap_dev_at(e->d_ro.p, c.N, c.E);
-        AO_HIP(e, hipMemcpyAsync(e->d_ro.p + tab_at, h_tab, static_cast<size_t>(c.count) * ao::kSnapRow * 4, hipMemcpyHostToDevice, e->stream));
-        if (ao::launch_tree_pack(e->tp, d, reinterpret_cast<const int32_t*>(e->d_ro.p + tab_at), c.count, e->stream))
-            return queue_refused(e, "ao_tree_export");
-        AO_HIP(e, hipGetLastError());
-        AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, ao::snap_packed_bytes(c.N, c.E), hipMemcpyDeviceToHost, e->stream));
-        AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffers are reused by the next chunk
-        const ao::SnapDev h = ao::snap_dev_at(e->h_ro.data(), c.N, c.E);
-        std::memcpy(out->p + e0, h.p, 8 * c.E);
-        std::memcpy(out->n + e0, h.n, 4 * c.E);
-        std::memcpy(out->w + e0, h.w, 4 * c.E);
-        std::memcpy(out->q + e0, h.q, 4 * c.E);
-        std::memcpy(out->child + e0, h.child, 4 * c.E);
-        std::memcpy(out->act + e0, h.act, c.E);
-        std::memcpy(out->nchild + n0, h.nchild, 4 * c.N);
-        std::memcpy(out->parent + n0, h.parent, 4 * c.N);
-        std::memcpy(out->parent_edge + n0, h.pedge, 4 * c.N);
-        n0 += c.N;
-        e0 += c.E;
-    }
-    // the streams (the pinned staging rows of ao_begin_move are free outside a move) and the host mirrors
-    AO_HIP(e, hipMemcpyAsync(e->h_mt, e->tp.mt, sizeof(uint32_t) * 624 * G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipMemcpyAsync(e->h_pos, e->tp.mtpos, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    for (int i = 0; i < ng; ++i) {
-        const int g = games[i];
-        int32_t* h = out->hdr + static_cast<size_t>(i) * AO_SNAP_HDR;
-        h[0] = nodes[i]; h[1] = edges[i]; h[2] = static_cast<int32_t>(e->moves[g].size()); h[3] = e->status[g]; h[4] = e->over[g];
-        h[5] = e->h_pos[g]; h[6] = e->has_gauss[g]; h[7] = 0;
-        out->gauss[i] = e->gauss[g];
-        std::memcpy(out->mt + static_cast<size_t>(i) * 624, e->h_mt + static_cast<size_t>(g) * 624, sizeof(uint32_t) * 624);
-        int32_t* mv = out->moves + static_cast<size_t>(i) * A;
-        std::fill(mv, mv + A, 0);
-        std::copy(e->moves[g].begin(), e->moves[g].end(), mv);
-    }
-    out->board = e->cfg.board; out->inplanes = e->cfg.inplanes; out->win_mark = e->tp.win_mark;
-    out->sims = e->S; out->noise = e->tp.noise; out->c_puct = e->tp.c_puct;
-    out->games = ng; out->nodes = N; out->edges = E;
-    return 0;
-}
-
-int ao_tree_snapshot_check(const ao_tree_snapshot* snap) {
-    std::string& why = ao::create_error<ao_engine>();
-    why = ao::snapshot_check(snap);
-    return why.empty() ? 0 : 1;
-}
-
-int ao_tree_import(ao_engine* e, const int32_t* host_games, int32_t n, const ao_tree_snapshot* snap) {
-    if (roll_refuses(e, "ao_tree_import")) return 1;
-    if (e->in_move) return e->fail("ao_tree_import inside a move (between ao_begin_move and ao_end_move)");
-    if (!snap || (n > 0 && !host_games)) return e->fail("ao_tree_import: null argument");
-    if (n != snap->games) return e->fail("ao_tree_import: " + std::to_string(n) + " games listed, the snapshot holds " + std::to_string(snap->games));
-    const int G = e->G, A = e->A;
-    std::vector<uint8_t> seen(G, 0);
-    for (int i = 0; i < n; ++i) {
-        if (host_games[i] < 0 || host_games[i] >= G) return e->fail("game index out of range");
-        if (seen[host_games[i]]) return e->fail("ao_tree_import: a game is listed twice");
-        seen[host_games[i]] = 1;
-    }
-    if (snap->board != e->cfg.board || snap->inplanes != e->cfg.inplanes || snap->win_mark != e->tp.win_mark)
-        return e->fail("ao_tree_import: the snapshot is of board " + std::to_string(snap->board) + ", inplanes " + std::to_string(snap->inplanes) +
-                       ", win_mark " + std::to_string(snap->win_mark) + "; the engine has board " + std::to_string(e->cfg.board) + ", inplanes " +
-                       std::to_string(e->cfg.inplanes) + ", win_mark " + std::to_string(e->tp.win_mark));
-    const std::string why = ao::snapshot_check(snap);
-    if (!why.empty()) return e->fail("ao_tree_import: inconsistent snapshot: " + why);
-    if (n == 0) return 0;
-    // a pending bar belongs to the position it was set for; a snapshot taken after a barred move brings kBarQ children with it
-    std::vector<uint8_t> listed(G, 0);
-    for (int i = 0; i < n; ++i) listed[host_games[i]] = 1;
-    if (bar_forget(e, listed.data())) return 1;
-    for (int64_t k = 0; k < snap->edges && !e->bar_dirty; ++k) e->bar_dirty = snap->q[k] == ao::kBarQ;
-    std::vector<int32_t> nodes(n), edges(n);
-    for (int i = 0; i < n; ++i) {
-        nodes[i] = snap->hdr[static_cast<size_t>(i) * AO_SNAP_HDR];
-        edges[i] = snap->hdr[static_cast<size_t>(i) * AO_SNAP_HDR + 1];
-        if (nodes[i] > e->tp.keep_max)
-            return e->fail("ao_tree_import: snapshot game " + std::to_string(i) + " has " + std::to_string(nodes[i]) + " nodes, this engine keeps at most node_cap - sims - 1 = " +
-                           std::to_string(e->tp.keep_max) + " (raise ao_config.node_cap)");
-    }
-    const std::vector<SnapChunk> chunks = snap_chunks(nodes, edges);
-    size_t ws = 0;
-    for (const SnapChunk& c : chunks) ws = std::max(ws, snap_chunk_bytes(c, A, true));
-    if (readout_begin(e, "ao_tree_import", ws)) return 1;
-    size_t n0 = 0, e0 = 0;
-    for (const SnapChunk& c : chunks) {
-        AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffer is free
-        const ao::SnapDev h = ao::snap_dev_at(e->h_ro.data(), c.N, c.E);
-        std::memcpy(h.p, snap->p + e0, 8 * c.E);
-        std::memcpy(h.n, snap->n + e0, 4 * c.E);
-        std::memcpy(h.w, snap->w + e0, 4 * c.E);
-        std::memcpy(h.q, snap->q + e0, 4 * c.E);
-        std::memcpy(h.child, snap->child + e0, 4 * c.E);
-        std::memcpy(h.act, snap->act + e0, c.E);
-        std::memcpy(h.nchild, snap->nchild + n0, 4 * c.N);
-        std::memcpy(h.parent, snap->parent + n0, 4 * c.N);
-        std::memcpy(h.pedge, snap->parent_edge + n0, 4 * c.N);
-        const size_t tab_at = snap_table_at(c);
-        int32_t* h_tab = reinterpret_cast<int32_t*>(e->h_ro.data() + tab_at);
-        int32_t* h_mv = h_tab + static_cast<size_t>(c.count) * ao::kSnapRow;
-        uint32_t* h_mt = reinterpret_cast<uint32_t*>(h_mv + static_cast<size_t>(c.count) * A);
-        size_t no = 0, eo = 0;
-        for (int k = 0; k < c.count; ++k) {
-            const int i = c.first + k;
-            const int32_t* hd = snap->hdr + static_cast<size_t>(i) * AO_SNAP_HDR;
-            int32_t* row = h_tab + static_cast<size_t>(k) * ao::kSnapRow;
-            row[0] = host_games[i]; row[1] = static_cast<int32_t>(no); row[2] = static_cast<int32_t>(eo); row[3] = nodes[i]; row[4] = edges[i];
-            row[5] = hd[2]; row[6] = hd[3]; row[7] = hd[5];
-            int32_t run = 0;   // a node's first edge inside its game
-            for (int j = 0; j < nodes[i]; ++j) {
-                h.first[no + j] = run;
-                run += h.nchild[no + j];
-            }
-            std::memcpy(h_mv + static_cast<size_t>(k) * A, snap->moves + static_cast<size_t>(i) * A, sizeof(int32_t) * A);
-            std::memcpy(h_mt + static_cast<size_t>(k) * 624, snap->mt + static_cast<size_t>(i) * 624, sizeof(uint32_t) * 624);
-            no += nodes[i];
-            eo += edges[i];
-        }
-        const size_t bytes = snap_chunk_bytes(c, A, true);
-        AO_HIP(e, hipMemcpyAsync(e->d_ro.p, e->h_ro.data(), bytes, hipMemcpyHostToDevice, e->stream));
-        const int32_t* d_tab = reinterpret_cast<const int32_t*>(e->d_ro.p + tab_at);
-        const int32_t* d_mv = d_tab + static_cast<size_t>(c.count) * ao::kSnapRow;
-        ao::launch_tree_unpack(e->tp, ao::snap_dev_at(e->d_ro.p, c.N, c.E), d_tab, d_mv,
-                               reinterpret_cast<const uint32_t*>(d_mv + static_cast<size_t>(c.count) * A), c.count, e->stream);
-        AO_HIP(e, hipGetLastError());
-        n0 += c.N;
-        e0 += c.E;
-    }
-    int32_t* herr = e->h_i32;
-    AO_HIP(e, hipMemcpyAsync(herr, e->tp.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    std::vector<uint8_t> bmask;
-    std::string bad;
-    for (int i = 0; i < n; ++i) {
-        const int g = host_games[i];
-        const int32_t* hd = snap->hdr + static_cast<size_t>(i) * AO_SNAP_HDR;
-        const int32_t* mv = snap->moves + static_cast<size_t>(i) * A;
-        e->moves[g].assign(mv, mv + hd[2]);
-        e->status[g] = hd[3];
-        e->over[g] = hd[4];
-        e->has_gauss[g] = hd[6];
-        e->gauss[g] = snap->gauss[i];
-        if (herr[g] & ao::ERR_BAD_MOVE) {
-            if (bmask.empty()) bmask.assign(G, 0);
-            bmask[g] = 1;
-            bad += (bad.empty() ? "" : ", ") + std::to_string(i);
-        }
-    }
-    e->ended = false;   // ao_play must follow a search on this engine, as on a fresh one
-    if (!bmask.empty()) {
-        ao_reset(e, bmask.data());
-        return e->fail("ao_tree_import: snapshot game(s) " + bad + ": an action lands on an occupied cell when the positions are rebuilt; reset (the other games of the call are imported)");
-    }
-    return 0;
-}
-
 int ao_tree_timing(ao_engine* e, int enable, double* ms_total, int64_t* launches) {
     AO_HIP(e, hipSetDevice(e->cfg.device));
     return e->timer.enable(e, enable, ms_total, launches);   // enable = n > 1: every n-th launch carries the event pair (their cost: see net_forward_il)
@@ -2222,679 +1524,6 @@ int ao_search_stats(ao_engine* e, int64_t* levels, int64_t* ties, int64_t* termi
     if (ties) *ties = static_cast<int64_t>(h[1]);
     if (terminal) *terminal = static_cast<int64_t>(h[2]);
     if (evaluated) *evaluated = static_cast<int64_t>(h[3]);
-    return 0;
-}
-
-// ---- the rolling search ------------------------------------------------------------------------
-// ao_search moves every game of the engine through one move per call: the launch loop of a move lasts until its LAST game has its
-// simulations. Here the launch loop never stops for a move: every turn_every launches the games that have their simulations are
-// TURNED -- move ended and played (k_roll_turn, k_reroot), the next one begun (k_roll_begin) -- while the others are mid-search
-// in the same launches. A game's search stays strictly sequential: the records equal ao_search + ao_play of that game to the bit.
-// Which games turn, what their next move is, when a run returns and the order of looks, launches and turns: roll_schedule.hpp.
-static void roll_count(ao_engine* e, size_t bytes) { e->roll.bytes += static_cast<int64_t>(bytes); }
-
-// every way out of a roll, the failures included: no game is in a move and the engine is between moves
-static void roll_close(ao_engine* e) {
-    RollState& r = e->roll;
-    if (r.tac.on) {   // the solver's stream first: no batch runs on when the buffers are reused; roots may hold the sentinels of a bar
-        (void)hipStreamSynchronize(r.tac.stream);
-        for (RollBatch& b : r.tac.slot) b.busy = false;
-        r.tac.pending.clear();
-        r.tac.n_waiting = 0;
-        r.tac.on = false;
-        e->bar_dirty = true;
-    }
-    r.open = false;
-    r.draining = false;
-    std::fill(r.in_move.begin(), r.in_move.end(), 0);
-    r.n_in_move = 0;
-    e->in_move = false;
-    e->ended = false;
-}
-
-// what a failure inside the loop leaves behind: error words cleared, the roll closed (check_game_errors does the same for its own)
-static int roll_fail(ao_engine* e, const std::string& m) {
-    clear_game_errors(e);
-    roll_close(e);
-    return e->fail(m);
-}
-
-// Takes the per-game fields of `o` for the games of `act` into the roll's tables -- after every column of theirs has been found in
-// range: a refused call has touched nothing. fresh: the tables of a roll that begins (what an earlier roll left is dropped).
-static int roll_take_tables(ao_engine* e, const ao_roll_opts* o, const std::vector<uint8_t>& act, bool fresh, const char* who) {
-    RollState& r = e->roll;
-    const int G = e->G;
-    if (o->sims && o->sims_stride < 1) return e->fail(std::string(who) + ": sims_stride must be >= 1");
-    if (o->noise && o->noise_stride < 1) return e->fail(std::string(who) + ": noise_stride must be >= 1");
-    if (!fresh && o->sims && !r.sims.empty() && o->sims_stride != r.sims_stride) return e->fail(std::string(who) + ": sims_stride differs from the open roll's");
-    if (!fresh && o->noise && !r.noise.empty() && o->noise_stride != r.noise_stride) return e->fail(std::string(who) + ": noise_stride differs from the open roll's");
-    for (int g = 0; g < G; ++g) {
-        if (!act[g]) continue;
-        const int cols = std::max(o->sims ? o->sims_stride : 1, o->noise ? o->noise_stride : 1);
-        for (int c = 0; c < cols; ++c) {
-            const ao::RollMove m = ao::roll_next_move(c, -1, o->sims ? o->sims + static_cast<size_t>(g) * o->sims_stride : nullptr, o->sims_stride,
-                                                      o->noise ? o->noise + static_cast<size_t>(g) * o->noise_stride : nullptr, o->noise_stride,
-                                                      e->tp.noise != 0, e->S, AO_ROOT_EXPANDED);
-            if (move_refused(e, who, g, m, " at ply " + std::to_string(c))) return 1;
-        }
-    }
-    if (fresh) {
-        r.tau_plies.clear(); r.sims.clear(); r.noise.clear();
-        r.sims_stride = r.noise_stride = 0;
-    }
-    if (o->tau_plies && r.tau_plies.empty()) r.tau_plies.assign(G, -1);
-    if (o->sims && r.sims.empty()) { r.sims_stride = o->sims_stride; r.sims.assign(static_cast<size_t>(G) * r.sims_stride, e->S); }
-    if (o->noise && r.noise.empty()) { r.noise_stride = o->noise_stride; r.noise.assign(static_cast<size_t>(G) * r.noise_stride, e->tp.noise ? 1 : 0); }
-    for (int g = 0; g < G; ++g) {
-        if (!act[g]) continue;
-        if (o->tau_plies) r.tau_plies[g] = std::max(o->tau_plies[g], 0);
-        if (o->sims) std::copy(o->sims + static_cast<size_t>(g) * r.sims_stride, o->sims + static_cast<size_t>(g + 1) * r.sims_stride, r.sims.begin() + static_cast<size_t>(g) * r.sims_stride);
-        if (o->noise) std::copy(o->noise + static_cast<size_t>(g) * r.noise_stride, o->noise + static_cast<size_t>(g + 1) * r.noise_stride, r.noise.begin() + static_cast<size_t>(g) * r.noise_stride);
-    }
-    return 0;
-}
-
-// Begins the next move of the listed games (not in a move, not over). rows: where game games[k]'s stream lies in the compact
-// staging rows (h_mt / h_pos, gathered by the turn that just played it), or null: the streams are gathered here. The Dirichlet
-// draw of the games that search with noise is the host's (host_rng.hpp), on the pool; everything travels in compact rows.
-// batches (with the solver beside the loop): the games are those of the listed finished batches, in order, and were waiting;
-// k_roll_verdict takes each batch's bar rows and verdicts to its games in front of k_roll_begin.
-static int roll_begin_games(ao_engine* e, const std::vector<int32_t>& games, const int32_t* rows, const std::vector<int>* batches = nullptr) {
-    RollState& r = e->roll;
-    const int n = static_cast<int>(games.size()), G = e->G, Ap = e->Ap;
-    if (n == 0) return 0;
-    int32_t* h_games = r.h_i32 + 4 * static_cast<size_t>(G);
-    int32_t* h_items = h_games + G;
-    std::vector<ao::RollMove> mv(n);
-    bool any_draw = false;
-    for (int k = 0; k < n; ++k) {   // the move each game begins now (roll_schedule.hpp), from the roll's tables and the host mirrors
-        const int g = games[k];
-        mv[k] = ao::roll_next_move(static_cast<int>(e->moves[g].size()), r.tau_plies.empty() ? -1 : r.tau_plies[g],
-                                   r.sims.empty() ? nullptr : r.sims.data() + static_cast<size_t>(g) * r.sims_stride, r.sims_stride,
-                                   r.noise.empty() ? nullptr : r.noise.data() + static_cast<size_t>(g) * r.noise_stride, r.noise_stride,
-                                   e->tp.noise != 0, e->S, e->status[g]);
-        any_draw = any_draw || mv[k].draw;
-    }
-    if (!rows) {
-        AO_HIP(e, hipStreamSynchronize(e->stream));   // (the pinned staging rows are free)
-        if (any_draw) {
-            std::copy(games.begin(), games.end(), h_games);
-            AO_HIP(e, hipMemcpyAsync(r.d_games, h_games, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
-            ao::launch_roll_gather(e->tp, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
-            AO_HIP(e, hipGetLastError());
-            AO_HIP(e, hipMemcpyAsync(e->h_mt, e->d_mt_backup, sizeof(uint32_t) * 624 * n, hipMemcpyDeviceToHost, e->stream));
-            AO_HIP(e, hipMemcpyAsync(e->h_pos, e->d_pos_backup, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
-            AO_HIP(e, hipStreamSynchronize(e->stream));
-            roll_count(e, static_cast<size_t>(n) * (4 + 624 * 4 + 4));
-        }
-    }
-    int nrows = 0;   // staging rows in use: [0, nrows)
-    std::vector<std::pair<int32_t, size_t>> draws;   // (no draw for a game without noise: its stream is not touched)
-    for (int k = 0; k < n; ++k) {
-        const int g = games[k];
-        const int row = rows ? rows[k] : k;
-        int32_t* it = h_items + static_cast<size_t>(k) * ao::kRollItem;
-        it[0] = g; it[1] = mv[k].target; it[2] = mv[k].gflags; it[3] = mv[k].tau;
-        it[4] = (r.early && mv[k].tau == 0) ? 1 : 0;
-        if (batches && mv[k].target != mv[k].budget) it[4] |= 2;   // (k_roll_verdict caps the budget, not the root's own expansion)
-        it[5] = mv[k].draw ? row : -1;
-        if (mv[k].draw) {
-            nrows = std::max(nrows, row + 1);
-            draws.emplace_back(g, row);
-        }
-    }
-    if (any_draw) {
-        draw_noise(e, draws);
-        AO_HIP(e, hipMemcpyAsync(e->d_mt_backup, e->h_mt, sizeof(uint32_t) * 624 * nrows, hipMemcpyHostToDevice, e->stream));
-        AO_HIP(e, hipMemcpyAsync(e->d_pos_backup, e->h_pos, sizeof(int32_t) * nrows, hipMemcpyHostToDevice, e->stream));
-        AO_HIP(e, hipMemcpyAsync(r.d_noise, e->h_noise, sizeof(double) * Ap * nrows, hipMemcpyHostToDevice, e->stream));
-        roll_count(e, static_cast<size_t>(nrows) * (624 * 4 + 4 + sizeof(double) * Ap));
-    }
-    AO_HIP(e, hipMemcpyAsync(r.d_items, h_items, sizeof(int32_t) * ao::kRollItem * n, hipMemcpyHostToDevice, e->stream));
-    roll_count(e, sizeof(int32_t) * ao::kRollItem * n);
-    if (batches) {
-        RollTactics& t = r.tac;
-        size_t at = 0;
-        for (int i : *batches) {
-            RollBatch& b = t.slot[i];
-            AO_HIP(e, hipStreamWaitEvent(e->stream, b.done, 0));   // (reached already: the host saw it, or waited for it)
-            ao::launch_roll_verdict(r.d_items + at * ao::kRollItem, b.view, e->A, t.solved_sims, e->d_bar, t.d_words, t.d_allowed, e->stream);
-            at += static_cast<size_t>(b.n);
-        }
-    }
-    ao::launch_roll_begin(r.loop.p, r.d_items, n, e->d_mt_backup, e->d_pos_backup, r.d_noise, e->d_tau, e->d_active, e->d_settled, e->d_early, e->stream);
-    AO_HIP(e, hipGetLastError());
-    e->settled_dirty = true;
-    for (int k = 0; k < n; ++k) {
-        const int g = games[k];
-        e->bonus[g] = mv[k].target - mv[k].budget;
-        e->active[g] = 1;
-        if (r.in_move[g] == ao::ROLL_OUT) ++r.n_in_move;   // (a game that waited for its verdict has been in a move since it was listed)
-        r.in_move[g] = ao::ROLL_SEARCHING;
-    }
-    return 0;
-}
-
-// ---- the solver beside the loop ----
-// the batch's buffer for n games, carved up: the solver's RootTacticsBufs, the position rows, the games; *view: what k_roll_verdict reads
-static int roll_batch_layout(ao_engine* e, RollBatch& b, int n, ao::RootTacticsBufs* bufs, ao::Pos** rows) {
-    RollTactics& t = e->roll.tac;
-    const size_t N = static_cast<size_t>(n), A = static_cast<size_t>(e->A);
-    auto up = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
-    const size_t at_pos = 0, at_won = up(at_pos + N * sizeof(ao::Pos)), at_bar = up(at_won + N * ao::kBBWords * 8), at_stage = up(at_bar + N * ao::kBBWords * 8),
-                 at_pair = up(at_stage + N * 8), at_words = up(at_pair + N * A * 4), at_allowed = up(at_words + N * 16),
-                 bytes = at_allowed + (t.want_allowed ? N * A : 0);
-    if (!b.buf.p || bytes > b.buf.n) {   // (grows: the slot's last batch was read by kernels queued on the engine's stream)
-        AO_HIP(e, hipStreamSynchronize(e->stream));
-        b.buf.pool = &e->pool;
-        if (b.buf.reserve(e, bytes)) return 1;
-    }
-    unsigned char* p = b.buf.p;
-    *rows = reinterpret_cast<ao::Pos*>(p + at_pos);
-    *bufs = ao::RootTacticsBufs{};
-    bufs->won = reinterpret_cast<uint64_t*>(p + at_won);
-    bufs->bar = reinterpret_cast<uint64_t*>(p + at_bar);
-    bufs->stage = reinterpret_cast<uint32_t*>(p + at_stage);
-    bufs->pair = reinterpret_cast<uint32_t*>(p + at_pair);
-    bufs->verdict = reinterpret_cast<int32_t*>(p + at_words);
-    bufs->depth = bufs->verdict + N; bufs->nodes = bufs->depth + N; bufs->unknown = bufs->nodes + N;
-    bufs->allowed = t.want_allowed ? p + at_allowed : nullptr;
-    b.view = ao::RollBatchView{bufs->bar, bufs->verdict, bufs->allowed, n};
-    return 0;
-}
-
-// Starts a batch for the listed games in a free slot: their root positions into the batch's rows on the engine's stream, the
-// three solver launches behind an event on the solver's. streams: the games' MT19937 states and positions ([n][624], [n]) as the
-// host holds them now -- the Dirichlet draw of the move comes from them when the batch's games begin.
-static int roll_batch_start(ao_engine* e, const std::vector<int32_t>& games, std::vector<uint32_t>&& mt, std::vector<int32_t>&& pos) {
-    RollState& r = e->roll;
-    RollTactics& t = r.tac;
-    const int n = static_cast<int>(games.size());
-    int i = 0;
-    while (i < ao::kRollBatchSlots && t.slot[i].busy) ++i;
-    if (i == ao::kRollBatchSlots) return e->fail("ao_roll: no free solver batch slot");   // (roll_must_block keeps one free)
-    RollBatch& b = t.slot[i];
-    ao::RootTacticsBufs bufs;
-    ao::Pos* rows = nullptr;
-    if (roll_batch_layout(e, b, n, &bufs, &rows)) return 1;
-    if (!b.ready) {
-        AO_HIP(e, hipEventCreateWithFlags(&b.ready, hipEventDisableTiming));
-        AO_HIP(e, hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
-    }
-    b.games = games;
-    b.mt = std::move(mt);
-    b.pos = std::move(pos);
-    b.n = n;
-    b.age = 0;
-    // (d_games is free: whatever listed these games -- a turn, a begin, a join -- has synchronised behind its last use)
-    AO_HIP(e, hipMemcpyAsync(r.d_games, b.games.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
-    ao::launch_roll_rootpos(e->tp, r.d_games, n, rows, e->stream);
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipEventRecord(b.ready, e->stream));
-    AO_HIP(e, hipStreamWaitEvent(t.stream, b.ready, 0));
-    AO_HIP(e, hipMemsetAsync(bufs.bar, 0, sizeof(uint64_t) * ao::kBBWords * n, t.stream));   // (no caller's bar under rolling)
-    ao::launch_root_tactics_rows(rows, n, e->tp.B, e->A, e->tp.win_mark, t.max_depth, t.max_nodes, bufs, t.stream);
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipEventRecord(b.done, t.stream));
-    b.busy = true;
-    t.pending.push_back(i);
-    for (int g : games) {
-        if (r.in_move[g] == ao::ROLL_OUT) ++r.n_in_move;
-        r.in_move[g] = ao::ROLL_WAITING;
-    }
-    t.n_waiting += n;
-    t.stats[0] += 1;
-    t.stats[5] += static_cast<int64_t>(sizeof(int32_t)) * n;
-    roll_count(e, sizeof(int32_t) * n);
-    return 0;
-}
-
-// The games of the taken batches begin their move, in one k_roll_begin: their streams go back into the staging rows first.
-static int roll_batches_begin(ao_engine* e, const std::vector<int>& taken) {
-    RollTactics& t = e->roll.tac;
-    if (taken.empty()) return 0;
-    std::vector<int32_t> games, rows;
-    for (int i : taken) {
-        RollBatch& b = t.slot[i];
-        for (int k = 0; k < b.n; ++k) {
-            const size_t row = games.size();
-            if (!b.mt.empty()) {
-                std::memcpy(e->h_mt + row * 624, b.mt.data() + static_cast<size_t>(k) * 624, sizeof(uint32_t) * 624);
-                e->h_pos[row] = b.pos[k];
-            }
-            games.push_back(b.games[k]);
-            rows.push_back(static_cast<int32_t>(row));
-        }
-    }
-    const int rc = roll_begin_games(e, games, rows.data(), &taken);
-    for (int i : taken) {
-        t.slot[i].busy = false;
-        t.n_waiting -= t.slot[i].n;
-        t.stats[1] += t.slot[i].n;
-    }
-    return rc;
-}
-
-// What a turn (at_turn), a begin or a join does about the solver once it knows which games are to begin a move (`next`; rows:
-// where their streams lie in the staging rows, or null: they are gathered here). The order matters: the streams of `next` leave
-// the staging rows first; the batches whose verdicts are in begin their games (which uses the staging rows, and reads the
-// batches' buffers on the engine's stream); only then does the new batch take a slot. The engine's stream has been synchronised
-// by the caller. The host waits for nothing but the oldest batch's recorded event, and only where roll_must_block says so.
-static int roll_tactics_step(ao_engine* e, const std::vector<int32_t>& next, const int32_t* rows, bool at_turn) {
-    RollState& r = e->roll;
-    RollTactics& t = r.tac;
-    const int n = static_cast<int>(next.size());
-    std::vector<uint32_t> mt;
-    std::vector<int32_t> pos;
-    if (!at_turn) AO_HIP(e, hipStreamSynchronize(e->stream));   // (the pinned staging rows are free)
-    if (n > 0 && e->tp.noise != 0) {
-        if (!rows) {
-            int32_t* h_games = r.h_i32 + 4 * static_cast<size_t>(e->G);
-            std::copy(next.begin(), next.end(), h_games);
-            AO_HIP(e, hipMemcpyAsync(r.d_games, h_games, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
-            ao::launch_roll_gather(e->tp, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
-            AO_HIP(e, hipGetLastError());
-            AO_HIP(e, hipMemcpyAsync(e->h_mt, e->d_mt_backup, sizeof(uint32_t) * 624 * n, hipMemcpyDeviceToHost, e->stream));
-            AO_HIP(e, hipMemcpyAsync(e->h_pos, e->d_pos_backup, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
-            AO_HIP(e, hipStreamSynchronize(e->stream));
-            roll_count(e, static_cast<size_t>(n) * (4 + 624 * 4 + 4));
-        }
-        mt.resize(static_cast<size_t>(n) * 624);
-        pos.resize(n);
-        for (int k = 0; k < n; ++k) {
-            const size_t row = rows ? rows[k] : k;
-            std::memcpy(mt.data() + static_cast<size_t>(k) * 624, e->h_mt + row * 624, sizeof(uint32_t) * 624);
-            pos[k] = e->h_pos[row];
-        }
-    }
-    std::vector<int> taken;
-    auto take_oldest = [&]() { taken.push_back(t.pending.front()); t.pending.erase(t.pending.begin()); };
-    if (at_turn)
-        for (int i : t.pending) { ++t.slot[i].age; t.stats[2] += t.slot[i].n; }
-    const int searching = r.n_in_move - t.n_waiting;
-    if (!t.pending.empty() && ao::roll_must_block(static_cast<int>(t.pending.size()), ao::kRollBatchSlots, n > 0, searching, static_cast<int>(t.pending.size()))) {
-        AO_HIP(e, hipEventSynchronize(t.slot[t.pending.front()].done));
-        ++t.stats[3];
-        take_oldest();
-    }
-    while (at_turn && !t.pending.empty()) {
-        const RollBatch& b = t.slot[t.pending.front()];
-        const hipError_t q = hipEventQuery(b.done);
-        if (q != hipSuccess && q != hipErrorNotReady) return e->fail(std::string("ao_roll: hipEventQuery: ") + hipGetErrorString(q));
-        if (!ao::roll_batch_begins(q == hipSuccess, b.age, t.hold, false)) break;
-        take_oldest();
-    }
-    if (roll_batches_begin(e, taken)) return 1;
-    if (n == 0) return 0;
-    if (roll_batch_start(e, next, std::move(mt), std::move(pos))) return 1;
-    if (ao::roll_must_block(static_cast<int>(t.pending.size()), ao::kRollBatchSlots, false, r.n_in_move - t.n_waiting, static_cast<int>(t.pending.size()))) {
-        // (nothing was pending before, or its games would be searching now: the staging rows are not in use)
-        AO_HIP(e, hipEventSynchronize(t.slot[t.pending.front()].done));
-        ++t.stats[3];
-        taken.clear();
-        take_oldest();
-        if (roll_batches_begin(e, taken)) return 1;
-    }
-    return 0;
-}
-
-// the games of a begin / join: listed (null: all), not over; a listed game that is in a move already is refused by name
-static int roll_listed(ao_engine* e, const uint8_t* active, std::vector<uint8_t>* act, const char* who) {
-    act->assign(e->G, 0);
-    for (int g = 0; g < e->G; ++g) {
-        if ((active && !active[g]) || e->over[g]) continue;
-        if (e->roll.open && e->roll.in_move[g]) {
-            if (active) return e->fail(std::string(who) + ": game " + std::to_string(g) + " is in a move already");
-            continue;
-        }
-        (*act)[g] = 1;
-    }
-    return 0;
-}
-
-int ao_roll_begin(ao_engine* e, ao_net* net, const ao_roll_opts* o) {
-    RollState& r = e->roll;
-    if (roll_refuses(e, "ao_roll_begin")) return 1;
-    if (e->in_move) return e->fail("ao_roll_begin inside a move (between ao_begin_move and ao_end_move)");
-    if (!net || !o) return e->fail("ao_roll_begin: null argument");
-    if (e->bar_pending || e->bar_on_device) return e->fail("ao_roll_begin: a root bar is pending (ao_set_root_bar / ao_root_tactics with apply): the rolling search has no root bar");
-    if (e->log_n > 0) return e->fail("ao_roll_begin: an eval log is set (ao_set_eval_log): the rolling search does not feed it");
-    if (e->proof_moves) return e->fail("ao_roll_begin: proof moves are on (ao_set_proof_moves): the roll's turn on the device does not apply them");
-    if (o->turn_every < 1) return e->fail("ao_roll_begin: turn_every must be >= 1");
-    RollTactics& t = r.tac;
-    const bool armed = t.max_depth > 0;
-    if (armed && (e->tp.win_mark < 3 || e->tp.win_mark > 5 || e->tp.win_mark > e->cfg.board))
-        return e->fail("ao_roll_begin: the solver (ao_roll_set_tactics) needs win_mark in 3..5 and at most the board size");
-    std::string why;
-    if (ao::net_check(net, e->cfg.board, e->cfg.inplanes, e->cfg.device, &why)) return e->fail("ao_roll_begin: " + why);
-    // (every turn re-roots: the bound is fixed per engine, so it is checked here, where the call can still be refused)
-    if (!ao::reroot_fits(e->tp)) return queue_refused(e, "ao_roll_begin");
-    const int G = e->G, A = e->A;
-    std::vector<uint8_t> act;
-    if (roll_listed(e, o->active, &act, "ao_roll_begin")) return 1;
-    AO_HIP(e, hipSetDevice(e->cfg.device));
-    if (!r.h_i32) {   // the compact buffers of the engine's first roll (a failed allocation refuses the call; what it got stays in the pool)
-        if (e->pool.alloc(e, &r.d_games, G) || e->pool.alloc(e, &r.d_items, static_cast<size_t>(G) * ao::kRollItem) ||
-            e->pool.alloc(e, &r.d_rec, static_cast<size_t>(G) * ao::kRollRec) || e->pool.alloc(e, &r.d_out, 3 * static_cast<size_t>(G) * A) ||
-            e->pool.alloc(e, &r.d_noise, static_cast<size_t>(G) * e->Ap))
-            return 1;
-        AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&r.h_i32), sizeof(int32_t) * G * (5 + ao::kRollItem + ao::kRollRec), hipHostMallocDefault));
-    }
-    if (armed && !t.stream) {   // the solver's stream and the per-game verdict rows, by the first roll that runs with it
-        if (e->pool.alloc(e, &t.d_words, static_cast<size_t>(G) * 4) || e->pool.alloc(e, &t.d_out_words, static_cast<size_t>(G) * 4)) return 1;
-        AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&t.h_words), sizeof(int32_t) * 4 * G, hipHostMallocDefault));
-        AO_HIP(e, hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
-    }
-    if (armed && t.want_allowed && !t.d_allowed) {
-        if (e->pool.alloc(e, &t.d_allowed, static_cast<size_t>(G) * A) || e->pool.alloc(e, &t.d_out_allowed, static_cast<size_t>(G) * A)) return 1;
-        AO_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&t.h_allowed), static_cast<size_t>(G) * A, hipHostMallocDefault));
-    }
-    if (roll_take_tables(e, o, act, true, "ao_roll_begin")) return 1;
-    // nothing can refuse the call any more
-    r.in_move.assign(G, 0);
-    r.net = net;
-    r.early = o->early_stop != 0;
-    r.want_visit = o->want_visit != 0;
-    r.want_policy = o->want_policy != 0;
-    r.cad = ao::RollCadence{};
-    r.cad.turn_every = o->turn_every;
-    r.cad.early = r.early;
-    r.look_pending = false;
-    r.n_in_move = 0;
-    r.draining = false;
-    t.on = armed;
-    t.hold = (armed && getenv("AO_ROLL_TACTICS_HOLD")) ? std::max(0, atoi(getenv("AO_ROLL_TACTICS_HOLD"))) : 0;
-    t.pending.clear();
-    t.n_waiting = 0;
-    t.rec_count = 0;
-    std::fill(t.stats, t.stats + 6, 0);
-    // the plan: rows per simulation for every G, the batch bounded by ao_set_row_cap
-    if (r.loop.plan(e, net, (e->row_cap > 0 && e->row_cap < G) ? e->row_cap : G)) return 1;
-    r.loop.per_sim = true;
-    r.loop.traffic = &r.bytes;   // (the row counters a harvest reads count as the roll's traffic, one word per launch)
-    ao::TreeParams& p = r.loop.p;
-    p.row_cap = static_cast<unsigned>(r.loop.cap_rows);
-    p.row_target = p.row_cap;
-    p.ctl = nullptr; p.live_prev = nullptr; p.order = nullptr; p.max_levels = 0;
-    // (a root may still hold kBarQ children of an earlier barred move: an all-zero bar turns them back where a move begins)
-    // (with the solver every game's row is the bar of its current move: k_roll_verdict writes it before the move begins)
-    p.bar = nullptr;
-    if (e->bar_dirty || t.on) {
-        AO_HIP(e, hipMemsetAsync(e->d_bar, 0, sizeof(uint64_t) * e->h_bar.size(), e->stream));
-        p.bar = e->d_bar;
-    }
-    if (r.loop.zero_ring()) return 1;
-    AO_HIP(e, hipMemsetAsync(e->d_active, 0, G, e->stream));
-    AO_HIP(e, hipMemsetAsync(e->d_early, 0, G, e->stream));
-    AO_HIP(e, hipMemsetAsync(e->d_settled, 0, G, e->stream));
-    AO_HIP(e, hipMemsetAsync(p.stats, 0, sizeof(unsigned) * 4 * G, e->stream));
-    std::fill(e->active.begin(), e->active.end(), 0);
-    r.open = true;
-    std::vector<int32_t> games;
-    for (int g = 0; g < G; ++g)
-        if (act[g]) games.push_back(g);
-    if (t.on ? roll_tactics_step(e, games, nullptr, false) : roll_begin_games(e, games, nullptr)) { roll_close(e); return 1; }
-    p.live = r.loop.slot(0);
-    ao::launch_select(p, e->stream);
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-int ao_roll_join(ao_engine* e, const ao_roll_opts* o) {
-    RollState& r = e->roll;
-    if (!r.open) return e->fail("ao_roll_join: no roll is open");
-    if (!o) return e->fail("ao_roll_join: null argument");
-    AO_HIP(e, hipSetDevice(e->cfg.device));
-    std::vector<uint8_t> act;
-    if (roll_listed(e, o->active, &act, "ao_roll_join")) return 1;
-    if (roll_take_tables(e, o, act, false, "ao_roll_join")) return 1;
-    std::vector<int32_t> games;
-    for (int g = 0; g < e->G; ++g)
-        if (act[g]) games.push_back(g);
-    // (a joined game has LS_IDLE: the next launch's expansion half does nothing for it, its selection half starts simulation 0)
-    if (e->roll.tac.on ? roll_tactics_step(e, games, nullptr, false) : roll_begin_games(e, games, nullptr)) return roll_fail(e, e->err);
-    return 0;
-}
-
-int ao_roll_drain(ao_engine* e) {
-    if (!e->roll.open) return e->fail("ao_roll_drain: no roll is open");
-    e->roll.draining = true;
-    return 0;
-}
-
-// one launch of the loop: the network on the rows the last selection handed out, then expansion + backup and the next selection
-static int roll_launch(ao_engine* e) {
-    LaunchLoop& loop = e->roll.loop;
-    if (loop.leaf_tactics(true)) return 1;
-    if (ao::net_forward_il(e->roll.net, loop.net_in, loop.cap_rows, e->d_policy, e->d_value, e->stream, loop.in_kind, 7, loop.slot(loop.launch),
-                           static_cast<unsigned>(loop.cap_rows)))
-        return roll_fail(e, std::string("ao_roll_run: network forward failed: ") + ao_net_last_error(e->roll.net));
-    if (loop.leaf_tactics(false)) return 1;
-    const bool timed = e->timer.tick();   // (see ao_tree_timing)
-    if (timed) e->timer.begin(e->stream);
-    if (loop.advance()) return 1;
-    ao::launch_expand_select(loop.p, e->stream);
-    if (timed) e->timer.end(e->stream);
-    AO_HIP(e, hipGetLastError());
-    return 0;
-}
-
-// the look: k_settle over the early-stop games (tau == 0 moves) that have run a simulation of their move; a leaf is under way
-static int roll_look(ao_engine* e) {
-    RollState& r = e->roll;
-    ao::launch_roll_mask(r.loop.p, e->d_early, e->d_mask, e->stream);
-    AO_HIP(e, hipMemsetAsync(e->d_settle, 0, sizeof(int32_t) * 4, e->stream));
-    ao::launch_settle(r.loop.p, e->d_mask, 0, 1, e->d_settled, e->d_settle, e->stream);
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(e->h_settle, e->d_settle, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, e->stream));
-    roll_count(e, sizeof(int32_t) * 4);
-    r.look_pending = true;
-    return 0;
-}
-
-// A turn. Reads the network's status word and the games' words first: on either kind of error no game is turned.
-static int roll_turn(ao_engine* e, ao_roll_records* out) {
-    RollState& r = e->roll;
-    const int G = e->G, A = e->A;
-    const int64_t bytes0 = r.bytes;
-    int32_t nflags = 0;
-    if (ao_net_status(r.net, e->stream, &nflags, 1)) return roll_fail(e, std::string("ao_roll_run: ao_net_status: ") + ao_net_last_error(r.net));
-    if (nflags & AO_NET_FP16_RANGE)
-        return roll_fail(e, "ao_roll_run: AO_NET_FP16_RANGE: an activation left the fp16 range (|x| > 65504) in the split-fp16 trunk; the rolling search does not "
-                            "repeat moves on the fp32-MFMA trunk (ao_search does). No game was turned, the roll is closed");
-    int32_t* h_done = r.h_i32;
-    int32_t* h_target = h_done + G;
-    int32_t* h_leaf = h_target + G;
-    int32_t* h_err = h_leaf + G;
-    int32_t* h_games = h_err + G;
-    int32_t* h_rec = h_games + G + static_cast<size_t>(G) * ao::kRollItem;
-    AO_HIP(e, hipMemcpyAsync(h_done, e->tp.sims_done, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipMemcpyAsync(h_target, e->tp.sims_target, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipMemcpyAsync(h_leaf, e->tp.leaf_status, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipMemcpyAsync(h_err, e->tp.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
-    roll_count(e, sizeof(int32_t) * 4 * G);
-    if (r.loop.harvest(r.loop.launch)) return 1;
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    if (r.look_pending) {
-        int unfinished = 0, owed = 0;
-        settle_harvest(e, &unfinished, &owed);
-        r.look_pending = false;
-    }
-    if (report_game_errors(e, h_err)) { roll_close(e); return 1; }
-    int n = 0;
-    for (int g = 0; g < G; ++g)
-        if (ao::roll_game_turns(r.in_move[g], h_done[g], h_target[g], h_leaf[g] == ao::LS_IDLE)) h_games[n++] = g;
-    ++r.turns;
-    r.last_games = n;
-    out->count = 0;
-    RollTactics& t = r.tac;
-    if (n == 0) {
-        if (t.on && roll_tactics_step(e, std::vector<int32_t>(), nullptr, true)) return roll_fail(e, e->err);   // (verdicts may be in)
-        r.last_bytes = r.bytes - bytes0;
-        return 0;
-    }
-    const size_t nA = static_cast<size_t>(n) * A;
-    double* d_pi = r.d_out;
-    double* d_visit = r.want_visit ? r.d_out + nA : nullptr;
-    double* d_policy = r.want_policy ? r.d_out + 2 * nA : nullptr;
-    AO_HIP(e, hipMemcpyAsync(r.d_games, h_games, sizeof(int32_t) * n, hipMemcpyHostToDevice, e->stream));
-    ao::launch_roll_turn(r.loop.p, r.d_games, n, e->d_active, e->d_settled, r.d_rec, d_pi, d_visit, d_policy, e->stream);
-    (void)ao::launch_reroot(r.loop.p, n, r.d_games, e->stream);   // (cannot refuse: ao_roll_begin checked reroot_fits)
-    AO_HIP(e, hipGetLastError());
-    AO_HIP(e, hipMemcpyAsync(h_rec, r.d_rec, sizeof(int32_t) * ao::kRollRec * n, hipMemcpyDeviceToHost, e->stream));
-    AO_HIP(e, hipMemcpyAsync(e->h_out, d_pi, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
-    if (d_visit) AO_HIP(e, hipMemcpyAsync(e->h_out + nA, d_visit, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
-    if (d_policy) AO_HIP(e, hipMemcpyAsync(e->h_out + 2 * nA, d_policy, sizeof(double) * nA, hipMemcpyDeviceToHost, e->stream));
-    roll_count(e, sizeof(int32_t) * (1 + ao::kRollRec) * n + sizeof(double) * nA * (1 + (d_visit ? 1 : 0) + (d_policy ? 1 : 0)));
-    if (t.on) {   // what the solver said at the root of the move each turned game just played: 16 B (+ A) per game
-        ao::launch_roll_words(r.d_games, n, A, t.d_words, t.d_allowed, t.d_out_words, t.want_allowed ? t.d_out_allowed : nullptr, e->stream);
-        AO_HIP(e, hipGetLastError());
-        AO_HIP(e, hipMemcpyAsync(t.h_words, t.d_out_words, sizeof(int32_t) * 4 * n, hipMemcpyDeviceToHost, e->stream));
-        if (t.want_allowed) AO_HIP(e, hipMemcpyAsync(t.h_allowed, t.d_out_allowed, nA, hipMemcpyDeviceToHost, e->stream));
-        const size_t bytes = static_cast<size_t>(n) * 16 + (t.want_allowed ? nA : 0);
-        t.stats[5] += static_cast<int64_t>(bytes);
-        roll_count(e, bytes);
-    }
-    const bool gather = e->tp.noise != 0 && !r.draining;   // the streams of the played games, for the draws of their next moves
-    if (gather) {
-        ao::launch_roll_gather(r.loop.p, r.d_games, n, e->d_mt_backup, e->d_pos_backup, e->stream);
-        AO_HIP(e, hipGetLastError());
-        AO_HIP(e, hipMemcpyAsync(e->h_mt, e->d_mt_backup, sizeof(uint32_t) * 624 * n, hipMemcpyDeviceToHost, e->stream));
-        AO_HIP(e, hipMemcpyAsync(e->h_pos, e->d_pos_backup, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
-        roll_count(e, static_cast<size_t>(n) * (624 * 4 + 4));
-    }
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    // The turned games' error words came back in their records (ERR_SHORT, ERR_BAD_MOVE): no second [G]-wide read. Any of them
-    // fails the call as ao_end_move / ao_play would, before a host mirror is touched; the roll is closed.
-    bool bad = false;
-    for (int b = 0; b < n; ++b) {
-        const int32_t* rec = h_rec + static_cast<size_t>(b) * ao::kRollRec;
-        h_err[rec[0]] = rec[7];   // (h_err was all zero: report_game_errors passed it above)
-        bad = bad || rec[7] != 0;
-    }
-    if (bad && report_game_errors(e, h_err)) { roll_close(e); return 1; }
-    std::vector<int32_t> next, next_rows;
-    for (int b = 0; b < n; ++b) {
-        const int32_t* rec = h_rec + static_cast<size_t>(b) * ao::kRollRec;
-        const int g = rec[0];
-        out->game[b] = g;
-        out->ply[b] = static_cast<int32_t>(e->moves[g].size());
-        out->action[b] = rec[1];
-        out->win[b] = rec[2];
-        out->tau[b] = rec[3];
-        out->sims[b] = std::max(0, rec[4] - e->bonus[g]);
-        out->settled[b] = rec[5];
-        e->moves[g].push_back(rec[1]);
-        e->status[g] = rec[6];
-        e->over[g] = rec[2];
-        e->active[g] = 0;
-        r.in_move[g] = ao::ROLL_OUT;
-        --r.n_in_move;
-        if (ao::roll_begins_next(rec[2], r.draining)) { next.push_back(g); next_rows.push_back(b); }
-    }
-    std::memcpy(out->pi, e->h_out, sizeof(double) * nA);
-    if (out->visit && d_visit) std::memcpy(out->visit, e->h_out + nA, sizeof(double) * nA);
-    if (out->policy && d_policy) std::memcpy(out->policy, e->h_out + 2 * nA, sizeof(double) * nA);
-    out->count = n;
-    r.games_turned += n;
-    if (t.on) {
-        t.rec_count = n;
-        t.rec_words.assign(t.h_words, t.h_words + 4 * static_cast<size_t>(n));
-        if (t.want_allowed) t.rec_allowed.assign(t.h_allowed, t.h_allowed + nA);
-        for (int b = 0; b < n; ++b) t.stats[4] += t.rec_words[4 * static_cast<size_t>(b) + 2];
-        // (with noise the streams of `next` lie in the staging rows; without, nothing of them is needed)
-        if (roll_tactics_step(e, next, gather ? next_rows.data() : nullptr, true)) return roll_fail(e, e->err);
-        r.last_bytes = r.bytes - bytes0;
-        return 0;
-    }
-    if (roll_begin_games(e, next, gather ? next_rows.data() : nullptr)) return roll_fail(e, e->err);
-    r.last_bytes = r.bytes - bytes0;
-    return 0;
-}
-
-int ao_roll_run(ao_engine* e, int64_t max_launches, ao_roll_records* out) {
-    RollState& r = e->roll;
-    if (!r.open) return e->fail("ao_roll_run: no roll is open");
-    if (!out || !out->game || !out->ply || !out->action || !out->win || !out->tau || !out->sims || !out->settled || !out->pi)
-        return e->fail("ao_roll_run: null record array");
-    if (max_launches < 0) return e->fail("ao_roll_run: max_launches must be >= 0");
-    AO_HIP(e, hipSetDevice(e->cfg.device));
-    out->count = 0;
-    r.tac.rec_count = 0;
-    int64_t launches = 0;
-    if (ao::roll_run_returns(0, r.n_in_move, launches, max_launches)) return 0;
-    for (;;) {
-        switch (r.cad.next()) {
-        case ao::ROLL_TURN:
-            if (roll_turn(e, out)) return 1;
-            if (ao::roll_run_returns(out->count, r.n_in_move, launches, max_launches)) return 0;
-            break;
-        case ao::ROLL_LOOK:
-            if (roll_look(e)) return 1;
-            break;
-        case ao::ROLL_LAUNCH:
-            if (roll_launch(e)) return 1;
-            ++launches;
-            if (!r.cad.turn_due() && ao::roll_run_returns(0, r.n_in_move, launches, max_launches)) return 0;
-            break;
-        }
-    }
-}
-
-int ao_roll_end(ao_engine* e) {
-    RollState& r = e->roll;
-    if (!r.open) return e->fail("ao_roll_end: no roll is open");
-    if (r.n_in_move > 0)
-        return e->fail("ao_roll_end: " + std::to_string(r.n_in_move) + " game(s) are still in a move (ao_roll_drain, then ao_roll_run until nothing is)");
-    AO_HIP(e, hipSetDevice(e->cfg.device));
-    if (r.loop.harvest(r.loop.launch)) return 1;
-    AO_HIP(e, hipStreamSynchronize(e->stream));
-    roll_close(e);
-    return 0;
-}
-
-int ao_roll_set_tactics(ao_engine* e, int32_t max_depth, int32_t max_nodes, int32_t solved_sims, int32_t want_allowed) {
-    if (roll_refuses(e, "ao_roll_set_tactics")) return 1;
-    RollTactics& t = e->roll.tac;
-    if (max_depth == 0) {
-        t.max_depth = t.max_nodes = t.solved_sims = 0;
-        t.want_allowed = false;
-        return 0;
-    }
-    const std::string bad_limits = ao::fw_limits_error("ao_roll_set_tactics", max_depth, max_nodes);
-    if (!bad_limits.empty()) return e->fail(bad_limits);
-    if (solved_sims < 0 || solved_sims > e->S)
-        return e->fail("ao_roll_set_tactics: solved_sims must be in 0.." + std::to_string(e->S) + " (0: no cap)");
-    t.max_depth = max_depth; t.max_nodes = max_nodes; t.solved_sims = solved_sims;
-    t.want_allowed = want_allowed != 0;
-    return 0;
-}
-
-int ao_roll_tactics_records(ao_engine* e, int32_t* verdict, int32_t* depth, int32_t* nodes, int32_t* unknown, uint8_t* allowed) {
-    const RollTactics& t = e->roll.tac;
-    if (allowed && t.rec_count > 0 && t.rec_allowed.size() < static_cast<size_t>(t.rec_count) * e->A)
-        return e->fail("ao_roll_tactics_records: allowed rows need ao_roll_set_tactics(..., want_allowed = 1)");
-    int32_t* out[4] = {verdict, depth, nodes, unknown};
-    for (int b = 0; b < t.rec_count; ++b)
-        for (int w = 0; w < 4; ++w)
-            if (out[w]) out[w][b] = t.rec_words[4 * static_cast<size_t>(b) + w];
-    if (allowed && t.rec_count > 0) std::memcpy(allowed, t.rec_allowed.data(), static_cast<size_t>(t.rec_count) * e->A);
-    return 0;
-}
-
-int ao_roll_tactics_stats(ao_engine* e, int64_t* out) {
-    if (!out) return e->fail("ao_roll_tactics_stats: null argument");
-    std::copy(e->roll.tac.stats, e->roll.tac.stats + 6, out);
-    return 0;
-}
-
-int ao_roll_stats(ao_engine* e, int64_t* turns, int64_t* games_turned, int64_t* bytes, int64_t* last_games, int64_t* last_bytes) {
-    if (turns) *turns = e->roll.turns;
-    if (games_turned) *games_turned = e->roll.games_turned;
-    if (bytes) *bytes = e->roll.bytes;
-    if (last_games) *last_games = e->roll.last_games;
-    if (last_bytes) *last_bytes = e->roll.last_bytes;
     return 0;
 }
 

@@ -138,7 +138,7 @@ struct TreeParams {
     const uint32_t* sym_key;
 };
 
-// Device buffers of ao_root_tactics (engine.hip -> launch_root_tactics, root_tactics.hip): the forced-win solver's verdict on the
+// Device buffers of ao_root_tactics (root_tactics.hip; a batch of the rolling search hands it its own): the forced-win solver's verdict on the
 // engine's own root positions. verdict: RT_NONE nothing proven (or a terminal / inactive game: everything zero), RT_WIN the
 // mover has a forced win, RT_DEFEND the opponent threatens one and some reply is not proven to lose, RT_LOST every reply is.
 enum : int32_t { RT_NONE = 0, RT_WIN = 1, RT_DEFEND = 2, RT_LOST = 3 };

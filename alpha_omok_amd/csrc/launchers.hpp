@@ -1,7 +1,8 @@
-// launchers.hpp -- the host entry points that one translation unit defines and another calls: the kernel launchers of the tree,
-// read-out, root-tactics and step kernels and the network's internal interface. Included by the callers AND by every file that
-// defines one of them, so that a changed signature is a compile error where it changes and never a second overload.
-// (tree_snapshot.hpp declares launch_tree_pack / launch_tree_unpack beside the chunk layout they take.)
+// launchers.hpp -- the host entry points that one translation unit defines and another calls: the launchers of the tree and step
+// kernels, the few of the proof, root-tactics and leaf-tactics kernels that a second file uses, and the network's internal
+// interface. Included by the callers AND by every file that defines one of them, so that a changed signature is a compile error
+// where it changes and never a second overload. A launcher whose only caller stands in its own file (roll.hip, tree_readout.hip,
+// tree_snapshot.hip, ao_root_tactics') is static there and has no entry here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,7 +20,7 @@ void launch_expand_select(const TreeParams& p, hipStream_t s);
 void launch_begin_move(const TreeParams& p, hipStream_t s);
 void launch_order(const TreeParams& p, int32_t* order, hipStream_t s);
 void launch_end_move(const TreeParams& p, hipStream_t s);
-// launch_play, launch_walk, launch_tree_stats, launch_tree_pack: non-zero = refused by walk_lds_bytes (tree_walk.hpp), nothing launched
+// launch_play, launch_walk, launch_reroot: non-zero = refused by walk_lds_bytes (tree_walk.hpp), nothing launched
 int launch_play(const TreeParams& p, hipStream_t s);
 int launch_walk(const TreeParams& p, int count, const int32_t* games, const int32_t* extra, int stride, const int32_t* m,
                 const int32_t* prev_known, int32_t* status_out, hipStream_t s);
@@ -29,42 +30,13 @@ void launch_reset(const TreeParams& p, const uint8_t* mask, hipStream_t s);
 void launch_settle(const TreeParams& p, const uint8_t* mask, int stop_now, int leaf_open, uint8_t* settled, int32_t* out, hipStream_t s);
 void launch_eval_log(const int32_t* games, int n, const int32_t* row_of_game, const float* policy, const float* value, int A,
                      float* out, const int32_t* sims_done, const int32_t* leaf_status, int what, hipStream_t s);
-// roll.hip: a turn of the rolling search for a compact list of n games (one wave per listed game)
-constexpr int kRollRec = 8;    // words of a turn record: game, action (-1: short of its simulations), win, tau, simulations done, settled, AO_ROOT_* of the new root, the game's error word behind the turn (0: none)
-constexpr int kRollItem = 6;   // words of a begin item: game, target, gflags, tau, settle mask, row of its stream and noise in the compact buffers (-1: no draw)
-void launch_roll_turn(const TreeParams& p, const int32_t* games, int n, uint8_t* active, const uint8_t* settled, int32_t* rec, double* rec_pi,
-                      double* rec_visit, double* rec_policy, hipStream_t s);
-void launch_roll_gather(const TreeParams& p, const int32_t* games, int n, uint32_t* out_mt, int32_t* out_pos, hipStream_t s);
-void launch_roll_begin(const TreeParams& p, const int32_t* items, int n, const uint32_t* in_mt, const int32_t* in_pos, const double* in_noise,
-                       int8_t* tau, uint8_t* active, uint8_t* settled, uint8_t* early, hipStream_t s);
-void launch_roll_mask(const TreeParams& p, const uint8_t* early, uint8_t* out, hipStream_t s);
-// ... with the solver beside the loop (ao_roll_set_tactics): the root positions of the listed games into a batch's compact rows;
-// a finished batch's bar rows, verdict words and allowed rows into its games' own rows, and the targets of its begin items
-// worked out from the verdicts; the verdict words of the turned games for their records
-struct RollBatchView {
-    const uint64_t* bar;      // [n][kBBWords]
-    const int32_t* verdict;   // [4][n]: verdict, depth, nodes, unknown
-    const uint8_t* allowed;   // [n][A] or null
-    int n;
-};
-void launch_roll_rootpos(const TreeParams& p, const int32_t* games, int n, Pos* rows, hipStream_t s);
-void launch_roll_verdict(int32_t* items, const RollBatchView& b, int A, int solved_sims, uint64_t* bar, int32_t* game_words, uint8_t* game_allowed,
-                         hipStream_t s);
-void launch_roll_words(const int32_t* games, int n, int A, const int32_t* game_words, const uint8_t* game_allowed, int32_t* out_words,
-                       uint8_t* out_allowed, hipStream_t s);
-// tree_readout.hip
-void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
-                        int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s);
-void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s);
-int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s);
-// tree_proofs.hip: exact minimax over what the roots reach (ws: int32 [G][cap] workspace; non-zero = refused, as launch_tree_stats),
-// and utils.proof_pi on TreeParams::out_pi in place
+// tree_proofs.hip, both for ao_end_move under ao_set_proof_moves as well: exact minimax over what the roots reach (ws: int32 [G][cap]
+// workspace; non-zero = refused, as launch_play), and utils.proof_pi on TreeParams::out_pi in place
 int launch_tree_proofs(const TreeParams& p, const uint8_t* mask, int32_t* ws, int max_len, int32_t* root_out, int8_t* child_status,
                        int16_t* child_plies, int32_t* line, int32_t* line_len, hipStream_t s);
 void launch_proof_pi(const TreeParams& p, const int8_t* child_status, const int16_t* child_plies, int32_t* verdict, hipStream_t s);
-// root_tactics.hip: the forced-win solver on the engine's own root positions (k_root_tactics_a, _b, k_root_tactics_rows)
-void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s);
-// the list form: the same three kernels on n compact position rows, every buffer of b indexed by the row (a batch of the rolling search)
+// root_tactics.hip: the solver's three kernels on n compact position rows, every buffer of b indexed by the row (a batch of the
+// rolling search, roll.hip)
 void launch_root_tactics_rows(const Pos* rows, int n, int B, int A, int win_mark, int max_depth, int max_nodes, const RootTacticsBufs& b,
                               hipStream_t s);
 // leaf_tactics.hip: the forced-win solver on the leaves of the simulation under way (k_leaf_tactics), and +1 into the value row

@@ -1,10 +1,14 @@
-// root_tactics.hip -- the forced-win solver on an engine's own roots (ao_root_tactics, engine.hip). No reference
+// root_tactics.hip -- the forced-win solver on an engine's own roots: the kernels, then ao_root_tactics. No reference
 // counterpart; the definition is utils.root_tactics, which goes through utils.forced_win alone. The positions are the engine's
 // TreeParams::rootpos, read on the device: no move list is staged. Three launches: the mover's search and the opponent's
 // search after a pass (k_root_tactics_a), every reply's search for the games that stand under a proven threat with no win
 // of their own (k_root_tactics_b), and one wavefront per game that puts the words together (k_root_tactics_rows). The
 // search, its word and the search after a reply are those of the position batch (tactics_device.hpp).
-#include "host_handle.hpp"
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "engine.hpp"
 #include "launchers.hpp"
 #include "tactics_device.hpp"
 
@@ -154,7 +158,7 @@ static void launch_root_tactics_q(const RootTacticsParams& q, hipStream_t s) {
                     hipLaunchKernelGGL(k_root_tactics_rows<NCH>, grid_r, block, 0, s, q));
 }
 
-void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s) {
+static void launch_root_tactics(const TreeParams& p, const uint8_t* active, int max_depth, int max_nodes, const RootTacticsBufs& b, hipStream_t s) {
     RootTacticsParams q{};
     q.rootpos = p.rootpos; q.active = active;
     q.G = p.G; q.B = p.B; q.A = p.A; q.win_mark = p.win_mark; q.max_depth = max_depth; q.max_nodes = max_nodes;
@@ -172,3 +176,53 @@ void launch_root_tactics_rows(const Pos* rows, int n, int B, int A, int win_mark
 }
 
 }  // namespace ao
+
+extern "C" {
+
+// utils.root_tactics of every active game's root position, read where it lives (TreeParams::rootpos): no move list goes to
+// the device. apply: the bar of the next move is left on the device -- the caller's pending masks (ao_set_root_bar)
+// intersected with what the solver allows, game by game; a game whose intersection would be empty keeps the caller's.
+int ao_root_tactics(ao_engine* e, const uint8_t* active, int32_t max_depth, int32_t max_nodes, int32_t apply, int32_t* verdict,
+                    int32_t* depth, uint8_t* allowed, int32_t* nodes, int32_t* unknown) {
+    if (roll_refuses(e, "ao_root_tactics")) return 1;
+    if (e->in_move) return e->fail("ao_root_tactics inside a move (between ao_begin_move and ao_end_move)");
+    const std::string bad_limits = ao::fw_limits_error("ao_root_tactics", max_depth, max_nodes);
+    if (!bad_limits.empty()) return e->fail(bad_limits);
+    if (e->tp.win_mark < 3 || e->tp.win_mark > 5 || e->tp.win_mark > e->cfg.board)
+        return e->fail("ao_root_tactics: the solver needs win_mark in 3..5 and at most the board size");
+    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A);
+    std::vector<uint8_t> act(G);
+    for (size_t g = 0; g < G; ++g) act[g] = (active ? active[g] : 1) && !e->over[g];
+    bool bar_any = false;
+    if (apply && bar_build(e, act, &bar_any, "ao_root_tactics")) return 1;   // (before any device call)
+    const size_t at_stage = G * ao::kBBWords * 8, at_pair = at_stage + G * 8, at_out = at_pair + G * A * 4;
+    const size_t out_bytes = G * 16 + G * A, at_mask = at_out + out_bytes;
+    if (readout_begin(e, "ao_root_tactics", at_mask + G)) return 1;
+    ao::RootTacticsBufs b{};
+    b.won = reinterpret_cast<uint64_t*>(e->d_ro.p);
+    b.stage = reinterpret_cast<uint32_t*>(e->d_ro.p + at_stage);
+    b.pair = reinterpret_cast<uint32_t*>(e->d_ro.p + at_pair);
+    b.verdict = reinterpret_cast<int32_t*>(e->d_ro.p + at_out);
+    b.depth = b.verdict + G; b.nodes = b.depth + G; b.unknown = b.nodes + G;
+    b.allowed = e->d_ro.p + at_out + G * 16;
+    uint8_t* d_act = e->d_ro.p + at_mask;
+    AO_HIP(e, hipMemcpyAsync(d_act, act.data(), G, hipMemcpyHostToDevice, e->stream));
+    if (apply) {
+        AO_HIP(e, hipMemcpyAsync(e->d_bar, e->h_bar.data(), sizeof(uint64_t) * e->h_bar.size(), hipMemcpyHostToDevice, e->stream));
+        b.bar = e->d_bar;
+    }
+    ao::launch_root_tactics(e->tp, d_act, max_depth, max_nodes, b, e->stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p + at_out, out_bytes, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    if (apply) e->bar_on_device = true;
+    const int32_t* h = reinterpret_cast<const int32_t*>(e->h_ro.data());
+    if (verdict) std::memcpy(verdict, h, 4 * G);
+    if (depth) std::memcpy(depth, h + G, 4 * G);
+    if (nodes) std::memcpy(nodes, h + 2 * G, 4 * G);
+    if (unknown) std::memcpy(unknown, h + 3 * G, 4 * G);
+    if (allowed) std::memcpy(allowed, e->h_ro.data() + G * 16, G * A);
+    return 0;
+}
+
+}  // extern "C"

@@ -342,7 +342,7 @@ __global__ void k_reset(TreeParams p, const uint8_t* mask) {
 }
 
 // ----------------------------------------------------------------------------------------------
-// launchers (called from engine.hip)
+// launchers (called from engine.hip and roll.hip; declared in launchers.hpp)
 // ----------------------------------------------------------------------------------------------
 void launch_select(const TreeParams& p, hipStream_t s) {
     if (p.sym_key) { AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL((k_select<NCH, true>), dim3(p.G), dim3(64), 0, s, p)); }

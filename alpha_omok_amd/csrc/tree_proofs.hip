@@ -13,10 +13,14 @@
 // A node's proof word is status | plies << 2 in an int32 workspace [G][cap] in HBM, indexed by arena node (the queue alone fills
 // the LDS at the largest node_cap). The waves of ONE workgroup hand the words to each other level by level: a workgroup-scope
 // release, the barrier, a workgroup-scope acquire. Nothing crosses workgroups.
+//
+// The host side (ao_tree_proofs, ao_set_proof_moves, ao_proof_move_records, proofs_alloc) follows the kernels.
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
+#include <string>
 
-#include "../../include/omok_hip.h"
-#include "host_handle.hpp"
+#include "engine.hpp"
 #include "launchers.hpp"
 #include "tree_walk.hpp"
 
@@ -308,7 +312,7 @@ __global__ __launch_bounds__(64) void k_proof_pi(TreeParams p, const int8_t* __r
 }
 
 // ----------------------------------------------------------------------------------------------
-// launchers (called from engine.hip)
+// launchers: both are ao_end_move's as well (engine.hip, under ao_set_proof_moves), so launchers.hpp declares them
 // ----------------------------------------------------------------------------------------------
 
 // non-zero: queue and level table of a `cap`-node arena do not fit the LDS of one workgroup -- nothing is launched
@@ -325,4 +329,77 @@ void launch_proof_pi(const TreeParams& p, const int8_t* child_status, const int1
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_proof_pi<NCH>, dim3(p.G), dim3(64), 0, s, p, child_status, child_plies, verdict));
 }
 
+// ----------------------------------------------------------------------------------------------
+// the host side
+// ----------------------------------------------------------------------------------------------
+int proofs_alloc(ao_engine* e) {
+    if (e->d_pf_ws) return 0;
+    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A);
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    if (e->pool.alloc(e, &e->d_pf_root, 4 * G) || e->pool.alloc(e, &e->d_pf_status, G * A) || e->pool.alloc(e, &e->d_pf_plies, G * A) ||
+        e->pool.alloc(e, &e->d_pf_verdict, G) || e->pool.alloc(e, &e->d_pf_ws, G * static_cast<size_t>(e->tp.cap)))
+        return 1;
+    AO_HIP(e, hipMemsetAsync(e->d_pf_verdict, 0, sizeof(int32_t) * G, e->stream));
+    return 0;
+}
+
 }  // namespace ao
+
+extern "C" {
+
+// utils.tree_proofs of every masked game
+int ao_tree_proofs(ao_engine* e, const uint8_t* mask, int32_t max_len, int32_t* root, int8_t* child_status, int16_t* child_plies,
+                   int32_t* line, int32_t* line_len) {
+    if (roll_refuses(e, "ao_tree_proofs")) return 1;
+    if (e->in_move) return e->fail("ao_tree_proofs inside a move (between ao_begin_move and ao_end_move)");
+    if (max_len < 1 || max_len > e->A) return e->fail("ao_tree_proofs: max_len must be in 1..A");
+    const size_t G = static_cast<size_t>(e->G), A = static_cast<size_t>(e->A), GL = G * static_cast<size_t>(max_len);
+    // workspace layout: line [G][max_len] and line_len [G] (int32), root [G][4] (int32), plies [G][A] (int16), status [G][A], mask [G]
+    const size_t o_len = 4 * GL, o_root = o_len + 4 * G, o_plies = o_root + 16 * G, o_status = o_plies + 2 * G * A, o_mask = o_status + G * A;
+    if (readout_begin(e, "ao_tree_proofs", o_mask + G) || proofs_alloc(e)) return 1;
+    uint8_t* h_mask = e->h_ro.data() + o_mask;
+    readout_mask(e, mask, h_mask);
+    unsigned char* d = e->d_ro.p;
+    AO_HIP(e, hipMemcpyAsync(d + o_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
+    if (ao::launch_tree_proofs(e->tp, d + o_mask, e->d_pf_ws, max_len, reinterpret_cast<int32_t*>(d + o_root), reinterpret_cast<int8_t*>(d + o_status),
+                               reinterpret_cast<int16_t*>(d + o_plies), reinterpret_cast<int32_t*>(d), reinterpret_cast<int32_t*>(d + o_len), e->stream))
+        return queue_refused(e, "ao_tree_proofs");
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), d, o_mask, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    const unsigned char* h = e->h_ro.data();
+    const int32_t* h_root = reinterpret_cast<const int32_t*>(h + o_root);
+    for (size_t g = 0; g < G; ++g)
+        if (h_mask[g] && h_root[4 * g + 3] < 0) return e->fail("ao_tree_proofs: game " + std::to_string(g) + ": the tree reaches more nodes than the arena holds (inconsistent tree)");
+    for (size_t g = 0; g < G; ++g) {
+        if (!h_mask[g]) continue;
+        if (root) std::memcpy(root + 4 * g, h_root + 4 * g, 16);
+        if (child_status) std::memcpy(child_status + g * A, h + o_status + g * A, A);
+        if (child_plies) std::memcpy(child_plies + g * A, h + o_plies + 2 * g * A, 2 * A);
+        if (line) std::memcpy(line + g * max_len, h + 4 * g * max_len, 4 * static_cast<size_t>(max_len));
+        if (line_len) line_len[g] = reinterpret_cast<const int32_t*>(h + o_len)[g];
+    }
+    return 0;
+}
+
+int ao_set_proof_moves(ao_engine* e, int enable) {
+    if (roll_refuses(e, "ao_set_proof_moves")) return 1;
+    if (e->in_move) return e->fail("ao_set_proof_moves inside a move (between ao_begin_move and ao_end_move)");
+    if (enable) {
+        if (!ao::reroot_fits(e->tp)) return queue_refused(e, "ao_set_proof_moves");
+        if (proofs_alloc(e)) return 1;
+        if (e->pm_verdict.empty()) e->pm_verdict.assign(e->G, 0);
+    }
+    e->proof_moves = enable != 0;
+    return 0;
+}
+
+int ao_proof_move_records(ao_engine* e, int32_t* verdict, int64_t totals[4], int reset) {
+    if (verdict)
+        for (int g = 0; g < e->G; ++g) verdict[g] = e->pm_verdict.empty() ? 0 : e->pm_verdict[g];
+    if (totals) std::memcpy(totals, e->pm_totals, sizeof(e->pm_totals));
+    if (reset) std::fill(e->pm_totals, e->pm_totals + 4, 0);
+    return 0;
+}
+
+}  // extern "C"

@@ -15,11 +15,16 @@
 // One wavefront per query / per game (k_tree_lookup, k_tree_pv: kReadPerWG of them per workgroup, nothing shared, no barrier);
 // k_tree_stats: one workgroup of kWalkWaves waves per game. Lanes run over a node's <= 225 edges in NCH chunks of 64; everything
 // that steers control flow (game, move, edge found, child link) is wave-uniform: ballots, readfirstlane, DPP reductions.
+//
+// The host side of the three calls (ao_tree_lookup, ao_tree_pv, ao_tree_stats) follows the kernels: each lays out the engine's
+// read-out workspace right above the launch that reads it.
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
 
-#include "../../include/omok_hip.h"
-#include "host_handle.hpp"
-#include "launchers.hpp"
+#include "engine.hpp"
 #include "tree_walk.hpp"
 
 namespace ao {
@@ -213,27 +218,175 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_tree_stats(TreeParams p, co
 }
 
 // ----------------------------------------------------------------------------------------------
-// launchers (called from engine.hip)
+// launchers
 // ----------------------------------------------------------------------------------------------
 
-void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, int32_t* status, int32_t* nchild, double* nwqp,
-                        int32_t* c_act, int32_t* c_n, float* c_w, float* c_q, double* c_p, hipStream_t s) {
-    const LookupOut o{status, nchild, nwqp, c_act, c_n, c_w, c_q, c_p};
+static void launch_tree_lookup(const TreeParams& p, const int32_t* queries, int n, int stride, const LookupOut& o, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>((n + kReadPerWG - 1) / kReadPerWG)), block(64 * kReadPerWG);
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_lookup<NCH>, grid, block, 0, s, p, queries, n, stride, o));
 }
 
-void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s) {
+static void launch_tree_pv(const TreeParams& p, const uint8_t* mask, int max_len, int32_t* act, int32_t* n, float* q, int32_t* len, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>((p.G + kReadPerWG - 1) / kReadPerWG)), block(64 * kReadPerWG);
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_pv<NCH>, grid, block, 0, s, p, mask, max_len, act, n, q, len));
 }
 
 // non-zero: the queue of a `cap`-node arena does not fit the LDS of one workgroup (walk_lds_bytes) -- nothing is launched
-int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s) {
+static int launch_tree_stats(const TreeParams& p, const uint8_t* mask, int32_t* out, hipStream_t s) {
     const size_t lds = walk_lds_bytes(p.cap);
     if (!lds) return 1;
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_stats<NCH>, dim3(p.G), dim3(64 * kWalkWaves), lds, s, p, mask, out));
     return 0;
 }
 
+// ----------------------------------------------------------------------------------------------
+// the host side: one device workspace of the engine (d_ro, grown on demand) and its host mirror (h_ro), shared with the other
+// calls that read trees or roots in bulk (tree_proofs.hip, root_tactics.hip, tree_snapshot.hip)
+// ----------------------------------------------------------------------------------------------
+int readout_begin(ao_engine* e, const char* who, size_t bytes) {
+    if (e->in_move) return e->fail(std::string(who) + " inside a move (between ao_begin_move and ao_end_move)");
+    AO_HIP(e, hipSetDevice(e->cfg.device));
+    if (bytes > e->d_ro.n) {
+        AO_HIP(e, hipStreamSynchronize(e->stream));   // nothing queued reads the old workspace
+        if (e->d_ro.reserve(e, bytes)) return 1;
+    }
+    if (e->h_ro.size() < bytes) e->h_ro.resize(bytes);
+    return 0;
+}
+
+// per game: 0 = not asked for, 1 = asked for, 2 = asked for and the root is a key of the reference's dict
+void readout_mask(const ao_engine* e, const uint8_t* mask, uint8_t* out) {
+    for (int g = 0; g < e->G; ++g)
+        out[g] = (mask && !mask[g]) ? 0 : (e->status[g] != AO_ROOT_FRESH ? 2 : 1);
+}
+
 }  // namespace ao
+
+extern "C" {
+
+// replaces self.tree[node_id] (agents.py:52,206-210)
+int ao_tree_lookup(ao_engine* e, const int32_t* games, const int32_t* moves, int32_t stride, const int32_t* m, int32_t n,
+                   int32_t* status, double* node_nwqp, int32_t* nchild, int32_t* child_action, int32_t* child_n, float* child_w,
+                   float* child_q, double* child_p) {
+    constexpr int kChunk = 1024;   // queries per launch
+    if (e->in_move) return e->fail("ao_tree_lookup inside a move (between ao_begin_move and ao_end_move)");
+    if (n < 0 || stride < 0) return e->fail("ao_tree_lookup: negative query count or stride");
+    if (n == 0) return 0;
+    if (!games || !m || (!moves && stride > 0)) return e->fail("ao_tree_lookup: null argument");
+    const int A = e->A;
+    for (int i = 0; i < n; ++i) {
+        if (games[i] < 0 || games[i] >= e->G) return e->fail("game index out of range");
+        if (m[i] < 0) return e->fail("ao_tree_lookup: negative id length");
+        if (m[i] > stride && m[i] <= A) return e->fail("ao_tree_lookup: m[i] exceeds the row stride");
+    }
+    const bool kids = child_action || child_n || child_w || child_q || child_p;
+    const size_t qs = 3 + static_cast<size_t>(A);   // a query row: game, suffix length, root_known, suffix
+    const size_t in_bytes = kChunk * qs * 4;
+    const size_t out_bytes = static_cast<size_t>(kChunk) * (32 + 8 + (kids ? 24 * static_cast<size_t>(A) : 0));
+    if (readout_begin(e, "ao_tree_lookup", in_bytes + out_bytes)) return 1;
+    for (int64_t first = 0; first < n; first += kChunk) {
+        const int c = static_cast<int>(std::min<int64_t>(kChunk, n - first));
+        const size_t cA = static_cast<size_t>(c) * A;
+        int32_t* hq = reinterpret_cast<int32_t*>(e->h_ro.data());
+        for (int k = 0; k < c; ++k) {
+            const int64_t i = first + k;
+            const int g = games[i];
+            const std::vector<int32_t>& cur = e->moves[g];
+            const int32_t* id = moves + i * static_cast<int64_t>(stride);
+            int32_t* row = hq + static_cast<size_t>(k) * qs;
+            const bool extends = m[i] <= A && static_cast<size_t>(m[i]) >= cur.size() && std::equal(cur.begin(), cur.end(), id);
+            row[0] = g;
+            row[1] = extends ? m[i] - static_cast<int>(cur.size()) : -1;
+            row[2] = e->status[g] != AO_ROOT_FRESH ? 1 : 0;
+            if (extends) std::copy(id + cur.size(), id + m[i], row + 3);
+        }
+        // device layout of a chunk of c queries: the 8-byte arrays first
+        unsigned char* d = e->d_ro.p + in_bytes;
+        double* d_nwqp = reinterpret_cast<double*>(d);
+        double* d_cp = d_nwqp + 4 * static_cast<size_t>(c);
+        int32_t* d_status = reinterpret_cast<int32_t*>(d_cp + (kids ? cA : 0));
+        int32_t* d_nchild = d_status + c;
+        int32_t* d_ca = d_nchild + c;
+        int32_t* d_cn = d_ca + cA;
+        float* d_cw = reinterpret_cast<float*>(d_cn + cA);
+        float* d_cq = d_cw + cA;
+        const size_t used = static_cast<size_t>(c) * (32 + 8 + (kids ? 24 * static_cast<size_t>(A) : 0));
+        AO_HIP(e, hipMemcpyAsync(e->d_ro.p, hq, static_cast<size_t>(c) * qs * 4, hipMemcpyHostToDevice, e->stream));
+        const ao::LookupOut o{d_status, d_nchild, d_nwqp, kids ? d_ca : nullptr, kids ? d_cn : nullptr, kids ? d_cw : nullptr,
+                              kids ? d_cq : nullptr, kids ? d_cp : nullptr};
+        ao::launch_tree_lookup(e->tp, reinterpret_cast<const int32_t*>(e->d_ro.p), c, static_cast<int>(qs), o, e->stream);
+        AO_HIP(e, hipGetLastError());
+        unsigned char* h = e->h_ro.data() + in_bytes;
+        AO_HIP(e, hipMemcpyAsync(h, d, used, hipMemcpyDeviceToHost, e->stream));
+        AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffers are reused by the next chunk
+        auto at = [&](const void* dev) { return h + (static_cast<const unsigned char*>(dev) - d); };
+        if (node_nwqp) std::memcpy(node_nwqp + 4 * first, at(d_nwqp), sizeof(double) * 4 * c);
+        if (status) std::memcpy(status + first, at(d_status), sizeof(int32_t) * c);
+        if (nchild) std::memcpy(nchild + first, at(d_nchild), sizeof(int32_t) * c);
+        if (child_action) std::memcpy(child_action + first * A, at(d_ca), sizeof(int32_t) * cA);
+        if (child_n) std::memcpy(child_n + first * A, at(d_cn), sizeof(int32_t) * cA);
+        if (child_w) std::memcpy(child_w + first * A, at(d_cw), sizeof(float) * cA);
+        if (child_q) std::memcpy(child_q + first * A, at(d_cq), sizeof(float) * cA);
+        if (child_p) std::memcpy(child_p + first * A, at(d_cp), sizeof(double) * cA);
+    }
+    return 0;
+}
+
+// the line the search expects to be played: arg-max of agents.py:67-69's visit vector, node after node
+int ao_tree_pv(ao_engine* e, const uint8_t* mask, int32_t max_len, int32_t* action, int32_t* n, float* q, int32_t* len) {
+    if (e->in_move) return e->fail("ao_tree_pv inside a move (between ao_begin_move and ao_end_move)");
+    if (max_len < 1 || max_len > e->A) return e->fail("ao_tree_pv: max_len must be in 1..A");
+    const size_t G = static_cast<size_t>(e->G), GL = G * static_cast<size_t>(max_len);
+    const size_t out_bytes = (3 * GL + G) * 4;
+    if (readout_begin(e, "ao_tree_pv", out_bytes + G)) return 1;
+    uint8_t* h_mask = e->h_ro.data() + out_bytes;
+    readout_mask(e, mask, h_mask);
+    uint8_t* d_mask = e->d_ro.p + out_bytes;
+    int32_t* d_act = reinterpret_cast<int32_t*>(e->d_ro.p);
+    int32_t* d_n = d_act + GL;
+    float* d_q = reinterpret_cast<float*>(d_n + GL);
+    int32_t* d_len = reinterpret_cast<int32_t*>(d_q + GL);
+    AO_HIP(e, hipMemcpyAsync(d_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
+    ao::launch_tree_pv(e->tp, d_mask, max_len, d_act, d_n, d_q, d_len, e->stream);
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, out_bytes, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    const int32_t* h_act = reinterpret_cast<const int32_t*>(e->h_ro.data());
+    const int32_t* h_n = h_act + GL;
+    const float* h_q = reinterpret_cast<const float*>(h_n + GL);
+    const int32_t* h_len = reinterpret_cast<const int32_t*>(h_q + GL);
+    for (size_t g = 0; g < G; ++g) {
+        if (!h_mask[g]) continue;
+        const size_t l = static_cast<size_t>(h_len[g]), o = g * max_len;
+        if (action) std::memcpy(action + o, h_act + o, 4 * l);
+        if (n) std::memcpy(n + o, h_n + o, 4 * l);
+        if (q) std::memcpy(q + o, h_q + o, 4 * l);
+        if (len) len[g] = h_len[g];
+    }
+    return 0;
+}
+
+// replaces the prints of del_parents (agents.py:241-250)
+int ao_tree_stats(ao_engine* e, const uint8_t* mask, int32_t* out) {
+    if (e->in_move) return e->fail("ao_tree_stats inside a move (between ao_begin_move and ao_end_move)");
+    if (!out) return e->fail("ao_tree_stats: null output");
+    const size_t G = static_cast<size_t>(e->G);
+    if (readout_begin(e, "ao_tree_stats", 16 * G + G)) return 1;
+    uint8_t* h_mask = e->h_ro.data() + 16 * G;
+    readout_mask(e, mask, h_mask);
+    uint8_t* d_mask = e->d_ro.p + 16 * G;
+    AO_HIP(e, hipMemcpyAsync(d_mask, h_mask, G, hipMemcpyHostToDevice, e->stream));
+    if (ao::launch_tree_stats(e->tp, d_mask, reinterpret_cast<int32_t*>(e->d_ro.p), e->stream))
+        return queue_refused(e, "ao_tree_stats");
+    AO_HIP(e, hipGetLastError());
+    AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, 16 * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    const int32_t* h = reinterpret_cast<const int32_t*>(e->h_ro.data());
+    for (size_t g = 0; g < G; ++g)
+        if (h_mask[g] && h[4 * g] < 0) return e->fail("ao_tree_stats: game " + std::to_string(g) + ": the tree reaches more nodes than the arena holds (inconsistent tree)");
+    for (size_t g = 0; g < G; ++g)
+        if (h_mask[g]) std::memcpy(out + 4 * g, h + 4 * g, 16);
+    return 0;
+}
+
+}  // extern "C"

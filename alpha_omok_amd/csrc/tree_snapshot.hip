@@ -6,9 +6,17 @@
 // bit the search without it. k_tree_unpack is the inverse: snapshot node i becomes record i of the game's current arena.
 //
 // Lanes run over a node's <= 225 edges in NCH chunks of 64; what steers control flow (node, level, counts) is wave-uniform.
+//
+// The host side (ao_tree_export, ao_tree_snapshot_check, ao_tree_import) follows the kernels: the games of a call travel in chunks
+// of bounded size through the engine's read-out workspace, each chunk laid out by tree_snapshot.hpp.
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
 
-#include "host_handle.hpp"
+#include "engine.hpp"
+#include "snapshot_check.hpp"
 #include "tree_snapshot.hpp"
 #include "tree_walk.hpp"
 
@@ -171,19 +179,255 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_tree_unpack(TreeParams p, S
 }
 
 // ----------------------------------------------------------------------------------------------
-// launchers (called from engine.hip)
+// launchers
 // ----------------------------------------------------------------------------------------------
 
-int launch_tree_pack(const TreeParams& p, const SnapDev& d, const int32_t* table, int games, hipStream_t s) {
+// non-zero: the breadth-first queue of a `cap`-node arena does not fit the LDS of one workgroup -- nothing is launched
+static int launch_tree_pack(const TreeParams& p, const SnapDev& d, const int32_t* table, int games, hipStream_t s) {
     const size_t lds = walk_lds_bytes(p.cap);
     if (!lds) return 1;
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_pack<NCH>, dim3(games), dim3(64 * kWalkWaves), lds, s, p, d, table));
     return 0;
 }
 
-void launch_tree_unpack(const TreeParams& p, const SnapDev& d, const int32_t* table, const int32_t* moves, const uint32_t* mt, int games,
-                        hipStream_t s) {
+static void launch_tree_unpack(const TreeParams& p, const SnapDev& d, const int32_t* table, const int32_t* moves, const uint32_t* mt, int games,
+                               hipStream_t s) {
     AO_DISPATCH_NCH(nch_of_cells(p.A), hipLaunchKernelGGL(k_tree_unpack<NCH>, dim3(games), dim3(64 * kWalkWaves), 0, s, p, d, table, moves, mt));
 }
 
 }  // namespace ao
+
+// ----------------------------------------------------------------------------------------------
+// the host side: export, check, import
+// ----------------------------------------------------------------------------------------------
+// games of one chunk: [first, first + count) of the call's list, N nodes and E edges together
+struct SnapChunk { int first, count; size_t N, E; };
+
+// closes a chunk when its packed games reach kSnapChunkBytes (a chunk holds at least one game): the device workspace is
+// bounded by that plus one game, whatever node_cap is
+static std::vector<SnapChunk> snap_chunks(const std::vector<int32_t>& nodes, const std::vector<int32_t>& edges) {
+    constexpr size_t kSnapChunkBytes = static_cast<size_t>(64) << 20;
+    std::vector<SnapChunk> out;
+    SnapChunk c{0, 0, 0, 0};
+    for (int i = 0; i < static_cast<int>(nodes.size()); ++i) {
+        c.count += 1;
+        c.N += static_cast<size_t>(nodes[i]);
+        c.E += static_cast<size_t>(edges[i]);
+        if (ao::snap_packed_bytes(c.N, c.E) >= kSnapChunkBytes) {
+            out.push_back(c);
+            c = SnapChunk{i + 1, 0, 0, 0};
+        }
+    }
+    if (c.count > 0) out.push_back(c);
+    return out;
+}
+
+// workspace of a chunk: the packed arrays (+ `first`), the game table, and for an import the moves and the streams
+static size_t snap_table_at(const SnapChunk& c) { return (ao::snap_dev_bytes(c.N, c.E) + 15) & ~static_cast<size_t>(15); }
+static size_t snap_chunk_bytes(const SnapChunk& c, int A, bool import) {
+    return snap_table_at(c) + static_cast<size_t>(c.count) * 4 * (ao::kSnapRow + (import ? A + 624 : 0));
+}
+
+extern "C" {
+
+int ao_tree_export(ao_engine* e, const uint8_t* mask, ao_tree_snapshot* out) {
+    if (roll_refuses(e, "ao_tree_export")) return 1;
+    if (e->in_move) return e->fail("ao_tree_export inside a move (between ao_begin_move and ao_end_move)");
+    if (!out) return e->fail("ao_tree_export: null snapshot");
+    const int G = e->G, A = e->A;
+    std::vector<int32_t> games;
+    for (int g = 0; g < G; ++g)
+        if (!mask || mask[g]) games.push_back(g);
+    const int ng = static_cast<int>(games.size());
+    if (ng > 0 && (!out->hdr || !out->gauss || !out->mt || !out->moves)) return e->fail("ao_tree_export: null hdr / gauss / mt / moves array");
+    // one stats pass: what every masked game's root reaches
+    std::vector<int32_t> st(static_cast<size_t>(G) * 4, 0);
+    if (ao_tree_stats(e, mask, st.data())) return 1;
+    std::vector<int32_t> nodes(ng), edges(ng);
+    int64_t N = 0, E = 0;
+    for (int i = 0; i < ng; ++i) {
+        const int32_t* s4 = st.data() + 4 * static_cast<size_t>(games[i]);
+        nodes[i] = s4[0];
+        edges[i] = s4[0] > 0 ? s4[1] - 1 : 0;
+        N += nodes[i];
+        E += edges[i];
+    }
+    if (N > out->nodes || E > out->edges)
+        return e->fail("ao_tree_export: the masked games hold " + std::to_string(N) + " nodes and " + std::to_string(E) + " edges, the snapshot's arrays " +
+                       std::to_string(out->nodes) + " and " + std::to_string(out->edges));
+    if (N > 0 && (!out->nchild || !out->parent || !out->parent_edge)) return e->fail("ao_tree_export: null node array");
+    if (E > 0 && (!out->act || !out->n || !out->w || !out->q || !out->p || !out->child)) return e->fail("ao_tree_export: null edge array");
+    const std::vector<SnapChunk> chunks = snap_chunks(nodes, edges);
+    size_t ws = 0;
+    for (const SnapChunk& c : chunks) ws = std::max(ws, snap_chunk_bytes(c, A, false));
+    if (readout_begin(e, "ao_tree_export", ws)) return 1;
+    size_t n0 = 0, e0 = 0;   // first node / edge of the chunk in the caller's arrays
+    for (const SnapChunk& c : chunks) {
+        if (c.N == 0) continue;
+        const size_t tab_at = snap_table_at(c);
+        int32_t* h_tab = reinterpret_cast<int32_t*>(e->h_ro.data() + tab_at);
+        size_t no = 0, eo = 0;
+        for (int k = 0; k < c.count; ++k) {
+            int32_t* row = h_tab + static_cast<size_t>(k) * ao::kSnapRow;
+            const int i = c.first + k;
+            row[0] = games[i]; row[1] = static_cast<int32_t>(no); row[2] = static_cast<int32_t>(eo); row[3] = nodes[i]; row[4] = edges[i];
+            row[5] = row[6] = row[7] = 0;
+            no += nodes[i];
+            eo += edges[i];
+        }
+        const ao::SnapDev d = ao::snap_dev_at(e->d_ro.p, c.N, c.E);
+        AO_HIP(e, hipMemcpyAsync(e->d_ro.p + tab_at, h_tab, static_cast<size_t>(c.count) * ao::kSnapRow * 4, hipMemcpyHostToDevice, e->stream));
+        if (ao::launch_tree_pack(e->tp, d, reinterpret_cast<const int32_t*>(e->d_ro.p + tab_at), c.count, e->stream))
+            return queue_refused(e, "ao_tree_export");
+        AO_HIP(e, hipGetLastError());
+        AO_HIP(e, hipMemcpyAsync(e->h_ro.data(), e->d_ro.p, ao::snap_packed_bytes(c.N, c.E), hipMemcpyDeviceToHost, e->stream));
+        AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffers are reused by the next chunk
+        const ao::SnapDev h = ao::snap_dev_at(e->h_ro.data(), c.N, c.E);
+        std::memcpy(out->p + e0, h.p, 8 * c.E);
+        std::memcpy(out->n + e0, h.n, 4 * c.E);
+        std::memcpy(out->w + e0, h.w, 4 * c.E);
+        std::memcpy(out->q + e0, h.q, 4 * c.E);
+        std::memcpy(out->child + e0, h.child, 4 * c.E);
+        std::memcpy(out->act + e0, h.act, c.E);
+        std::memcpy(out->nchild + n0, h.nchild, 4 * c.N);
+        std::memcpy(out->parent + n0, h.parent, 4 * c.N);
+        std::memcpy(out->parent_edge + n0, h.pedge, 4 * c.N);
+        n0 += c.N;
+        e0 += c.E;
+    }
+    // the streams (the pinned staging rows of ao_begin_move are free outside a move) and the host mirrors
+    AO_HIP(e, hipMemcpyAsync(e->h_mt, e->tp.mt, sizeof(uint32_t) * 624 * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipMemcpyAsync(e->h_pos, e->tp.mtpos, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    for (int i = 0; i < ng; ++i) {
+        const int g = games[i];
+        int32_t* h = out->hdr + static_cast<size_t>(i) * AO_SNAP_HDR;
+        h[0] = nodes[i]; h[1] = edges[i]; h[2] = static_cast<int32_t>(e->moves[g].size()); h[3] = e->status[g]; h[4] = e->over[g];
+        h[5] = e->h_pos[g]; h[6] = e->has_gauss[g]; h[7] = 0;
+        out->gauss[i] = e->gauss[g];
+        std::memcpy(out->mt + static_cast<size_t>(i) * 624, e->h_mt + static_cast<size_t>(g) * 624, sizeof(uint32_t) * 624);
+        int32_t* mv = out->moves + static_cast<size_t>(i) * A;
+        std::fill(mv, mv + A, 0);
+        std::copy(e->moves[g].begin(), e->moves[g].end(), mv);
+    }
+    out->board = e->cfg.board; out->inplanes = e->cfg.inplanes; out->win_mark = e->tp.win_mark;
+    out->sims = e->S; out->noise = e->tp.noise; out->c_puct = e->tp.c_puct;
+    out->games = ng; out->nodes = N; out->edges = E;
+    return 0;
+}
+
+int ao_tree_snapshot_check(const ao_tree_snapshot* snap) {
+    std::string& why = ao::create_error<ao_engine>();
+    why = ao::snapshot_check(snap);
+    return why.empty() ? 0 : 1;
+}
+
+int ao_tree_import(ao_engine* e, const int32_t* host_games, int32_t n, const ao_tree_snapshot* snap) {
+    if (roll_refuses(e, "ao_tree_import")) return 1;
+    if (e->in_move) return e->fail("ao_tree_import inside a move (between ao_begin_move and ao_end_move)");
+    if (!snap || (n > 0 && !host_games)) return e->fail("ao_tree_import: null argument");
+    if (n != snap->games) return e->fail("ao_tree_import: " + std::to_string(n) + " games listed, the snapshot holds " + std::to_string(snap->games));
+    const int G = e->G, A = e->A;
+    std::vector<uint8_t> seen(G, 0);
+    for (int i = 0; i < n; ++i) {
+        if (host_games[i] < 0 || host_games[i] >= G) return e->fail("game index out of range");
+        if (seen[host_games[i]]) return e->fail("ao_tree_import: a game is listed twice");
+        seen[host_games[i]] = 1;
+    }
+    if (snap->board != e->cfg.board || snap->inplanes != e->cfg.inplanes || snap->win_mark != e->tp.win_mark)
+        return e->fail("ao_tree_import: the snapshot is of board " + std::to_string(snap->board) + ", inplanes " + std::to_string(snap->inplanes) +
+                       ", win_mark " + std::to_string(snap->win_mark) + "; the engine has board " + std::to_string(e->cfg.board) + ", inplanes " +
+                       std::to_string(e->cfg.inplanes) + ", win_mark " + std::to_string(e->tp.win_mark));
+    const std::string why = ao::snapshot_check(snap);
+    if (!why.empty()) return e->fail("ao_tree_import: inconsistent snapshot: " + why);
+    if (n == 0) return 0;
+    // a pending bar belongs to the position it was set for; a snapshot taken after a barred move brings kBarQ children with it
+    std::vector<uint8_t> listed(G, 0);
+    for (int i = 0; i < n; ++i) listed[host_games[i]] = 1;
+    if (bar_forget(e, listed.data())) return 1;
+    for (int64_t k = 0; k < snap->edges && !e->bar_dirty; ++k) e->bar_dirty = snap->q[k] == ao::kBarQ;
+    std::vector<int32_t> nodes(n), edges(n);
+    for (int i = 0; i < n; ++i) {
+        nodes[i] = snap->hdr[static_cast<size_t>(i) * AO_SNAP_HDR];
+        edges[i] = snap->hdr[static_cast<size_t>(i) * AO_SNAP_HDR + 1];
+        if (nodes[i] > e->tp.keep_max)
+            return e->fail("ao_tree_import: snapshot game " + std::to_string(i) + " has " + std::to_string(nodes[i]) + " nodes, this engine keeps at most node_cap - sims - 1 = " +
+                           std::to_string(e->tp.keep_max) + " (raise ao_config.node_cap)");
+    }
+    const std::vector<SnapChunk> chunks = snap_chunks(nodes, edges);
+    size_t ws = 0;
+    for (const SnapChunk& c : chunks) ws = std::max(ws, snap_chunk_bytes(c, A, true));
+    if (readout_begin(e, "ao_tree_import", ws)) return 1;
+    size_t n0 = 0, e0 = 0;
+    for (const SnapChunk& c : chunks) {
+        AO_HIP(e, hipStreamSynchronize(e->stream));   // the staging buffer is free
+        const ao::SnapDev h = ao::snap_dev_at(e->h_ro.data(), c.N, c.E);
+        std::memcpy(h.p, snap->p + e0, 8 * c.E);
+        std::memcpy(h.n, snap->n + e0, 4 * c.E);
+        std::memcpy(h.w, snap->w + e0, 4 * c.E);
+        std::memcpy(h.q, snap->q + e0, 4 * c.E);
+        std::memcpy(h.child, snap->child + e0, 4 * c.E);
+        std::memcpy(h.act, snap->act + e0, c.E);
+        std::memcpy(h.nchild, snap->nchild + n0, 4 * c.N);
+        std::memcpy(h.parent, snap->parent + n0, 4 * c.N);
+        std::memcpy(h.pedge, snap->parent_edge + n0, 4 * c.N);
+        const size_t tab_at = snap_table_at(c);
+        int32_t* h_tab = reinterpret_cast<int32_t*>(e->h_ro.data() + tab_at);
+        int32_t* h_mv = h_tab + static_cast<size_t>(c.count) * ao::kSnapRow;
+        uint32_t* h_mt = reinterpret_cast<uint32_t*>(h_mv + static_cast<size_t>(c.count) * A);
+        size_t no = 0, eo = 0;
+        for (int k = 0; k < c.count; ++k) {
+            const int i = c.first + k;
+            const int32_t* hd = snap->hdr + static_cast<size_t>(i) * AO_SNAP_HDR;
+            int32_t* row = h_tab + static_cast<size_t>(k) * ao::kSnapRow;
+            row[0] = host_games[i]; row[1] = static_cast<int32_t>(no); row[2] = static_cast<int32_t>(eo); row[3] = nodes[i]; row[4] = edges[i];
+            row[5] = hd[2]; row[6] = hd[3]; row[7] = hd[5];
+            int32_t run = 0;   // a node's first edge inside its game
+            for (int j = 0; j < nodes[i]; ++j) {
+                h.first[no + j] = run;
+                run += h.nchild[no + j];
+            }
+            std::memcpy(h_mv + static_cast<size_t>(k) * A, snap->moves + static_cast<size_t>(i) * A, sizeof(int32_t) * A);
+            std::memcpy(h_mt + static_cast<size_t>(k) * 624, snap->mt + static_cast<size_t>(i) * 624, sizeof(uint32_t) * 624);
+            no += nodes[i];
+            eo += edges[i];
+        }
+        const size_t bytes = snap_chunk_bytes(c, A, true);
+        AO_HIP(e, hipMemcpyAsync(e->d_ro.p, e->h_ro.data(), bytes, hipMemcpyHostToDevice, e->stream));
+        const int32_t* d_tab = reinterpret_cast<const int32_t*>(e->d_ro.p + tab_at);
+        const int32_t* d_mv = d_tab + static_cast<size_t>(c.count) * ao::kSnapRow;
+        ao::launch_tree_unpack(e->tp, ao::snap_dev_at(e->d_ro.p, c.N, c.E), d_tab, d_mv,
+                               reinterpret_cast<const uint32_t*>(d_mv + static_cast<size_t>(c.count) * A), c.count, e->stream);
+        AO_HIP(e, hipGetLastError());
+        n0 += c.N;
+        e0 += c.E;
+    }
+    int32_t* herr = e->h_i32;
+    AO_HIP(e, hipMemcpyAsync(herr, e->tp.err, sizeof(int32_t) * G, hipMemcpyDeviceToHost, e->stream));
+    AO_HIP(e, hipStreamSynchronize(e->stream));
+    std::vector<uint8_t> bmask;
+    std::string bad;
+    for (int i = 0; i < n; ++i) {
+        const int g = host_games[i];
+        const int32_t* hd = snap->hdr + static_cast<size_t>(i) * AO_SNAP_HDR;
+        const int32_t* mv = snap->moves + static_cast<size_t>(i) * A;
+        e->moves[g].assign(mv, mv + hd[2]);
+        e->status[g] = hd[3];
+        e->over[g] = hd[4];
+        e->has_gauss[g] = hd[6];
+        e->gauss[g] = snap->gauss[i];
+        if (herr[g] & ao::ERR_BAD_MOVE) {
+            if (bmask.empty()) bmask.assign(G, 0);
+            bmask[g] = 1;
+            bad += (bad.empty() ? "" : ", ") + std::to_string(i);
+        }
+    }
+    e->ended = false;   // ao_play must follow a search on this engine, as on a fresh one
+    if (!bmask.empty()) {
+        ao_reset(e, bmask.data());
+        return e->fail("ao_tree_import: snapshot game(s) " + bad + ": an action lands on an occupied cell when the positions are rebuilt; reset (the other games of the call are imported)");
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// tree_snapshot.hpp -- what engine.hip and tree_snapshot.hip share: the device layout of one chunk of packed games.
+// tree_snapshot.hpp -- what the kernels and the host driver of tree_snapshot.hip share: the layout of one chunk of packed games.
 #pragma once
 #include "engine_types.hpp"
 
@@ -34,10 +34,5 @@ inline SnapDev snap_dev_at(unsigned char* base, size_t N, size_t E) {
 // a chunk's game table, kSnapRow int32 per game: engine slot, first node and first edge inside the chunk, nodes, edges, and for
 // the import the number of moves, the AO_ROOT_* status and the stream position
 constexpr int kSnapRow = 8;
-
-// non-zero: the breadth-first queue of a `cap`-node arena does not fit the LDS of one workgroup -- nothing is launched
-int launch_tree_pack(const TreeParams& p, const SnapDev& d, const int32_t* table, int games, hipStream_t s);
-void launch_tree_unpack(const TreeParams& p, const SnapDev& d, const int32_t* table, const int32_t* moves, const uint32_t* mt, int games,
-                        hipStream_t s);
 
 }  // namespace ao
